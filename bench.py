@@ -12,16 +12,25 @@ plain SGD + L2 - one "step" = forward + loss + backward (+ gradient all-reduce f
 + update on synthetic features already resident in HBM.  Weak scaling: 128 chunks per GPU.
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  The headline (`value`, `ms_per_step`,
-`roofline`, `dtype` "f32") is the engine's default arithmetic: fp32 operands on the fp32-input MFMA, the
-reference's own dtype.  At N = 1 the same run then times the opt-in split-precision mode (`precision:
-"f16x3"`: every fp32 operand as two fp16 planes, three fp16 MFMA products per fp32 product, fp32
-accumulate) for the same K steps and reports it separately under `"f16x3"` with its own roofline; an
-`e2e` leg repeats the headline with the host->device copy of each feature batch inside the timed
-region; `cpu_baseline` = the NumPy oracle's fp32 train_step on the full 128-chunk batch on this box's
-host cores (1 thread and the faster multi-thread settings).  `roofline` is for the dominant kernel: its
-launches are bracketed by hipEvents on their stream inside the timed region; an untimed probe pass
-brackets every MFMA GEMM kind for the per-kernel table.  At N > 1 `comm` carries, per rank, the RCCL
-world size and the all-reduce time of every gradient slice (events on the communication stream).
+`dtype` "f32") is the engine's default arithmetic: fp32 operands on the fp32-input MFMA, the reference's
+own dtype.  A plain run does only what the headline needs: set up, warm up, time K steps, print the line.
+At N > 1 `comm` carries, per rank, the RCCL world size and the all-reduce time of every gradient slice
+(events on the communication stream inside the timed region).
+
+--full adds everything else, in the same process: `roofline` for the dominant kernel (its launches are
+bracketed by hipEvents on their stream inside the timed region; an untimed probe pass brackets every MFMA
+GEMM kind for the per-kernel `kernels` table, an untimed isolated pass times each kind alone); at N = 1 the
+opt-in split-precision mode (`precision: "f16x3"`: every fp32 operand as two fp16 planes, three fp16 MFMA
+products per fp32 product, fp32 accumulate) for the same K steps, reported separately under `"f16x3"` with
+its own roofline; an `e2e` leg that repeats the headline with the host->device copy of each feature batch
+inside the timed region; `cpu_baseline` = the NumPy oracle's fp32 train_step on the full 128-chunk batch on
+this box's host cores (1 thread and the faster multi-thread settings).
+
+--dump-outputs DIR writes what the last timed step of the headline mode left to its caller, as .npy files
+(`loss`: float64 [raw, regularisation]; `variables`: every variable after the update, BN moving statistics
+included; `gradients`: the step's gradient buffer), at most DUMP_MAX_FLOATS float32 values in all: an array
+that does not fit is replaced by a fixed, seeded sample of its elements.  Inputs and initial variables are
+seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -53,6 +62,32 @@ KIND_SYMBOLS = ["xv_gemm_nt_kernel<true,", "xv_gemm_nt_kernel<false,", "xv_gemm_
                 "xv_gemm16_nt_kernel<true>", "xv_gemm16_nt_kernel<false>", "xv_gemm16_tn_kernel"]
 # algorithmic-FLOP peak of each kind: an f16x3 product issues 3 fp16 MFMAs (hi*hi + hi*lo + lo*hi)
 KIND_PEAK = [PEAK_F32_MFMA_TFLOPS] * 3 + [PEAK_F16_MFMA_TFLOPS / 3.0] * 3
+# --dump-outputs: float32 values written in all (60 MB); `variables` first, up to DUMP_MAX_VARIABLES of them
+DUMP_MAX_FLOATS = 15000000
+DUMP_MAX_VARIABLES = 10500000
+
+
+def dump_sample(a, cap, seed):
+    """The flat array `a` if it holds at most `cap` values, else `cap` of its elements at fixed, seeded positions (in order)."""
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.size <= cap:
+        return a
+    idx = np.sort(np.random.RandomState(seed).choice(a.size, cap, replace=False))
+    return a[idx]
+
+
+def capture_outputs(eng):
+    """Host copies of what the last train_step left to its caller (see --dump-outputs)."""
+    raw, reg = eng.losses()
+    variables = dump_sample(eng.variables.cpu().numpy(), DUMP_MAX_VARIABLES, 1)
+    gradients = dump_sample(eng.grads.cpu().numpy(), DUMP_MAX_FLOATS - variables.size, 2)
+    return {"loss": np.array([raw, reg], np.float64), "variables": variables.astype(np.float32), "gradients": gradients.astype(np.float32)}
+
+
+def write_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def pmc_traffic(kind):
@@ -202,10 +237,11 @@ def _profile_table(lib, _lib, which):
     return [int(c) for c in cnt], [float(m) for m in ms], [float(f) for f in fl]
 
 
-def run_mode(precision, args, dev, rank, world, dist, chunks, t_lo, t_hi, h2d=False, light=False):
+def run_mode(precision, args, dev, rank, world, dist, chunks, t_lo, t_hi, h2d=False, light=False, dump=False):
     """Build an engine in `precision`, warm up, then time EXACTLY args.steps optimiser steps between barrier +
     synchronize brackets.  h2d: every step first copies its feature / label batch from pinned host memory on the compute
-    stream (the reference boundary hands host arrays).  light: skip the probe / isolated passes (e2e leg)."""
+    stream (the reference boundary hands host arrays).  light: skip the probe / isolated passes (plain run, e2e leg).
+    dump: keep host copies of the last timed step's outputs in res["outputs"] (capture_outputs)."""
     from tf_kaldi_speaker_amd import _lib, engine as E
     from tf_kaldi_speaker_amd.parallel import GradAllReduce
     lib = _lib.load()
@@ -307,6 +343,8 @@ def run_mode(precision, args, dev, rank, world, dist, chunks, t_lo, t_hi, h2d=Fa
         res["host"].update(throttled_periods=thr1[0] - thr0[0], throttled_thread_ms=round((thr1[1] - thr0[1]) / 1e3, 1))
     if not light:
         res["timed"] = _profile_table(lib, _lib, "timed")
+    if dump:
+        res["outputs"] = capture_outputs(eng)
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -510,10 +548,17 @@ def main():
     ap.add_argument("--extended", action="store_true", help="BASELINE configs[4]: 10-layer extended-context TDNN + A-Softmax (m = 4) instead of the "
                     "reference's 5-layer TDNN + AM-Softmax; use with --frames 400 (no reference counterpart, SURVEY.md D4)")
     ap.add_argument("--precision", choices=["f32", "f16x3"], default="f32",
-                    help="arithmetic of the headline (default f32 = the engine's default); at one GPU the other mode is timed as well "
-                         "and reported separately unless --single-mode")
-    ap.add_argument("--single-mode", action="store_true", help="time only --precision (no second mode, no e2e leg)")
+                    help="arithmetic of the headline (default f32 = the engine's default); with --full at one GPU the other mode is timed "
+                         "as well and reported separately unless --single-mode")
+    ap.add_argument("--single-mode", action="store_true", help="with --full: time only --precision (no second mode, no e2e leg)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline and per-kernel table (probe and isolated passes), "
+                    "at one GPU the other precision, the e2e leg and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs of the headline mode to "
+                    "DIR/<name>.npy (loss, variables, gradients; at most %d float32 values in all, larger arrays as a fixed seeded sample)"
+                    % DUMP_MAX_FLOATS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -548,9 +593,12 @@ def main():
     if world > 1 and t_lo != t_hi:
         sys.exit("bench.py: variable-length batches are a single-GPU diagnostic (ranks would draw different T)")
 
-    head = run_mode(args.precision, args, dev, rank, world, dist, chunks, t_lo, t_hi)
+    head = run_mode(args.precision, args, dev, rank, world, dist, chunks, t_lo, t_hi, light=not args.full,
+                    dump=args.dump_outputs is not None and rank == 0)
+    if "outputs" in head:
+        write_outputs(args.dump_outputs, head.pop("outputs"))
     other, e2e = None, None
-    if world == 1 and not args.single_mode:
+    if args.full and world == 1 and not args.single_mode:
         other = run_mode("f16x3" if args.precision == "f32" else "f32", args, dev, rank, world, dist, chunks, t_lo, t_hi)
         e2e = run_mode(args.precision, args, dev, rank, world, dist, chunks, t_lo, t_hi, h2d=True, light=True)
 
@@ -592,16 +640,17 @@ def main():
                                       "+RCCL all-reduce" if world > 1 else "", chunks, args.frames, D, NSPK),
                        "chunks_per_gpu": chunks, "frames": t_lo if t_lo == t_hi else [t_lo, t_hi], "mean_frames": hs["mean_frames"],
                        "feat_dim": D, "num_speakers": NSPK, "precision": args.precision, "parallelism": "dp%d" % world},
-            "roofline": hs["roofline"],
             "step_flops": hs["step_flops"],
             "step_bytes": dict(hs["step_bytes"], note="compulsory bytes under perfect fusion (5 S + 2 X + 5 P); the step is MFMA-bound, this "
                                                       "fraction cannot exceed ~0.06 in fp32 / ~0.25 at the f16x3 MFMA roof"),
-            "kernels": hs["kernels"],
-            "kernels_note": "per-kind figures come from an untimed 3-step probe pass with every GEMM launch bracketed by HIP events; "
-                            "the timed region brackets only the dominant kind (`roofline`), which keeps the events' queue time out of `value`",
             "loss": hs["loss"],
             "host": head["host"],
         }
+        if "roofline" in hs:
+            out["roofline"] = hs["roofline"]
+            out["kernels"] = hs["kernels"]
+            out["kernels_note"] = ("per-kind figures come from an untimed 3-step probe pass with every GEMM launch bracketed by HIP events; "
+                                   "the timed region brackets only the dominant kind (`roofline`), which keeps the events' queue time out of `value`")
         if other is not None:
             os_ = summarize(other, args, world, chunks)
             out[other["precision"]] = {"dtype": DT[other["precision"]], "value": os_["value"], "unit": "chunks/s", "ms_per_step": os_["ms_per_step"],
@@ -616,7 +665,7 @@ def main():
                                   "the product feeds it (pinned host batch -> device on a copy stream that never waits for the GPU, the compute stream waits for the copy's event); never `value`"}
         if comm_all is not None:
             out["comm"] = comm_all
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if dist is not None:

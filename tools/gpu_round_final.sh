@@ -12,7 +12,7 @@ timeout 900 python3 tools/bench_kernel.py pool 2>&1 | grep -v amdgpu.ids > $O/po
 timeout 900 python3 tools/bench_kernel.py segment 2>&1 | grep -v amdgpu.ids > $O/segment_bench.txt
 timeout 900 python3 tools/bench_host.py e2e_ab --rounds 2 2>&1 | grep -v amdgpu.ids > $O/e2e_ab.txt
 timeout 900 python3 tools/bench_host.py extract 2>&1 | grep -v amdgpu.ids > $O/extract_bench.txt; timeout 900 python3 tools/bench_host.py extract_driver 2>&1 | grep -v amdgpu.ids >> $O/extract_bench.txt; tail -4 $O/extract_bench.txt
-timeout 900 python3 bench.py --extended --frames 400 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_extended.json
+timeout 900 python3 bench.py --extended --frames 400 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_extended.json
 python3 tools/bench_summary.py $O/bench_extended.json | grep -E "^f32|^f16x3"
 timeout 900 python3 tools/shape_sweep.py --precision f32 2>/dev/null > $O/shapes_f32.json
 timeout 900 python3 tools/shape_sweep.py --precision f16x3 2>/dev/null > $O/shapes_f16x3.json
