@@ -63,6 +63,11 @@ int xv_profile_end(int64_t launches[XV_PROFILE_KINDS], double ms[XV_PROFILE_KIND
  * 0 one workgroup per tile (xv_gemm_nt_kernel), 1 the evenly scheduled kernel (xv_gemm_nt_sk_kernel), 2 whole tiles + shares of the
  * remaining tiles (xv_gemm_nt_kernel), 3 split-K + slab sum.  tools/pmc_traffic.py attributes layers to kernels with it. */
 int xv_debug_nt_schedule(int M, int N, int K, int stats, int co_running);
+/* Diagnostics: the plan xv_affine_wgrad (direct = 0) and the engine's loss-head weight gradient (direct = 1: an unsplit result is stored
+ * straight into the destination) run for P[M][N] = sum_r A[r][M] . B[r][N] over R reduction rows.  out[0]: 0 the general kernel
+ * (xv_gemm_tn_kernel), 1 the 129 ... 160-row kernel (xv_gemm_tn160_kernel); out[1]: splits (slabs summed by the reduce launch);
+ * out[2]: reduction rows per split (a multiple of 16); out[3]: 1 when the general kernel stages two K-steps ahead.  Host arithmetic. */
+int xv_debug_tn_plan(int M, int N, int R, int direct, int out[4]);
 
 /* dst[r][0..cols) = src[r][0..cols) for r < rows (device to device, pitches in floats). */
 int xv_copy_2d(void* stream, float* dst, size_t ldd, const float* src, size_t lds, int rows, int cols);

@@ -102,10 +102,11 @@ def test_affine_dgrad_wgrad(ops, segs, t_in, c, k, o):
     dzp[:, pad:pad + t_out] = dz
     d_dzp = dev(dzp.reshape(-1, o))
     c_pad = (c + 3) // 4 * 4
-    if c % 4 == 0:
-        wf = ops.prep_weight_dgrad(dev(kern))
-        dx = ops.affine_dgrad(d_dzp, segs, t_out, o, k, wf, c)
-        assert_close(host(dx), dx_ref.reshape(-1, c), name="affine_dgrad")
+    # c % 4 != 0 too (the input layer's 30 channels): dx is the GEMM's N, which has no alignment requirement - the row-store epilogue
+    # falls back to four-byte stores
+    wf = ops.prep_weight_dgrad(dev(kern))
+    dx = ops.affine_dgrad(d_dzp, segs, t_out, o, k, wf, c)
+    assert_close(host(dx), dx_ref.reshape(-1, c), name="affine_dgrad")
     xp = ops.pad_channels(dev(x.reshape(-1, c)), c_pad).view(segs, t_in, c_pad)
     l2 = 1e-2
     dk = ops.affine_wgrad(xp, k, c, d_dzp, t_out + 2 * pad, pad, o, dev(kern), l2)
@@ -568,22 +569,31 @@ SEGMENT_CASES = [(128, 512, 3000), (64, 512, 512), (128, 7351, 512), (128, 512, 
                  (1, 512, 3000), (37, 100, 68), (128, 33, 4), (2, 600, 1204)]
 
 
-# (segs, t_in, c, k, o): tile counts between one and four per CU with a remainder -> whole tiles + shares (csrc/xv_gemm.hip xv_nt_shares)
+# (segs, t_in, c, k, o) and SHARE_PLANS (forward plan, data-gradient plan): tile counts between one and four per CU with a remainder -> whole tiles + shares
+# (csrc/xv_gemm.hip xv_nt_shares) in the forward launch; the data gradient runs beside the weight-gradient stream, where shares need tiles of
+# >= 100 K-steps and >= 512 tiles are dealt one workgroup per tile.  Plans: 0 one workgroup per tile, 1 even schedule, 2 shares, 3 split-K
+# (xv_debug_nt_schedule; tests/test_gpu_gemm_plans.py runs every plan against the oracle)
 SHARE_CASES = [
-    (130, 135, 192, 5, 512),     # forward 17 030 rows x 512 = 536 tiles (24 remaining), K = 960; data gradient 17 550 rows = 552 tiles
-    (66, 151, 64, 5, 512),       # forward 9 702 rows = 304 tiles: one whole tile per CU - shared in the forward launch only
-    (1, 5600, 512, 1, 1500),     # dense, ragged N: 44 x 12 = 528 tiles, K = 512 (32 K-steps)
+    (130, 135, 192, 5, 512),     # forward 17 030 rows x 512 = 536 tiles (24 remaining), K = 960; data gradient 17 550 x 192 = 276 tiles: even
+    (64, 135, 64, 7, 512),       # forward 8 256 rows = 260 tiles: one whole tile per CU + 4 shared; data gradient 64 columns, K = 3 584: split-K
+    (1, 5600, 512, 1, 1500),     # dense, ragged N: 44 x 12 = 528 tiles, K = 512 (32 K-steps); data gradient K = 1 500 on 176 tiles: split-K
 ]
+SHARE_PLANS = {SHARE_CASES[0]: (2, 1), SHARE_CASES[1]: (2, 3), SHARE_CASES[2]: (2, 3)}      # (forward, data gradient)
 
 
 @pytest.mark.parametrize("segs,t_in,c,k,o", SHARE_CASES)
 def test_whole_tiles_plus_shares(ops, segs, t_in, c, k, o):
-    """The remainder tiles of these launches are summed from K shares by their last block (slab hand-over inside xv_gemm_nt_kernel): values and
-    BatchNorm partials against the oracle, and every repetition - beside an uneven load on another stream - bit-identical to the first
-    (a stale slab word or a ticket left non-zero would show)."""
+    """The remainder tiles of these forward launches are summed from K shares by their last block (slab hand-over inside xv_gemm_nt_kernel):
+    values and BatchNorm partials against the oracle, and every repetition - beside an uneven load on another stream - bit-identical to the
+    first (a stale slab word or a ticket left non-zero would show).  The data gradient of the same layer rides along on its own plan."""
     import torch
-    rs = np.random.RandomState(segs + t_in)
+    from tf_kaldi_speaker_amd import _lib
+    plan = _lib.load().xv_debug_nt_schedule
+    fwd_plan, dgrad_plan = SHARE_PLANS[(segs, t_in, c, k, o)]
     t_out = t_in - k + 1
+    assert plan(segs * t_out, o, k * c, 1, 0) == fwd_plan, "forward of %s: the plan changed" % ((segs, t_in, c, k, o),)
+    assert plan(segs * t_in, c, k * o, 0, 1) == dgrad_plan, "data gradient of %s: the plan changed" % ((segs, t_in, c, k, o),)
+    rs = np.random.RandomState(segs + t_in)
     x = rs.randn(segs, t_in, c).astype(np.float32)
     kern = (rs.randn(k, c, o) / np.sqrt(k * c)).astype(np.float32)
     bias = rs.randn(o).astype(np.float32)
@@ -606,7 +616,7 @@ def test_whole_tiles_plus_shares(ops, segs, t_in, c, k, o):
     wf = ops.prep_weight_dgrad(dev(kern))
     dx = ops.affine_dgrad(d_dzp, segs, t_out, o, k, wf, c).clone()
     dx_ref = O.conv1d_valid_bwd(x.astype(np.float64), kern.astype(np.float64), dz.astype(np.float64))[0]
-    assert_close(host(dx), dx_ref.reshape(-1, c), name="affine_dgrad (shares)")
+    assert_close(host(dx), dx_ref.reshape(-1, c), name="affine_dgrad (plan %d)" % dgrad_plan)
     side = torch.cuda.Stream()
     big = torch.randn(4096, 4096, device="cuda")
     bad = 0

@@ -206,3 +206,40 @@ def test_context_window_kernel_256_row_tiles():
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "passed" in r.stdout
+
+
+# (segs, t_in, c, k, o): the K-tail and ragged-N rows of tests/test_gpu_gemm_plans.py where the split-precision constraints allow them (planes
+# of 8-half rows: K = k * ceil8(c) is a multiple of 8, so the tails are K % 16 = 8 and 0; any N); a 20-dim feature input, N = 97 / 1499
+F16X3_TAIL_CASES = [(1, 16, 20, 1, 97), (4, 50, 20, 5, 1499), (4, 50, 24, 3, 512), (1, 333, 512, 1, 1499), (16, 196, 512, 1, 1500)]
+
+
+@pytest.mark.parametrize("segs,t_in,c,k,o", F16X3_TAIL_CASES)
+def test_affine_forward_dgrad_k_tails_and_ragged_n_f16x3(ops, segs, t_in, c, k, o):
+    rs = np.random.RandomState(segs * 97 + c + o)
+    t_out = t_in - k + 1
+    x = np.maximum(rs.randn(segs, t_in, c), 0).astype(np.float32) * 1.7
+    kern = (rs.randn(k, c, o) / np.sqrt(k * c)).astype(np.float32)
+    bias = rs.randn(o).astype(np.float32)
+    dz = (rs.randn(segs, t_out, o) * 3e-4).astype(np.float32)
+    x64, k64 = x.astype(np.float64), kern.astype(np.float64)
+    ref = O.conv1d_valid_fwd(x64, k64, bias.astype(np.float64)).reshape(-1, o)
+    xp = ops.split_planes(dev(x.reshape(-1, c)))
+    wtp = ops.split_planes(ops.prep_weight_fwd(dev(kern), xp.ld))
+    z, part = ops.affine_forward_f16x3(xp, segs, t_in, k, wtp, dev(bias), o, with_stats=True)
+    assert_close(host(z), ref, name="affine_forward_f16x3")
+    assert_close(host(ops.affine_forward_f16x3(xp, segs, t_in, k, wtp, dev(bias), o)), ref, name="affine_forward_f16x3 (no stats)")
+    gamma, beta = rs.rand(o).astype(np.float32) + 0.5, rs.randn(o).astype(np.float32)
+    mean, invstd, _, _ = ops.bn_finalize(part, ref.shape[0], dev(gamma), dev(beta), 1e-3, 0.99, False, None, None)
+    assert_close(host(mean), ref.mean(0), 2e-5, 1e-4, "bn mean")
+    assert_close(host(invstd), 1 / np.sqrt(ref.var(0) + 1e-3), 2e-5, 1e-4, "bn invstd")
+    if c % 8 == 0:                                                               # dx is [rows][c]: the f16x3 data gradient needs c % 8 == 0
+        pad = k - 1
+        dzp_host = np.zeros((segs, t_out + 2 * pad, o), np.float32)
+        dzp_host[:, pad:pad + t_out] = dz
+        dzp = ops.split_planes(dev(dzp_host.reshape(-1, o)))
+        wf = ops.prep_weight_dgrad(dev(kern)) if k > 1 else dev(kern[0])
+        if dzp.ld != o:
+            wf = torch.nn.functional.pad(wf.view(c, k, o), (0, dzp.ld - o)).reshape(c, k * dzp.ld).contiguous()
+        dx = ops.affine_dgrad_f16x3(dzp, segs, t_out, k, ops.split_planes(wf), c)
+        dx_ref = O.conv1d_valid_bwd(x64, k64, dz.astype(np.float64))[0]
+        assert_close(host(dx), dx_ref.reshape(-1, c), name="affine_dgrad_f16x3")

@@ -227,19 +227,37 @@ def test_no_shuffle_starts_at_frame_zero_and_few_speakers_are_duplicated(nl, dat
             assert any(np.array_equal(m[:30], feats[i]) for m in decoded.values())
 
 
-def test_eight_concurrent_loaders_scale_with_the_host(tmp_path):
+def _usable_cpus():
+    """CPUs this process may run on: the affinity mask, capped by the cgroup's CPU quota (os.cpu_count() is the whole machine's count)"""
+    import os
+    import sys
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from bench import cgroup_cpus
+    quota = cgroup_cpus()
+    return max(1, min(n, int(quota)) if quota else n)
+
+
+def test_concurrent_loaders_scale_with_the_usable_cpus(tmp_path):
     """One native loader per rank, as an 8-GPU job runs them (tools/bench_host.py loader_scale): the instances share nothing but the page
-    cache, so 8 single-threaded loaders in 8 processes must deliver close to 8x one of them when the host has the cores (no
-    global lock, no shared queue) - the property the >= 6x 1 -> 8 GPU scaling target rests on.  The absolute
-    figure against the per-GPU step rate is printed by the tool on the GPU box's host (profiles/)."""
+    cache, so up to 8 single-threaded loaders in as many processes must deliver close to that many times one of them when the host has
+    the cores (no global lock, no shared queue) - the property the >= 6x 1 -> 8 GPU scaling target rests on.  The
+    absolute figure against the per-GPU step rate is printed by the tool on the GPU box's host (profiles/).
+    A loader keeps one CPU busy, so the loader count is the CPUs this process may use (affinity and cgroup quota), at most 8.  Rates are
+    the best of three interleaved rounds with timed windows of about a second: another process's burst on a shared host lowers a
+    throughput sample and never raises one, so the best sample is the capability the bound is about."""
     import os
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
     import bench_host
     root, spklist, _ = make_data_dir(str(tmp_path / "d"), num_spk=40, utts_per_spk=4, dim=30, min_frames=450, max_frames=600, seed=3)
-    cores = os.cpu_count() or 1
-    procs = min(8, cores)
-    one = bench_host.loader_scale_run(1, 1, 150, chunks=32, root=root, spklist=spklist)
-    many = bench_host.loader_scale_run(procs, 1, 150, chunks=32, root=root, spklist=spklist)
-    print("one loader %.0f chunks/s, %d loaders %.0f chunks/s aggregate" % (one["aggregate_chunks_per_s"], procs, many["aggregate_chunks_per_s"]))
-    assert many["aggregate_chunks_per_s"] >= 0.35 * procs * one["aggregate_chunks_per_s"], (one, many)
+    procs = min(8, _usable_cpus())
+    ones, manys = [], []
+    for _ in range(3):
+        ones.append(bench_host.loader_scale_run(1, 1, 500, chunks=32, root=root, spklist=spklist))
+        manys.append(bench_host.loader_scale_run(procs, 1, 500, chunks=32, root=root, spklist=spklist))
+    one = max(ones, key=lambda r: r["aggregate_chunks_per_s"])
+    many = max(manys, key=lambda r: r["aggregate_chunks_per_s"])
+    print("one loader %.0f chunks/s, %d loaders %.0f chunks/s aggregate (best of 3)" % (one["aggregate_chunks_per_s"], procs,
+                                                                                        many["aggregate_chunks_per_s"]))
+    assert many["aggregate_chunks_per_s"] >= 0.35 * procs * one["aggregate_chunks_per_s"], (ones, manys)

@@ -1306,15 +1306,16 @@ static bool tn_wide_rows(int M) { return M > BM && M <= TNW_M; }
 // XV_WGS_PER_CU (4) workgroups fit a CU (LDS 32 KB, 128 VGPRs each), i.e. 1 024 - more costs a second round (2 x on the first build, +2 % in
 // the round-5 step at 1 536 / 2 048), fewer leaves matrix pipes idle.  The history of this choice (768 / 896 workgroups, an even schedule,
 // unsplit segment-level gradients, tdnn1 as 128 ... 512 workgroups, wave groups) is DESIGN.md Appendix A.
-struct XvTnPlan { int splits, chunk; };
+struct XvTnPlan { int splits, chunk; bool wide, ahead; };      // wide: xv_gemm_tn160_kernel; ahead: TNArgs::ahead of xv_gemm_tn_kernel
 static XvTnPlan xv_tn_plan(int M, int N, int R, bool direct = false) {
     const int tiles = xv_cdiv(M, BM) * xv_cdiv(N, BN);
     const int ksteps = xv_cdiv(R, BK);
-    XvTnPlan pl = {1, 0};
+    XvTnPlan pl = {1, 0, false, false};
     if (tn_wide_rows(M)) {      // xv_gemm_tn160_kernel: one round of 512 workgroups (2 per CU), at least 4 K-steps each
         const int splits = std::max(1, std::min(TNW_WGS / xv_cdiv(N, BN), ksteps / 4));
         pl.chunk = xv_cdiv(ksteps, splits) * BK;
         pl.splits = xv_cdiv(R, pl.chunk);
+        pl.wide = true;         // (plain double buffering only: no `ahead` form)
         return pl;
     }
     const int min_ksteps = 2;                                          // fewest K-steps a workgroup is given
@@ -1335,10 +1336,21 @@ static XvTnPlan xv_tn_plan(int M, int N, int R, bool direct = false) {
     if (tiles <= 16) splits = std::min(splits, std::max(1, 256 / tiles));
     pl.chunk = xv_cdiv(ksteps, splits) * BK;
     pl.splits = xv_cdiv(R, pl.chunk);
+    pl.ahead = pl.chunk / BK >= XV_TN_AHEAD_MIN;      // (Appendix B, note 9)
     return pl;
 }
 int xv_tn_splits(int M, int N, int R) { return xv_tn_plan(M, N, R).splits; }
 int xv_tn_splits_direct(int M, int N, int R) { return xv_tn_plan(M, N, R, true).splits; }
+// diagnostics (tests/test_gemm_plans.py restates the plan against it): what xv_launch_gemm_tn runs for P[M][N] = sum over R rows
+extern "C" int xv_debug_tn_plan(int M, int N, int R, int direct, int out[4]) {
+    XV_REQUIRE(M > 0 && N > 0 && R > 0 && out, "debug_tn_plan: empty problem");
+    const XvTnPlan pl = xv_tn_plan(M, N, R, direct != 0);
+    out[0] = pl.wide ? 1 : 0;
+    out[1] = pl.splits;
+    out[2] = pl.chunk;
+    out[3] = pl.ahead ? 1 : 0;
+    return 0;
+}
 
 int xv_launch_gemm_tn(hipStream_t s, const XvGemmTN& g) {
     XV_REQUIRE(g.M % 4 == 0 && g.N % 4 == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0,
@@ -1370,11 +1382,11 @@ int xv_launch_gemm_tn(hipStream_t s, const XvGemmTN& g) {
     const XvTnPlan pl = xv_tn_plan(g.M, g.N, g.R, g.direct != 0);
     XV_REQUIRE(pl.splits == g.splits, "gemm_tn: splits must come from xv_tn_splits%s (%d vs %d)", g.direct ? "_direct" : "", pl.splits, g.splits);
     p.r_chunk = pl.chunk;
-    p.ahead = p.r_chunk / BK >= XV_TN_AHEAD_MIN;      // (Appendix B, note 9)
+    p.ahead = pl.ahead ? 1 : 0;
     const int wgs = p.tiles_m * p.tiles_n * pl.splits;
     {
         XvProfScope prof(s, 2, 2.0 * g.M * g.N * g.R);
-        if (tn_wide_rows(g.M)) hipLaunchKernelGGL(xv_gemm_tn160_kernel, dim3(p.tiles_n * pl.splits), dim3(256), 0, s, p);
+        if (pl.wide) hipLaunchKernelGGL(xv_gemm_tn160_kernel, dim3(p.tiles_n * pl.splits), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(xv_gemm_tn_kernel, dim3(wgs), dim3(256), 0, s, p);
     }
     XV_LAUNCH_CHECK();

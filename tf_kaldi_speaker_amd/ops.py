@@ -74,14 +74,17 @@ def prep_weight_dgrad(kernel):
     return wf
 
 
-def affine_forward(x, k, wt, bias, o, with_stats=False):
-    """x: [segs, t_in, c_pad] -> z [segs*(t_in-k+1), o] (+ bn_part)."""
+def affine_forward(x, k, wt, bias, o, with_stats=False, ldz=None):
+    """x: [segs, t_in, c_pad] -> z [segs*(t_in-k+1), o] (+ bn_part).  ldz: row pitch of z (>= o; the engine writes 1500 columns on a 1504
+    pitch): z is then the [rows, o] view of a [rows, ldz] buffer whose columns o .. ldz-1 the launch does not write."""
     segs, t_in, c_pad = x.shape
     rows = segs * (t_in - k + 1)
-    z = _f32((rows, o), x)
+    ldz = o if ldz is None else int(ldz)
+    z = _f32((rows, ldz), x)
     part = _f32((4, (rows + TILE_M - 1) // TILE_M, o), x) if with_stats else None
     wp, wb = _ws(x)
-    _lib.call("xv_affine_forward", _s(), _p(x), segs, t_in, c_pad, k, _p(wt), _p(bias), _p(z), o, o, _p(part), wp, wb)
+    _lib.call("xv_affine_forward", _s(), _p(x), segs, t_in, c_pad, k, _p(wt), _p(bias), _p(z), o, ldz, _p(part), wp, wb)
+    z = z[:, :o] if ldz != o else z
     return (z, part) if with_stats else z
 
 
