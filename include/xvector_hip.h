@@ -68,6 +68,10 @@ int xv_debug_nt_schedule(int M, int N, int K, int stats, int co_running);
  * (xv_gemm_tn_kernel), 1 the 129 ... 160-row kernel (xv_gemm_tn160_kernel); out[1]: splits (slabs summed by the reduce launch);
  * out[2]: reduction rows per split (a multiple of 16); out[3]: 1 when the general kernel stages two K-steps ahead.  Host arithmetic. */
 int xv_debug_tn_plan(int M, int N, int R, int direct, int out[4]);
+/* Diagnostics: the form of the margin / cross-entropy row kernel xv_margin_softmax_rows (and the engine's loss) runs for a logits pitch of
+ * ldl floats with logits and dlogits at those addresses: 8 or 16 (the row held in registers, RQ float4 per thread: ldl % 4 == 0, both
+ * addresses 16-byte aligned, ldl <= 8192 or 16384), 0 (three passes over memory: any other pitch or alignment).  Host arithmetic. */
+int xv_debug_softmax_rows_form(int ldl, uintptr_t logits, uintptr_t dlogits);
 
 /* dst[r][0..cols) = src[r][0..cols) for r < rows (device to device, pitches in floats). */
 int xv_copy_2d(void* stream, float* dst, size_t ldd, const float* src, size_t lds, int rows, int cols);
@@ -333,7 +337,9 @@ int xv_segment_dgrad_bn_backward(void* stream, const float* dy, long lddy, const
                                  uint32_t* tickets);
 
 /* tf.nn.l2_normalize(w, dim=0), loss.py:104: inv_norm[n], wn[c][ldn] = w*inv, wnt[n][c] = wn^T.
- * normalize == 0 copies unnormalised (plain softmax, loss.py:30). */
+ * normalize == 0 copies unnormalised (plain softmax, loss.py:30).  inv_norm carries the column's liveness: a column whose fp32
+ * ss = sum_c w[c][n]^2 is below 1e-12f (clamped by the maximum()) holds exactly 1e6f = rsqrt(1e-12f); a live one holds
+ * min(rsqrt(ss), 999999.9375f), one ulp below, and xv_loss_weight_backward keeps the projection term for it. */
 int xv_loss_prep_weight(void* stream, const float* w, int c, int n, int normalize,
                         float* inv_norm, float* wn, int ldn, float* wnt);
 /* Given logits = x . wn (+bias) [rows][ldl]: margin transform of the target logit, lambda
@@ -345,7 +351,7 @@ int xv_margin_softmax_rows(void* stream, int kind, const float* logits, int rows
                            float* dlogits, float* dnorm, float* row_loss, float* loss_out);
 /* dx[r][:] += dnorm[r] * x[r][:] / ||x[r]||  (the ||x|| paths of loss.py:122,147). */
 int xv_add_norm_grad(void* stream, const float* x, const float* dnorm, int rows, int c, float* dx);
-/* Gradient through l2_normalize: dw = inv*(dwn - wn*colsum(dwn*wn)) + l2_scale*w. */
+/* Gradient through l2_normalize: dw = inv*(dwn - live*wn*colsum(dwn*wn)) + l2_scale*w, live = inv_norm[n] != 1e6f (see xv_loss_prep_weight). */
 int xv_loss_weight_backward(void* stream, const float* dwn, int lddwn, const float* wn, int ldn,
                             const float* inv_norm, const float* w, int c, int n, int normalize,
                             float l2_scale, float* dw, void* ws, size_t ws_bytes);

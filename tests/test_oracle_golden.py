@@ -44,6 +44,69 @@ def test_loss_family_matches_reference_numpy_oracles(dtype):
     assert worst < 5e-5
 
 
+def test_margin_softmax_rows_ref_reproduces_margin_softmax_loss():
+    """oracle.margin_softmax_rows_ref (the loss head on given logits, what tests/test_gpu_loss_head.py holds the row kernel to) against
+    margin_softmax_loss on every golden case: logits = x . wn, then loss = mean of the row losses, d x = dlogits . wn^T + d||x|| x/||x||
+    and d W through l2_normalize, to 1e-12."""
+    for i in range(len(G["loss"])):
+        kind = str(G["kind"][i])
+        m = float(G["m"][i])
+        if kind == "asoftmax":
+            m = int(m)
+        emb, w, labels = G["emb"][i].astype(np.float64), G["w"][i].astype(np.float64), G["labels"][i]
+        if G["feature_norm"][i]:
+            emb, _ = O.l2_scaling_fwd(emb, 0.1)
+        lam = O.margin_lambda(*G["sched"][i], int(G["step"][i]))
+        loss, logits, (dfeat, dkernel) = O.margin_softmax_loss(kind, emb, labels, w, m, lam)
+        # the same float64 operations as the oracle's l2_normalize: ArcFace rows at theta ~ 0 / pi turn a rounding-level change of the
+        # logits into a 1e-5 relative change of d phi / d cos = cos / sin
+        wn = w * (1.0 / np.sqrt(np.maximum((w * w).sum(axis=0, keepdims=True), 1e-12)))
+        xnorm = np.sqrt((emb * emb).sum(axis=1))
+        assert np.array_equal(logits, emb @ wn)
+        rl, dlogits, dnorm = O.margin_softmax_rows_ref(kind, emb @ wn, xnorm, labels, m, lam)
+        assert rl.shape == dnorm.shape == (emb.shape[0],) and dlogits.shape == logits.shape
+        assert abs(rl.mean() - loss) <= 1e-12 * max(1.0, abs(loss)), (i, kind, m)
+        if kind == "asoftmax" and m == 1:
+            assert np.all(dnorm == 0)
+        got_dfeat = dlogits @ wn.T + (dnorm / xnorm)[:, None] * emb
+        got_dk = O.l2_normalize_w_backward(w, emb.T @ dlogits)
+        for got, ref, name in ((got_dfeat, dfeat, "dfeat"), (got_dk, dkernel, "dkernel")):
+            assert np.abs(got - ref).max() <= 1e-12 * max(1.0, np.abs(ref).max()), (i, kind, m, name)
+
+
+@pytest.mark.parametrize("kind,m", [("softmax", 0), ("asoftmax", 1), ("asoftmax", 2), ("asoftmax", 4), ("additive_margin_softmax", 0.35),
+                                    ("additive_angular_margin_softmax", 0.5)])
+def test_margin_softmax_rows_ref_gradients_match_finite_differences(kind, m):
+    """The gradients of the per-row reference are those of its mean loss: central differences in logits and in ||x||, with the target
+    cosines kept 0.02 from the clamp, the A-Softmax region edges and the ArcFace branch point."""
+    rs = np.random.RandomState(7)
+    rows, n, lam = 6, 9, 0.5
+    labels = rs.randint(0, n, rows)
+    xnorm = rs.uniform(2, 6, rows)
+    cos = rs.uniform(-1, 1, (rows, n))
+    edges = np.array([-1, -0.5 ** 0.5, 0, 0.5 ** 0.5, 1, np.cos(np.pi - 0.5)])
+    for r in range(rows):
+        while np.abs(cos[r, labels[r]] - edges).min() < 0.02:
+            cos[r, labels[r]] = rs.uniform(-1, 1)
+    logits = cos * xnorm[:, None]
+
+    def mean_loss(lg, xn):
+        return O.margin_softmax_rows_ref(kind, lg, xn, labels, m, lam)[0].mean()
+
+    _, dlogits, dnorm = O.margin_softmax_rows_ref(kind, logits, xnorm, labels, m, lam)
+    h = 1e-6
+    for r in range(rows):
+        for j in range(n):
+            e = np.zeros_like(logits)
+            e[r, j] = h
+            fd = (mean_loss(logits + e, xnorm) - mean_loss(logits - e, xnorm)) / (2 * h)
+            assert abs(fd - dlogits[r, j]) <= 1e-7, (kind, m, r, j, fd, dlogits[r, j])
+        e = np.zeros(rows)
+        e[r] = h
+        fd = (mean_loss(logits, xnorm + e) - mean_loss(logits, xnorm - e)) / (2 * h)
+        assert abs(fd - dnorm[r]) <= 1e-7, (kind, m, r, fd, dnorm[r])
+
+
 def test_lambda_schedule_values():
     # shipped AM schedule: min 0, base 1000, gamma 1e-4, power 5 (tdnn_amsoftmax_*.json:9-13)
     assert O.margin_lambda(0, 1000, 1e-4, 5, 0) == 1000.0

@@ -31,7 +31,12 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 }
 
 // inv_norm[n] = rsqrt(max(sum_c w[c][n]^2, 1e-12))   (tf.nn.l2_normalize(w, dim=0), loss.py:104)
-// block = 256 threads = 32 columns x 8 row lanes (rows c = lane, lane+8, ...), fixed-order combine
+// block = 256 threads = 32 columns x 8 row lanes (rows c = lane, lane+8, ...), fixed-order combine.
+// A clamped column (fp32 ss < 1e-12f) stores exactly XV_INV_NORM_FROZEN and a live one at most the float below it, so
+// loss_weight_bwd_kernel reads the liveness of TF's maximum() back from the value (v_rsq_f32 is approximate: its result
+// for an ss just above 1e-12f can reach or pass rsqrt(1e-12f), hence the min)
+#define XV_INV_NORM_FROZEN 1.0e6f              // rsqrt(1e-12f), correctly rounded
+#define XV_INV_NORM_LIVE_MAX 999999.9375f      // one ulp below
 __global__ __launch_bounds__(256) void col_inv_norm_kernel(const float* __restrict__ w, int C, int N, int normalize,
                                                            float* __restrict__ inv) {
     XV_EW_FILLER();
@@ -48,7 +53,7 @@ __global__ __launch_bounds__(256) void col_inv_norm_kernel(const float* __restri
     ss = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) ss += red[k][cx];
-    inv[n] = rsqrtf(fmaxf(ss, 1e-12f));
+    inv[n] = ss >= 1e-12f ? fminf(rsqrtf(ss), XV_INV_NORM_LIVE_MAX) : XV_INV_NORM_FROZEN;
 }
 
 // wn[c][ldn] = w[c][n]*inv[n] (pad columns zero), wnt[n][C] = wn^T through a 32x32 LDS tile
@@ -273,15 +278,26 @@ __global__ void mean_kernel(const float* __restrict__ v, int n, float* __restric
     if (threadIdx.x == 0) *out = s / (float)n;
 }
 
+// The form of margin_softmax_rows_kernel a launch runs: RQ = 8 / 16 (the row in registers) when ldl % 4 == 0, both row bases are
+// 16-byte aligned and ldl <= 256 * 4 * RQ; RQ = 0 (three passes) otherwise
+static int softmax_rows_form(int ldl, uintptr_t logits, uintptr_t dlogits) {
+    if (ldl % 4 != 0 || logits % 16 != 0 || dlogits % 16 != 0) return 0;
+    const int nq = ldl / 4;
+    return nq <= 256 * 8 ? 8 : nq <= 256 * 16 ? 16 : 0;
+}
+
+extern "C" int xv_debug_softmax_rows_form(int ldl, uintptr_t logits, uintptr_t dlogits) {
+    return softmax_rows_form(ldl, logits, dlogits);
+}
+
 static void launch_margin_softmax_rows(hipStream_t s, int kind, const float* logits, int rows, int n, int ldl, const float* x, int c,
                                        const int32_t* labels, float m, float lambda, float* dlogits, float* dnorm, float* row_loss, float* xnorm,
                                        uint32_t* ticket, float* loss_out) {
-    const bool vec = ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)dlogits % 16) == 0;
-    const int nq = ldl / 4;
+    const int form = softmax_rows_form(ldl, (uintptr_t)logits, (uintptr_t)dlogits);
 #define XV_MSR_LAUNCH(RQ) hipLaunchKernelGGL(margin_softmax_rows_kernel<RQ>, dim3(rows), dim3(256), 0, s, kind, logits, rows, n, (long)ldl, x, c, \
                                              (const int*)labels, m, lambda, dlogits, dnorm, row_loss, xnorm, (unsigned*)ticket, loss_out)
-    if (vec && nq <= 256 * 8) XV_MSR_LAUNCH(8);
-    else if (vec && nq <= 256 * 16) XV_MSR_LAUNCH(16);
+    if (form == 8) XV_MSR_LAUNCH(8);
+    else if (form == 16) XV_MSR_LAUNCH(16);
     else XV_MSR_LAUNCH(0);
 #undef XV_MSR_LAUNCH
 }
@@ -363,7 +379,7 @@ __global__ void loss_weight_bwd_kernel(const float* __restrict__ dwn, long lddwn
         float g = dwn[(long)c * lddwn + n];
         if (normalize) {
             // ss < eps columns are frozen by the maximum() of l2_normalize: only the scale term survives
-            float ss_live = inv[n] < 0.99e6f ? 1.f : 0.f;   // inv == rsqrt(1e-12) ~ 1e6 when clamped
+            float ss_live = inv[n] != XV_INV_NORM_FROZEN ? 1.f : 0.f;   // col_inv_norm_kernel: exactly XV_INV_NORM_FROZEN when clamped
             g = inv[n] * (g - ss_live * wn[(long)c * ldn + n] * dot[n]);
         }
         dw[i] = g + l2 * w[i];
