@@ -365,7 +365,8 @@ int xv_momentum_update(void* stream, float* p, const float* g, float* acc, size_
                        float lr, float momentum, int nesterov, float grad_scale);
 int xv_adam_update(void* stream, float* p, const float* g, float* m, float* v, size_t count,
                    float lr, float beta1, float beta2, float eps, int t, float grad_scale);
-/* sum of squares of a flat range accumulated into *out (for tf.clip_by_global_norm). */
+/* sum of squares of a flat range accumulated into *out (for tf.clip_by_global_norm): per-block partials added in index order, so the same
+ * input gives the same bits on every call (no float atomics); xv_l2_reg_loss likewise. */
 int xv_sumsq(void* stream, const float* g, size_t count, float* out_accum);
 
 /* ---------------------------------------------------------------------------------
@@ -494,6 +495,9 @@ int xv_engine_apply(xv_engine* e, void* stream, float lr, float grad_scale, int 
 size_t xv_engine_arena_bytes(const xv_engine* e);
 /* scalars of the last step, device pointers to 1 float each: raw loss, regularisation loss */
 int xv_engine_loss_ptrs(xv_engine* e, float** raw_loss, float** reg_loss);
+/* Diagnostics: device pointer to 1 float, the sum of squares over the gradient buffer [0, trainable count) as the last xv_engine_apply
+ * with clip_gradient_norm > 0 took it - before grad_scale: that update's global norm is sqrtf(*sumsq) * grad_scale.  Read-only. */
+int xv_debug_engine_clip_sumsq(xv_engine* e, float** sumsq);
 /* endpoint by reference name ("tdnn1_conv", ..., "pooling", "tdnn6_dense", "output", "logits"):
  * device pointer, rows, cols, leading dimension of the most recent forward. */
 int xv_engine_endpoint(xv_engine* e, const char* name, float** ptr, int32_t* rows, int32_t* cols, int32_t* ld);

@@ -56,6 +56,8 @@ def _make(kw, B, T, N=37, P=1500, seed=0, max_batch=None, max_frames=None, D=30,
     cfg_o = O.Config(feat_dim=D, num_speakers=N, num_nodes_pooling_layer=P, num_nodes_last_layer=L, **kw)
     ekw = dict(kw)
     ekw.pop("loss_func", None)
+    if not ekw.pop("clip_gradient", False):       # the engine clips when its bound is positive (model/tdnn.py::engine_config)
+        ekw.pop("clip_gradient_norm", None)
     c = E.make_config(D, N, loss_func=kw.get("loss_func", "softmax"), num_nodes_pooling_layer=P, num_nodes_last_layer=L,
                       max_batch=max_batch or B, max_frames=max_frames or T, **ekw)
     eng = E.Engine(engine_cfg if engine_cfg is not None else c)       # engine_cfg: built by the product's own Params mapping
@@ -127,9 +129,13 @@ def gpu_relu_pattern(eng, fwd, max_flip_fraction=1e-4, cfg_o=None):
     return ep_gpu
 
 
-def oracle_backward_and_update(V, cfg_o, fwd, ep_for_backward, labels, lr, step, opt_state):
+def oracle_backward_and_update(V, cfg_o, fwd, ep_for_backward, labels, lr, step, opt_state, grad_scale=1.0, frozen=()):
     """Loss, every gradient (incl. the regulariser) and the optimiser step of the oracle, with the ReLU masks of
-    `ep_for_backward` (same code path as O.train_step)."""
+    `ep_for_backward` (same code path as O.train_step, its clip-by-global-norm branch included).
+    grad_scale: the gradients are multiplied by it before clipping (1 / world size in a data-parallel step); frozen: trainable
+    variables outside the optimiser's var_list (trainer.py:379-403) - not in the global norm, neither they nor their slots move.
+    info["grads"] are the gradients as the backward pass leaves them, info["applied_grads"] what the optimiser saw,
+    info["global_norm"] the norm the clip took (None without clipping)."""
     ep, caches, bn_new = fwd["ep"], fwd["caches"], fwd["bn_new"]
     raw_loss, logits, dfeat, Gl = O.loss_forward_backward(V, cfg_o, fwd["feats"], labels, step)
     reg, Gr = O.regularization(V, cfg_o)
@@ -141,11 +147,20 @@ def oracle_backward_and_update(V, cfg_o, fwd, ep_for_backward, labels, lr, step,
     ep["logits"] = logits
     newV, new_state = {}, {}
     t = opt_state.get("__t__", 0) + 1
+    applied = {k: g * grad_scale for k, g in G.items() if k not in frozen}
+    global_norm = None
+    if cfg_o.clip_gradient:
+        applied, global_norm = O.clip_by_global_norm(applied, cfg_o.clip_gradient_norm)
     for name, p in V.items():
         if not O.is_trainable(name):
             newV[name] = bn_new.get(name, p)
             continue
-        g = G[name].reshape(p.shape)
+        if name in frozen:
+            newV[name] = p
+            if name in opt_state:
+                new_state[name] = opt_state[name]
+            continue
+        g = applied[name].reshape(p.shape)
         if cfg_o.optimizer == "sgd":
             newV[name] = O.sgd_update(p, g, lr)
         elif cfg_o.optimizer == "momentum":
@@ -156,11 +171,11 @@ def oracle_backward_and_update(V, cfg_o, fwd, ep_for_backward, labels, lr, step,
             pn, m, v = O.adam_update(p, g, m, v, t, lr)
             newV[name], new_state[name] = pn, (m, v)
     new_state["__t__"] = t
-    info = {"raw_loss": raw_loss, "reg_loss": reg, "grads": G, "endpoints": ep}
+    info = {"raw_loss": raw_loss, "reg_loss": reg, "grads": G, "endpoints": ep, "applied_grads": applied, "global_norm": global_norm}
     return newV, new_state, info
 
 
-def oracle_step_with_gpu_relu_pattern(eng, V, cfg_o, x, labels, lr, step, opt_state, fwd=None):
+def oracle_step_with_gpu_relu_pattern(eng, V, cfg_o, x, labels, lr, step, opt_state, fwd=None, **update_kw):
     """Oracle train step whose ReLU on/off pattern is taken from the GPU forward.
 
     ReLU makes the gradient a discontinuous function of the forward values: a pre-activation
@@ -171,7 +186,7 @@ def oracle_step_with_gpu_relu_pattern(eng, V, cfg_o, x, labels, lr, step, opt_st
     fewer than 1e-4 of the positions, then (2) checks all gradients at 1e-4 against the oracle
     evaluated on the GPU's pattern."""
     fwd = fwd if fwd is not None else oracle_forward(V, cfg_o, x)
-    return oracle_backward_and_update(V, cfg_o, fwd, gpu_relu_pattern(eng, fwd, cfg_o=cfg_o), labels, lr, step, opt_state)
+    return oracle_backward_and_update(V, cfg_o, fwd, gpu_relu_pattern(eng, fwd, cfg_o=cfg_o), labels, lr, step, opt_state, **update_kw)
 
 
 @pytest.mark.parametrize("kw", CASES, ids=lambda d: "-".join(str(v).replace(" ", "") for v in d.values()))
@@ -303,10 +318,10 @@ def test_every_shipped_switch_combination_steps_like_the_oracle(combo, tmp_path)
     f.write_text(json.dumps(d))
     params = Params(str(f))
     B, T, N, D = 4, 24, 13, 30
-    if d.get("clip_gradient", False):
-        pytest.skip("clip_gradient is false in every shipped config; covered by test_gpu_ops")
     cfg = engine_config(params, D, N, d["loss_func"], B, T)
     kw = _oracle_kw_from_params(params.dict)
+    if d.get("clip_gradient", False):         # false in every shipped config; tests/test_gpu_update_stage.py runs the clipped branches
+        kw.update(clip_gradient=True, clip_gradient_norm=float(d["clip_gradient_norm"]))
     _check_train_step(kw, B, T, N=N, P=params.dict["num_nodes_pooling_layer"], D=D, L=params.dict["num_nodes_last_layer"], engine_cfg=cfg)
 
 
@@ -383,7 +398,7 @@ def compare_step_with_oracle(eng, cfg_o, newV, info, lr, endpoint_tol=5e-5, grad
         # (tiny batches have gradients that are large against the weights)
         slack = 0.0
         if cfg_o.optimizer in ("sgd", "momentum") and name in info["grads"]:      # first momentum step: lr*g, lr*(1+m)*g with nesterov
-            slack = lr * (1.0 + (cfg_o.momentum if cfg_o.optimizer == "momentum" else 0.0)) * grad_tol * np.abs(info["grads"][name]).max()
+            slack = lr * (1.0 + (cfg_o.momentum if cfg_o.optimizer == "momentum" else 0.0)) * grad_tol * np.abs(info["applied_grads"][name]).max()
         if report is not None:
             report["var:" + name] = diff.max() / denom
         assert diff.max() <= var_tol * denom + slack, (name, diff.max() / denom)

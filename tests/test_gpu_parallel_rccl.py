@@ -78,7 +78,8 @@ rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 torch.cuda.set_device(0)                       # both ranks share the one GPU of the box; RCCL refuses that, gloo stages through the host
 dist.init_process_group("gloo", rank=rank, world_size=world)
 B, T, N, D, lr, steps = 8, 60, 29, 30, 0.05, 2
-kw = dict(loss_func="additive_margin_softmax", margin_m=0.2, last_layer_linear=True, max_batch=B, max_frames=T)
+clip = float(sys.argv[2]) if len(sys.argv) > 2 else 0.0       # clip_gradient_norm (0: no clipping)
+kw = dict(loss_func="additive_margin_softmax", margin_m=0.2, last_layer_linear=True, max_batch=B, max_frames=T, clip_gradient_norm=clip)
 def batch(r, step):
     rs = np.random.RandomState(100 * r + step)
     return rs.randn(B, T, D).astype(np.float32), rs.randint(0, N, B).astype(np.int32)
@@ -95,6 +96,8 @@ mine = eng.variables[:eng.n_train].cpu().numpy().copy()
 gathered = [torch.zeros(eng.n_train) for _ in range(world)]
 dist.all_gather(gathered, torch.from_numpy(mine))
 res = {"rank": rank, "replicas_identical": bool(all(np.array_equal(g.numpy(), mine) for g in gathered))}
+if clip > 0:
+    res["clip_norm"] = float(np.sqrt(eng.clip_sumsq())) / world      # the last step's global norm of the averaged gradient
 if rank == 0:
     # reference on one engine: per step, the gradients of both ranks' batches from the same weights, summed, update with 1/world.
     # BN moving statistics are per rank by design, so they follow rank 0's batch only.
@@ -138,6 +141,26 @@ def test_two_ranks_sharing_the_gpu_average_gradients_like_one_engine(tmp_path):
     assert len(lines) == 2 and all(l["replicas_identical"] for l in lines), lines
     r0 = [l for l in lines if l["rank"] == 0][0]
     assert r0["moved"] > 1e-4 and r0["max_diff_vs_single_engine"] == 0.0, r0
+
+
+def test_two_ranks_sharing_the_gpu_stay_bit_identical_with_clipping(tmp_path):
+    """The same two-rank run with clip_gradient_norm far below the norm of the averaged gradient: every rank takes its own sum of
+    squares of the all-reduced buffer and scales by clip / max(sqrt(sumsq) / world, clip), so the replicas stay bit-identical only if
+    that sum is the same bits on every rank - and equal to the single engine that applies the summed gradients with 1 / world."""
+    clip = 0.05
+    script = tmp_path / "worker2.py"
+    script.write_text(TWO_RANK_WORKER % ROOT)
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(29700 + os.getpid() % 200), str(script), str(tmp_path), str(clip)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [json.load(open(tmp_path / ("rank%d.json" % r))) for r in range(2)]
+    assert all(l["clip_norm"] > 4 * clip for l in lines), lines                     # the scaled branch
+    assert lines[0]["clip_norm"] == lines[1]["clip_norm"], lines
+    assert len(lines) == 2 and all(l["replicas_identical"] for l in lines), lines
+    r0 = [l for l in lines if l["rank"] == 0][0]
+    assert r0["moved"] > 1e-5 and r0["max_diff_vs_single_engine"] == 0.0, r0
 
 
 def test_bench_two_ranks_sharing_the_gpu():

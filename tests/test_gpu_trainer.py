@@ -347,13 +347,19 @@ def test_finetune_driver_with_two_ranks_sharing_the_gpu(tmp_path, xv_precision):
     assert not np.array_equal(ft["softmax/output/kernel"], ck["softmax/output/kernel"])
 
 
-@pytest.mark.parametrize("optimizer", ["momentum", "adam"])
+@pytest.mark.parametrize("optimizer", ["momentum", "adam", "momentum_clipped", "adam_clipped"])
 def test_resume_from_checkpoint_is_bit_identical(tmp_path, optimizer):
     """Four optimiser steps in one go == two steps, save, a fresh Trainer that loads the checkpoint, two more steps: variables,
-    BN moving statistics, optimiser slots and (for Adam) the update count all travel through the checkpoint."""
+    BN moving statistics, optimiser slots and (for Adam) the update count all travel through the checkpoint.
+    *_clipped: with clip_gradient on and a bound far below the gradient norm, so every update goes through the sum of squares and
+    the clip scale."""
     from tf_kaldi_speaker_amd.misc.utils import Params
     from tf_kaldi_speaker_amd.model.trainer import Trainer
+    clipped = optimizer.endswith("_clipped")
+    optimizer = optimizer.replace("_clipped", "")
     cfg = dict(CONFIG, optimizer=optimizer, momentum=0.9, use_nesterov=(optimizer == "momentum"))
+    if clipped:
+        cfg.update(clip_gradient=True, clip_gradient_norm=0.01)
     cfg_path = tmp_path / "config.json"
     cfg_path.write_text(json.dumps(cfg))
     rs = np.random.RandomState(4)
@@ -366,7 +372,10 @@ def test_resume_from_checkpoint_is_bit_identical(tmp_path, optimizer):
         return tr
 
     a = trainer(str(tmp_path / "a"))
+    assert (a.engine.config.clip_gradient_norm > 0) == clipped
     assert a.train_batches(iter(batches), 0.02, 0, num_steps=4) == 4
+    if clipped:
+        assert np.sqrt(a.engine.clip_sumsq()) > 10 * 0.01         # the bound was in force in the last step
     want = a.engine.variables.cpu().numpy().copy()
     want_opt = a.engine.opt_state.cpu().numpy().copy()
     v_init = None

@@ -291,3 +291,159 @@ def test_bn_moving_average_switch():
     _, mvu = O.batchnorm_moving_update(np.zeros(3), np.ones(3), mean, var, 10, 0.99, True)
     assert np.allclose(mvu, 0.99 + 0.01 * z.var(axis=0, ddof=1))
     assert np.allclose(mm, 0.01 * z.mean(axis=0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The update stage: clip-by-global-norm and the optimiser recurrences (ground truth of tests/test_gpu_update_stage.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _toy_grads(seed=0):
+    rs = np.random.RandomState(seed)
+    return {"a/kernel": rs.randn(7, 5), "a/bias": rs.randn(5), "b/kernel": 10.0 * rs.randn(3, 4, 2), "r": rs.randn(1)}
+
+
+def _global_norm(G):
+    return np.sqrt(sum((np.asarray(g, np.float64) ** 2).sum() for g in G.values()))
+
+
+def test_clip_by_global_norm_below_the_bound_is_the_identity():
+    G = _toy_grads()
+    gn = _global_norm(G)
+    for bound in (gn * (1 + 1e-12), 2 * gn, 1e9):
+        C, got = O.clip_by_global_norm(G, bound)
+        assert got == pytest.approx(gn, rel=1e-14)
+        assert set(C) == set(G)
+        for k in G:
+            assert C[k].dtype == G[k].dtype and np.array_equal(C[k], G[k]), (bound, k)       # g * 1.0: bit for bit
+    G32 = {k: g.astype(np.float32) for k, g in G.items()}
+    C32, _ = O.clip_by_global_norm(G32, 1e9)
+    for k in G32:
+        assert C32[k].dtype == np.float32 and np.array_equal(C32[k], G32[k]), k
+
+
+def test_clip_by_global_norm_above_the_bound_has_the_bound_as_its_norm():
+    G = _toy_grads(1)
+    gn = _global_norm(G)
+    for ratio in (0.5, 0.05, 1e-6):
+        C, got = O.clip_by_global_norm(G, ratio * gn)
+        assert got == pytest.approx(gn, rel=1e-14)
+        assert _global_norm(C) == pytest.approx(ratio * gn, rel=1e-13)
+        for k in G:                                               # one common factor: the direction is kept
+            assert np.allclose(C[k], G[k] * ratio, rtol=1e-13, atol=0), k
+
+
+def test_clip_scale_is_tf_clip_by_global_norm_not_torch_clip_grad_norm():
+    """tf.clip_by_global_norm (reference model/trainer.py:408-410) scales by clip_norm / max(global_norm, clip_norm);
+    torch.nn.utils.clip_grad_norm_ scales by min(1, clip_norm / (global_norm + 1e-6)).  A tiny gradient with a tinier bound separates
+    them: there the 1e-6 of torch's denominator is as large as the norm itself."""
+    G = {"w": np.array([3e-6, 4e-6])}                                                    # norm 5e-6
+    C, gn = O.clip_by_global_norm(G, 1e-6)
+    assert gn == pytest.approx(5e-6, rel=1e-12)
+    assert np.allclose(C["w"], G["w"] * (1e-6 / 5e-6), rtol=1e-13, atol=0)               # clip / max(norm, clip)
+    p = torch.nn.Parameter(torch.zeros(2, dtype=torch.float64))
+    p.grad = torch.tensor(G["w"])
+    torch.nn.utils.clip_grad_norm_([p], 1e-6)
+    torch_scaled = p.grad.numpy()
+    assert np.allclose(torch_scaled, G["w"] * (1e-6 / (5e-6 + 1e-6)), rtol=1e-9, atol=0)   # what torch does ...
+    assert np.abs(C["w"] - torch_scaled).max() > 0.1 * np.abs(C["w"]).max()              # ... is not what the oracle does
+    # at ordinary magnitudes the two agree to ~1e-6 / norm, so torch pins the common part of the formula
+    G = _toy_grads(2)
+    ps = [torch.nn.Parameter(torch.zeros(g.shape, dtype=torch.float64)) for g in G.values()]
+    for q, g in zip(ps, G.values()):
+        q.grad = torch.tensor(g)
+    C, gn = O.clip_by_global_norm(G, 0.25 * _global_norm(G))
+    total = torch.nn.utils.clip_grad_norm_(ps, 0.25 * _global_norm(G))
+    assert float(total) == pytest.approx(gn, rel=1e-13)
+    for q, k in zip(ps, G):
+        assert np.allclose(q.grad.numpy(), C[k], rtol=2e-6 / gn + 1e-12, atol=0), k
+
+
+@pytest.mark.parametrize("opt", [dict(optimizer="sgd"), dict(optimizer="momentum", momentum=0.9), dict(optimizer="momentum", momentum=0.9, use_nesterov=True),
+                                 dict(optimizer="adam")], ids=["sgd", "momentum", "nesterov", "adam"])
+def test_train_step_with_clipping_is_the_unclipped_step_on_prescaled_gradients(opt):
+    kw = dict(feat_dim=6, num_speakers=11, num_nodes_pooling_layer=20, num_nodes_last_layer=16, loss_func="additive_margin_softmax", margin_m=0.2,
+              last_layer_linear=True, aux_loss_func=("ring_loss",), ring_loss_init=3.0, ring_loss_lambda=0.05, **opt)
+    cfg = O.Config(**kw)
+    V = O.init_variables(cfg, seed=3, dtype=np.float64)
+    rs = np.random.RandomState(7)
+    x, labels = rs.randn(5, 22, 6), rs.randint(0, 11, 5)
+    state = {}
+    if opt["optimizer"] == "momentum":
+        state = {k: 0.01 * rs.randn(*v.shape) for k, v in V.items() if O.is_trainable(k)}
+    elif opt["optimizer"] == "adam":
+        state = {k: (0.01 * rs.randn(*v.shape), 1e-4 * rs.rand(*v.shape)) for k, v in V.items() if O.is_trainable(k)}
+        state["__t__"] = 4
+    lr = 0.05
+    _, _, plain = O.train_step(V, state, cfg, x, labels, lr, 100)
+    assert plain["global_norm"] is None
+    G = plain["grads"]
+    assert set(G) == {k for k in V if O.is_trainable(k)}                     # the norm runs over exactly the trainable set
+    gn = _global_norm(G)
+    for ratio in (2.0, 0.3):
+        cfg_c = O.Config(clip_gradient=True, clip_gradient_norm=ratio * gn, **kw)
+        newV, new_state, info = O.train_step(V, state, cfg_c, x, labels, lr, 100)
+        assert info["global_norm"] == pytest.approx(gn, rel=1e-13)
+        k = min(1.0, ratio)
+        t = state.get("__t__", 0) + 1
+        for name, p in V.items():
+            if not O.is_trainable(name):
+                continue
+            g = (G[name] * (ratio * gn / max(gn, ratio * gn))).reshape(p.shape)
+            assert np.allclose(info["grads"][name].reshape(p.shape), G[name].reshape(p.shape) * k, rtol=1e-13, atol=0), name
+            if opt["optimizer"] == "sgd":
+                want = O.sgd_update(p, g, lr)
+            elif opt["optimizer"] == "momentum":
+                want, acc = O.momentum_update(p, g, state[name], lr, 0.9, bool(opt.get("use_nesterov")))
+                assert np.array_equal(new_state[name], acc), name
+            else:
+                want, m, v = O.adam_update(p, g, state[name][0], state[name][1], t, lr)
+                assert np.array_equal(new_state[name][0], m) and np.array_equal(new_state[name][1], v), name
+            assert np.array_equal(newV[name], want), name
+        if ratio < 1 and opt["optimizer"] == "sgd":
+            moved = _global_norm({n: newV[n] - V[n] for n in G})
+            assert moved == pytest.approx(lr * ratio * gn, rel=1e-12)         # an SGD step of length lr * bound
+
+
+def test_nesterov_momentum_matches_torch_over_several_steps():
+    """tf.train.MomentumOptimizer(use_nesterov=True): acc = m*acc + g; p -= lr*(g + m*acc) - torch.optim.SGD(nesterov=True, dampening=0)
+    with a constant learning rate, float64, a fresh gradient every step and two momenta."""
+    rs = np.random.RandomState(5)
+    for mom in (0.9, 0.5):
+        p0 = rs.randn(64)
+        p = torch.nn.Parameter(torch.tensor(p0))
+        opt = torch.optim.SGD([p], lr=0.1, momentum=mom, nesterov=True)
+        pn, acc = p0.copy(), np.zeros(64)
+        for _ in range(7):
+            g = rs.randn(64)
+            p.grad = torch.tensor(g)
+            opt.step()
+            pn, acc = O.momentum_update(pn, g, acc, 0.1, mom, True)
+            assert np.allclose(pn, p.detach().numpy(), rtol=1e-12, atol=1e-12)
+            assert np.allclose(acc, opt.state[p]["momentum_buffer"].numpy(), rtol=1e-12, atol=1e-12)
+
+
+def test_adam_matches_the_tf_recurrence_over_several_steps():
+    """tf.train.AdamOptimizer: m, v plain moving averages; p -= lr * sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps) - epsilon OUTSIDE
+    the bias-corrected square root ("epsilon hat").  torch.optim.Adam divides by sqrt(v / (1 - b2^t)) + eps instead and is not a reference:
+    the two differ where sqrt(v) is not far above eps, which the 1e-9 gradients below make visible."""
+    rs = np.random.RandomState(6)
+    n, lr, b1, b2, eps = 48, 0.01, 0.9, 0.999, 1e-8
+    p0 = rs.randn(n)
+    scale = np.where(np.arange(n) % 3 == 0, 1e-9, 1.0)
+    pn, m, v = p0.copy(), np.zeros(n), np.zeros(n)
+    pr, mr, vr = p0.copy(), np.zeros(n), np.zeros(n)
+    pt = torch.nn.Parameter(torch.tensor(p0))
+    topt = torch.optim.Adam([pt], lr=lr, betas=(b1, b2), eps=eps)
+    for t in range(1, 13):
+        g = rs.randn(n) * scale
+        pn, m, v = O.adam_update(pn, g, m, v, t, lr)
+        for i in range(n):                                                    # the recurrence, element by element
+            mr[i] = b1 * mr[i] + (1.0 - b1) * g[i]
+            vr[i] = b2 * vr[i] + (1.0 - b2) * g[i] * g[i]
+            pr[i] = pr[i] - lr * (1.0 - b2 ** t) ** 0.5 / (1.0 - b1 ** t) * mr[i] / (vr[i] ** 0.5 + eps)
+        assert np.allclose(m, mr, rtol=1e-13, atol=0) and np.allclose(v, vr, rtol=1e-13, atol=0), t
+        assert np.allclose(pn, pr, rtol=1e-13, atol=1e-15), t
+        pt.grad = torch.tensor(g)
+        topt.step()
+    small = scale < 1.0
+    assert np.abs(pn[small] - pt.detach().numpy()[small]).max() > 1e-3 * lr       # torch's placement of epsilon is another update
+    assert np.allclose(pn[~small], pt.detach().numpy()[~small], rtol=0, atol=1e-6 * lr * 12)     # ... that coincides where sqrt(v) >> eps

@@ -203,6 +203,9 @@ int xv_tn_splits(int M, int N, int R);
 int xv_tn_splits_direct(int M, int N, int R);
 int xv_nt_shares(int tiles, int ksteps, bool stats, bool beside_wgrad, size_t ws_bytes);      // NT: shares per remaining tile of the "whole tiles + shares" schedule (0: not used)
 int xv_launch_gemm_tn(hipStream_t s, const XvGemmTN& g);
+// *out += scale * sum(w[0 .. count)^2) by a fixed-order two-stage reduction (xv_elementwise.hip); part: XV_SUMSQ_PARTS floats of scratch
+#define XV_SUMSQ_PARTS 512
+int xv_sumsq_ordered(hipStream_t s, const float* w, size_t count, float scale, float* out, float* part);
 int xv_launch_wgrad_reduce(hipStream_t s, const float* P, int splits, int k, int C, int c_pad, int n_in, int n_out, const float* w,
                            long ldw, float l2, float* out, long ldo);
 

@@ -1964,7 +1964,11 @@ extern "C" int xv_l2_scaling_backward(void* stream, const float* x, const float*
 // ------------------------------------------------------------------------------------
 // scalar reductions (reporting / clip-by-global-norm only) and optimisers
 // ------------------------------------------------------------------------------------
-__global__ void sumsq_kernel(const float* __restrict__ w, size_t count, float scale, float* __restrict__ out) {
+// Fixed-order sum of squares: every block leaves its partial in part[blockIdx.x], then one block adds the partials in index order
+// (as colsum_partial_kernel / colsum_final_kernel do).  The result is the same bits on every run and on every rank: with
+// clip_gradient_norm > 0 the clip scale is a function of it, and replicas, a resumed run and a replayed step must not drift apart
+// over the arrival order of float atomics.
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ w, size_t count, float* __restrict__ part) {
     XV_EW_PRIORITY();
     __shared__ float red[4];
     float s = 0.f;
@@ -1972,19 +1976,42 @@ __global__ void sumsq_kernel(const float* __restrict__ w, size_t count, float sc
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, scale * ((red[0] + red[1]) + (red[2] + red[3])));
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restrict__ part, int nparts, float scale, float* __restrict__ out) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *out += scale * ((red[0] + red[1]) + (red[2] + red[3]));
+}
+// *out += scale * sum(w^2); part: XV_SUMSQ_PARTS floats of scratch owned by the caller's stream
+int xv_sumsq_ordered(hipStream_t s, const float* w, size_t count, float scale, float* out, float* part) {
+    XV_REQUIRE(count > 0 && w && out && part, "sumsq: bad arguments");
+    const int nb = grid_for((long)count, 256, XV_SUMSQ_PARTS);
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, s, w, count, part);
+    XV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, (const float*)part, nb, scale, out);
+    XV_LAUNCH_CHECK();
+    return 0;
+}
+// the C-ABI forms own no workspace: a stream-ordered allocation carries the partials
+static int sumsq_with_scratch(hipStream_t s, const float* w, size_t count, float scale, float* out) {
+    float* part = nullptr;
+    XV_CHECK_HIP(hipMallocAsync((void**)&part, XV_SUMSQ_PARTS * sizeof(float), s));
+    const int rc = xv_sumsq_ordered(s, w, count, scale, out, part);
+    XV_CHECK_HIP(hipFreeAsync(part, s));
+    return rc;
 }
 extern "C" int xv_l2_reg_loss(void* stream, const float* w, size_t count, float scale, float* out_accum) {
     XV_REQUIRE(count > 0, "l2_reg_loss: empty");
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for((long)count, 256, 512)), dim3(256), 0, (hipStream_t)stream, w, count, 0.5f * scale, out_accum);
-    XV_LAUNCH_CHECK();
-    return 0;
+    return sumsq_with_scratch((hipStream_t)stream, w, count, 0.5f * scale, out_accum);
 }
 extern "C" int xv_sumsq(void* stream, const float* g, size_t count, float* out_accum) {
     XV_REQUIRE(count > 0, "sumsq: empty");
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for((long)count, 256, 512)), dim3(256), 0, (hipStream_t)stream, g, count, 1.0f, out_accum);
-    XV_LAUNCH_CHECK();
-    return 0;
+    return sumsq_with_scratch((hipStream_t)stream, g, count, 1.0f, out_accum);
 }
 
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, size_t count, float lr, float gs) {

@@ -1092,12 +1092,12 @@ static int compute_reg_loss(xv_engine* e, hipStream_t s) {
     const xv_config& c = e->cfg;
     XV_CHECK_HIP(hipMemsetAsync(e->scalars + 1, 0, sizeof(float), s));
     for (int i = 0; i < e->NL; ++i) {
-        int rc = xv_l2_reg_loss(s, vptr(e, e->L[i].v_kernel), e->vars[e->L[i].v_kernel].count, c.weight_l2_regularizer, e->scalars + 1);
+        int rc = xv_sumsq_ordered(s, vptr(e, e->L[i].v_kernel), e->vars[e->L[i].v_kernel].count, 0.5f * c.weight_l2_regularizer, e->scalars + 1, (float*)e->ws);
         if (rc) return rc;
     }
     if (e->N > 0) {
         float ol2 = c.output_weight_l2_regularizer >= 0.f ? c.output_weight_l2_regularizer : c.weight_l2_regularizer;
-        int rc = xv_l2_reg_loss(s, vptr(e, e->v_loss_kernel), e->vars[e->v_loss_kernel].count, ol2, e->scalars + 1);
+        int rc = xv_sumsq_ordered(s, vptr(e, e->v_loss_kernel), e->vars[e->v_loss_kernel].count, 0.5f * ol2, e->scalars + 1, (float*)e->ws);
         if (rc) return rc;
     }
     e->reg_valid = true;
@@ -1702,7 +1702,8 @@ extern "C" int xv_engine_apply(xv_engine* e, void* stream, float lr, float grad_
     }
     if (c.clip_gradient_norm > 0.f) {
         XV_CHECK_HIP(hipMemsetAsync(e->scalars + 2, 0, sizeof(float), s));
-        int rc = xv_sumsq(s, e->G, e->n_train, e->scalars + 2);
+        XV_REQUIRE(e->ws_bytes >= XV_SUMSQ_PARTS * sizeof(float), "engine_apply: workspace too small for the gradient norm");
+        int rc = xv_sumsq_ordered(s, e->G, e->n_train, 1.0f, e->scalars + 2, (float*)e->ws);      // fixed order: the same bits on every rank and run
         if (rc) return rc;
         hipLaunchKernelGGL(clip_scale_kernel, dim3(2048), dim3(256), 0, s, e->G, e->n_train, (const float*)(e->scalars + 2), grad_scale,
                            c.clip_gradient_norm);
@@ -1726,6 +1727,12 @@ extern "C" int xv_engine_loss_ptrs(xv_engine* e, float** raw_loss, float** reg_l
     }
     if (raw_loss) *raw_loss = e->scalars + 0;
     if (reg_loss) *reg_loss = e->scalars + 1;
+    return 0;
+}
+
+extern "C" int xv_debug_engine_clip_sumsq(xv_engine* e, float** sumsq) {
+    XV_REQUIRE(e && e->scalars && sumsq, "debug_engine_clip_sumsq: engine not created");
+    *sumsq = e->scalars + 2;
     return 0;
 }
 

@@ -332,6 +332,15 @@ class Engine(object):
         _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), 1, raw, 1, 1, 1), "xv_copy_2d")
         return float(out.cpu().numpy()[0])
 
+    def clip_sumsq(self):
+        """Sum of squares of the flat gradient buffer as the last clipped apply() took it, before grad_scale (diagnostics: the
+        global norm of that update is sqrt(clip_sumsq()) * grad_scale) - synchronises."""
+        p = C.c_void_p()
+        _lib.check(self.lib.xv_debug_engine_clip_sumsq(self.h, C.byref(p)), "xv_debug_engine_clip_sumsq")
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), 1, p, 1, 1, 1), "xv_copy_2d")
+        return float(out.cpu().numpy()[0])
+
     def endpoint(self, name):
         """Copy of an endpoint of the most recent forward as a torch tensor [rows, cols]."""
         p = C.c_void_p()
