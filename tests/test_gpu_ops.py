@@ -148,10 +148,12 @@ def test_bn_relu_backward(ops, relu, pad):
     assert_close(host(db), db_ref, 2e-5, 1e-4, "dbeta")
 
 
+@pytest.mark.parametrize("pad", [0, 4])
 @pytest.mark.parametrize("kind", ["prelu", "lrelu"])
-def test_bn_activation_through_the_op_level_abi(ops, kind):
+def test_bn_activation_through_the_op_level_abi(ops, kind, pad):
     """network_relu_type prelu / lrelu (tdnn.py:24-30, common.py:27-42) on the OP-level entry points: the slope travels through
-    xv_set_activation (include/xvector_hip.h), as a foreign binding would pass it - not only through the engine."""
+    xv_set_activation (include/xvector_hip.h), as a foreign binding would pass it - not only through the engine.
+    pad > 0: dz in the segment-padded layout (the strip kernel instead of the dense one), pad rows zero."""
     rs = np.random.RandomState(11)
     segs, t, n = 5, 41, 512
     z = (rs.randn(segs * t, n) * 2 + 0.3).astype(np.float32)
@@ -168,10 +170,13 @@ def test_bn_activation_through_the_op_level_abi(ops, kind):
     d_dalpha = dev(np.zeros(n, np.float32)) if kind == "prelu" else None
     with ops.activation(d_alpha, d_dalpha):
         a = ops.bn_apply(dev(z), scale, shift, 1)
-        dz, dg, db = ops.bn_relu_backward(dev(da), dev(z), segs, t, dev(gamma), mean, invstd, scale, shift, 1, 0)
+        dz, dg, db = ops.bn_relu_backward(dev(da), dev(z), segs, t, dev(gamma), mean, invstd, scale, shift, 1, pad)
     assert_close(host(a), a_ref, 2e-5, 2e-4, "bn + %s" % kind)
     assert (host(a) < 0).any()                                             # the negative side is really there
-    assert_close(host(dz).reshape(-1, n), dz_ref, 2e-5, 2e-4, "bn dz (%s)" % kind)
+    dzh = host(dz).reshape(segs, t + 2 * pad, n)
+    if pad:
+        assert np.all(dzh[:, :pad] == 0) and np.all(dzh[:, pad + t:] == 0)
+    assert_close(dzh[:, pad:pad + t].reshape(-1, n), dz_ref, 2e-5, 2e-4, "bn dz (%s)" % kind)
     assert_close(host(dg), dg_ref, 2e-5, 1e-4, "dgamma")
     assert_close(host(db), db_ref, 2e-5, 1e-4, "dbeta")
     if kind == "prelu":
@@ -257,7 +262,7 @@ def test_pooling_fused_into_bn(ops, b, t, n):
     assert_close(host(db), db_ref, 2e-5, 1e-4, "pooled dbeta")
 
 
-@pytest.mark.parametrize("b,t,n", [(5, 37, 1500), (128, 186, 512), (7, 64, 96)])
+@pytest.mark.parametrize("b,t,n", [(5, 37, 1500), (128, 186, 512), (7, 64, 96), (5, 19, 96)])      # t = 19: chunks shorter than a strip, the strip kernel
 def test_pooled_bn_backward_closed_form(ops, b, t, n):
     """The closed-form reductions (xv_bn_relu_backward_pooled_aux: sum dy and sum dy*xhat per channel from the pooled statistics and
     the forward's by-product wpos, no pass over z) against the composed oracle and against the direct pass - also with chunks that
@@ -296,7 +301,7 @@ def test_pooled_bn_backward_closed_form(ops, b, t, n):
 
 
 @pytest.mark.parametrize("kind,weighted,b,t,n", [("prelu", False, 5, 37, 1500), ("lrelu", False, 3, 186, 512), ("relu", True, 4, 70, 512),
-                                                  ("prelu", True, 3, 129, 96), ("none", False, 2, 64, 512)])
+                                                  ("prelu", True, 3, 129, 96), ("none", False, 2, 64, 512), ("lrelu", False, 4, 19, 96)])
 def test_pooled_bn_backward_direct_pass(ops, kind, weighted, b, t, n):
     """The pass over z that serves the cases without a closed form (bn_bwd_reduce_pooled_kernel: prelu / lrelu slopes, attention frame
     weights, no activation; common.py:27-42, pooling.py:148-155): T below, at and above the 64-row block, T not a multiple of 4."""

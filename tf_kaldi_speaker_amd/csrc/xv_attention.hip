@@ -2,20 +2,16 @@
 //   key   = tanh?(dense(relu(bn(dense(tdnn4_relu)))))      - the two dense layers run on the frame-level GEMM kernels
 //   score = key . query / sqrt(dk)                         - att_score_kernel (one wave per frame)
 //   w     = softmax over the frames of a chunk             - softmax_segments_kernel
-//   out   = [sum_t w v, sqrt(sum_t w (v - mean)^2)]        - stat_pool_fwd_kernel with weights (xv_elementwise.hip)
+//   out   = [sum_t w v, sqrt(sum_t w (v - mean)^2)]        - stat_pool_fwd_kernel with weights (xv_pool.hip)
 // and its backward pieces.  The value tensor v = relu(bn(z5)) is evaluated on the fly from tdnn5's pre-BN output, as
 // for statistics pooling: neither v nor dv is ever written; dv enters tdnn5's BN backward through PoolGrad.w.
 #include "xv_common.h"
+#include "xv_ew.h"
 
 #include <algorithm>
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -133,11 +129,8 @@ __global__ __launch_bounds__(256) void att_pool_dw_kernel(const float* __restric
             f32x4 zz = zq[u];
             f32x4 a = zz;
             if (scale) a = zz * *(const f32x4*)(scale + c) + *(const f32x4*)(shift + c);
-            if (relu && slope) {      // prelu / leaky ReLU value tensor (act context, xv_common.h)
-                const f32x4 sl = *(const f32x4*)(slope + c);
-                a.x = a.x > 0.f ? a.x : a.x * sl.x; a.y = a.y > 0.f ? a.y : a.y * sl.y;
-                a.z = a.z > 0.f ? a.z : a.z * sl.z; a.w = a.w > 0.f ? a.w : a.w * sl.w;
-            } else if (relu) { a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f); }
+            if (relu && slope) a = act4(a, *(const f32x4*)(slope + c));      // prelu / leaky ReLU value tensor (act context, xv_common.h)
+            else if (relu) a = relu4(a);
             f32x4 mean = *(const f32x4*)(o + c), sd = *(const f32x4*)(o + n + c);
             f32x4 dm = *(const f32x4*)(g + c), dsd = *(const f32x4*)(g + n + c);
             f32x4 dv;
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(256) void att_key_bwd_kernel(const float* __restric
                 k.x = tanhf(zz.x); k.y = tanhf(zz.y); k.z = tanhf(zz.z); k.w = tanhf(zz.w);
                 dk = dk - k * k;
             } else if (act == 1) {
-                dk.x = zz.x > 0.f ? 1.f : 0.f; dk.y = zz.y > 0.f ? 1.f : 0.f; dk.z = zz.z > 0.f ? 1.f : 0.f; dk.w = zz.w > 0.f ? 1.f : 0.f;
+                dk = mask_grad4(dk, zz, f32x4{0, 0, 0, 0}, false);      // relu'(zk): the 1 set above where zk > 0, else 0
                 k = k * dk;
             }
             const float d = ds[r];

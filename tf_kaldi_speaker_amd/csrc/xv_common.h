@@ -203,7 +203,7 @@ int xv_tn_splits(int M, int N, int R);
 int xv_tn_splits_direct(int M, int N, int R);
 int xv_nt_shares(int tiles, int ksteps, bool stats, bool beside_wgrad, size_t ws_bytes);      // NT: shares per remaining tile of the "whole tiles + shares" schedule (0: not used)
 int xv_launch_gemm_tn(hipStream_t s, const XvGemmTN& g);
-// *out += scale * sum(w[0 .. count)^2) by a fixed-order two-stage reduction (xv_elementwise.hip); part: XV_SUMSQ_PARTS floats of scratch
+// *out += scale * sum(w[0 .. count)^2) by a fixed-order two-stage reduction (xv_update.hip); part: XV_SUMSQ_PARTS floats of scratch
 #define XV_SUMSQ_PARTS 512
 int xv_sumsq_ordered(hipStream_t s, const float* w, size_t count, float scale, float* out, float* part);
 int xv_launch_wgrad_reduce(hipStream_t s, const float* P, int splits, int k, int C, int c_pad, int n_in, int n_out, const float* w,
@@ -234,7 +234,7 @@ struct XvGemm16TN {
 int xv_tn16_splits(int M, int N, int R);
 int xv_launch_gemm16_tn(hipStream_t s, const XvGemm16TN& g);
 
-// All kernel-layout weight copies of one optimiser step in two launches (xv_elementwise.hip): the per-layer
+// All kernel-layout weight copies of one optimiser step in two launches (xv_prep.hip): the per-layer
 // prep / amax / split launches (~25 of 5 us each) were 5 % of a step.
 enum { XV_PREP_T32 = 0,     // wt[o][j*c_pad + c] = w[(j*C + c)*O + o]                (fp32, forward layout)
        XV_PREP_F32 = 1,     // wf[c][(k-1-j)*o_ld + o] = w[(j*C + c)*O + o]           (fp32, tap-flipped data-gradient layout)
@@ -259,7 +259,7 @@ int xv_launch_amax_multi(hipStream_t s, const XvAmaxJobs& J);
 
 // Segment-level BatchNorm (rows = chunks per batch, a few hundred at most) in ONE launch each way: statistics, moving
 // averages, scale/shift and the activation (forward); both reductions and dz (backward).  The three-kernel forms are
-// built for 25 k-row tensors; on 128 rows their launches and gaps were what the layer cost.  (xv_elementwise.hip)
+// built for 25 k-row tensors; on 128 rows their launches and gaps were what the layer cost.  (xv_bn.hip)
 #define XV_BN_SMALL_MAX_ROWS 4096
 int xv_bn_small_forward(hipStream_t s, const float* z, int rows, int n, const float* gamma, const float* beta, float eps, float momentum,
                         int unbiased_moving, float* moving_mean, float* moving_var, float* mean, float* invstd, float* scale, float* shift,
@@ -268,15 +268,23 @@ int xv_bn_small_backward(hipStream_t s, const float* da, const float* z, int row
                          const float* invstd, const float* scale, const float* shift, int relu, float* dz, float* dgamma, float* dbeta,
                          float* dbias);
 
-// Engine-internal form of xv_bn_relu_backward_split / _pooled_split / _split_from_part: the upstream gradient is `da`, or the
-// (weighted) pooling backward of (pool_out, dpool) when pool_out != null; ext_part: reductions already done by a GEMM epilogue;
-// zero_amax = false: *dz_amax was zeroed by the caller (one memset per backward pass instead of one per layer).
-struct XvBnBwdSplit { const float* da; const float* pool_out; const float* dpool; const float* weights; int pool_t;
-                      const float* ext_part; int ext_chunks; bool zero_amax; const float* wpos; const float* pamax; };
-int xv_bn_relu_backward_split_ex(hipStream_t s, const XvBnBwdSplit& x, const float* z, int segs, int t, int n, const float* gamma,
-                                 const float* mean, const float* invstd, const float* scale, const float* shift, const float* zmin,
-                                 const float* zmax, int relu, int pad, void* dz_planes, int ldp, size_t plane_stride, uint32_t* dz_amax,
-                                 float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes);
+// BatchNorm (+ activation) backward of a frame-level layer, the engine-internal forms behind the xv_bn_relu_backward* family (xv_bn_bwd.hip).
+// XvBnUpstream says where the upstream gradient comes from: the tensor `da`, or - pool_out != null - the (weighted) statistics-pooling
+// backward of (pool_out, dpool) over chunks of pool_t frames, evaluated on the fly.  wpos / pamax [b][n] (optional, from
+// xv_stat_pool_forward_bn_ex): with wpos and a plain ReLU the two reductions have a closed form and the pass over z is skipped; pamax
+// bounds |d a| for the split-precision dz scale (unit frame weights).  ext_part [ext_chunks][3][n]: the reductions of `da` already done by
+// a GEMM epilogue (xv_epilogue.h XvBwdStats).
+struct XvBnUpstream { const float* da; const float* pool_out; const float* dpool; int pool_t; const float* weights; const float* wpos;
+                      const float* pamax; const float* ext_part; int ext_chunks; };
+// dz in fp32; ldz: floats per row of z and dz, 0 = n; a pitch needs wpos (the closed form) and a plain ReLU
+int xv_bn_backward_f32(hipStream_t s, const XvBnUpstream& up, const float* z, int segs, int t, int n, const float* gamma, const float* mean,
+                       const float* invstd, const float* scale, const float* shift, int relu, int pad, float* dz_pad, int ldz, float* dgamma,
+                       float* dbeta, float* dbias, void* ws, size_t ws_bytes);
+// dz as fp16 planes; zero_amax = false: *dz_amax was zeroed by the caller (one memset per backward pass instead of one per layer)
+int xv_bn_backward_split(hipStream_t s, const XvBnUpstream& up, const float* z, int segs, int t, int n, const float* gamma, const float* mean,
+                         const float* invstd, const float* scale, const float* shift, const float* zmin, const float* zmax, int relu, int pad,
+                         void* dz_planes, int ldp, size_t plane_stride, uint32_t* dz_amax, bool zero_amax, float* dgamma, float* dbeta,
+                         float* dbias, void* ws, size_t ws_bytes);
 
 // Segment-level GEMM C[M][N] = A[M][K] . Bt[N][K]^T, M <= 128 rows (the chunks of one batch), with the split-K sum and the consumer's
 // per-column work in the same launch (xv_skinny.hip).  `ws` holds the [splits][N/32][128][32] slabs, `tickets` one zeroed uint32 per
@@ -301,10 +309,10 @@ struct XvSkinny {
 int xv_launch_skinny(hipStream_t s, const XvSkinny& g);
 size_t xv_skinny_tickets(int max_n);
 
-// Statistics pooling fused with the last frame layer's BatchNorm, engine forms (xv_elementwise.hip): the forward also writes
+// Statistics pooling fused with the last frame layer's BatchNorm, engine form (xv_pool.hip): the forward also writes
 // wpos [b][c] = the share of each chunk's frame weights on frames with an active ReLU; given that, the BatchNorm backward gets its
 // two reductions in closed form from the pooled statistics instead of a pass over z (plain ReLU / no activation); amax [b][c] = each
-// chunk's largest activation, which bounds |d a| for the split-precision dz scale (XvBnBwdSplit.wpos / .pamax, unit frame weights)
+// chunk's largest activation, which bounds |d a| for the split-precision dz scale (XvBnUpstream.wpos / .pamax, unit frame weights)
 // frames (optional, device [b]) / shrink: chunk i pools only its first frames[i] - shrink rows (batched extraction: utterances of different
 // lengths padded to t rows; shrink = the frames the frame layers consumed)
 int xv_stat_pool_forward_bn_ex(hipStream_t s, const float* z, int b, int t, int c, const float* scale, const float* shift, int relu,
@@ -312,10 +320,6 @@ int xv_stat_pool_forward_bn_ex(hipStream_t s, const float* z, int b, int t, int 
                                int ldz = 0 /* floats per row of z; 0 = c */);
 // softmax over the first frames[i] - shrink scores of chunk i (weights beyond are 0); frames == nullptr: all t (xv_attention.hip)
 int xv_softmax_segments_ex(hipStream_t s, const float* score, int b, int t, float* weights, const int32_t* frames, int shrink);
-int xv_bn_relu_backward_pooled_ex(hipStream_t s, const float* pool_out, const float* dpool, const float* weights, const float* wpos, int b, int t,
-                                  const float* z, int n, const float* gamma, const float* mean, const float* invstd, const float* scale,
-                                  const float* shift, int relu, float* dz, float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes,
-                                  int ldz = 0 /* floats per row of z and dz; 0 = n; a pitch needs wpos (the closed form) and a plain ReLU */);
 
 // xv_margin_softmax_rows in one launch (mean folded in through a ticket) that also writes ||x[r]|| (xv_loss.hip)
 int xv_margin_softmax_rows_ex(hipStream_t s, int kind, const float* logits, int rows, int n, int ldl, const float* x, int c,
@@ -324,7 +328,7 @@ int xv_margin_softmax_rows_ex(hipStream_t s, int kind, const float* logits, int 
 
 // Activation behind a BatchNorm in the layer being processed (network_relu_type, tdnn.py:24-30): y > 0 ? y : slope[c] * y.
 // slope == nullptr: ReLU.  Set by the engine around a layer's calls (prelu: the layer's alpha variable, with dalpha = its gradient;
-// lrelu: a constant 0.2 vector); every entry point that takes a `relu` flag reads it (xv_elementwise.hip).
+// lrelu: a constant 0.2 vector); every entry point that takes a `relu` flag reads it (xv_bn.hip owns it).
 struct XvActContext { const float* slope; float* dalpha; };
 void xv_set_act_context(const float* slope, float* dalpha);
 XvActContext xv_act_context();

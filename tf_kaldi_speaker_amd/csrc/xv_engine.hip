@@ -1162,6 +1162,14 @@ float* ring_take(xv_engine* e, hipStream_t s) {
     return e->bufZ[zi];
 }
 
+// The upstream gradient of the last frame layer (tdnn5): the (attention-weighted) statistics-pooling backward of (pool, d pool)
+XvBnUpstream pooled_upstream(const xv_engine* e) {
+    XvBnUpstream up = {};
+    up.pool_out = e->pool; up.dpool = e->d_small0; up.pool_t = e->Tl[e->F]; up.weights = e->att ? e->att_w : nullptr;
+    if (e->pool_closed_form) { up.wpos = e->pool_wpos; up.pamax = e->pool_amax; }
+    return up;
+}
+
 // dz of layer `a` (fp32 path) from the gradient w.r.t. its output: BN (+activation) backward, the activation alone, or da itself.
 // *ring: dz was written into the ring's current slot (ring_take) - the caller's weight gradient then owns the slot.
 int layer_dz(xv_engine* e, hipStream_t s, Affine& a, const float* da, int segs, int t_out, int pad, const float* act_out,
@@ -1175,9 +1183,8 @@ int layer_dz(xv_engine* e, hipStream_t s, Affine& a, const float* da, int segs, 
     XV_REQUIRE(Z, "engine_backward: waiting for a dz slot failed");
     if (!da) {       // tdnn5: the upstream gradient is the statistics-pooling backward of (pool, d pool)
         XV_REQUIRE(lidx == e->F - 1 && a.has_bn, "engine_backward: only the last frame layer takes its gradient from the pooling layer");
-        rc = xv_bn_relu_backward_pooled_ex(s, e->pool, e->d_small0, e->att ? e->att_w : nullptr, e->pool_closed_form ? e->pool_wpos : nullptr, e->B, e->Tl[e->F], a.z, a.c_out,
-                                           vptr(e, a.v_gamma), a.mean, a.invstd, a.scale, a.shift, 1, Z, gptr(e, a.v_gamma), gptr(e, a.v_beta),
-                                           gptr(e, a.v_bias), e->ws, e->ws_bytes, a.ldz);
+        rc = xv_bn_backward_f32(s, pooled_upstream(e), a.z, e->B * e->Tl[e->F], 1, a.c_out, vptr(e, a.v_gamma), a.mean, a.invstd, a.scale, a.shift, 1,
+                                0, Z, a.ldz, gptr(e, a.v_gamma), gptr(e, a.v_beta), gptr(e, a.v_bias), e->ws, e->ws_bytes);
     } else if (a.has_bn && pad == 0 && segs * t_out <= XV_BN_SMALL_MAX_ROWS && !is_frame(e, lidx)) {      // segment-level layers: one launch
         rc = xv_bn_small_backward(s, da, a.z, segs * t_out, a.c_out, vptr(e, a.v_gamma), a.mean, a.invstd, a.scale, a.shift,
                                   a.has_relu ? 1 : 0, Z, gptr(e, a.v_gamma), gptr(e, a.v_beta), gptr(e, a.v_bias));
@@ -1294,20 +1301,19 @@ int layer_backward_f16(xv_engine* e, hipStream_t s, int li, const float* da, int
         if (rc) return rc;
         rc = xv_colsum(s, da, segs * t_out, a.c_out, a.c_out, gptr(e, a.v_bias), e->ws, e->ws_bytes);
     } else {
-        XvBnBwdSplit x = {};
-        x.da = da;
-        x.zero_amax = false;           // the dz slots were zeroed at the start of this backward pass
-        if (!da) {       // tdnn5: the upstream gradient is the (attention-weighted) pooling backward of (pool, d pool)
+        XvBnUpstream up = {};
+        up.da = da;
+        if (!da) {       // tdnn5
             XV_REQUIRE(li == e->F - 1, "engine_backward: only the last frame layer takes its gradient from the pooling layer");
-            x.pool_out = e->pool; x.dpool = e->d_small0; x.pool_t = e->Tl[e->F]; x.weights = e->att ? e->att_w : nullptr;
-            if (e->pool_closed_form) { x.wpos = e->pool_wpos; x.pamax = e->pool_amax; }
+            up = pooled_upstream(e);
         } else if (e->bwd_part_layer == li && e->bwd_part_chunks == xv_cdiv(segs * t_out, XV_TILE_M)) {
             // the GEMM that produced `da` already reduced it against this layer's z (xv_affine_dgrad_bnstats_f16x3)
-            x.ext_part = e->bwd_part; x.ext_chunks = e->bwd_part_chunks;
+            up.ext_part = e->bwd_part; up.ext_chunks = e->bwd_part_chunks;
         }
-        rc = xv_bn_relu_backward_split_ex(s, x, a.z, da ? segs : e->B * e->Tl[e->F], da ? t_out : 1, a.c_out, vptr(e, a.v_gamma), a.mean, a.invstd,
-                                          a.scale, a.shift, a.zmin, a.zmax, 1, pad, Z, a.o_ld, zstride, zamax, gptr(e, a.v_gamma),
-                                          gptr(e, a.v_beta), gptr(e, a.v_bias), e->ws, e->ws_bytes);
+        // zero_amax = false: the dz slots were zeroed at the start of this backward pass
+        rc = xv_bn_backward_split(s, up, a.z, da ? segs : e->B * e->Tl[e->F], da ? t_out : 1, a.c_out, vptr(e, a.v_gamma), a.mean, a.invstd,
+                                  a.scale, a.shift, a.zmin, a.zmax, 1, pad, Z, a.o_ld, zstride, zamax, false, gptr(e, a.v_gamma),
+                                  gptr(e, a.v_beta), gptr(e, a.v_bias), e->ws, e->ws_bytes);
     }
     e->bwd_part_layer = -1;
     if (rc) return rc;

@@ -78,7 +78,7 @@ __device__ __forceinline__ void xv_tile_stats_epilogue(const f32x16 (&acc)[2][NB
 // Data-gradient epilogue: the tile in `acc` is d a (the gradient w.r.t. a BN+ReLU output); together with the matching
 // tile of that layer's pre-BN tensor z it yields the per-tile partials of the BN backward reductions
 //   part[tile_m][0][n] = sum_rows dd,   [1] = sum_rows dd * xhat,   [2] = max_rows |dd|,     dd = (z*scale+shift > 0) ? d a : 0,
-// i.e. what bn_bwd_reduce_kernel computes from memory - without re-reading d a (xv_elementwise.hip consumes the partials).
+// i.e. what bn_bwd_reduce_kernel computes from memory - without re-reading d a (xv_bn_bwd.hip consumes the partials).
 struct XvBwdStats { const float* z; const float* scale; const float* shift; const float* mean; const float* invstd; float* part; };
 
 template <int NB>

@@ -18,6 +18,7 @@
 // The spliced (context-window) row map of xv_gemm.hip applies unchanged to both kernels.
 #include "xv_common.h"
 #include "xv_epilogue.h"
+#include "xv_ew.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -145,15 +146,11 @@ __global__ void bn_apply_split_kernel(const float* __restrict__ z, long rows, in
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int c = col + 4 * q;
-            float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+            f32x4 y = {0, 0, 0, 0};
             if (c < n) {
-                float4 zz = *(const float4*)(z + r * ldz + c), sc = *(const float4*)(scale + c), sh = *(const float4*)(shift + c);
-                y.x = zz.x * sc.x + sh.x; y.y = zz.y * sc.y + sh.y; y.z = zz.z * sc.z + sh.z; y.w = zz.w * sc.w + sh.w;
-                if (relu && slope) {       // prelu / leaky ReLU (act context, xv_common.h)
-                    const float4 sl = *(const float4*)(slope + c);
-                    y.x = y.x > 0.f ? y.x : y.x * sl.x; y.y = y.y > 0.f ? y.y : y.y * sl.y;
-                    y.z = y.z > 0.f ? y.z : y.z * sl.z; y.w = y.w > 0.f ? y.w : y.w * sl.w;
-                } else if (relu) { y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f); }
+                y = *(const f32x4*)(z + r * ldz + c) * *(const f32x4*)(scale + c) + *(const f32x4*)(shift + c);
+                if (relu && slope) y = act4(y, *(const f32x4*)(slope + c));      // prelu / leaky ReLU (act context, xv_common.h)
+                else if (relu) y = relu4(y);
             }
             v[4 * q] = y.x; v[4 * q + 1] = y.y; v[4 * q + 2] = y.z; v[4 * q + 3] = y.w;
         }

@@ -2,7 +2,7 @@
 
     f(features, aux_features, endpoints, params, is_training) -> [batch, 2 * dim]
 
-`statistics_pooling` and `self_attention` run on the GPU through the op-level C-ABI (csrc/xv_elementwise.hip,
+`statistics_pooling` and `self_attention` run on the GPU through the op-level C-ABI (csrc/xv_pool.hip,
 csrc/xv_attention.hip); inside the training engine the same kernels are driven natively (csrc/xv_engine.hip), so these
 callables are the evaluation forms a caller of the reference API reaches.  `self_attention` covers the single-head form
 every shipped attention config uses (key network on `endpoints[att_key_input]`, value = `endpoints[att_value_input]`, key
@@ -71,7 +71,7 @@ def _get(name, shape, init):
 
 def statistics_pooling(features, aux_features, endpoints, params, is_training):
     """[batch, length, dim] -> [batch, 2*dim] = concat(mean, stddev) with the variance floor of
-    reference pooling.py:9-34 (wave-shuffle Welford kernel, csrc/xv_elementwise.hip)."""
+    reference pooling.py:9-34 (wave-shuffle Welford kernel, csrc/xv_pool.hip)."""
     x = to_device(features)
     assert x.dim() == 3
     if x.shape[2] % 4 != 0:
