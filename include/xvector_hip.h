@@ -35,7 +35,8 @@ extern "C" {
 
 /* 2: xv_config starts with struct_bytes (round 5).  3: xv_engine_arena_bytes (round 6).  Bumped whenever xv_config's layout or an entry point's signature changes: a host
  * built against another header must fail at load (xv_abi_version) or at xv_engine_create (struct_bytes), never read fields past the end
- * of a shorter struct. */
+ * of a shorter struct.  xv_frontend came later and left it at 3: a new entry point beside the old ones, xv_config untouched - a host
+ * built against the earlier header runs unchanged against this library. */
 #define XV_ABI_VERSION 3
 
 const char* xv_last_error(void);
@@ -97,6 +98,27 @@ int xv_cm_decode(void* stream, const uint8_t* packed, int b, int t, int d, size_
  * [cols i32][d x (p0, p25, p75, p100) u16][d x rows[i] u8, column after column] - at byte offsets[i] of `packed`; it is decoded into
  * out[i][0 .. rows[i]) of the [b][t][d] tensor and the padding rows behind it are zeroed.  offsets / rows: device arrays [b]. */
 int xv_cm_decode_ragged(void* stream, const uint8_t* packed, const int64_t* offsets, const int32_t* rows, int b, int t, int d, float* out);
+
+/* The feature front end of extraction on a decoded batch: sliding-window cepstral mean normalisation, then voiced-frame selection - the
+ * two Kaldi programs the reference recipe pipes in front of extract.py (egs/voxceleb/v1/nnet/run_extract_embeddings.sh:47):
+ *   apply-cmvn-sliding --norm-vars=false --center=true --cmn-window=W   (featbin/apply-cmvn-sliding.cc, SlidingWindowCmn in
+ *                                                                        feat/feature-functions.cc)
+ *   select-voiced-frames                                                (ivectorbin/select-voiced-frames.cc)
+ * x: [b][t_in][d], piece i holding rows_in[i] raw frames (n below), as xv_cm_decode_ragged leaves them.  out: [b][t_out][d].
+ *   CMN (cmn_window = W > 0; 0 = off): for raw frame t, s = t - W/2 (integer division), e = s + W; if s < 0: e -= s, s = 0;
+ *     if e > n: s -= e - n, e = n, s = max(s, 0); y[t] = x[t] - mean(x[s:e]), the mean accumulated in double and the difference rounded
+ *     to fp32 once.  The window spans RAW frames: voicing does not enter it (in the pipe CMN runs first).
+ *   Selection: masks = one byte per raw frame, non-zero = voiced, the masks of all pieces back to back in one buffer of mask_bytes
+ *     bytes, piece i's at byte mask_offsets[i] (any alignment; pieces may share a mask); masks = NULL keeps every frame.  With sel the
+ *     ascending raw indices of piece i's voiced frames: out[i][j] = y[sel[first[i] + j]] for j < rows_out[i] = min(count[i], |sel| -
+ *     first[i]), rows rows_out[i] .. t_out are zero.  first / count (NULL: 0 / t_out) cut a chunk out of the SELECTED frames - how
+ *     extract.py:69-79 splits an utterance longer than --chunk-size; every chunk is a piece that holds the whole raw utterance.
+ * rows_in, mask_offsets, first, count, rows_out: device arrays [b].  ws: b * t_out * 4 bytes when masks are given (the selected indices;
+ * none otherwise) - fewer is an error.  x and out must not overlap.  d <= 128.  Two launches (one without masks), no atomics: the same
+ * bits on every call. */
+int xv_frontend(void* stream, const float* x, const int32_t* rows_in, int b, int t_in, int d, int cmn_window, const uint8_t* masks,
+                size_t mask_bytes, const int64_t* mask_offsets, const int32_t* first, const int32_t* count, int t_out, float* out,
+                int32_t* rows_out, void* ws, size_t ws_bytes);
 
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);

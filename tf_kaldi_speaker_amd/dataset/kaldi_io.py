@@ -197,6 +197,58 @@ def read_vec_flt_ark(file_or_fd):
             fd.close()
 
 
+def read_vec_flt_scp(file_or_fd):
+    """generator of (key, vector) from an scp file: one "<key> <rxfilename>[:offset]" per line (reference kaldi_io.py:573-592)."""
+    fd = open_or_fd(file_or_fd)
+    try:
+        for line in fd:
+            key, rxfile = line.decode().strip().split(None, 1)
+            yield key, read_vec_flt(rxfile)
+    finally:
+        if fd is not file_or_fd:
+            fd.close()
+
+
+class VecFltTable(object):
+    """Float vectors by key from an "ark:" or "scp:" rspecifier (the VAD decisions of nnet/lib/extract.py --vad): an archive is read up
+    front, an scp file only as its table of rxfilenames - a vector is read when it is asked for - so the vectors need not come in the
+    order of the features they belong to.  get(key) -> vector or None."""
+
+    def __init__(self, rspecifier):
+        self.vectors, self.rxfiles, self.fds = {}, {}, {}
+        m = _PREFIX.search(rspecifier)
+        if m is not None and m.group(1) == "scp":
+            fd = open_or_fd(rspecifier)
+            try:
+                for line in fd:
+                    if line.strip():
+                        key, rxfile = line.decode().strip().split(None, 1)
+                        self.rxfiles[key] = rxfile
+            finally:
+                fd.close()
+        else:
+            self.vectors = dict(read_vec_flt_ark(rspecifier))
+
+    def get(self, key):
+        rxfile = self.rxfiles.get(key)
+        if rxfile is None:
+            return self.vectors.get(key)
+        m = re.match(r"^(.*\S)\s*:([0-9]+)$", rxfile)
+        if m is None or m.group(1).endswith("|") or m.group(1).endswith(".gz"):
+            return read_vec_flt(rxfile)
+        # "<archive>:<offset>", what copy-vector / compute-vad write: every archive stays open (FeatureReader does the same for feats.scp)
+        fd = self.fds.get(m.group(1))
+        if fd is None:
+            fd = self.fds[m.group(1)] = open(m.group(1), "rb")
+        fd.seek(int(m.group(2)))
+        return read_vec_flt(fd)
+
+    def close(self):
+        for fd in self.fds.values():
+            fd.close()
+        self.fds = {}
+
+
 def write_vec_flt(file_or_fd, v, key=""):
     """"<key> " + "\\0B" + "FV " + \\x04 + int32 dim + data   (reference kaldi_io.py:624-653)."""
     fd = open_or_fd(file_or_fd, mode="wb")
@@ -374,6 +426,34 @@ class PackedMatrix(object):
         data = buf[head:].reshape(self.cols, self.rows)[:, start:start + length]
         return PackedMatrix(length, self.cols, buf[:8].tobytes() + struct.pack("<ii", length, self.cols) + buf[self.HEADER:head].tobytes() +
                             np.ascontiguousarray(data).tobytes())
+
+
+class VoicedRows(object):
+    """Rows of an utterance AFTER voiced-frame selection, for the GPU front end (xv_frontend, Trainer.predict_batch): `item` is the RAW
+    utterance (a PackedMatrix or a float32 matrix), `voiced` one uint8 per raw frame (non-zero = kept; None = every frame) and
+    [first, first + count) a range of the kept frames - the whole utterance, or one of the chunks extract.py cuts a long one into.  shape and
+    row_range() count kept frames, so the chunking and batching code sees the utterance the network will see."""
+    __slots__ = ("item", "voiced", "total", "first", "count")
+
+    def __init__(self, item, voiced=None, first=0, count=None, total=None):
+        self.item = item
+        if voiced is not None and total is None:
+            voiced = np.ascontiguousarray(np.asarray(voiced) != 0).view(np.uint8)
+            if voiced.shape != (int(item.shape[0]),):
+                raise ValueError("VoicedRows: %d voicing decisions for %d frames" % (voiced.size, int(item.shape[0])))
+        self.voiced = voiced
+        self.total = int(total) if total is not None else (int(item.shape[0]) if voiced is None else int(np.count_nonzero(voiced)))
+        self.first = int(first)
+        self.count = self.total - self.first if count is None else int(count)
+        assert 0 <= self.first and 0 <= self.count and self.first + self.count <= self.total
+
+    @property
+    def shape(self):
+        return (self.count, int(self.item.shape[1]))
+
+    def row_range(self, start, length):
+        assert 0 <= start and start + length <= self.count
+        return VoicedRows(self.item, self.voiced, self.first + start, length, total=self.total)
 
 
 def read_mat_ark_packed(file_or_fd, block_bytes=8 << 20):

@@ -284,6 +284,33 @@ class Engine(object):
         self._keep_decode = [pk, off]
         return out, rw
 
+    def frontend(self, x, rows_in, cmn_window=0, masks=None, mask_offsets=None, first=None, count=None, t_out=None):
+        """The recipe's feature pipe on a decoded batch (xv_frontend): x [b, t_in, feat_dim] device tensor with rows_in[i] raw frames per
+        piece -> (features [b, t_out, feat_dim], rows_out int32 [b]), both on the device: sliding-window CMN over cmn_window raw frames
+        (0 = off), then the frames whose mask byte is non-zero (masks: uint8 device tensor, piece i's mask at byte mask_offsets[i]; None
+        = all), of which a piece keeps rows first[i] .. first[i] + count[i] (None: all; t_out: the largest count)."""
+        b, t_in, d = x.shape
+        if d != self.config.feat_dim:
+            raise ValueError("feature dim %d != %d" % (d, self.config.feat_dim))
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+            raise ValueError("frontend: x must be a contiguous float32 device tensor (decode_packed's output, or an uploaded padded batch)")
+        for name, a, dtype in (("rows_in", rows_in, torch.int32), ("masks", masks, torch.uint8), ("mask_offsets", mask_offsets, torch.int64),
+                               ("first", first, torch.int32), ("count", count, torch.int32)):
+            if a is not None and not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == dtype and a.is_contiguous()):
+                raise ValueError("frontend: %s must be a contiguous %s device tensor" % (name, dtype))
+            if a is not None and name != "masks" and a.numel() != b:
+                raise ValueError("frontend: %d entries in %s for %d pieces" % (a.numel(), name, b))
+        t_out = int(t_in if t_out is None else t_out)
+        out = torch.empty((b, t_out, d), dtype=torch.float32, device=x.device)
+        rows_out = torch.empty(b, dtype=torch.int32, device=x.device)
+        ws = torch.empty((b, t_out), dtype=torch.int32, device=x.device) if masks is not None else None
+        _lib.check(self.lib.xv_frontend(_stream(), _ptr(x), _ptr(rows_in), int(b), int(t_in), int(d), int(cmn_window), _ptr(masks),
+                                        C.c_size_t(masks.numel() if masks is not None else 0), _ptr(mask_offsets), _ptr(first), _ptr(count),
+                                        t_out, _ptr(out), _ptr(rows_out), _ptr(ws), C.c_size_t(ws.numel() * 4 if ws is not None else 0)),
+                   "xv_frontend")
+        self._keep_frontend = [x, rows_in, masks, mask_offsets, first, count, ws]
+        return out, rows_out
+
     def loss(self, labels, global_step, with_margin=True):
         y = self._dev(labels, torch.int32)
         self._keep.append(y)

@@ -397,6 +397,25 @@ def utterance_embedding(predict, feature, chunk_size, normalize):
     return np.asarray(embedding, np.float32), len(chunks)
 
 
+def select_voiced(key, feature, vad):
+    """What `select-voiced-frames` makes of one utterance of the extraction driver's input, without touching a frame (the GPU selects:
+    xv_frontend): -> (kaldi_io.VoicedRows, None), or (None, the log line that says why the utterance is skipped) - no VAD entry
+    (vad is None), as many decisions as frames or the utterance is dropped, and at least one voiced frame."""
+    try:
+        from ..dataset.kaldi_io import VoicedRows
+    except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT
+        from dataset.kaldi_io import VoicedRows
+    frames = int(feature.shape[0])
+    if vad is None:
+        return None, "[INFO] Key %s has no VAD entry, skip." % key
+    if len(vad) != frames:
+        return None, "[INFO] Key %s has %d frames but %d VAD decisions, skip." % (key, frames, len(vad))
+    rows = VoicedRows(feature, vad)
+    if rows.total == 0:
+        return None, "[INFO] Key %s has no voiced frame, skip." % key
+    return rows, None
+
+
 def plan_length_batches(lengths, max_rows, max_chunks, min_fill=0.9, min_rows=8192):
     """Utterances of different lengths -> padded batches for one forward each: [(indices, t)] with t = the longest utterance of the
     batch.  Sorted by length (longest first), a batch takes utterances while it stays within max_chunks utterances and max_rows =

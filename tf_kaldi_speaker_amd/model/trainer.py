@@ -29,7 +29,7 @@ try:
     from ..parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from ..dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
     from ..misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state, plan_length_batches
-    from ..dataset.kaldi_io import PackedMatrix
+    from ..dataset.kaldi_io import PackedMatrix, VoicedRows
     from ..misc import tf_checkpoint
     from .tdnn import tdnn, extended_tdnn, engine_config, collect_endpoints, check_params
     from . import loss as _loss
@@ -39,7 +39,7 @@ except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_RO
     from parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
     from misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state, plan_length_batches
-    from dataset.kaldi_io import PackedMatrix
+    from dataset.kaldi_io import PackedMatrix, VoicedRows
     from misc import tf_checkpoint
     from model.tdnn import tdnn, extended_tdnn, engine_config, collect_endpoints, check_params
     from model import loss as _loss
@@ -473,12 +473,16 @@ class Trainer(object):
     PREDICT_ROWS = 49152
     PREDICT_CHUNKS = 128
 
-    def predict_batch(self, items, return_device=False):
+    def predict_batch(self, items, return_device=False, cmn_window=0, voiced=None):
         """Embeddings of MANY utterances of different lengths, [n, E] in the order given - the batched form of the loop
         extract.py:64-93 runs one predict() at a time.  items: float32 matrices [T_i, D] and / or kaldi_io.PackedMatrix ('CM '
         matrices as read from the archive, decoded on the GPU).  Utterances are sorted by length, padded to the longest of their
         batch (misc.utils.plan_length_batches) and run through xv_engine_forward_lengths, whose pooling sees only each utterance's
-        own frames; the embedding node must be a segment-level one (tdnn6_dense, tdnn7_*, output)."""
+        own frames; the embedding node must be a segment-level one (tdnn6_dense, tdnn7_*, output).
+        cmn_window / voiced: the recipe's feature pipe on the GPU (Engine.frontend) for items that are RAW features - sliding-window
+        CMN over cmn_window frames (0 = off), then the frames whose entry in voiced[i] (one uint8 array per item; None = all) is
+        non-zero.  An item may also be a kaldi_io.VoicedRows (raw utterance + mask + a range of its kept frames: extract.py's chunks).
+        Lengths - the batch plan, the receptive-field check - then count the frames left after selection."""
         if not self.is_loaded:
             if os.path.isfile(os.path.join(self.model, "checkpoint")):
                 self.load()
@@ -487,7 +491,16 @@ class Trainer(object):
         n = len(items)
         if n == 0:
             return np.zeros((0, 0), np.float32)
-        lengths = [int(it.shape[0]) for it in items]
+        cmn_window = int(cmn_window)
+        if voiced is not None and len(voiced) != n:
+            raise ValueError("predict_batch: %d voicing masks for %d items" % (len(voiced), n))
+        pieces = None      # the front end is on: every item as a VoicedRows (raw utterance, mask, range of kept frames)
+        if cmn_window > 0 or voiced is not None or any(isinstance(it, VoicedRows) for it in items):
+            if voiced is not None and any(isinstance(it, VoicedRows) for it in items):
+                raise ValueError("predict_batch: a VoicedRows item carries its own mask (voiced must be None)")
+            pieces = [it if isinstance(it, VoicedRows) else VoicedRows(it, None if voiced is None else voiced[i]) for i, it in enumerate(items)]
+            items = [p.item for p in pieces]
+        lengths = [int(it.shape[0]) for it in items] if pieces is None else [p.count for p in pieces]
         dim = self.dim
         # every matrix must have the model's feature dimension: the GPU decoder takes the column stride from `dim`, not from the archive
         # header, so a mismatch would decode garbage (and read past the record) instead of failing; predict() rejects it through
@@ -528,18 +541,62 @@ class Trainer(object):
         # byte offsets and frame counts of every batch in ONE pinned upload as well: a pageable host -> device copy per batch makes the
         # host wait for the stream (the previous batch's forward), i.e. host and GPU work would take turns instead of overlapping
         flat = [i for idx, _ in plan for i in idx]
-        meta = torch.empty((2, len(flat)), dtype=torch.int64, pin_memory=True)
-        mv = meta.numpy()
-        mv[0] = [base[id(items[i].block)] + items[i].start if isinstance(items[i], PackedMatrix) else 0 for i in flat]
-        mv[1] = [lengths[i] for i in flat]
-        meta_dev = meta.to(eng.device, non_blocking=True)
-        rows_dev = meta_dev[1].to(torch.int32)
+        offsets = [base[id(items[i].block)] + items[i].start if isinstance(items[i], PackedMatrix) else 0 for i in flat]
+        if pieces is None:
+            meta = torch.empty((2, len(flat)), dtype=torch.int64, pin_memory=True)
+            mv = meta.numpy()
+            mv[0] = offsets
+            mv[1] = [lengths[i] for i in flat]
+            meta_dev = meta.to(eng.device, non_blocking=True)
+            rows_dev = meta_dev[1].to(torch.int32)
+        else:
+            # the front end's arguments ride in the same upload: per piece the byte offset of its mask, its raw frame count and the range
+            # of kept frames it covers, then the masks themselves back to back (one copy per utterance: the chunks of a long one share
+            # theirs; a piece without a mask beside pieces with one points at a run of ones)
+            raw = [int(items[i].shape[0]) for i in flat]
+            mask_at, mask_list, mask_total = {}, [], 0
+            if any(pieces[i].voiced is not None for i in flat):
+                ones = np.ones(max([r for r, i in zip(raw, flat) if pieces[i].voiced is None] or [0]), np.uint8)
+                for i in flat:
+                    v = pieces[i].voiced if pieces[i].voiced is not None else ones
+                    if id(v) not in mask_at:
+                        mask_at[id(v)] = mask_total
+                        mask_list.append(v)
+                        mask_total += len(v)
+            head = 5 * 8 * len(flat)
+            meta = torch.empty(head + mask_total, dtype=torch.uint8, pin_memory=True)
+            mv = meta.numpy()[:head].view(np.int64).reshape(5, len(flat))
+            mv[0] = offsets
+            mv[1] = [mask_at[id(pieces[i].voiced if pieces[i].voiced is not None else ones)] for i in flat] if mask_total else 0
+            mv[2] = raw
+            mv[3] = [pieces[i].first for i in flat]
+            mv[4] = [pieces[i].count for i in flat]
+            for v in mask_list:
+                meta.numpy()[head + mask_at[id(v)]:head + mask_at[id(v)] + len(v)] = v
+            meta_all = meta.to(eng.device, non_blocking=True)
+            meta_dev = meta_all[:head].view(torch.int64).view(5, len(flat))
+            masks_dev = meta_all[head:] if mask_total else None
+            fe_dev = meta_dev[2:5].to(torch.int32)      # raw rows, first, count
         cursor = 0
         for idx, t in plan:
             b = len(idx)
             sl = slice(cursor, cursor + b)
             cursor += b
-            if all(isinstance(items[i], PackedMatrix) for i in idx):
+            packed = all(isinstance(items[i], PackedMatrix) for i in idx)
+            if pieces is not None:
+                # the raw batch is as long as its longest RAW utterance (the plan's t counts kept frames); host matrices take the same kernel
+                t_raw = max(int(items[i].shape[0]) for i in idx)
+                if packed:
+                    xr, _ = eng.decode_packed(packed_dev, meta_dev[0, sl], fe_dev[0, sl], t_raw)
+                else:
+                    host = np.zeros((b, t_raw, dim), np.float32)
+                    for j, i in enumerate(idx):
+                        m = items[i].decode() if isinstance(items[i], PackedMatrix) else np.asarray(items[i], np.float32)
+                        host[j, :m.shape[0]] = m
+                    xr = torch.from_numpy(host).to(eng.device)
+                x, rows = eng.frontend(xr, fe_dev[0, sl], cmn_window, masks_dev, meta_dev[1, sl] if masks_dev is not None else None,
+                                       fe_dev[1, sl], fe_dev[2, sl], t)
+            elif packed:
                 x, rows = eng.decode_packed(packed_dev, meta_dev[0, sl], rows_dev[sl], t)
             else:
                 host = np.zeros((b, t, dim), np.float32)

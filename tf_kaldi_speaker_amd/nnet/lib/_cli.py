@@ -23,6 +23,10 @@ ARGUMENTS = {
     "chunk_size": (("-s", "--chunk-size"), dict(type=int, default=10000, help="Longer segments are split and averaged.")),
     "normalize": (("-n", "--normalize"), dict(action="store_true", help="Normalize the embedding before averaging and output.")),
     "node": (("--node",), dict(type=str, default="", help="The node to output the embeddings.")),
+    "cmn_window": (("--cmn-window",), dict(type=int, default=0, help="Sliding-window CMN over this many frames on the GPU (apply-cmvn-sliding "
+                                                                     "--norm-vars=false --center=true); 0: the features are normalised already.")),
+    "vad": (("--vad",), dict(type=str, default="", help="ark: or scp: rspecifier of the VAD decisions; voiced frames are selected on the GPU "
+                                                        "(select-voiced-frames).  Empty: every frame is kept.")),
     # positionals
     "train_dir": (("train_dir",), dict(type=str, help="The data directory of the training set.")),
     "train_spklist": (("train_spklist",), dict(type=str, help="The spklist file maps the TRAINING speakers to the indices.")),

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Drop-in for egs/voxceleb/v1/nnet/lib/extract.py (same CLI, wrap/extract_wrapper.sh:39-40):
 
-    python nnet/lib/extract.py [-g GPU] [-m MIN] [-s CHUNK] [-n] [--node NAME] model_dir rspecifier wspecifier
+    python nnet/lib/extract.py [-g GPU] [-m MIN] [-s CHUNK] [-n] [--node NAME] [--cmn-window N] [--vad RSPECIFIER] model_dir rspecifier wspecifier
 
 Reads an ark / input pipe of feature matrices, writes a Kaldi float-vector ark of embeddings
 (is_training=False graph, moving BN statistics).  Utterances longer than --chunk-size are cut into
 half-overlapping chunks whose embeddings are length-weighted averaged (reference extract.py:65-94).
 -g selects the HIP device (the reference's CPU mode `-g -1` maps to device 0: there is no CPU path).
+--cmn-window / --vad (not in the reference's CLI) take over the two Kaldi programs the recipe pipes in front of this script
+(run_extract_embeddings.sh:47: apply-cmvn-sliding --cmn-window=300 | select-voiced-frames): the rspecifier then names the RAW features,
+both steps run on the GPU behind the 'CM ' decode (Trainer.predict_batch), and every length - --min-chunk-size, --chunk-size, the log
+lines - counts the frames left after selection, as it does behind the pipe.
 """
 import logging
 import os
@@ -15,8 +19,8 @@ import time
 
 import _cli
 from model.trainer import Trainer
-from misc.utils import Params, EmbeddingWindow, prefetch_iter
-from dataset.kaldi_io import open_or_fd, read_mat_ark_packed, write_vec_flt
+from misc.utils import Params, EmbeddingWindow, prefetch_iter, select_voiced
+from dataset.kaldi_io import open_or_fd, read_mat_ark_packed, write_vec_flt, VecFltTable, VoicedRows
 
 # utterances gathered before they go to the GPU together (sorted by length into padded batches, Trainer.predict_batch); results are
 # written in archive order.  One utterance per forward, as the reference runs (extract.py:64-93), left the chip at 9-20 % of its
@@ -27,7 +31,7 @@ WINDOW_FRAMES = 400000
 
 def main():
     log = _cli.logger(batched=True)
-    args = _cli.parser_for("gpu", "min_chunk_size", "chunk_size", "normalize", "node", "model_dir", "rspecifier", "wspecifier").parse_args()
+    args = _cli.parser_for("gpu", "min_chunk_size", "chunk_size", "normalize", "node", "cmn_window", "vad", "model_dir", "rspecifier", "wspecifier").parse_args()
     # -g is an enable flag in the reference ("an arbitrary number except -1"; run_extract_embeddings.sh passes the JOB
     # number with --gpuid), device choice being left to CUDA_VISIBLE_DEVICES.  Here: among the devices HIP_VISIBLE_DEVICES
     # leaves visible, job N takes device N modulo their count, so `nj` parallel jobs spread over the GPUs of the node and
@@ -49,6 +53,9 @@ def main():
     trainer.build("predict", dim=dim)
     if "." in args.rspecifier and args.rspecifier.rsplit(".", 1)[1] == "scp":
         sys.exit("The rspecifier must be ark or input pipe")
+    if args.cmn_window < 0:
+        sys.exit("--cmn-window must be 0 (off) or a number of frames")
+    vad = VecFltTable(args.vad) if len(args.vad) != 0 else None
     fp_out = open_or_fd(args.wspecifier, "wb")
     window, window_frames = [], 0
     pending = []           # the window whose forward passes are on the GPU while the next one is read, planned and enqueued
@@ -57,8 +64,9 @@ def main():
     def submit():
         entries = list(window)
         del window[:]
-        keep = [feature for _, feature in entries if feature.shape[0] >= args.min_chunk_size]
-        job = EmbeddingWindow(lambda pieces: trainer.predict_batch(pieces, return_device=True), keep, args.chunk_size, args.normalize)
+        keep = [feature for _, feature, skip in entries if skip is None and feature.shape[0] >= args.min_chunk_size]
+        job = EmbeddingWindow(lambda pieces: trainer.predict_batch(pieces, return_device=True, cmn_window=args.cmn_window), keep, args.chunk_size,
+                              args.normalize)
         finish()           # the previous window: read back, log, write - while this one runs
         pending.append((entries, job))
 
@@ -67,7 +75,10 @@ def main():
             return
         entries, job = pending.pop()
         results = iter(job.results())
-        for key, feature in entries:         # log lines and output vectors in archive order, as the one-at-a-time loop gives them
+        for key, feature, skip in entries:   # log lines and output vectors in archive order, as the one-at-a-time loop gives them
+            if skip is not None:             # dropped by the voiced-frame selection (no VAD entry, wrong length, nothing voiced)
+                log.info(skip)
+                continue
             frames = feature.shape[0]
             if frames < args.min_chunk_size:
                 log.info("[INFO] Key %s length too short, %d < %d, skip." % (key, frames, args.min_chunk_size))
@@ -84,8 +95,13 @@ def main():
 
     # the reader runs ahead of the GPU in its own thread; 'CM ' matrices arrive undecoded (kaldi_io.PackedMatrix) and are decoded on the GPU
     for key, feature in prefetch_iter(read_mat_ark_packed(args.rspecifier), depth=2 * WINDOW_UTTERANCES):
-        window.append((key, feature))
-        window_frames += feature.shape[0]
+        skip = None
+        if vad is not None:              # from here on `feature` counts voiced frames: the raw matrix, its mask, nothing selected yet
+            feature, skip = select_voiced(key, feature, vad.get(key))
+        elif args.cmn_window > 0:
+            feature = VoicedRows(feature)
+        window.append((key, feature, skip))
+        window_frames += feature.shape[0] if skip is None else 0
         if len(window) >= WINDOW_UTTERANCES or window_frames >= WINDOW_FRAMES:
             submit()
             window_frames = 0
@@ -97,6 +113,8 @@ def main():
         if stats["utts"] > u1 and now > t1 else ""
     log.info("[INFO] Extracted %d utterances (%d frames) in %.2f s%s." % (stats["utts"], stats["frames"], now - stats["t0"], rate))
     fp_out.close()
+    if vad is not None:
+        vad.close()
     trainer.close()
 
 

@@ -58,6 +58,21 @@ def cm_decode(packed, b, t, d):
     return out
 
 
+def frontend(x, rows_in, cmn_window=0, masks=None, mask_offsets=None, first=None, count=None, t_out=None):
+    """Sliding-window CMN (cmn_window frames, 0 = off), then voiced-frame selection, on a decoded batch x [b, t_in, d] with rows_in[i] raw
+    frames per piece (xv_frontend).  masks: uint8 device tensor, the pieces' voicing masks back to back, piece i's at byte
+    mask_offsets[i] (int64) - None keeps every frame; first / count (int32, None = 0 / t_out): the range of SELECTED rows a piece
+    keeps.  -> (out [b, t_out, d], rows_out int32 [b])."""
+    b, t_in, d = x.shape
+    t_out = t_in if t_out is None else int(t_out)
+    out = torch.empty((b, t_out, d), dtype=torch.float32, device=x.device)
+    rows_out = torch.empty(b, dtype=torch.int32, device=x.device)
+    ws = torch.empty((b, t_out), dtype=torch.int32, device=x.device) if masks is not None else None
+    _lib.call("xv_frontend", _s(), _p(x), _p(rows_in), b, t_in, d, int(cmn_window), _p(masks), C.c_size_t(masks.numel() if masks is not None else 0),
+              _p(mask_offsets), _p(first), _p(count), t_out, _p(out), _p(rows_out), _p(ws), C.c_size_t(ws.numel() * 4 if ws is not None else 0))
+    return out, rows_out
+
+
 def prep_weight_fwd(kernel, c_pad):
     """kernel: [k, C, O] -> [O, k*c_pad]"""
     k, c, o = kernel.shape

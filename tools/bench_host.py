@@ -11,7 +11,8 @@ sub-command per question (they used to be eight scripts); every one builds its o
   python tools/bench_host.py trainer [steps=400]                Trainer.train itself: one epoch incl. checkpoint load + save, shipped batch shape
   python tools/bench_host.py soak [steps=2000]                  loader-fed steps: sustained rate, finite loss, host / device memory before and after
   python tools/bench_host.py extract [utterances=300]           extraction: engine one utterance at a time, then Trainer.predict_batch (host fp32 / 'CM ' + GPU decode)
-  python tools/bench_host.py extract_driver                     nnet/lib/extract.py end to end on a 5 000-utterance 'CM ' ark, three times
+  python tools/bench_host.py extract_driver [frontend]          nnet/lib/extract.py end to end on a 5 000-utterance 'CM ' ark, three times; frontend: every
+                                                                round is followed by one with --cmn-window 300 --vad (~70 % voiced) on the same archive
 """
 import json
 import os
@@ -354,25 +355,36 @@ def cmd_extract_driver(argv):
     model = os.path.join(tmp, "exp")
     make_extract_model(model)
     env = dict(os.environ, TF_KALDI_ROOT=PKG, PYTHONPATH=PKG)
+    frontend = "frontend" in argv
     frames = 0
     for n in (5000, 5000, 5000):         # the same archive three times: run-to-run spread on this box
         ark = os.path.join(tmp, "in%d.ark" % n)
+        vad = os.path.join(tmp, "vad%d.ark" % n)
         if not os.path.isfile(ark):
             rs = np.random.RandomState(n)
-            with open(ark, "wb") as f:
+            with open(ark, "wb") as f, open(vad, "wb") as fv:
                 for i in range(n):
                     t = int(rs.randint(400, 2001))
                     f.write(("utt%05d " % i).encode())
                     kaldi_io.write_compressed_mat(f, rs.randn(t, 30).astype(np.float32))
+                    if frontend:
+                        kaldi_io.write_vec_flt(fv, (rs.rand(t) < 0.7).astype(np.float32), key="utt%05d" % i)
                     frames += t
-        t0 = time.perf_counter()
-        r = subprocess.run([sys.executable, os.path.join(PKG, "nnet", "lib", "extract.py"), "--node", "tdnn6_dense", model, "ark:" + ark,
-                            "ark:" + os.path.join(tmp, "out%d.ark" % n)], env=env, cwd=PKG, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        wall = time.perf_counter() - t0
-        last = [ln for ln in r.stderr.splitlines() if "Extracted" in ln]
-        print("%4d utterances (%.2f M frames): %.2f s wall incl. process start-up, imports, checkpoint load; driver's own clock: %s"
-              % (n, frames / 1e6, wall, last[-1].split("[INFO] ", 1)[-1] if last else "?"))
+        # the front-end leg reads the SAME archive as raw features: the network then sees ~70 % of the frames, so the figure to compare is the
+        # rate in raw frames (the driver's own M frames/s counts the frames left after selection)
+        for leg, options in (("plain", []), ("frontend", ["--cmn-window", "300", "--vad", "ark:" + vad]))[:2 if frontend else 1]:
+            t0 = time.perf_counter()
+            r = subprocess.run([sys.executable, os.path.join(PKG, "nnet", "lib", "extract.py"), "--node", "tdnn6_dense"] + options + [model, "ark:" + ark,
+                                "ark:" + os.path.join(tmp, "out%d.ark" % n)], env=env, cwd=PKG, capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-2000:]
+            wall = time.perf_counter() - t0
+            last = [ln for ln in r.stderr.splitlines() if "Extracted" in ln]
+            line = last[-1].split("[INFO] ", 1)[-1] if last else "?"
+            raw_rate = ""
+            if frontend and " utterances/s" in line:
+                raw_rate = " = %.2f M RAW frames/s" % (float(line.split(", ")[-1].split(" utterances/s")[0]) * frames / n / 1e6)
+            print("%-8s %4d utterances (%.2f M raw frames): %.2f s wall incl. process start-up, imports, checkpoint load; driver's own clock: %s%s"
+                  % (leg, n, frames / 1e6, wall, line, raw_rate))
 
 
 COMMANDS = {"loader": cmd_loader, "loader_scale": cmd_loader_scale, "e2e": cmd_e2e, "e2e_ab": cmd_e2e_ab, "trainer": cmd_trainer, "soak": cmd_soak,
