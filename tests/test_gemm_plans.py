@@ -106,7 +106,7 @@ def lib_tn(M, N, R, direct):
 
 # ---- the problems --------------------------------------------------------------------------------------------------------------------
 def layer_problems(B, T, layers, feat_pad=32, lout=512, ldl=7352, pool=1500):
-    """The GEMM problems of one training step (frame layers as (context, width), xv_engine.hip): ("nt", M, N, K, stats, co_running) and
+    """The GEMM problems of one training step (frame layers as (context, width), xv_engine_fwd.hip / xv_engine_bwd.hip): ("nt", M, N, K, stats, co_running) and
     ("tn", M, N, R, direct)"""
     out = []
     c, t_in = feat_pad, T
@@ -248,7 +248,7 @@ def test_tn_advice_cases():
 
 def test_tn_slabs_fit_the_workspaces():
     """xv_affine_wgrad's slabs fit xv_op_workspace_bytes; the engine sizes its slab space at the largest rows of a layer and with
-    xv_op_workspace_bytes (xv_engine.hip): a smaller batch's plan must fit the same bytes (the split count is not monotone in R)."""
+    xv_op_workspace_bytes (xv_engine.hip, workspace_bytes): a smaller batch's plan must fit the same bytes (the split count is not monotone in R)."""
     ws = _lib().xv_op_workspace_bytes
     ws.restype = ctypes.c_size_t
     for M, N, R in _tn_grid():

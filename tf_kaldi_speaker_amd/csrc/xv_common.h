@@ -206,6 +206,8 @@ int xv_launch_gemm_tn(hipStream_t s, const XvGemmTN& g);
 // *out += scale * sum(w[0 .. count)^2) by a fixed-order two-stage reduction (xv_update.hip); part: XV_SUMSQ_PARTS floats of scratch
 #define XV_SUMSQ_PARTS 512
 int xv_sumsq_ordered(hipStream_t s, const float* w, size_t count, float scale, float* out, float* part);
+// g[0 .. count) *= grad_scale * clip / max(grad_scale * sqrt(*sumsq), clip)   (tf.clip_by_global_norm; xv_update.hip)
+int xv_clip_scale(hipStream_t s, float* g, size_t count, const float* sumsq, float grad_scale, float clip);
 int xv_launch_wgrad_reduce(hipStream_t s, const float* P, int splits, int k, int C, int c_pad, int n_in, int n_out, const float* w,
                            long ldw, float l2, float* out, long ldo);
 

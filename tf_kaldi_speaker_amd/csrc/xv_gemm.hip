@@ -1323,7 +1323,7 @@ static XvTnPlan xv_tn_plan(int M, int N, int R, bool direct = false) {
     if (splits > ksteps / min_ksteps) splits = std::max(1, ksteps / min_ksteps);
     // A short reduction over many tiles (the loss head's weight gradient: 232 tiles x 8 K-steps at 128 chunks) is not split: four splits of two
     // K-steps each wrote and re-read 60 MB of slabs beside the latency-bound chain of the segment layers (its d-out launch ran 45 instead of
-    // 23 us); one workgroup per tile can store the result where it belongs (xv_engine.hip, loss_head_wgrad)
+    // 23 us); one workgroup per tile can store the result where it belongs (xv_engine_bwd.hip, loss_head_wgrad)
     // - only for the caller that asks for it (XvGemmTN::direct: its unsplit result is stored straight into the destination); a LAYER's
     // weight gradient with many tiles and a short reduction (small-batch fine-tuning) keeps its splits - unsplit it would leave most of the
     // chip idle
@@ -1426,7 +1426,7 @@ int xv_affine_dgrad_ld(hipStream_t stream, const float* dz_pad, int ldo, int seg
     g.C = dx; g.ldc = c;
     g.M = segs * (t_out + k - 1); g.N = c; g.K = k * o;
     g.ws = ws; g.ws_bytes = ws_bytes;
-    g.co_running = 1;          // the data gradient runs beside the layer's weight gradient (xv_engine.hip: two streams)
+    g.co_running = 1;          // the data gradient runs beside the layer's weight gradient (xv_engine_bwd.hip: two streams)
     return xv_launch_gemm_nt(stream, g);
 }
 extern "C" int xv_affine_dgrad(void* stream, const float* dz_pad, int segs, int t_out, int o, int k, const float* wf, float* dx,

@@ -114,6 +114,19 @@ extern "C" int xv_sumsq(void* stream, const float* g, size_t count, float* out_a
     return sumsq_with_scratch((hipStream_t)stream, g, count, 1.0f, out_accum);
 }
 
+__global__ void clip_scale_kernel(float* __restrict__ g, size_t count, const float* __restrict__ sumsq, float grad_scale, float clip) {
+    // tf.clip_by_global_norm: g * clip / max(norm, clip)
+    float norm = sqrtf(*sumsq) * grad_scale;
+    float k = grad_scale * (clip / fmaxf(norm, clip));
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) g[i] *= k;
+}
+// g *= grad_scale * clip / max(grad_scale * sqrt(*sumsq), clip): the engine's clip-by-global-norm, *sumsq from xv_sumsq_ordered
+int xv_clip_scale(hipStream_t s, float* g, size_t count, const float* sumsq, float grad_scale, float clip) {
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(2048), dim3(256), 0, s, g, count, sumsq, grad_scale, clip);
+    XV_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, size_t count, float lr, float gs) {
     XV_EW_PRIORITY();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)

@@ -1,4 +1,4 @@
-"""Host-side handle on the native engine (csrc/xv_engine.hip).
+"""Host-side handle on the native engine (csrc/xv_engine.hip and its units xv_engine_fwd / _bwd / _step.hip; state in xv_engine.h).
 
 torch is used here for exactly three things: owning device memory (the flat
 variables / gradient / optimiser-state buffers), naming the HIP stream, and

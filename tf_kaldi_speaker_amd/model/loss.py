@@ -4,8 +4,8 @@
         -> (loss, endpoints{"logits", "labels"})        side effect: params.dict["softmax_w"] = w
 
 These are the *forward* (evaluation) forms on GPU buffers; gradients of the same kernels are
-produced inside the engine (csrc/xv_engine.hip) that Trainer drives.  Variables live in a module-level
-store keyed by "<name>/output/kernel" exactly like the TF variable scope, so a second call with
+produced inside the engine (csrc/xv_engine_fwd.hip: xv_engine_loss_forward; its gradient: csrc/xv_engine_bwd.hip)
+that Trainer drives.  Variables live in a module-level store keyed by "<name>/output/kernel" exactly like the TF variable scope, so a second call with
 reuse_variables=True sees the same weight (loss.py:96-102).
 """
 from collections import OrderedDict

@@ -3,7 +3,7 @@
     f(features, aux_features, endpoints, params, is_training) -> [batch, 2 * dim]
 
 `statistics_pooling` and `self_attention` run on the GPU through the op-level C-ABI (csrc/xv_pool.hip,
-csrc/xv_attention.hip); inside the training engine the same kernels are driven natively (csrc/xv_engine.hip), so these
+csrc/xv_attention.hip); inside the training engine the same kernels are driven natively (csrc/xv_engine_fwd.hip, csrc/xv_engine_bwd.hip), so these
 callables are the evaluation forms a caller of the reference API reaches.  `self_attention` covers the single-head form
 every shipped attention config uses (key network on `endpoints[att_key_input]`, value = `endpoints[att_value_input]`, key
 not split, no value network, no penalty term, no post non-linearity); the other options of the reference function are

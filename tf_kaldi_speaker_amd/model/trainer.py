@@ -8,8 +8,8 @@
     .save(step) / .load() -> step / .reset() / .close()
     attributes callers touch: .sess, .embeddings, .endpoints, .params, .model
 
-The TF1 session/graph is replaced by the native MI355X engine (csrc/xv_engine.hip) reached through
-the C-ABI; this file is host logic only (loader, loop, logging, checkpoints, data parallelism).
+The TF1 session/graph is replaced by the native MI355X engine (csrc/xv_engine.hip; forward, backward and update in
+csrc/xv_engine_fwd / _bwd / _step.hip) reached through the C-ABI; this file is host logic only (loader, loop, logging, checkpoints, data parallelism).
 Checkpoints: <model>/nnet/model-<step>.npz (variables by TF name + optimiser state) plus the
 TF-format text index <model>/nnet/checkpoint that run_extract_embeddings.sh tests for.
 """

@@ -9,7 +9,7 @@
 mode=$1; shift
 R=$(cd $(dirname $0)/.. && pwd)
 src=$R/tf_kaldi_speaker_amd/csrc
-UNITS="xv_gemm xv_gemm16 xv_skinny xv_runtime xv_prep xv_bn xv_bn_bwd xv_pool xv_update xv_loss xv_attention xv_engine"
+UNITS="xv_gemm xv_gemm16 xv_skinny xv_runtime xv_prep xv_bn xv_bn_bwd xv_pool xv_update xv_loss xv_attention xv_engine xv_engine_fwd xv_engine_bwd xv_engine_step"
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$R/include -I$src -Wall -Wno-unused-function"
 throttle() { while [ $(jobs -r | wc -l) -ge 4 ]; do sleep 0.5; done; }      # at most 4 compilers at a time (8 CPUs, 64 GB)
 case $mode in
