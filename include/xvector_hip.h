@@ -120,6 +120,42 @@ int xv_frontend(void* stream, const float* x, const int32_t* rows_in, int b, int
                 size_t mask_bytes, const int64_t* mask_offsets, const int32_t* first, const int32_t* count, int t_out, float* out,
                 int32_t* rows_out, void* ws, size_t ws_bytes);
 
+/* Cosine trial scoring with adaptive symmetric score normalisation (AS-norm) on embedding matrices: the stage behind extract.py, for
+ * which the reference recipe goes to Kaldi (ivector-mean | ivector-subtract-global-mean | ivector-normalize-length, then
+ * ivector-compute-dot-products; egs/voxceleb/v1/run.sh, cosine back end).  All arrays on the device, pitches in floats.  No
+ * floating-point atomics, no cross-workgroup hand-over: the output bits depend on the shape of the call only.
+ *
+ * Row sums of the first two ops: one wave per row; a lane's partial takes the elements lane, lane + 64, ... (groups of four when d,
+ * the pitches and the bases are multiples of 4 floats / 16 bytes, single elements otherwise) with one fma each, a six-step butterfly
+ * adds the lanes.  The longest add chain is chain(d) = 4 * ceil(d / 256) + 6 roundings in either form.
+ *
+ * score_prepare: y[r][c] = v[c] * rsqrt(max(sum_c v[c]^2, 1e-12)) with v[c] = x[r][c] - mean[c] (mean = NULL: v = x) for c < d - the
+ * epsilon rule of xv_l2_scaling_forward - and y[r][c] = 0 for d <= c < ldy, in every row (y holds rows * ldy floats), so y is a GEMM
+ * operand as it stands.  A zero row gives a zero row.  In place (y == x and ldy == ldx) is allowed; any other overlap of x or mean
+ * with y is refused. */
+int xv_score_prepare(void* stream, const float* x, int rows, int d, int ldx, const float* mean, float* y, int ldy);
+/* score_trials: s = sum_{c<d} e[ei[j]][c] * t[ti[j]][c] for j < m.  e_stats == t_stats == NULL: out[j] = s.  Both given ([ne][2] and
+ * [nt][2]: mean, deviation of each row's cohort scores, from xv_score_cohort_stats): out[j] = 0.5 * ((s - e_stats[ei[j]][0]) /
+ * e_stats[ei[j]][1] + (s - t_stats[ti[j]][0]) / t_stats[ti[j]][1]).  One of the two alone is refused.  ei, ti: device int32 [m];
+ * they are NOT checked on the device - the caller guarantees 0 <= ei[j] < ne and 0 <= ti[j] < nt (ops.score_trials checks the host
+ * arrays before the upload). */
+int xv_score_trials(void* stream, const float* e, int lde, int ne, const float* t, int ldt, int nt, int d, const int32_t* ei,
+                    const int32_t* ti, int64_t m, const float* e_stats, const float* t_stats, float* out);
+/* score_cohort_stats: stats[r] = (mean, sqrt(max(var, 1e-12))) - var the biased variance, taken around that mean in a second pass -
+ * of the k = min(top_k, n_cohort) largest of the scores sum_c x[r][c] * cohort[j][c], j < n_cohort.  The scores come from the fp32 GEMM
+ * behind xv_affine_forward (k = 1, segs = rows, t_in = 1, the cohort in the wt[o][c] layout) with K = d rounded up to 4: columns d .. K
+ * of both operands are read and must be zero (xv_score_prepare writes them), and the GEMM's own operand rules hold (pitches multiples
+ * of 4, 16-byte aligned bases, each operand below 4 GB) - it refuses by name.  It writes a slab [tile][n_cohort rounded up to 4] in ws,
+ * tile = the largest multiple of 128 rows ws_bytes holds; rows beyond a tile take further GEMM launches.  xv_score_cohort_workspace_bytes
+ * is the size at which one launch covers all rows; a workspace that holds one 128-row tile works, less (or a base off the 16-byte grid)
+ * is refused.  Per row one workgroup then selects the k-th largest score exactly (radix select on the order-preserving unsigned key of
+ * the float, four 8-bit passes) and sums in double, in a fixed order, the scores strictly above it plus (k - their count) copies of it -
+ * a cut through a run of equal scores is well defined - and the squared distances to the mean the same way.  top_k <= 0 and
+ * n_cohort <= 0 are refused. */
+size_t xv_score_cohort_workspace_bytes(int rows, int n_cohort, int d);
+int xv_score_cohort_stats(void* stream, const float* x, int ldx, int rows, const float* cohort, int ldc, int n_cohort, int d, int top_k,
+                          float* stats, void* ws, size_t ws_bytes);
+
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);
  * columns c in [C, c_pad) are zero. */

@@ -160,6 +160,10 @@ SIGNATURES = {
     "xv_cm_decode": (_I, [_VP, _VP, _I, _I, _I, _SZ, _VP]),
     "xv_cm_decode_ragged": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "xv_frontend": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _SZ, _VP, _VP, _VP, _I, _VP, _VP, _VP, _SZ]),
+    "xv_score_prepare": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I]),
+    "xv_score_trials": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
+    "xv_score_cohort_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "xv_score_cohort_stats": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _SZ]),
     "xv_add_norm_grad": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "xv_segment_gemm": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, _VP, C.c_long, _VP, C.c_long, _VP, _SZ, _VP]),
     "xv_segment_affine_bn_forward": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, _F, _F, _I, _VP, _VP, _VP, _VP, _VP,

@@ -217,10 +217,8 @@ def get_pretrain_model(pretrain_model, target_model, checkpoint="-1"):
 
 def compute_cos_pairwise_eer(embeddings, labels, max_num_embeddings=1000):
     """Pairwise cosine EER (reference utils.py:273-312): L2-normalise, subsample to <= max_num_embeddings
-    with an integer stride, score all pairs i<j, EER = root of 1 - x - tpr(x) on the ROC curve."""
-    from scipy.interpolate import interp1d
-    from scipy.optimize import brentq
-    from sklearn import metrics
+    with an integer stride, score all pairs i<j, EER = root of 1 - x - tpr(x) on the ROC curve (misc/scoring.py compute_eer)."""
+    from .scoring import compute_eer
     embeddings = embeddings / np.sqrt(np.sum(embeddings ** 2, axis=1, keepdims=True) + 1e-12)
     labels = np.asarray(labels)
     n = embeddings.shape[0]
@@ -233,8 +231,7 @@ def compute_cos_pairwise_eer(embeddings, labels, max_num_embeddings=1000):
     iu = np.triu_indices(n, k=1)                # same (i, j>i) order as the reference's double loop
     scores = score_mat[iu]
     keys = (labels[iu[0]] == labels[iu[1]]).astype(np.float64)
-    fpr, tpr, _ = metrics.roc_curve(keys, scores, pos_label=1)
-    return float(brentq(lambda x: 1.0 - x - interp1d(fpr, tpr)(x), 0.0, 1.0))
+    return compute_eer(scores, keys)
 
 
 def substring_in_list(s, varlist):

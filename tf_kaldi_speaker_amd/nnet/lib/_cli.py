@@ -27,7 +27,16 @@ ARGUMENTS = {
                                                                      "--norm-vars=false --center=true); 0: the features are normalised already.")),
     "vad": (("--vad",), dict(type=str, default="", help="ark: or scp: rspecifier of the VAD decisions; voiced frames are selected on the GPU "
                                                         "(select-voiced-frames).  Empty: every frame is kept.")),
+    "center_on": (("--center-on",), dict(type=str, default="", help="ark: or scp: rspecifier of the vectors whose mean is subtracted from every "
+                                                                    "vector, cohort included (ivector-mean | ivector-subtract-global-mean).  Empty: no centring.")),
+    "cohort": (("--cohort",), dict(type=str, default="", help="ark: or scp: rspecifier of the cohort vectors: scores are AS-normalised against "
+                                                              "them.  Empty: raw cosine scores.")),
+    "top_k": (("--top-k",), dict(type=int, default=300, help="Cohort scores per vector that enter its AS-norm statistics (the largest ones).")),
     # positionals
+    "trials": (("trials",), dict(type=str, help="Kaldi trial list: `enrol test [target|nontarget]` per line.")),
+    "enrol_rspecifier": (("enrol_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the enrolment vectors.")),
+    "test_rspecifier": (("test_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the test vectors (may equal enrol_rspecifier).")),
+    "scores_out": (("scores_out",), dict(type=str, help="Output file: `enrol test score` per kept trial, in trial order.")),
     "train_dir": (("train_dir",), dict(type=str, help="The data directory of the training set.")),
     "train_spklist": (("train_spklist",), dict(type=str, help="The spklist file maps the TRAINING speakers to the indices.")),
     "valid_dir": (("valid_dir",), dict(type=str, help="The data directory of the validation set.")),

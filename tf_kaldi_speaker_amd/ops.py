@@ -73,6 +73,73 @@ def frontend(x, rows_in, cmn_window=0, masks=None, mask_offsets=None, first=None
     return out, rows_out
 
 
+def _pitched(t, what):
+    """(rows, pitch in floats) of a 2-D float32 device view with contiguous rows."""
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("%s: a 2-D float32 tensor with contiguous rows is expected" % what)
+    return t.shape[0], t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def score_prepare(x, d=None, mean=None, out=None):
+    """Rows of x [rows, >= d] minus mean [d] (None: nothing subtracted), scaled to unit length (xv_score_prepare).  d: the columns that
+    hold the vector (default: all of x).  out: the [rows, ldy] tensor to write (may be x itself, in place); default a new tensor whose
+    pitch is d rounded up to 4 - columns d .. ldy come back zero, so the result is a GEMM operand for score_cohort_stats."""
+    rows, ldx = _pitched(x, "score_prepare: x")
+    d = x.shape[1] if d is None else int(d)
+    if out is None:
+        out = torch.empty((rows, (d + 3) // 4 * 4), dtype=torch.float32, device=x.device)
+    _, ldy = _pitched(out, "score_prepare: out")
+    if out.shape[1] != ldy:
+        raise ValueError("score_prepare: out must be the whole [rows, pitch] buffer (its padding columns are written)")
+    if mean is not None and (mean.dtype != torch.float32 or mean.numel() != d or not mean.is_contiguous()):
+        raise ValueError("score_prepare: mean must be %d contiguous float32 values" % d)
+    _lib.call("xv_score_prepare", _s(), _p(x), rows, d, ldx, _p(mean), _p(out), ldy)
+    return out
+
+
+def score_trials(e, t, d, ei, ti, e_stats=None, t_stats=None):
+    """out[j] = e[ei[j]][:d] . t[ti[j]][:d], AS-normalised with the rows' cohort statistics when both are given (xv_score_trials).
+    ei, ti: HOST integer arrays (NumPy / sequences): the kernel does not check indices, so they are checked here, before the upload."""
+    import numpy as np
+    ne, lde = _pitched(e, "score_trials: e")
+    nt, ldt = _pitched(t, "score_trials: t")
+    ei, ti = np.asarray(ei), np.asarray(ti)
+    if ei.ndim != 1 or ei.shape != ti.shape or ei.size == 0 or ei.dtype.kind not in "iu" or ti.dtype.kind not in "iu":
+        raise ValueError("score_trials: ei and ti must be two non-empty 1-D integer arrays of one length")
+    if ei.min() < 0 or ei.max() >= ne:
+        raise IndexError("score_trials: ei holds an index outside 0 .. %d" % (ne - 1))
+    if ti.min() < 0 or ti.max() >= nt:
+        raise IndexError("score_trials: ti holds an index outside 0 .. %d" % (nt - 1))
+    for st, n, name in ((e_stats, ne, "e_stats"), (t_stats, nt, "t_stats")):
+        if st is not None and (st.dtype != torch.float32 or tuple(st.shape) != (n, 2) or not st.is_contiguous()):
+            raise ValueError("score_trials: %s must be a contiguous float32 [%d, 2] tensor" % (name, n))
+    ei_d = torch.from_numpy(np.ascontiguousarray(ei, dtype=np.int32)).to(e.device)
+    ti_d = torch.from_numpy(np.ascontiguousarray(ti, dtype=np.int32)).to(e.device)
+    out = torch.empty(ei.size, dtype=torch.float32, device=e.device)
+    _lib.call("xv_score_trials", _s(), _p(e), lde, ne, _p(t), ldt, nt, int(d), _p(ei_d), _p(ti_d), C.c_int64(ei.size), _p(e_stats), _p(t_stats),
+              _p(out))
+    return out
+
+
+def score_cohort_workspace_bytes(rows, n_cohort, d):
+    return int(_lib.load().xv_score_cohort_workspace_bytes(int(rows), int(n_cohort), int(d)))
+
+
+def score_cohort_stats(x, cohort, d, top_k, ws_bytes=None):
+    """[rows, 2] = (mean, biased deviation) of each row's min(top_k, n_cohort) largest scores against the cohort rows
+    (xv_score_cohort_stats).  x, cohort: prepared matrices (score_prepare: zero padding up to a pitch that is a multiple of 4).
+    ws_bytes: size of the score slab (default: the whole call in one GEMM launch); fewer bytes run the rows in tiles."""
+    rows, ldx = _pitched(x, "score_cohort_stats: x")
+    n_cohort, ldc = _pitched(cohort, "score_cohort_stats: cohort")
+    if ws_bytes is None:
+        ws_bytes = score_cohort_workspace_bytes(rows, n_cohort, d)
+    ws = torch.empty(max(int(ws_bytes) // 4, 1), dtype=torch.float32, device=x.device)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+    _lib.call("xv_score_cohort_stats", _s(), _p(x), ldx, rows, _p(cohort), ldc, n_cohort, int(d), int(top_k), _p(stats), _p(ws),
+              C.c_size_t(int(ws_bytes)))
+    return stats
+
+
 def prep_weight_fwd(kernel, c_pad):
     """kernel: [k, C, O] -> [O, k*c_pad]"""
     k, c, o = kernel.shape

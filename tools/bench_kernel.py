@@ -11,6 +11,7 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py pool [frames=186] [channels=1500] statistics pooling (+ BatchNorm) and its backward, warm (Infinity Cache) and cold
   python tools/bench_kernel.py segment                          the segment-level GEMMs: one-launch form (xv_skinny.hip) against GEMM + slab-sum launches
   python tools/bench_kernel.py staged                           plain step vs the staged (multi-GPU) backward, without / with a one-rank RCCL all-reduce
+  python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
 
 Environment: XV_DATA_SCALE=0 (all-zero operands: DVFS check), XV_B (chunks, gemm16), ITERS (segment), XV_LIB (another build of the library).
 """
@@ -266,7 +267,50 @@ def cmd_staged(argv):
     dist.destroy_process_group()
 
 
-COMMANDS = {"gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+def cmd_score(argv):
+    """Time per op of the scoring stage; the trial kernel's traffic against the 8 TB/s HBM peak (2 rows of d floats, two indices and one score
+    per trial - a flat streaming kernel reaches 0.82 of the peak here); the cohort op's GEMM launches alone (the same
+    row tiles through xv_affine_forward without scratch, as xv_score_cohort_stats runs them) against the whole op: the rest is the selection."""
+    import ctypes as C
+    from tf_kaldi_speaker_amd import _lib, ops
+    from tf_kaldi_speaker_amd.ops import _p, _s
+    d, ws_bytes = 512, 1 << 30
+    sizes = {"small": ("VoxCeleb1-O-sized", 4708, 37720, 2000, 200), "large": ("VoxCeleb1-E-sized", 145160, 581480, 6000, 300)}
+    for key in (argv or ["small", "large"]):
+        name, n, m, n_cohort, top_k = sizes[key]
+        raw, craw = rnd(n, d), rnd(n_cohort, d)
+        x, cohort = ops.score_prepare(raw), ops.score_prepare(craw)
+        ei, ti = rs.randint(0, n, m), rs.randint(0, n, m)
+        print("%s: %d vectors, %d trials, cohort %d, top-k %d, d = %d" % (name, n, m, n_cohort, top_k, d), flush=True)
+        us = timeit(lambda: ops.score_prepare(raw, out=x), 10, 2)
+        print("  prepare                 %9.1f us  %.2f TB/s (one read, one write)" % (us, 2.0 * n * d * 4 / us / 1e6), flush=True)
+        ei_d, ti_d = torch.from_numpy(ei.astype(np.int32)).cuda(), torch.from_numpy(ti.astype(np.int32)).cuda()
+        out = torch.empty(m, device="cuda")
+        stats = ops.score_cohort_stats(x, cohort, d, top_k, ws_bytes=ws_bytes)
+        for label, st in (("trials (raw)", None), ("trials (AS-norm)", stats)):
+            us = timeit(lambda: _lib.call("xv_score_trials", _s(), _p(x), d, n, _p(x), d, n, d, _p(ei_d), _p(ti_d), C.c_int64(m), _p(st), _p(st), _p(out)),
+                        10, 2)
+            mb = m * (2.0 * d * 4 + 12 + (16 if st is not None else 0)) / 1e6
+            print("  %-22s  %9.1f us  %.2f TB/s = %.2f of the 8 TB/s peak (gathered rows; the tables are %.0f MB)" % (label, us, mb / us, mb / us / 8.0, n * d * 4 / 1e6),
+                  flush=True)
+        ws = torch.empty(ws_bytes // 4, device="cuda")
+        ldn = (n_cohort + 3) // 4 * 4
+        tile = min((n + 127) // 128 * 128, ws_bytes // (ldn * 4) // 128 * 128)
+
+        def whole():
+            _lib.call("xv_score_cohort_stats", _s(), _p(x), d, n, _p(cohort), d, n_cohort, d, top_k, _p(stats), _p(ws), C.c_size_t(ws_bytes))
+
+        def gemms():
+            for r0 in range(0, n, tile):
+                rows = min(tile, n - r0)
+                _lib.call("xv_affine_forward", _s(), _p(x[r0:]), rows, 1, d, 1, _p(cohort), None, _p(ws), n_cohort, ldn, None, None, C.c_size_t(0))
+        us_all, us_gemm = timeit(whole, 5, 1), timeit(gemms, 5, 1)
+        fl = 2.0 * n * n_cohort * d
+        print("  cohort statistics       %9.1f us in %d row tile(s) of %d: GEMM %.1f us (%.1f TF) = %.2f of the op, selection %.1f us = %.2f"
+              % (us_all, (n + tile - 1) // tile, tile, us_gemm, fl / us_gemm / 1e6, us_gemm / us_all, us_all - us_gemm, 1.0 - us_gemm / us_all), flush=True)
+
+
+COMMANDS = {"score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
