@@ -156,6 +156,54 @@ size_t xv_score_cohort_workspace_bytes(int rows, int n_cohort, int d);
 int xv_score_cohort_stats(void* stream, const float* x, int ldx, int rows, const float* cohort, int ldc, int n_cohort, int d, int top_k,
                           float* stats, void* ws, size_t ws_bytes);
 
+/* The LDA / PLDA back end behind extraction, device side: what ivector-mean (with and without spk2utt), ivector-compute-lda,
+ * ivector-compute-plda, ivector-subtract-global-mean and ivector-plda-scoring --normalize-length=true do on the embedding tables
+ * (egs/voxceleb/v1/run.sh:370-401, egs/sre/v1/run.sh:397-490).  The eigendecompositions and the EM of the two estimators run on the host
+ * in fp64 (misc/backend.py); the affine maps A v + b and offset + transform y are xv_affine_forward (k = 1, bias = the offset).  All
+ * arrays on the device, pitches in floats.  No floating-point atomics, no cross-workgroup hand-over: the output bits depend on the shape
+ * of the call only.  d <= 0 is refused by every op.
+ *
+ * group_means (ivector-mean ark:spk2utt, and the per-speaker averages of both estimators): group g lists the rows
+ * rows[offsets[g] .. offsets[g + 1]) of x [n][ldx] (CSR: offsets int64 [groups + 1], offsets[0] = 0, offsets[groups] = total; rows int32
+ * [total]; a row may be listed more than once and in any order).  mean64[g][c] = the sum of the listed rows, added in list order in
+ * double, divided by their count - IEEE adds and one IEEE divide, so the bits are defined by the list; mean32 (optional) [groups][ldm] =
+ * its fp32 rounding, columns d .. ldm zero.  One thread per (group, column).  groups <= 0 and total < groups (some group would be
+ * empty) are refused; offsets and rows are NOT checked on the device - the caller guarantees non-empty groups and 0 <= rows[i] < n
+ * (ops.backend_group_means checks the host arrays before the upload and refuses an empty group by name). */
+int xv_backend_group_means(void* stream, const float* x, int n, int ldx, int d, const int64_t* offsets, const int32_t* rows, int groups,
+                           int64_t total, double* mean64, float* mean32, int ldm);
+/* center (ivector-subtract-global-mean alone, the input of the LDA): y[r][c] = x[r][c] - mean[c] in fp32 (mean = NULL: a copy) for
+ * c < d, 0 for d <= c < ldy in every row, so y is a GEMM operand as it stands.  In place (y == x and ldy == ldx) is allowed; any other
+ * overlap of x or mean with y is refused. */
+int xv_backend_center(void* stream, const float* x, int rows, int d, int ldx, const float* mean, float* y, int ldy);
+/* scatter (the statistics of ivector-compute-lda / ivector-compute-plda): c64 [d][d] (double) = sum_r v_r v_r^T over the rows of
+ * x [n][ldx], v = x[r] - mean in fp32 as score_prepare subtracts it (mean = NULL: v = x[r]).  The rows are taken in blocks of 8 192; a
+ * block's products come from the fp32 TN GEMM behind xv_affine_wgrad (k = 1, segs = rows, t_in = 1, the block on both sides, M = N = d
+ * rounded up to 4), which writes its split slabs into ws; one more kernel adds the slabs into c64 in slab order, block after block, in
+ * double, one thread per element - so no fp32 add chain is longer than the reduction rows of one GEMM workgroup (out[2] of
+ * xv_debug_tn_plan(d4, d4, block rows, 0, out)), whatever n is.  An element (i, j) is read from the upper triangle of the slabs:
+ * c64 is bit-symmetric.  A block is first copied into ws (centred, padding columns zeroed) unless it is a GEMM operand as it stands (no
+ * mean, d and ldx multiples of 4, 16-byte aligned base); the copy is exact.  ws: xv_backend_scatter_workspace_bytes(n, d) bytes, 16-byte
+ * aligned - fewer (less than the centred block plus the slabs) is refused, and the GEMM refuses by name what it refuses. */
+size_t xv_backend_scatter_workspace_bytes(int n, int d);
+int xv_backend_scatter(void* stream, const float* x, int n, int d, int ldx, const float* mean, double* c64, void* ws, size_t ws_bytes);
+/* plda_normalize (Plda::TransformIvector, normalize_length = true, simple_length_norm = false): out[r][c] = u[r][c] * sqrt(d / s_r),
+ * s_r = sum_c u[r][c]^2 / (psi[c] + 1 / n_utts[r]) (n_utts = NULL: 1 everywhere) for c < d, 0 for d <= c < ldo.  One wave per row, the
+ * lanes and the chain(d) of score_prepare.  A row whose sum is 0 stays 0.  In place (out == u and ldo == ldu) is allowed; any other
+ * overlap of u or psi with out is refused. */
+int xv_backend_plda_normalize(void* stream, const float* u, int rows, int d, int ldu, const float* psi, const int32_t* n_utts, float* out,
+                              int ldo);
+/* plda_trials (Plda::LogLikelihoodRatio): out[j] = k0[q] + sum_{c<d} (-0.5 iv[q][c] (t_c - a[q][c] e_c)^2 + 0.5 g[c] t_c^2), e = row ei[j] of
+ * e [ne][lde], t = row ti[j] of t [nt][ldt], q = nidx[ei[j]] the enrol row's entry in the table of distinct utterance counts:
+ * coef [n_distinct][2][ldc] = (a = n psi / (n psi + 1), iv = 1 / (1 + psi / (n psi + 1))), g[c] = 1 / (psi[c] + 1), k0[q] = -0.5 sum log v +
+ * 0.5 sum log(psi + 1), all built on the host in double and rounded once (misc/backend.py plda_coefficients): no division and no
+ * logarithm on the device.  One wave per trial; the two quadratic forms are one interleaved sum per lane.  ei, ti [m], nidx [ne]: device
+ * int32, NOT checked on the device - the caller guarantees 0 <= ei[j] < ne, 0 <= ti[j] < nt, 0 <= nidx[i] < n_distinct
+ * (ops.backend_plda_trials checks the host arrays before the upload). */
+int xv_backend_plda_trials(void* stream, const float* e, int lde, int ne, const float* t, int ldt, int nt, int d, const int32_t* ei,
+                           const int32_t* ti, int64_t m, const int32_t* nidx, const float* coef, int ldc, int n_distinct, const float* g,
+                           const float* k0, float* out);
+
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);
  * columns c in [C, c_pad) are zero. */

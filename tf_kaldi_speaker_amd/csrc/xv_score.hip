@@ -9,38 +9,10 @@
 
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_rowsum.h"      // sc_row_dot and chain(d), SC_ROWS_PER_WG, sc_aligned16, sc_overlap
 
-#define SC_ROWS_PER_WG 4          // one wave per row / trial, four to a workgroup of 256
 #define SC_SEL_THREADS 256
 #define SC_TILE_ROWS 128          // the score slab holds a whole number of GEMM row tiles
-
-// Σ over one row by one wave.  The add chain both row kernels share: a lane's partial takes the elements (vector form: float4 groups)
-// lane, lane + 64, ... one fma each - ceil(d / 64) fmas in the scalar form, 4 * ceil(d / 256) in the vector form - and the butterfly
-// adds six more, so no sum is longer than
-//     chain(d) = 4 * ceil(d / 256) + 6
-// roundings (the scalar form's ceil(d / 64) + 6 never exceeds it).  tests/test_gpu_score.py derives its tolerance from this figure.
-template <bool VEC, bool SUB>
-__device__ __forceinline__ float sc_row_dot(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ mean, int d, int lane) {
-    float acc = 0.f;
-    if (VEC) {
-        for (int q = lane; q < d / 4; q += XV_WAVE) {
-            f32x4 u = *(const f32x4*)(a + 4 * q), v = *(const f32x4*)(b + 4 * q);
-            if (SUB) {      // (the prepare kernel: a == b, the row minus the mean dotted with itself)
-                const f32x4 m = *(const f32x4*)(mean + 4 * q);
-                u -= m;
-                v = u;
-            }
-            acc = fmaf(u.x, v.x, acc); acc = fmaf(u.y, v.y, acc); acc = fmaf(u.z, v.z, acc); acc = fmaf(u.w, v.w, acc);
-        }
-    } else {
-        for (int c = lane; c < d; c += XV_WAVE) {
-            float u = a[c], v = b[c];
-            if (SUB) { u -= mean[c]; v = u; }
-            acc = fmaf(u, v, acc);
-        }
-    }
-    return wave_sum(acc);
-}
 
 // y[r][c] = v * rsqrt(max(Σ v², 1e-12)), v = x[r][c] - mean[c], for c < d; y[r][d .. ldy) = 0.  One wave per row.  In place (y == x,
 // ldy == ldx) a lane reads back exactly the elements it then overwrites, and the padding belongs to the row.
@@ -207,12 +179,6 @@ __global__ __launch_bounds__(SC_SEL_THREADS) void score_select_kernel(const floa
         stats[2 * (long)blockIdx.x] = (float)mean;
         stats[2 * (long)blockIdx.x + 1] = (float)sqrt(fmax(var, 1e-12));
     }
-}
-
-static bool sc_aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-// [a, a + an) and [b, b + bn) floats share an address
-static bool sc_overlap(const float* a, size_t an, const float* b, size_t bn) {
-    return (uintptr_t)a < (uintptr_t)(b + bn) && (uintptr_t)b < (uintptr_t)(a + an);
 }
 
 extern "C" int xv_score_prepare(void* stream, const float* x, int rows, int d, int ldx, const float* mean, float* y, int ldy) {

@@ -605,6 +605,46 @@ def write_mat(file_or_fd, m, key=""):
             fd.close()
 
 
+def write_plda(file_or_fd, mean, transform, psi):
+    """Kaldi's binary Plda object (ivector/plda.cc Plda::Write): "\\0B" + "<Plda> " + mean ("DV " + \\x04 + int32 dim + doubles) + transform
+    ("DM " + \\x04 rows + \\x04 cols + row-major doubles) + psi ("DV ") + "</Plda> ".  Restated from the format; byte compatibility with a
+    file Kaldi wrote is not pinned by a test."""
+    mean, transform, psi = (np.ascontiguousarray(a, dtype=np.float64) for a in (mean, transform, psi))
+    if mean.ndim != 1 or psi.shape != mean.shape or transform.shape != (mean.shape[0], mean.shape[0]):
+        raise ValueError("write_plda: mean [d], transform [d, d] and psi [d] are expected")
+    fd = open_or_fd(file_or_fd, mode="wb")
+    try:
+        fd.write(b"\0B<Plda> ")
+        fd.write(b"DV \x04" + struct.pack("<i", mean.shape[0]) + mean.tobytes())
+        fd.write(b"DM \x04" + struct.pack("<i", transform.shape[0]) + b"\x04" + struct.pack("<i", transform.shape[1]) + transform.tobytes())
+        fd.write(b"DV \x04" + struct.pack("<i", psi.shape[0]) + psi.tobytes())
+        fd.write(b"</Plda> ")
+    finally:
+        if fd is not file_or_fd:
+            fd.close()
+
+
+def read_plda(file_or_fd):
+    """(mean [d], transform [d, d], psi [d]) float64 of a binary Plda object as write_plda writes it; anything else is refused by name."""
+    fd = open_or_fd(file_or_fd)
+    try:
+        if fd.read(9) != b"\0B<Plda> ":
+            raise BadInputFormat("not a binary Plda object: it does not start with \\0B<Plda>")
+        mean = _read_vec_flt_binary(fd)
+        transform = _read_mat_binary(fd)
+        psi = _read_vec_flt_binary(fd)
+        if fd.read(8) != b"</Plda> ":
+            raise BadInputFormat("the Plda object does not end with </Plda>")
+        if mean.dtype != np.float64 or transform.dtype != np.float64 or psi.dtype != np.float64:
+            raise BadInputFormat("a Plda object holds doubles (DV / DM)")
+        if transform.shape != (mean.shape[0], mean.shape[0]) or psi.shape != mean.shape:
+            raise BadInputFormat("Plda: mean %s, transform %s and psi %s do not fit together" % (mean.shape, transform.shape, psi.shape))
+        return mean, transform, psi
+    finally:
+        if fd is not file_or_fd:
+            fd.close()
+
+
 def write_compressed_mat(file_or_fd, m, key=""):
     """Kaldi 'CM ' (kSpeechFeature) writer.  The reference has no CM writer (it only reads what
     Kaldi's copy-feats --compress=true produced); this follows compressed-matrix.cc

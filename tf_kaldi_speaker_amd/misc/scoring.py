@@ -2,7 +2,7 @@
 
 Host side: Kaldi trial lists, float-vector archives by key, EER and the normalised minimum detection cost.  Device side: CosineScorer,
 which keeps prepared (centred, unit-length) embedding matrices on the GPU and runs the three kernels of csrc/xv_score.hip through ops.py.
-Not here: LDA / PLDA, multi-utterance enrolment (spk2utt averaging), DET plots.
+LDA / PLDA and multi-utterance enrolment (spk2utt averaging): misc/backend.py.  Not here: DET plots.
 """
 import numpy as np
 

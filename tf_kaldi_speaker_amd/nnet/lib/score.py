@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Cosine scoring of a trial list on the GPU, with optional centring and adaptive symmetric score normalisation (AS-norm):
+"""Scoring of a trial list on the GPU: cosine with optional centring and adaptive symmetric score normalisation (AS-norm), or behind a
+trained LDA / PLDA back end, with optional multi-utterance enrolment:
 
-    python nnet/lib/score.py [-g GPU] [--center-on RSPECIFIER] [--cohort RSPECIFIER --top-k N] trials enrol_rspecifier test_rspecifier scores_out
+    python nnet/lib/score.py [-g GPU] [--center-on RSPECIFIER] [--cohort RSPECIFIER --top-k N]
+                             [--backend DIR --scoring {cosine,lda_cos,plda}] [--enrol-spk2utt FILE] trials enrol_rspecifier test_rspecifier scores_out
 
 The stage behind extract.py, for which the reference recipe goes to Kaldi (egs/voxceleb/v1/run.sh, cosine back end: ivector-mean,
 ivector-subtract-global-mean | ivector-normalize-length, ivector-compute-dot-products, compute-eer).  The rspecifiers name float-vector
@@ -11,7 +13,14 @@ tables as extract.py writes them (`ark:FILE` or `scp:FILE`); enrol_rspecifier ==
 largest scores of the enrolment / test vector against the cohort vectors.
 Output: `enrol test score` lines in trial order.  A trial whose key is missing from its table is logged and skipped; the number skipped is
 logged at the end.  When every kept trial carries a label, EER, minDCF08 and minDCF10 are logged.
-Not here: LDA / PLDA, multi-utterance enrolment (spk2utt averaging), DET plots.
+--backend DIR (nnet/lib/train_backend.py wrote it) with --scoring lda_cos | plda: every vector is centred on the back end's mean.vec (giving
+--center-on as well is refused), taken through transform.mat and length-normalised (run.sh stage 10-11: ivector-subtract-global-mean |
+transform-vec | ivector-normalize-length); lda_cos scores the cosine, plda the log-likelihood ratio of ivector-plda-scoring
+--normalize-length=true.  --scoring plda with --cohort is refused (AS-norm of PLDA scores: DESIGN.md section 7).
+--enrol-spk2utt FILE (any scoring mode): a model is the plain average of its speaker's raw enrolment vectors (ivector-mean ark:spk2utt), the
+trials name speakers on the enrol side, and with plda the number of utterances enters the score (--num-utts).
+Without the three new options the output is what it was before they existed, byte for byte.
+Not here: ivector-adapt-plda, AS-norm of PLDA scores, DET plots.
 """
 import sys
 
@@ -21,11 +30,53 @@ import _cli
 from misc import scoring
 
 
+def backend_scores(args, log, device, trials, enrol_keys, enrol, test_keys, test, same, center, cohort):
+    """The paths the options --backend and --enrol-spk2utt open: (scores, kept trials, skipped trials)."""
+    from misc import backend as B
+    be = B.Backend.load(args.backend) if args.backend else None
+    if be is not None and be.d != enrol.shape[1]:
+        sys.exit("dimension mismatch: enrol_rspecifier holds vectors of %d dimensions, the back end %s works on %d" % (enrol.shape[1], args.backend, be.d))
+    if be is None:      # cosine on averaged models: a back end that only centres
+        be = B.Backend(np.zeros(enrol.shape[1], np.float32) if center is None else scoring.center_mean(center).astype(np.float32))
+    if args.scoring == "plda" and be.plda is None:
+        sys.exit("--scoring plda: the back end %s holds no plda file" % args.backend)
+    scorer = B.BackendScorer(be, "plda" if args.scoring == "plda" else "lda_cos", device)
+    model_keys, models, counts = enrol_keys, enrol, None
+    if args.enrol_spk2utt:
+        model_keys, models, counts = scorer.enrol_average(enrol, enrol_keys, B.read_spk2utt(args.enrol_spk2utt), log)
+    same = same and not args.enrol_spk2utt
+    kept, ei, ti, skipped = scoring.index_trials(trials, model_keys, model_keys if same else test_keys)
+    for a, b, _ in skipped:
+        log.info("[INFO] Trial %s %s: %s, skip." % (a, b, "no vector for a key"))
+    if not kept:
+        return np.zeros(0, np.float32), kept, skipped
+    e_prep = scorer.prepare(models, n_utts=counts if args.scoring == "plda" else None)
+    t_prep = e_prep if same else scorer.prepare(test)
+    if args.scoring == "plda":
+        return scorer.score(e_prep, t_prep, ei, ti, enrol_n=counts), kept, skipped
+    if cohort is None:
+        return scorer.score(e_prep, t_prep, ei, ti), kept, skipped
+    # AS-norm behind the chain: the prepared tables are unit-length rows on a zero-padded pitch, what CosineScorer works on
+    cos = scoring.CosineScorer(device)
+    cos.d = be.dim
+    cos._cohort, cos.top_k = scorer.prepare(cohort), args.top_k
+    return cos.score(e_prep, t_prep, ei, ti), kept, skipped
+
+
 def main():
     log = _cli.logger()
-    args = _cli.parser_for("gpu", "center_on", "cohort", "top_k", "trials", "enrol_rspecifier", "test_rspecifier", "scores_out").parse_args()
+    args = _cli.parser_for("gpu", "center_on", "cohort", "top_k", "backend", "scoring", "enrol_spk2utt", "trials", "enrol_rspecifier",
+                           "test_rspecifier", "scores_out").parse_args()
     if args.cohort and args.top_k <= 0:
         sys.exit("--top-k must be positive (got %d)" % args.top_k)
+    if args.scoring != "cosine" and not args.backend:
+        sys.exit("--scoring %s needs --backend DIR (a directory written by train_backend.py)" % args.scoring)
+    if args.backend and args.scoring == "cosine":
+        sys.exit("--backend is given but --scoring is cosine: choose --scoring lda_cos or plda")
+    if args.backend and args.center_on:
+        sys.exit("--backend and --center-on exclude each other: with a back end the centre is its mean.vec")
+    if args.scoring == "plda" and args.cohort:
+        sys.exit("--cohort with --scoring plda is not supported: AS-norm of PLDA scores is out of scope (DESIGN.md section 7)")
     import torch
     device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
     trials = scoring.read_trials(args.trials)
@@ -44,11 +95,14 @@ def main():
     for name, table in tables:
         if table.shape[1] != d:
             sys.exit("dimension mismatch: enrol_rspecifier holds vectors of %d dimensions, %s of %d" % (d, name, table.shape[1]))
-    kept, ei, ti, skipped = scoring.index_trials(trials, enrol_keys, test_keys)
-    for a, b, _ in skipped:
-        log.info("[INFO] Trial %s %s: %s, skip." % (a, b, "no vector for a key"))
-    scores = np.zeros(0, np.float32)
-    if kept:
+    if args.backend or args.enrol_spk2utt:
+        scores, kept, skipped = backend_scores(args, log, device, trials, enrol_keys, enrol, test_keys, test, same, center, cohort)
+    else:
+        kept, ei, ti, skipped = scoring.index_trials(trials, enrol_keys, test_keys)
+        for a, b, _ in skipped:
+            log.info("[INFO] Trial %s %s: %s, skip." % (a, b, "no vector for a key"))
+        scores = np.zeros(0, np.float32)
+    if kept and not (args.backend or args.enrol_spk2utt):
         scorer = scoring.CosineScorer(device, center=None if center is None else scoring.center_mean(center))
         e_prep = scorer.prepare(enrol)
         t_prep = e_prep if same else scorer.prepare(test)

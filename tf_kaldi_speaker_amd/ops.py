@@ -140,6 +140,135 @@ def score_cohort_stats(x, cohort, d, top_k, ws_bytes=None):
     return stats
 
 
+def _host_int(a, what, lo, hi):
+    """A 1-D host integer array with every value in [lo, hi), as a contiguous NumPy array (its dtype unchanged)."""
+    import numpy as np
+    a = np.asarray(a)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+        raise ValueError("%s must be a non-empty 1-D integer array" % what)
+    if a.min() < lo or a.max() >= hi:
+        raise IndexError("%s holds a value outside %d .. %d" % (what, lo, hi - 1))
+    return a
+
+
+def backend_group_means(x, d, offsets, rows, want32=True):
+    """Averages of groups of rows of x [n, >= d] (xv_backend_group_means): group g = rows[offsets[g]:offsets[g + 1]], added in list order in
+    double.  offsets, rows: HOST integer arrays (the kernel does not check them, so they are checked here: an empty group and a row outside
+    x are refused).  -> (mean64 [groups, d] float64, mean32 [groups, d rounded up to 4] float32 with zero padding, or None)."""
+    import numpy as np
+    n, ldx = _pitched(x, "backend_group_means: x")
+    offsets = np.asarray(offsets)
+    if offsets.ndim != 1 or offsets.size < 2 or offsets.dtype.kind not in "iu" or offsets[0] != 0:
+        raise ValueError("backend_group_means: offsets must be a 1-D integer array [groups + 1] that starts at 0")
+    counts = np.diff(offsets.astype(np.int64))
+    if counts.min() <= 0:
+        raise ValueError("backend_group_means: group %d is empty" % int(np.argmax(counts <= 0)))
+    rows = _host_int(rows, "backend_group_means: rows", 0, n)
+    if rows.size != int(offsets[-1]):
+        raise ValueError("backend_group_means: offsets end at %d, rows holds %d indices" % (int(offsets[-1]), rows.size))
+    groups = offsets.size - 1
+    off_d = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(x.device)
+    rows_d = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(x.device)
+    mean64 = torch.empty((groups, int(d)), dtype=torch.float64, device=x.device)
+    mean32 = torch.empty((groups, (int(d) + 3) // 4 * 4), dtype=torch.float32, device=x.device) if want32 else None
+    _lib.call("xv_backend_group_means", _s(), _p(x), n, ldx, int(d), _p(off_d), _p(rows_d), groups, C.c_int64(rows.size), _p(mean64), _p(mean32),
+              mean32.shape[1] if want32 else 0)
+    return mean64, mean32
+
+
+def backend_center(x, d=None, mean=None, out=None):
+    """Rows of x [rows, >= d] minus mean [d] (None: a copy) on a zero-padded pitch (xv_backend_center); out as in score_prepare."""
+    rows, ldx = _pitched(x, "backend_center: x")
+    d = x.shape[1] if d is None else int(d)
+    if out is None:
+        out = torch.empty((rows, (d + 3) // 4 * 4), dtype=torch.float32, device=x.device)
+    _, ldy = _pitched(out, "backend_center: out")
+    if out.shape[1] != ldy:
+        raise ValueError("backend_center: out must be the whole [rows, pitch] buffer (its padding columns are written)")
+    if mean is not None and (mean.dtype != torch.float32 or mean.numel() != d or not mean.is_contiguous()):
+        raise ValueError("backend_center: mean must be %d contiguous float32 values" % d)
+    _lib.call("xv_backend_center", _s(), _p(x), rows, d, ldx, _p(mean), _p(out), ldy)
+    return out
+
+
+def backend_scatter_workspace_bytes(n, d):
+    return int(_lib.load().xv_backend_scatter_workspace_bytes(int(n), int(d)))
+
+
+def backend_scatter(x, d=None, mean=None, ws_bytes=None):
+    """[d, d] float64 = sum over the rows of x [n, >= d] of v v^T, v = x[r][:d] - mean (xv_backend_scatter).  ws_bytes: size of the
+    workspace handed to the call (default: what xv_backend_scatter_workspace_bytes asks for; fewer is refused by the library)."""
+    n, ldx = _pitched(x, "backend_scatter: x")
+    d = x.shape[1] if d is None else int(d)
+    if mean is not None and (mean.dtype != torch.float32 or mean.numel() != d or not mean.is_contiguous()):
+        raise ValueError("backend_scatter: mean must be %d contiguous float32 values" % d)
+    if ws_bytes is None:
+        ws_bytes = backend_scatter_workspace_bytes(n, d)
+    ws = torch.empty(max(int(ws_bytes) // 4, 1), dtype=torch.float32, device=x.device)
+    c64 = torch.empty((max(d, 1), max(d, 1)), dtype=torch.float64, device=x.device)
+    _lib.call("xv_backend_scatter", _s(), _p(x), n, d, ldx, _p(mean), _p(c64), _p(ws), C.c_size_t(int(ws_bytes)))
+    return c64
+
+
+def backend_plda_normalize(u, d, psi, n_utts=None, out=None):
+    """u[r][:d] * sqrt(d / sum_c u_c^2 / (psi_c + 1 / n_utts[r])) (xv_backend_plda_normalize).  psi: device float32 [d]; n_utts: HOST
+    integer array [rows] (None: 1 everywhere), checked positive here.  out: the [rows, pitch] tensor to write, u itself for in place;
+    default a new tensor on the pitch d rounded up to 4.  Padding columns come back zero."""
+    import numpy as np
+    rows, ldu = _pitched(u, "backend_plda_normalize: u")
+    d = int(d)
+    if psi.dtype != torch.float32 or psi.numel() != d or not psi.is_contiguous():
+        raise ValueError("backend_plda_normalize: psi must be %d contiguous float32 values" % d)
+    if out is None:
+        out = torch.empty((rows, (max(d, 1) + 3) // 4 * 4), dtype=torch.float32, device=u.device)
+    _, ldo = _pitched(out, "backend_plda_normalize: out")
+    if out.shape[1] != ldo:
+        raise ValueError("backend_plda_normalize: out must be the whole [rows, pitch] buffer (its padding columns are written)")
+    n_d = None
+    if n_utts is not None:
+        n_utts = _host_int(n_utts, "backend_plda_normalize: n_utts", 1, 1 << 31)
+        if n_utts.size != rows:
+            raise ValueError("backend_plda_normalize: n_utts must hold one count per row (%d, got %d)" % (rows, n_utts.size))
+        n_d = torch.from_numpy(np.ascontiguousarray(n_utts, dtype=np.int32)).to(u.device)
+    _lib.call("xv_backend_plda_normalize", _s(), _p(u), rows, d, ldu, _p(psi), _p(n_d), _p(out), ldo)
+    return out
+
+
+def backend_plda_trials(e, t, d, ei, ti, nidx, coef, g, k0):
+    """PLDA log-likelihood ratios of trials (xv_backend_plda_trials): enrol row ei[j] of e against test row ti[j] of t, both transformed
+    and normalised.  coef: device float32 [n_distinct, 2, ldc]; g: [>= d]; k0: [n_distinct]; nidx: HOST integer array [enrol rows] into the
+    table.  ei, ti, nidx are checked here, before the upload: the kernel does not check indices."""
+    import numpy as np
+    ne, lde = _pitched(e, "backend_plda_trials: e")
+    nt, ldt = _pitched(t, "backend_plda_trials: t")
+    d = int(d)
+    if coef.dim() != 3 or coef.shape[1] != 2 or coef.dtype != torch.float32 or not coef.is_contiguous() or coef.shape[2] < d:
+        raise ValueError("backend_plda_trials: coef must be a contiguous float32 [n_distinct, 2, >= d] tensor")
+    nq, ldc = coef.shape[0], coef.shape[2]
+    if g.dtype != torch.float32 or g.numel() < d or not g.is_contiguous() or k0.dtype != torch.float32 or k0.numel() != nq or not k0.is_contiguous():
+        raise ValueError("backend_plda_trials: g must hold >= d and k0 n_distinct contiguous float32 values")
+    ei = _host_int(ei, "backend_plda_trials: ei", 0, ne)
+    ti = _host_int(ti, "backend_plda_trials: ti", 0, nt)
+    nidx = _host_int(nidx, "backend_plda_trials: nidx", 0, nq)
+    if ei.shape != ti.shape or nidx.size != ne:
+        raise ValueError("backend_plda_trials: ei and ti must be of one length, nidx one entry per enrol row")
+    dev = e.device
+    ei_d, ti_d, nidx_d = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev) for a in (ei, ti, nidx))
+    out = torch.empty(ei.size, dtype=torch.float32, device=dev)
+    _lib.call("xv_backend_plda_trials", _s(), _p(e), lde, ne, _p(t), ldt, nt, d, _p(ei_d), _p(ti_d), C.c_int64(ei.size), _p(nidx_d), _p(coef), ldc,
+              nq, _p(g), _p(k0), _p(out))
+    return out
+
+
+def backend_affine(x, wt, bias):
+    """x [rows, c_pad] (zero padding up to a pitch that is a multiple of 4) times wt [o, c_pad]^T plus bias [o]: the project's fp32 NT GEMM
+    (xv_affine_forward, k = 1).  The caller pads wt / bias with zero rows so that o is a multiple of 4: the result is then a GEMM operand."""
+    rows, ld = _pitched(x, "backend_affine: x")
+    if x.shape[1] != ld or wt.shape[1] != ld or not wt.is_contiguous():
+        raise ValueError("backend_affine: x must be the whole [rows, pitch] buffer and wt [o, pitch] contiguous")
+    return affine_forward(x.view(rows, 1, ld), 1, wt, bias, wt.shape[0])
+
+
 def prep_weight_fwd(kernel, c_pad):
     """kernel: [k, C, O] -> [O, k*c_pad]"""
     k, c, o = kernel.shape

@@ -12,6 +12,7 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py segment                          the segment-level GEMMs: one-launch form (xv_skinny.hip) against GEMM + slab-sum launches
   python tools/bench_kernel.py staged                           plain step vs the staged (multi-GPU) backward, without / with a one-rank RCCL all-reduce
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
+  python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
 
 Environment: XV_DATA_SCALE=0 (all-zero operands: DVFS check), XV_B (chunks, gemm16), ITERS (segment), XV_LIB (another build of the library).
 """
@@ -310,7 +311,39 @@ def cmd_score(argv):
               % (us_all, (n + tile - 1) // tile, tile, us_gemm, fl / us_gemm / 1e6, us_gemm / us_all, us_all - us_gemm, 1.0 - us_gemm / us_all), flush=True)
 
 
-COMMANDS = {"score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+def cmd_backend(argv):
+    """Time per device op of the LDA / PLDA back end: scatter (the TN GEMM's FLOPs against the whole op: the rest is the centred copy and the
+    slab sums), per-speaker means (gathered rows against the 8 TB/s peak), PLDA normalisation (one read, one write) and the trial kernel
+    (2 rows of dim floats, the coefficient rows, three indices and one score per trial)."""
+    from tf_kaldi_speaker_amd import ops
+    from tf_kaldi_speaker_amd.misc import backend as B
+    d, dim = 512, 200
+    sizes = {"small": ("VoxCeleb1-sized", 148642, 1211, 37720), "large": ("VoxCeleb2-dev-sized", 1092009, 5994, 581480)}
+    for key in (argv or ["small", "large"]):
+        name, n, speakers, m = sizes[key]
+        x, mean = rnd(n, d), rnd(d)
+        print("%s: %d vectors of %d speakers, %d trials, d = %d, dim = %d" % (name, n, speakers, m, d, dim), flush=True)
+        us = timeit(lambda: ops.backend_scatter(x, mean=mean), 5, 1)
+        print("  scatter (centred)       %9.1f us  %.1f TF (2 n d^2)" % (us, 2.0 * n * d * d / us / 1e6), flush=True)
+        offsets = np.linspace(0, n, speakers + 1).astype(np.int64)
+        rows = rs.permutation(n)
+        us = timeit(lambda: ops.backend_group_means(x, d, offsets, rows), 5, 1)
+        print("  group means             %9.1f us  %.2f TB/s (gathered rows; includes the index upload)" % (us, n * d * 4.0 / us / 1e6), flush=True)
+        psi = np.sort(rs.uniform(0.05, 5.0, dim))[::-1].copy()
+        u, psi_d = rnd(n, dim), torch.from_numpy(psi.astype(np.float32)).cuda()
+        out = torch.empty_like(u)
+        us = timeit(lambda: ops.backend_plda_normalize(u, dim, psi_d, out=out), 10, 2)
+        print("  plda_normalize          %9.1f us  %.2f TB/s (one read, one write)" % (us, 2.0 * n * dim * 4 / us / 1e6), flush=True)
+        n_e = rs.choice([1, 3, 8], n)
+        distinct, nidx = np.unique(n_e, return_inverse=True)
+        coef, g, k0 = (torch.from_numpy(a).cuda() for a in B.plda_coefficients(psi, distinct))
+        ei, ti = rs.randint(0, n, m), rs.randint(0, n, m)
+        us = timeit(lambda: ops.backend_plda_trials(out, out, dim, ei, ti, nidx, coef, g, k0), 5, 1)
+        mb = m * (2.0 * dim * 4 + 16) / 1e6
+        print("  plda_trials             %9.1f us  %.2f TB/s of gathered rows (includes the index checks and uploads of ops.py)" % (us, mb / us), flush=True)
+
+
+COMMANDS = {"backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
