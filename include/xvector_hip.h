@@ -36,7 +36,8 @@ extern "C" {
 /* 2: xv_config starts with struct_bytes (round 5).  3: xv_engine_arena_bytes (round 6).  Bumped whenever xv_config's layout or an entry point's signature changes: a host
  * built against another header must fail at load (xv_abi_version) or at xv_engine_create (struct_bytes), never read fields past the end
  * of a shorter struct.  xv_frontend came later and left it at 3: a new entry point beside the old ones, xv_config untouched - a host
- * built against the earlier header runs unchanged against this library. */
+ * built against the earlier header runs unchanged against this library.  The same holds for xv_mfcc_num_frames, xv_mfcc_table_floats,
+ * xv_mfcc_tables, xv_mfcc and xv_energy_vad, which bring their own struct (xv_mfcc_config, size-checked like xv_config). */
 #define XV_ABI_VERSION 3
 
 const char* xv_last_error(void);
@@ -119,6 +120,71 @@ int xv_cm_decode_ragged(void* stream, const uint8_t* packed, const int64_t* offs
 int xv_frontend(void* stream, const float* x, const int32_t* rows_in, int b, int t_in, int d, int cmn_window, const uint8_t* masks,
                 size_t mask_bytes, const int64_t* mask_offsets, const int32_t* first, const int32_t* count, int t_out, float* out,
                 int32_t* rows_out, void* ws, size_t ws_bytes);
+
+/* MFCC features and the energy VAD from waveforms: the first stage of the recipe, for which the reference goes to Kaldi
+ * (egs/voxceleb/v1/run.sh:59-63, egs/sre/v1/run.sh:103-115: steps/make_mfcc.sh --mfcc-config conf/mfcc.conf = compute-mfcc-feats,
+ * sid/compute_vad_decision.sh = compute-vad-decision).  Kaldi is not available where this project is built and tested: parity is BY
+ * RESTATEMENT - the rules below are the specification, tests/mfcc_ref.py restates them in fp64 NumPy and the kernels are held against
+ * that.  Dither is not supported (this is the --dither=0 program).  No floating-point atomics, no cross-workgroup hand-over: the output
+ * bits depend on the shape of the call only.
+ *
+ * With sf = sample_frequency: L = (int)(sf * 0.001 * frame_length_ms) samples per frame, S the same of frame_shift_ms, N the smallest
+ * power of two >= L; N must be 128, 256, 512 or 1024.  An utterance of n int16 samples (used as floats, unscaled) has
+ *   T = snip_edges ? (n < L ? 0 : 1 + (n - L) / S) : (n + S / 2) / S   frames (integer division); frame f starts at sample
+ *   snip_edges ? f * S : S * f + S / 2 - L / 2; an index i outside [0, n) is replaced by -i - 1 (i < 0) or 2 n - 1 - i until it is inside.
+ * Per frame: subtract sum / L (remove_dc_offset); logE = log(max(sum w^2, FLT_EPSILON)) (raw_energy); w[i] -= p w[i - 1] for i = L - 1 ..
+ * 1, w[0] -= p w[0]; multiply by the Povey window (0.5 - 0.5 cos(2 pi i / (L - 1)))^0.85; logE by the same formula here when raw_energy
+ * is off; zero-pad to N, real FFT, P[k] = |X[k]|^2; mel energies E[m] = sum_k W[m][k] P[k] over k < N / 2 (the Nyquist bin is not used)
+ * with mel(f) = 1127 ln(1 + f / 700), bin m's left / centre / right at mel(low) + (m, m + 1, m + 2) (mel(high) - mel(low)) / (bins + 1),
+ * W non-zero only where left < mel(k sf / N) < right: (mel - left) / (centre - left) if mel <= centre else (right - mel) / (right -
+ * centre); logmel = log(max(E, FLT_EPSILON)); DCT-II (row 0 sqrt(1 / bins), row c sqrt(2 / bins) cos(pi / bins (m + 0.5) c)), first
+ * num_ceps rows, times the lifter 1 + 0.5 Q sin(pi c / Q) (Q = cepstral_lifter, 0 = none); use_energy: coefficient 0 = logE, floored
+ * at log(energy_floor) when energy_floor > 0. */
+typedef struct xv_mfcc_config {
+    int32_t struct_bytes;             /* = sizeof(xv_mfcc_config) of the header the host was built against; anything else is refused */
+    float sample_frequency;           /* 16000 */
+    float frame_length_ms;            /* 25 */
+    float frame_shift_ms;             /* 10 */
+    int32_t num_mel_bins;             /* 30; <= 128 */
+    int32_t num_ceps;                 /* 30; <= num_mel_bins */
+    float low_freq;                   /* 20 */
+    float high_freq;                  /* 7600; <= 0: the Nyquist frequency plus this value */
+    int32_t snip_edges;               /* 0 (the VoxCeleb conf sets false; Kaldi's own default is true) */
+    float preemphasis;                /* 0.97 */
+    int32_t remove_dc_offset;         /* 1 */
+    float cepstral_lifter;            /* 22 */
+    int32_t use_energy;               /* 1 */
+    int32_t raw_energy;               /* 1 */
+    float energy_floor;               /* 0 */
+} xv_mfcc_config;
+/* T of an utterance of `samples` samples; -1 (xv_last_error) for a configuration that is refused.  Host arithmetic. */
+int64_t xv_mfcc_num_frames(const xv_mfcc_config* cfg, int64_t samples);
+/* The constant tables of xv_mfcc, computed in double and rounded to fp32 once - host arithmetic, no GPU call: a C host builds them
+ * without Python and copies them to the device.  xv_mfcc_table_floats: their size (0 for a refused configuration); xv_mfcc_tables
+ * writes them into host_out (`floats` must be that size).  Layout, in floats, one block behind the other:
+ *   window   [L]            the Povey window
+ *   twiddles [N / 2][2]     (cos, -sin)(2 pi k / N), k < N / 2
+ *   mel_bins [bins][3]      per mel bin: the first FFT bin with a non-zero weight, how many consecutive FFT bins have one, the offset
+ *                           of the bin's weights in the next block (whole numbers stored as floats; an empty bin is 0, 0, its offset)
+ *   mel_w    [sum of counts] the non-zero weights, bin after bin
+ *   dct      [num_ceps][bins] DCT row c times the lifter of c */
+size_t xv_mfcc_table_floats(const xv_mfcc_config* cfg);
+int xv_mfcc_tables(const xv_mfcc_config* cfg, float* h_out, size_t floats);
+/* out[i][f][:] = the MFCC of frame f of utterance i for f < rows_out[i] = min(T_i, t_out), zero rows behind - fp32 [b][t_out][num_ceps],
+ * the layout xv_cm_decode_ragged leaves, so xv_frontend and xv_engine_forward_lengths take it as it is.  pcm: device int16, the samples
+ * of all utterances back to back; utterance i starts at sample offsets[i] (device int64 [b], any 2-byte alignment) and has samples[i]
+ * samples (device int32 [b]; <= 0: no frame) - the caller guarantees that every [offsets[i], offsets[i] + samples[i]) lies inside the
+ * buffer (ops.mfcc checks the host arrays before the upload).  tables_dev: what xv_mfcc_tables wrote for the same cfg, on the device.
+ * One launch: a wave per frame, four waves walking sixteen frames per workgroup behind one copy of the tables into LDS. */
+int xv_mfcc(void* stream, const xv_mfcc_config* cfg, const float* tables_dev, const int16_t* pcm, const int64_t* offsets,
+            const int32_t* samples, int b, int t_out, float* out, int32_t* rows_out);
+/* compute-vad-decision on a padded batch of feature matrices x [b][t][d], piece i holding rows[i] frames (T below; clamped to 0 .. t),
+ * e[f] = x[i][f][0]: thr = threshold + mean_scale * mean(e) (the mean summed in double in a fixed order; mean_scale == 0: threshold
+ * alone); frame f is voiced iff #{f' in [f - c, f + c] and [0, T) : e[f'] > thr} >= (size of that window) * proportion, c =
+ * frames_context.  masks: one byte per frame [b][t], 1 or 0, bytes behind rows[i] zero - the mask form xv_frontend reads, with
+ * mask_offsets[i] = i * t.  rows: device int32 [b].  One workgroup per piece.  The VoxCeleb vad.conf: 5.5, 0.5, 2, 0.12. */
+int xv_energy_vad(void* stream, const float* x, const int32_t* rows, int b, int t, int d, float threshold, float mean_scale,
+                  int frames_context, float proportion, uint8_t* masks);
 
 /* Cosine trial scoring with adaptive symmetric score normalisation (AS-norm) on embedding matrices: the stage behind extract.py, for
  * which the reference recipe goes to Kaldi (ivector-mean | ivector-subtract-global-mean | ivector-normalize-length, then

@@ -77,6 +77,38 @@ class XvConfig(C.Structure):
     ]
 
 
+class XvMfccConfig(C.Structure):
+    """Mirror of `struct xv_mfcc_config` (include/xvector_hip.h) with its defaults - the VoxCeleb conf/mfcc.conf, dither 0; struct_bytes is
+    filled in on construction."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("sample_frequency", C.c_float),
+        ("frame_length_ms", C.c_float),
+        ("frame_shift_ms", C.c_float),
+        ("num_mel_bins", C.c_int32),
+        ("num_ceps", C.c_int32),
+        ("low_freq", C.c_float),
+        ("high_freq", C.c_float),
+        ("snip_edges", C.c_int32),
+        ("preemphasis", C.c_float),
+        ("remove_dc_offset", C.c_int32),
+        ("cepstral_lifter", C.c_float),
+        ("use_energy", C.c_int32),
+        ("raw_energy", C.c_int32),
+        ("energy_floor", C.c_float),
+    ]
+    DEFAULTS = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, num_mel_bins=30, num_ceps=30, low_freq=20.0,
+                    high_freq=7600.0, snip_edges=0, preemphasis=0.97, remove_dc_offset=1, cepstral_lifter=22.0, use_energy=1, raw_energy=1,
+                    energy_floor=0.0)
+
+    def __init__(self, *args, **kw):
+        if args:
+            raise TypeError("XvMfccConfig takes keyword arguments only (its first field is struct_bytes, filled in here)")
+        super(XvMfccConfig, self).__init__(**dict(self.DEFAULTS, **kw))
+        self.struct_bytes = C.sizeof(XvMfccConfig)
+
+
 LOSS_KINDS = {
     "softmax": 0,
     "asoftmax": 1,
@@ -160,6 +192,11 @@ SIGNATURES = {
     "xv_cm_decode": (_I, [_VP, _VP, _I, _I, _I, _SZ, _VP]),
     "xv_cm_decode_ragged": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "xv_frontend": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _SZ, _VP, _VP, _VP, _I, _VP, _VP, _VP, _SZ]),
+    "xv_mfcc_num_frames": (C.c_int64, [_VP, C.c_int64]),
+    "xv_mfcc_table_floats": (_SZ, [_VP]),
+    "xv_mfcc_tables": (_I, [_VP, _VP, _SZ]),
+    "xv_mfcc": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
+    "xv_energy_vad": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _F, _I, _F, _VP]),
     "xv_score_prepare": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I]),
     "xv_score_trials": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "xv_score_cohort_workspace_bytes": (_SZ, [_I, _I, _I]),

@@ -645,10 +645,17 @@ def read_plda(file_or_fd):
             fd.close()
 
 
-def write_compressed_mat(file_or_fd, m, key=""):
+def write_compressed_mat(file_or_fd, m, key="", header="quartiles"):
     """Kaldi 'CM ' (kSpeechFeature) writer.  The reference has no CM writer (it only reads what
     Kaldi's copy-feats --compress=true produced); this follows compressed-matrix.cc
-    ComputeColHeader / FloatToChar so that synthetic training data can be produced without Kaldi."""
+    ComputeColHeader / FloatToChar so that synthetic training data can be produced without Kaldi.
+    header: where a column's four header points lie.  "quartiles" (the default): its minimum, 25th and 75th percentile and maximum, as
+    Kaldi's ComputeColHeader chooses them - 64 / 128 / 63 codes between them, so where an outer quarter of the values spans most of the
+    column's range the rounding error reaches (max - min) / 126.  "uniform": minimum, minimum + range / 4, minimum + 3 range / 4, maximum -
+    the codes are evenly spaced, the rounding error is at most (max - min) / 504 plus the header's own uint16 grid, (matrix range) / 65535.
+    The decoder reads the points from the file, so every 'CM ' reader decodes both."""
+    if header not in ("quartiles", "uniform"):
+        raise ValueError("write_compressed_mat: header must be 'quartiles' or 'uniform' (got %r)" % (header,))
     m = np.asarray(m, np.float32)
     rows, cols = m.shape
     gmin, gmax = float(m.min()), float(m.max())
@@ -664,7 +671,14 @@ def write_compressed_mat(file_or_fd, m, key=""):
     srt = np.sort(m, axis=0)
     q = [0, rows // 4, (3 * rows) // 4, rows - 1] if rows >= 5 else None
     hdr = np.zeros(cols, _COL_HDR)
-    if q is not None:
+    if header == "uniform":
+        # the end points are rounded outwards on the uint16 grid, so no value is clipped: a column whose range is near that grid (a
+        # constant log-energy beside cepstra of +-100) keeps an error of half a code of the points it got, not half a grid unit
+        f0, f100 = ((srt[i].astype(np.float64) - float(gmin)) / float(grange) * 65535.0 for i in (0, -1))
+        p0, p100 = np.clip(np.floor(f0), 0, 65535), np.clip(np.ceil(f100), 0, 65535)
+        p = [p0.astype(np.uint16), np.rint(p0 + 0.25 * (p100 - p0)).astype(np.uint16), np.rint(p0 + 0.75 * (p100 - p0)).astype(np.uint16),
+             p100.astype(np.uint16)]
+    elif q is not None:
         p = [to_u16(srt[i]) for i in q]
     else:   # compressed-matrix.cc small-matrix branch: spread the available order statistics
         p0 = to_u16(srt[0])

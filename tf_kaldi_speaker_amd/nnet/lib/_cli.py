@@ -43,7 +43,17 @@ ARGUMENTS = {
     "lda_dim": (("--lda-dim",), dict(type=int, default=200, help="Dimensions the LDA keeps (ivector-compute-lda --dim).")),
     "no_lda": (("--no-lda",), dict(action="store_true", help="Train the PLDA on the centred, length-normalised vectors without an LDA in front.")),
     "num_em_iters": (("--num-em-iters",), dict(type=int, default=10, help="EM iterations of the PLDA estimation (ivector-compute-plda).")),
+    "mfcc_config": (("--mfcc-config",), dict(type=str, default="", help="Kaldi conf file of compute-mfcc-feats options (--name=value lines).  Empty: "
+                                                                        "the VoxCeleb conf/mfcc.conf values.")),
+    "vad_config": (("--vad-config",), dict(type=str, default="", help="Kaldi conf file of compute-vad-decision options.  Empty: the VoxCeleb "
+                                                                      "conf/vad.conf values.")),
+    "compress": (("--compress",), dict(type=str, default="true", choices=("true", "false"),
+                                       help="true: 'CM ' compressed feature matrices (copy-feats --compress=true); false: 'FM '.")),
+    "write_utt2num_frames": (("--write-utt2num-frames",), dict(type=str, default="", help="Write `key frames` lines to this file.")),
     # positionals
+    "wav_scp": (("wav_scp",), dict(type=str, help="Kaldi wav.scp: `key rxfilename` per line, the rxfilename a RIFF PCM-16 file or `command |`.")),
+    "feats_wspecifier": (("feats_wspecifier",), dict(type=str, help="`ark,scp:feats.ark,feats.scp` (or `ark:feats.ark`): the feature table.")),
+    "vad_wspecifier": (("vad_wspecifier",), dict(type=str, help="`ark,scp:vad.ark,vad.scp` (or `ark:vad.ark`): the table of VAD decisions.")),
     "train_rspecifier": (("train_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the training vectors.")),
     "spk2utt": (("spk2utt",), dict(type=str, help="Kaldi spk2utt of the training vectors: `speaker utt1 utt2 ...` per line.")),
     "out_dir": (("out_dir",), dict(type=str, help="The back-end directory to write (mean.vec, transform.mat, plda).")),

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""MFCC features and energy VAD decisions from a wav.scp on the GPU:
+
+    python nnet/lib/make_mfcc.py [-g GPU] [--mfcc-config conf/mfcc.conf] [--vad-config conf/vad.conf] [--compress {true,false}]
+                                 [--write-utt2num-frames FILE] wav.scp ark,scp:feats.ark,feats.scp ark,scp:vad.ark,vad.scp
+
+The first stage of the recipe, for which the reference goes to Kaldi (egs/voxceleb/v1/run.sh:59-63: steps/make_mfcc.sh --mfcc-config
+conf/mfcc.conf = compute-mfcc-feats | copy-feats --compress=true, then sid/compute_vad_decision.sh = compute-vad-decision).  wav.scp:
+`key rxfilename` lines, the rxfilename a RIFF PCM-16 file or a `command |` that writes one.  The feature archive ('CM ' matrices with
+--compress=true, the default; 'FM ' otherwise) and the archive of VAD decisions (float vectors of 1 / 0 per frame) are what
+extract.py --cmn-window 300 --vad scp:vad.scp and the loaders read.  `ark:FILE` alone writes no scp.  The 'CM ' matrices carry evenly spaced
+header points per column, not copy-feats' quartiles: the same format for every reader, and a rounding error below (max - min) / 255 of
+the column whatever its distribution (dataset/kaldi_io.py write_compressed_mat, header="uniform").
+This is the --dither=0 program: the conf may say --dither=0, any other value is refused (misc/features.py says why); so is every other
+option of the two Kaldi programs that is not implemented, by name.  An utterance too short for one frame is logged and skipped.
+"""
+import sys
+import time
+
+import numpy as np
+
+import _cli
+from misc import features
+from dataset import kaldi_io
+
+# utterances read before they go to the GPU together (FeatureExtractor cuts them into calls that fit its workspace)
+WINDOW_UTTERANCES = 256
+WINDOW_SAMPLES = 64 << 20
+
+
+class _Table(object):
+    """A Kaldi table writer for `ark:FILE` or `ark,scp:ARK,SCP`: write(key, emit) calls emit(fd, key) and records the offset behind "key "."""
+
+    def __init__(self, wspecifier, what):
+        kind, _, rest = wspecifier.partition(":")
+        kinds = kind.split(",")
+        if not rest or "ark" not in kinds or any(k not in ("ark", "scp") for k in kinds):
+            sys.exit("%s: `ark:FILE` or `ark,scp:ARK,SCP` is expected (got %s)" % (what, wspecifier))
+        names = rest.split(",")
+        if len(names) != len(kinds):
+            sys.exit("%s: %s names %d file(s) for %d table type(s)" % (what, wspecifier, len(names), len(kinds)))
+        self.ark_path = names[kinds.index("ark")]
+        self.ark = open(self.ark_path, "wb")
+        self.scp = open(names[kinds.index("scp")], "w") if "scp" in kinds else None
+
+    def write(self, key, emit):
+        at = self.ark.tell() + len(key) + 1
+        emit(self.ark, key)
+        if self.scp is not None:
+            self.scp.write("%s %s:%d\n" % (key, self.ark_path, at))
+
+    def close(self):
+        self.ark.close()
+        if self.scp is not None:
+            self.scp.close()
+
+
+def main():
+    log = _cli.logger()
+    args = _cli.parser_for("gpu", "mfcc_config", "vad_config", "compress", "write_utt2num_frames", "wav_scp", "feats_wspecifier",
+                           "vad_wspecifier").parse_args()
+    try:
+        mfcc = features.MfccOptions.from_conf(args.mfcc_config) if args.mfcc_config else features.MfccOptions()
+        vad = features.VadOptions.from_conf(args.vad_config) if args.vad_config else features.VadOptions()
+    except ValueError as e:
+        sys.exit(str(e))
+    import torch
+    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    log.info("[INFO] MFCC without dither (--dither=0): on digital silence the features sit at the FLT_EPSILON floors; --energy-floor lifts the energy.")
+    fx = features.FeatureExtractor(mfcc, vad, device)
+    feats_out, vad_out = _Table(args.feats_wspecifier, "feats_wspecifier"), _Table(args.vad_wspecifier, "vad_wspecifier")
+    counts = open(args.write_utt2num_frames, "w") if args.write_utt2num_frames else None
+    # 'CM ' with evenly spaced header points: the rounding error stays below (max - min) / 255 of a column whatever its distribution
+    # (Kaldi's quartile points let it reach (max - min) / 126); every 'CM ' reader decodes it (kaldi_io.write_compressed_mat)
+    if args.compress == "true":
+        def write_mat(fd, m, key):
+            kaldi_io.write_compressed_mat(fd, m, key=key, header="uniform")
+    else:
+        write_mat = kaldi_io.write_mat
+    stats = {"utts": 0, "frames": 0, "voiced": 0, "skipped": 0, "t0": time.time()}
+    window, window_samples = [], 0
+
+    def flush():
+        results = fx.extract([w for _, w in window])
+        for (key, w), (feats, decisions) in zip(window, results):
+            if feats.shape[0] == 0:
+                log.info("[INFO] Key %s has %d samples, too few for one frame, skip." % (key, len(w)))
+                stats["skipped"] += 1
+                continue
+            log.info("[INFO] Key %s: %d samples, %d frames, %d voiced." % (key, len(w), feats.shape[0], int(decisions.sum())))
+            feats_out.write(key, lambda fd, k: write_mat(fd, feats, key=k))
+            vad_out.write(key, lambda fd, k: kaldi_io.write_vec_flt(fd, decisions, key=k))
+            if counts is not None:
+                counts.write("%s %d\n" % (key, feats.shape[0]))
+            stats["utts"] += 1
+            stats["frames"] += feats.shape[0]
+            stats["voiced"] += int(decisions.sum())
+        del window[:]
+
+    with open(args.wav_scp, "r") as scp:
+        for line in scp:
+            if not line.strip():
+                continue
+            parts = line.strip().split(None, 1)
+            if len(parts) != 2:
+                sys.exit("%s: `key rxfilename` is expected, got `%s`" % (args.wav_scp, line.strip()))
+            try:
+                wav = features.read_wav(parts[1], mfcc, parts[0])
+            except ValueError as e:
+                sys.exit(str(e))
+            window.append((parts[0], wav))
+            window_samples += len(wav)
+            if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
+                flush()
+                window_samples = 0
+    flush()
+    feats_out.close()
+    vad_out.close()
+    if counts is not None:
+        counts.close()
+    log.info("[INFO] Computed features of %d utterances (%d frames, %d voiced) in %.2f s, skipped %d."
+             % (stats["utts"], stats["frames"], stats["voiced"], time.time() - stats["t0"], stats["skipped"]))
+
+
+if __name__ == "__main__":
+    main()

@@ -73,6 +73,74 @@ def frontend(x, rows_in, cmn_window=0, masks=None, mask_offsets=None, first=None
     return out, rows_out
 
 
+def mfcc_config(**kw):
+    """xv_mfcc_config with the VoxCeleb conf/mfcc.conf defaults (dither 0); keyword arguments name the fields to change."""
+    return _lib.XvMfccConfig(**kw)
+
+
+def mfcc_num_frames(cfg, samples):
+    n = int(_lib.load().xv_mfcc_num_frames(C.byref(cfg), C.c_int64(int(samples))))
+    if n < 0:
+        _lib.check(2, "xv_mfcc_num_frames")
+    return n
+
+
+def mfcc_tables(cfg):
+    """The constant tables of xv_mfcc for cfg as a host float32 array (xv_mfcc_tables: host arithmetic, no GPU call)."""
+    import numpy as np
+    lib = _lib.load()
+    n = int(lib.xv_mfcc_table_floats(C.byref(cfg)))
+    if n == 0:
+        _lib.check(2, "xv_mfcc_table_floats")
+    flat = np.empty(n, np.float32)
+    _lib.check(lib.xv_mfcc_tables(C.byref(cfg), C.c_void_p(flat.ctypes.data), C.c_size_t(n)), "xv_mfcc_tables")
+    return flat
+
+
+def mfcc(cfg, tables, pcm, offsets, samples, t_out=None):
+    """MFCCs of a batch of waveforms (xv_mfcc).  tables: mfcc_tables(cfg) on the device; pcm: int16 device tensor, the utterances back to back;
+    offsets / samples: HOST integer arrays [b] - utterance i is pcm[offsets[i] : offsets[i] + samples[i]] (the kernel does not check them, so
+    they are checked here, before the upload).  t_out: rows of the output (default: the longest frame count).
+    -> (out [b, t_out, num_ceps] float32, rows_out int32 [b] = min(frames, t_out); rows behind are zero)."""
+    import numpy as np
+    if pcm.dtype != torch.int16 or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError("mfcc: pcm must be a contiguous 1-D int16 tensor")
+    offsets, samples = np.asarray(offsets), np.asarray(samples)
+    if offsets.ndim != 1 or offsets.shape != samples.shape or offsets.size == 0 or offsets.dtype.kind not in "iu" or samples.dtype.kind not in "iu":
+        raise ValueError("mfcc: offsets and samples must be two non-empty 1-D integer arrays of one length")
+    if offsets.min() < 0 or samples.min() < 0 or (offsets.astype(np.int64) + samples.astype(np.int64)).max() > pcm.numel():
+        raise IndexError("mfcc: an utterance lies outside the %d samples of pcm" % pcm.numel())
+    if samples.max() >= 2 ** 31:
+        raise ValueError("mfcc: an utterance holds 2^31 samples or more")
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != int(_lib.load().xv_mfcc_table_floats(C.byref(cfg))):
+        raise ValueError("mfcc: tables must be mfcc_tables(cfg) as a contiguous float32 device tensor")
+    b = offsets.size
+    if t_out is None:
+        t_out = max(max(mfcc_num_frames(cfg, n) for n in samples), 1)
+    t_out = int(t_out)
+    off_d = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(pcm.device)
+    n_d = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int32)).to(pcm.device)
+    out = torch.empty((b, t_out, int(cfg.num_ceps)), dtype=torch.float32, device=pcm.device)
+    rows_out = torch.empty(b, dtype=torch.int32, device=pcm.device)
+    _lib.call("xv_mfcc", _s(), C.byref(cfg), _p(tables), _p(pcm), _p(off_d), _p(n_d), b, t_out, _p(out), _p(rows_out))
+    return out, rows_out
+
+
+def energy_vad(x, rows, threshold=5.5, mean_scale=0.5, frames_context=2, proportion=0.12):
+    """compute-vad-decision on a padded batch x [b, t, d] with rows[i] (int32 device tensor) frames per piece (xv_energy_vad; the defaults
+    are the VoxCeleb vad.conf) -> uint8 [b, t], 1 = voiced, bytes behind rows[i] zero: the masks ops.frontend reads with
+    mask_offsets[i] = i * t."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("energy_vad: x must be a contiguous float32 [b, t, d] tensor")
+    if rows.dtype != torch.int32 or rows.numel() != x.shape[0]:
+        raise ValueError("energy_vad: rows must hold one int32 per piece")
+    b, t, d = x.shape
+    masks = torch.empty((b, t), dtype=torch.uint8, device=x.device)
+    _lib.call("xv_energy_vad", _s(), _p(x), _p(rows), b, t, d, C.c_float(threshold), C.c_float(mean_scale), int(frames_context),
+              C.c_float(proportion), _p(masks))
+    return masks
+
+
 def _pitched(t, what):
     """(rows, pitch in floats) of a 2-D float32 device view with contiguous rows."""
     if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):

@@ -13,6 +13,7 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py staged                           plain step vs the staged (multi-GPU) backward, without / with a one-rank RCCL all-reduce
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
   python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
+  python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
 
 Environment: XV_DATA_SCALE=0 (all-zero operands: DVFS check), XV_B (chunks, gemm16), ITERS (segment), XV_LIB (another build of the library).
 """
@@ -343,7 +344,37 @@ def cmd_backend(argv):
         print("  plda_trials             %9.1f us  %.2f TB/s of gathered rows (includes the index checks and uploads of ops.py)" % (us, mb / us), flush=True)
 
 
-COMMANDS = {"backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+def cmd_mfcc(argv):
+    """Frames per second of xv_mfcc alone and of xv_mfcc + xv_energy_vad on one padded batch (VoxCeleb conf: 16 kHz, 25 / 10 ms, 30 bins, 30
+    coefficients); the bytes the kernel has to move (2 S bytes of new samples in, 4 num_ceps bytes out per frame, plus the zeroed padding
+    rows) against the 8 TB/s HBM peak show how far from memory-bound it is: LDS traffic and issue rate bound it (csrc/xv_mfcc.hip)."""
+    from tf_kaldi_speaker_amd import ops
+    n_utts = int(argv[0]) if argv else 256
+    sf = 16000
+    lens = rs.randint(4 * sf, 20 * sf + 1, n_utts)
+    t = np.arange(int(lens.max())) / float(sf)
+    tone = 3000.0 * np.sin(2.0 * np.pi * 220.0 * t) + 1500.0 * np.sin(2.0 * np.pi * 1830.0 * t)
+    pcm = np.concatenate([np.rint(tone[:n] * (0.02 if i % 3 == 2 else 1.0) + rs.randn(n) * 40.0).astype(np.int16) for i, n in enumerate(lens)])
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    cfg = ops.mfcc_config()
+    tables = torch.from_numpy(ops.mfcc_tables(cfg)).cuda()
+    pcm_d = torch.from_numpy(pcm).cuda()
+    frames = np.asarray([ops.mfcc_num_frames(cfg, n) for n in lens])
+    t_out = int(frames.max())
+    x, rows = ops.mfcc(cfg, tables, pcm_d, offsets, lens, t_out)
+    print("%d utterances of %.1f - %.1f s (16 kHz): %.1f M samples, %d frames, padded to [%d, %d, 30]"
+          % (n_utts, lens.min() / sf, lens.max() / sf, pcm.size / 1e6, frames.sum(), n_utts, t_out), flush=True)
+    us = timeit(lambda: ops.mfcc(cfg, tables, pcm_d, offsets, lens, t_out), 10, 2)
+    mb = (2.0 * pcm.size + 4.0 * 30 * n_utts * t_out) / 1e6
+    print("  xv_mfcc                 %9.1f us  %.2f M frames/s  (%.0f MB in + out: %.3f TB/s = %.3f of the 8 TB/s peak; includes the offset uploads of ops.py)"
+          % (us, frames.sum() / us, mb, mb / us, mb / us / 8.0), flush=True)
+    us_vad = timeit(lambda: ops.energy_vad(x, rows), 10, 2)
+    print("  xv_energy_vad           %9.1f us  %.2f M frames/s" % (us_vad, frames.sum() / us_vad), flush=True)
+    us_both = timeit(lambda: ops.energy_vad(*ops.mfcc(cfg, tables, pcm_d, offsets, lens, t_out)), 10, 2)
+    print("  xv_mfcc + xv_energy_vad %9.1f us  %.2f M frames/s = %.0f x real time" % (us_both, frames.sum() / us_both, frames.sum() / us_both * 1e6 / 100.0), flush=True)
+
+
+COMMANDS = {"mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
