@@ -74,6 +74,19 @@ int xv_debug_tn_plan(int M, int N, int R, int direct, int out[4]);
  * ldl floats with logits and dlogits at those addresses: 8 or 16 (the row held in registers, RQ float4 per thread: ldl % 4 == 0, both
  * addresses 16-byte aligned, ldl <= 8192 or 16384), 0 (three passes over memory: any other pitch or alignment).  Host arithmetic. */
 int xv_debug_softmax_rows_form(int ldl, uintptr_t logits, uintptr_t dlogits);
+/* Diagnostics: the form xv_col_stats runs for n columns at a pitch of ldz floats with z and bn_part at those addresses: 4 (rows of whole
+ * float4s, one pass over memory: n % 4 == 0, ldz % 4 == 0, both addresses 16-byte aligned) or 1 (the scalar form).  Host arithmetic. */
+int xv_debug_col_stats_form(int n, int ldz, uintptr_t z, uintptr_t bn_part);
+/* Diagnostics: the launch plan of the BatchNorm (+ activation) backward of rows = segs * t frame rows.  pooled: the upstream gradient is the
+ * pooling backward over chunks of pool_t frames (rows % pool_t == 0); pad: zero frames around each segment of dz; relu: the entry point's
+ * flag; has_slope / has_dalpha: what xv_set_activation holds; has_wpos / has_weights / has_pamax: which optional pooled inputs are given;
+ * split: dz as fp16 planes with a |dz| bound; ext_chunks > 0: reduction partials left by a GEMM epilogue (plain ReLU only).
+ * out[0] the reduction form: 0 closed form from the pooled statistics, 1 the pooled pass over z, 2 the plain pass, 3 external partials;
+ * out[1] the pooled pass's instantiation (4 activation | 2 slope | 1 frame weights; 0 for the other forms); out[2] statistics per chunk
+ * (4 with a slope and a d alpha buffer, else 3); out[3] partial rows (chunks of 64 rows, per pooled chunk in the pooled forms; ext_chunks);
+ * out[4] the apply pass: 0 dense (pad == 0 and, pooled, pool_t >= 32), 1 strip, 2 split planes.  Host arithmetic, nothing is launched. */
+int xv_debug_bn_bwd_plan(int rows, int pooled, int pool_t, int pad, int relu, int has_slope, int has_dalpha, int has_wpos, int has_weights,
+                         int split, int has_pamax, int ext_chunks, int out[5]);
 
 /* dst[r][0..cols) = src[r][0..cols) for r < rows (device to device, pitches in floats). */
 int xv_copy_2d(void* stream, float* dst, size_t ldd, const float* src, size_t lds, int rows, int cols);

@@ -8,6 +8,7 @@ import torch
 
 from oracle import xvector_oracle as O
 from tests.test_gpu_ops import assert_close, dev, host, AFFINE_CASES, _pooled_case
+from tests import test_bn_plans as P
 
 pytestmark = pytest.mark.gpu
 
@@ -120,6 +121,8 @@ def test_bn_relu_backward_split(ops, relu, pad, n):
     part = ops.col_stats(dev(z))
     mean, invstd, scale, shift, zmin, zmax, _ = ops.bn_finalize(part, segs * t, dev(gamma), dev(beta), 1e-3, 0.99, False, None, None,
                                                                 with_range=True)
+    # the plain pass and the split apply form (tests/test_bn_plans.py)
+    assert P.lib_bn_bwd_plan(segs * t, pad=pad, relu=bool(relu), split=True) == (P.PLAIN_PASS, 0, 3, P.cdiv(segs * t, P.BB_ROWS), P.SPLIT)
     dzp, dg, db, dbias = ops.bn_relu_backward_split(dev(da), dev(z), segs, t, dev(gamma), mean, invstd, scale, shift, zmin, zmax, relu, pad)
     bound = _bits_to_float(dzp.amax)
     true_max = np.abs(dz_ref).max()
@@ -143,6 +146,8 @@ def test_pooling_fused_into_bn_split(ops):
     mean, invstd, scale, shift, zmin, zmax, _ = ops.bn_finalize(part, b * t, dev(gamma), dev(beta), 1e-3, 0.99, False, None, None,
                                                                 with_range=True)
     pool = ops.stat_pool_forward_bn(dev(z), b, t, scale, shift, True)
+    # without wpos / pamax: the pooled pass <RELU> and the split apply form (tests/test_bn_plans.py)
+    assert P.lib_bn_bwd_plan(b * t, pooled=True, pool_t=t, split=True) == (P.POOLED_PASS, P.RELU, 3, b * P.pooled_pass_geometry(t)[0], P.SPLIT)
     dzp, dg, db, dbias = ops.bn_relu_backward_pooled_split(pool, dev(dout), b, t, dev(z), dev(gamma), mean, invstd, scale, shift, zmin, zmax)
     bound = _bits_to_float(dzp.amax)
     assert np.abs(dz_ref).max() <= bound

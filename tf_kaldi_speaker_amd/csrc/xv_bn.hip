@@ -124,10 +124,16 @@ __global__ __launch_bounds__(256) void col_stats4_kernel(const float* __restrict
     }
 }
 
+// The form xv_col_stats runs: 4 = col_stats4_kernel (rows of whole, 16-byte aligned float4s on both sides), 1 = col_stats_kernel.
+static int col_stats_form(int n, int ldz, uintptr_t z, uintptr_t bn_part) {
+    return (n % 4 == 0 && ldz % 4 == 0 && z % 16 == 0 && bn_part % 16 == 0) ? 4 : 1;
+}
+extern "C" int xv_debug_col_stats_form(int n, int ldz, uintptr_t z, uintptr_t bn_part) { return col_stats_form(n, ldz, z, bn_part); }
+
 extern "C" int xv_col_stats(void* stream, const float* z, int rows, int n, int ldz, float* bn_part) {
     XV_REQUIRE(rows > 0 && n > 0 && ldz >= n, "col_stats: bad shape");
     int tiles = xv_cdiv(rows, XV_TILE_M);
-    if (n % 4 == 0 && ldz % 4 == 0 && ((uintptr_t)z % 16) == 0 && ((uintptr_t)bn_part % 16) == 0)
+    if (col_stats_form(n, ldz, (uintptr_t)z, (uintptr_t)bn_part) == 4)
         hipLaunchKernelGGL(col_stats4_kernel, dim3(xv_cdiv(n, 128), tiles), dim3(256), 0, (hipStream_t)stream, z, rows, n, (long)ldz, bn_part, tiles);
     else
         hipLaunchKernelGGL(col_stats_kernel, dim3(xv_cdiv(n, 32), tiles), dim3(256), 0, (hipStream_t)stream, z, rows, n, (long)ldz, bn_part, tiles);

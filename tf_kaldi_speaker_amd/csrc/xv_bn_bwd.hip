@@ -8,6 +8,13 @@
 #include "xv_ew.h"
 #include "xv_epilogue.h"
 
+// The launch plan of the backward (bn_bwd_plan below; xv_debug_bn_bwd_plan reports it).  Reduction forms, the template flags of the pooled
+// pass, apply forms:
+enum { XV_BNB_CLOSED = 0, XV_BNB_POOLED = 1, XV_BNB_PLAIN = 2, XV_BNB_EXTERNAL = 3 };
+enum { XV_BNB_ATT = 1, XV_BNB_HS = 2, XV_BNB_RELU = 4 };
+enum { XV_BNB_DENSE = 0, XV_BNB_STRIP = 1, XV_BNB_SPLIT = 2 };
+struct BnBwdPlan { int reduce, flags, nstat, chunks, apply; };
+
 // Upstream gradient of a layer whose output feeds statistics pooling directly (tdnn5): instead of reading a
 // materialised d(activation), the BN backward evaluates the pooling backward (pooling.py:9-34) on the fly from the
 // pooled statistics [b][mean | std] and their gradient:  da = dmean/T + dstd/(T*std) * (a - mean),  a = relu?(z*scale+shift).
@@ -173,16 +180,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_pooled_kernel(PoolGrad pg, 
     bn_bwd_store_partials(red, s1, s2, s3, s4, rl, qx, col, n, nstat, part);
 }
 
-// the POOLED reductions of (z, pooled statistics) into part [bn_bwd_pooled_chunks][nstat][n]
+// the POOLED reductions of (z, pooled statistics) into part [bn_bwd_pooled_chunks][nstat][n]; flags: the instantiation (bn_bwd_plan)
 static void launch_bn_bwd_reduce_pooled(hipStream_t s, const PoolGrad& pg, const float* z, int rows, int n, const float* mean, const float* invstd,
-                                        const float* scale, const float* shift, int relu, float* part, const float* slope, int nstat) {
+                                        const float* scale, const float* shift, int flags, float* part, const float* slope, int nstat) {
     const int nb = rows / pg.t, nsub = xv_cdiv(pg.t, BBP_ROWS), rows_per = xv_cdiv(pg.t, nsub);
     const dim3 grid(xv_cdiv(n / 4, 64), nb * nsub), block(256);
 #define XV_BBP(R, H, A) hipLaunchKernelGGL((bn_bwd_reduce_pooled_kernel<R, H, A>), grid, block, 0, s, pg, z, n, nsub, rows_per, mean, invstd, scale, shift, part, slope, nstat)
-    const bool hs = relu && slope, att = pg.w != nullptr;
-    if (!relu) { if (att) XV_BBP(false, false, true); else XV_BBP(false, false, false); }
-    else if (hs) { if (att) XV_BBP(true, true, true); else XV_BBP(true, true, false); }
-    else { if (att) XV_BBP(true, false, true); else XV_BBP(true, false, false); }
+    switch (flags) {
+    case XV_BNB_ATT: XV_BBP(false, false, true); break;
+    case 0: XV_BBP(false, false, false); break;
+    case XV_BNB_RELU | XV_BNB_HS | XV_BNB_ATT: XV_BBP(true, true, true); break;
+    case XV_BNB_RELU | XV_BNB_HS: XV_BBP(true, true, false); break;
+    case XV_BNB_RELU | XV_BNB_ATT: XV_BBP(true, false, true); break;
+    default: XV_BBP(true, false, false); break;
+    }
 #undef XV_BBP
 }
 static int bn_bwd_pooled_chunks(int rows, int t) { return (rows / t) * xv_cdiv(t, BBP_ROWS); }
@@ -539,22 +550,58 @@ static PoolGrad pool_grad_of(const XvBnUpstream& up) {
     return up.pool_out ? PoolGrad{up.pool_out, up.dpool, up.pool_t, up.weights, up.wpos, up.pamax} : PoolGrad{nullptr, nullptr, 1, nullptr, nullptr, nullptr};
 }
 
-// The reduction stage of both backward forms (each has checked its shape): validates the chunking and the workspace, carves part [chunks][nstat][n] | coef [2][n] out of the workspace,
+// Every choice of kernel of the backward, from what the caller has (host arithmetic only).  rows = segs * t; pooled: the upstream gradient is
+// the pooling backward over chunks of pool_t frames; has_slope / has_dalpha: the activation context; split: dz as fp16 planes with a |dz|
+// bound (dz_amax); ext_chunks > 0: reduction partials a GEMM epilogue left.
+//   reduce: closed form from the pooled statistics (needs wpos and no slope; split precision also needs pamax, unit frame weights and no
+//           external partials) | external partials | the pooled pass (flags: its RELU, HS, ATT instantiation) | the plain pass
+//   nstat:  4 with a slope and a d alpha buffer (prelu), else 3
+//   chunks: partial rows the finalize kernel sums (and the workspace holds, unless external)
+//   apply:  split planes | dense (pad == 0 and, pooled, chunks of at least one BAF_ROWS strip) | strip
+static BnBwdPlan bn_bwd_plan(int rows, bool pooled, int pool_t, int pad, bool relu, bool has_slope, bool has_dalpha, bool has_wpos,
+                             bool has_weights, bool split, bool has_pamax, int ext_chunks) {
+    BnBwdPlan p;
+    const bool slope = relu && has_slope, ext = ext_chunks > 0;
+    p.nstat = (slope && has_dalpha) ? 4 : 3;      // prelu: one more reduction, sum d act * min(y, 0)
+    // the partials either come from the data-gradient GEMM's epilogue (one chunk per 128-row tile) or are computed into the workspace
+    p.chunks = ext ? ext_chunks : pooled ? bn_bwd_pooled_chunks(rows, pool_t) : xv_cdiv(rows, BB_ROWS);
+    // statistics pooling behind a plain ReLU (or no activation): reductions and finalize in closed form from the pooled statistics, no pass over z
+    bool closed = pooled && has_wpos && !slope;
+    // ... whose |dz| bound, where one is wanted, comes from each chunk's largest activation: that needs pamax and unit frame weights, and
+    // partials a GEMM epilogue already produced are consumed instead
+    if (split) closed = closed && has_pamax && !has_weights && !ext;
+    p.reduce = closed ? XV_BNB_CLOSED : ext ? XV_BNB_EXTERNAL : pooled ? XV_BNB_POOLED : XV_BNB_PLAIN;
+    p.flags = p.reduce == XV_BNB_POOLED ? (relu ? XV_BNB_RELU : 0) | (slope ? XV_BNB_HS : 0) | (has_weights ? XV_BNB_ATT : 0) : 0;
+    p.apply = split ? XV_BNB_SPLIT : (pad == 0 && (!pooled || pool_t >= BAF_ROWS)) ? XV_BNB_DENSE : XV_BNB_STRIP;
+    return p;
+}
+static BnBwdPlan bn_bwd_plan_of(const XvBnUpstream& up, const PoolGrad& pg, int rows, int pad, int relu, const XvActContext& act, bool split) {
+    return bn_bwd_plan(rows, pg.out != nullptr, pg.t, pad, relu != 0, act.slope != nullptr, act.dalpha != nullptr, pg.wpos != nullptr,
+                       pg.w != nullptr, split, pg.amax != nullptr, up.ext_part ? up.ext_chunks : 0);
+}
+extern "C" int xv_debug_bn_bwd_plan(int rows, int pooled, int pool_t, int pad, int relu, int has_slope, int has_dalpha, int has_wpos,
+                                    int has_weights, int split, int has_pamax, int ext_chunks, int out[5]) {
+    XV_REQUIRE(out && rows > 0 && pad >= 0 && ext_chunks >= 0, "debug_bn_bwd_plan: bad arguments");
+    XV_REQUIRE(!pooled || (pool_t > 0 && rows % pool_t == 0), "debug_bn_bwd_plan: %d rows are not whole chunks of %d pooled frames", rows, pool_t);
+    XV_REQUIRE(!(ext_chunks && relu && has_slope), "debug_bn_bwd_plan: GEMM-epilogue partials only exist for a plain ReLU");
+    XV_REQUIRE(!has_dalpha || has_slope, "debug_bn_bwd_plan: a d alpha buffer needs a slope vector");
+    const BnBwdPlan p = bn_bwd_plan(rows, pooled != 0, pool_t, pad, relu != 0, has_slope != 0, has_dalpha != 0, has_wpos != 0, has_weights != 0,
+                                    split != 0, has_pamax != 0, ext_chunks);
+    out[0] = p.reduce; out[1] = p.flags; out[2] = p.nstat; out[3] = p.chunks; out[4] = p.apply;
+    return 0;
+}
+
+// The reduction stage of both backward forms (each has checked its shape and made the plan): validates the workspace, carves part [chunks][nstat][n] | coef [2][n] out of it,
 // reduces the upstream gradient against z - in closed form from the pooled statistics, by the pooled or the plain pass over z, or not at all
 // when a GEMM epilogue already left the partials (up.ext_part) - and finalizes: dgamma, dbeta, dbias, d alpha, *coef_out = coef (c1, c2 of
 // the apply pass).  dz_amax (split precision, with zmin / zmax): also atomicMax'es the |dz| bound into it, zeroed first if zero_amax.
 // `who` names the caller in errors.
-static int bn_bwd_reductions(hipStream_t s, const char* who, const XvBnUpstream& up, const PoolGrad& pg, const float* z, int rows, int n,
-                             const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
+static int bn_bwd_reductions(hipStream_t s, const char* who, const BnBwdPlan& plan, const XvBnUpstream& up, const PoolGrad& pg, const float* z,
+                             int rows, int n, const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift,
                              const float* zmin, const float* zmax, uint32_t* dz_amax, bool zero_amax, int relu, const XvActContext& act,
                              float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes, const float** coef_out) {
-    const bool pooled = pg.out != nullptr;
-    XV_REQUIRE(!pooled || (pg.t > 0 && rows % pg.t == 0), "%s: %d rows are not whole chunks of %d pooled frames", who, rows, pg.t);
     const float* slope = relu ? act.slope : nullptr;
-    XV_REQUIRE(!(up.ext_part && slope), "%s: GEMM-epilogue partials only exist for a plain ReLU", who);
-    const int nstat = (slope && act.dalpha) ? 4 : 3;      // prelu: one more reduction, sum d act * min(y, 0)
-    // the partials either come from the data-gradient GEMM's epilogue (one chunk per 128-row tile) or are computed here into the workspace
-    const int chunks = up.ext_part ? up.ext_chunks : pooled ? bn_bwd_pooled_chunks(rows, pg.t) : xv_cdiv(rows, BB_ROWS);
+    const int nstat = plan.nstat, chunks = plan.chunks;
     const size_t part_floats = up.ext_part ? 0 : (size_t)chunks * nstat * n;
     const size_t need = (part_floats + 2 * n) * sizeof(float);
     XV_REQUIRE(need <= ws_bytes, "%s: workspace too small (%zu > %zu)", who, need, ws_bytes);
@@ -562,25 +609,18 @@ static int bn_bwd_reductions(hipStream_t s, const char* who, const XvBnUpstream&
     float* coef = (float*)ws + part_floats;
     *coef_out = coef;
     if (dz_amax && zero_amax) XV_CHECK_HIP(hipMemsetAsync(dz_amax, 0, sizeof(uint32_t), s));
-    // statistics pooling behind a plain ReLU (or no activation): reductions and finalize in closed form from the pooled statistics, no pass over z
-    bool closed = pooled && pg.wpos && !slope;
-    // ... whose |dz| bound, where one is wanted, comes from each chunk's largest activation: that needs pamax and unit frame weights, and
-    // partials a GEMM epilogue already produced are consumed instead
-    if (dz_amax) closed = closed && pg.amax && !pg.w && !up.ext_part;
-    if (closed) {
+    if (plan.reduce == XV_BNB_CLOSED) {
         hipLaunchKernelGGL(bn_bwd_pooled_stats_kernel, dim3(xv_cdiv(n / 4, PS_QUADS)), dim3(256), 0, s, pg, rows / pg.t, n, rows, gamma, shift, mean,
                            invstd, scale, dgamma, dbeta, coef, dbias, zmin, zmax, (unsigned*)dz_amax);
         XV_LAUNCH_CHECK();
         return 0;
     }
-    if (!up.ext_part) {
-        if (pooled)
-            launch_bn_bwd_reduce_pooled(s, pg, z, rows, n, mean, invstd, scale, shift, relu, part, slope, nstat);
-        else
-            hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(xv_cdiv(n / 4, 64), chunks), dim3(256), 0, s,
-                               up.da, z, rows, n, mean, invstd, scale, shift, relu, part, slope, nstat);
-        XV_LAUNCH_CHECK();
-    }
+    if (plan.reduce == XV_BNB_POOLED)
+        launch_bn_bwd_reduce_pooled(s, pg, z, rows, n, mean, invstd, scale, shift, plan.flags, part, slope, nstat);
+    else if (plan.reduce == XV_BNB_PLAIN)
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(xv_cdiv(n / 4, 64), chunks), dim3(256), 0, s,
+                           up.da, z, rows, n, mean, invstd, scale, shift, relu, part, slope, nstat);
+    if (plan.reduce != XV_BNB_EXTERNAL) XV_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(xv_cdiv(n, FIN_CH)), dim3(256), 0, s, (const float*)part, chunks, n, rows,
                        dgamma, dbeta, coef, gamma, invstd, dbias, mean, zmin, zmax, (unsigned*)dz_amax, nstat,
                        nstat == 4 ? act.dalpha : (float*)nullptr);
@@ -601,15 +641,18 @@ int xv_bn_backward_f32(hipStream_t s, const XvBnUpstream& up, const float* z, in
     if (ldz == 0) ldz = n;
     XV_REQUIRE(ldz >= n && ldz % 4 == 0 && (ldz == n || (pooled && pg.wpos && !slope)), "bn_relu_backward: a row pitch is only supported on the closed-form pooled path");
     XV_REQUIRE((long)segs * (t + 2 * pad) * (n / 4) < (1L << 31), "bn_relu_backward: tensor too large for 32-bit indexing");
+    XV_REQUIRE(!pooled || (pg.t > 0 && (segs * t) % pg.t == 0), "bn_relu_backward: %d rows are not whole chunks of %d pooled frames", segs * t, pg.t);
+    XV_REQUIRE(!(up.ext_part && slope), "bn_relu_backward: GEMM-epilogue partials only exist for a plain ReLU");
+    const BnBwdPlan plan = bn_bwd_plan_of(up, pg, segs * t, pad, relu, act, false);
     const float* coef = nullptr;
-    const int rc = bn_bwd_reductions(s, "bn_relu_backward", up, pg, z, segs * t, n, gamma, mean, invstd, scale, shift, nullptr, nullptr, nullptr,
+    const int rc = bn_bwd_reductions(s, "bn_relu_backward", plan, up, pg, z, segs * t, n, gamma, mean, invstd, scale, shift, nullptr, nullptr, nullptr,
                                      false, relu, act, dgamma, dbeta, dbias, ws, ws_bytes, &coef);
     if (rc) return rc;
     dim3 agrid(xv_cdiv(n / 4, 64), xv_cdiv(segs * (t + 2 * pad), BAF_ROWS));
     // [measured, round 6, profiles/r06_pooled_kernels.txt] two other forms of the pooled pass were built and dropped: a workgroup per (chunk, 256
     // channels) with the parameters set up once and two batches of eight loads in flight (78 us for statistics + apply alone, as this strip form),
     // and whole-row workgroups that stream consecutive bytes as torch's flat element-wise kernel does (82 us)
-    if (pad == 0 && (!pooled || pg.t >= BAF_ROWS))
+    if (plan.apply == XV_BNB_DENSE)
         hipLaunchKernelGGL(pooled ? bn_bwd_apply_dense_kernel<true> : bn_bwd_apply_dense_kernel<false>, agrid, dim3(256), 0, s, up.da, pg, z, segs * t, n,
                            gamma, mean, invstd, scale, shift, coef, relu, dz_pad, slope, ldz);
     else
@@ -630,8 +673,11 @@ int xv_bn_backward_split(hipStream_t s, const XvBnUpstream& up, const float* z, 
     XV_REQUIRE((long)segs * (t + 2 * pad) * (ldp / 8) < (1L << 31), "bn_relu_backward_split: tensor too large for 32-bit indexing");
     const PoolGrad pg = pool_grad_of(up);
     const XvActContext act = xv_act_context();
+    XV_REQUIRE(!pg.out || (pg.t > 0 && (segs * t) % pg.t == 0), "bn_relu_backward_split: %d rows are not whole chunks of %d pooled frames", segs * t, pg.t);
+    XV_REQUIRE(!(up.ext_part && relu && act.slope), "bn_relu_backward_split: GEMM-epilogue partials only exist for a plain ReLU");
+    const BnBwdPlan plan = bn_bwd_plan_of(up, pg, segs * t, pad, relu, act, true);
     const float* coef = nullptr;
-    const int rc = bn_bwd_reductions(s, "bn_relu_backward_split", up, pg, z, segs * t, n, gamma, mean, invstd, scale, shift, zmin, zmax, dz_amax,
+    const int rc = bn_bwd_reductions(s, "bn_relu_backward_split", plan, up, pg, z, segs * t, n, gamma, mean, invstd, scale, shift, zmin, zmax, dz_amax,
                                      zero_amax, relu, act, dgamma, dbeta, dbias, ws, ws_bytes, &coef);
     if (rc) return rc;
     dim3 agrid(xv_cdiv(ldp / 8, 64), xv_cdiv(segs * (t + 2 * pad), BAS_ROWS));

@@ -418,11 +418,27 @@ def bn_inference_scale(gamma, beta, moving_mean, moving_var, eps):
     return scale, shift
 
 
-def bn_apply(z, scale, shift, relu):
+def bn_output_range(part, rows, scale, shift, relu=True):
+    """Per-channel range of z from the min / max planes of `part` (col_stats layout) and the largest |relu?(z*scale+shift)| over the batch
+    for the given scale / shift (the activation context applies): -> zmin, zmax [n], amax [1]."""
+    n = scale.numel()
+    zmin, zmax = _f32((n,), scale), _f32((n,), scale)
+    amax = torch.zeros(1, dtype=torch.int32, device=scale.device)
+    _lib.call("xv_bn_output_range", _s(), _p(part), rows, n, _p(scale), _p(shift), int(relu), _p(zmin), _p(zmax), _p(amax))
+    return zmin, zmax, amax.view(torch.float32)
+
+
+def bn_apply(z, scale, shift, relu, ldz=None, lda=None, out=None):
+    """a = relu?(z*scale+shift).  ldz: floats per row of z (default: z's own row stride); lda: floats per row of the result (default n) -
+    the result is then the [rows, n] view of a [rows, lda] buffer (`out`, or a new one)."""
     rows, n = z.shape
-    a = _f32((rows, n), z)
-    _lib.call("xv_bn_apply", _s(), _p(z), rows, n, n, _p(scale), _p(shift), int(relu), _p(a), n)
-    return a
+    ldz = z.stride(0) if ldz is None else int(ldz)
+    lda = n if lda is None else int(lda)
+    buf = _f32((rows, lda), z) if out is None else out
+    if buf.shape != (rows, lda) or not buf.is_contiguous():
+        raise ValueError("bn_apply: out must be a contiguous [rows, lda] buffer")
+    _lib.call("xv_bn_apply", _s(), _p(z), rows, n, ldz, _p(scale), _p(shift), int(relu), _p(buf), lda)
+    return buf[:, :n]
 
 
 def bn_relu_backward(da, z, segs, t, gamma, mean, invstd, scale, shift, relu, pad, with_dbias=False):
