@@ -87,6 +87,14 @@ int xv_debug_col_stats_form(int n, int ldz, uintptr_t z, uintptr_t bn_part);
  * out[4] the apply pass: 0 dense (pad == 0 and, pooled, pool_t >= 32), 1 strip, 2 split planes.  Host arithmetic, nothing is launched. */
 int xv_debug_bn_bwd_plan(int rows, int pooled, int pool_t, int pad, int relu, int has_slope, int has_dalpha, int has_wpos, int has_weights,
                          int split, int has_pamax, int ext_chunks, int out[5]);
+/* Diagnostics: the launch plan of the segment-level GEMM kernel (xv_segment_gemm, xv_segment_affine_bn_forward,
+ * xv_segment_dgrad_bn_backward) for an m x n result over k with a workspace of ws_bytes.  out[0] column tiles of 32 (gridDim.x); out[1]
+ * splits of k (gridDim.y): 256 / tiles, at most k / 64, no more than ws_bytes holds [128][32] float slabs for, then what the chunk leaves;
+ * out[2] k per split, a multiple of 32.  Fails with the launcher's message for a shape the launcher refuses.  Host arithmetic. */
+int xv_debug_segment_plan(int m, int n, int k, size_t ws_bytes, int out[3]);
+/* Diagnostics: the form xv_att_score runs for rows of n columns at a pitch of ldz floats with zk and query at those addresses: 1 (column
+ * quads: n % 4 == 0, ldz % 4 == 0, both addresses 16-byte aligned) or 0 (the scalar form).  Host arithmetic. */
+int xv_debug_att_score_form(int n, int ldz, uintptr_t zk, uintptr_t query);
 
 /* dst[r][0..cols) = src[r][0..cols) for r < rows (device to device, pitches in floats). */
 int xv_copy_2d(void* stream, float* dst, size_t ldd, const float* src, size_t lds, int rows, int cols);

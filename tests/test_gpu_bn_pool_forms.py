@@ -166,15 +166,22 @@ def be():
     write_ledger("gpu", time.time() - t0)
 
 
-def write_ledger(tag, seconds):
+def write_ledger(tag, seconds, ledger=None, shares=None, title=None):
+    """Appends to $XV_BOUNDS_OUT; the later form modules hand in their own ledger, shares and a title, which are emptied once written: the CPU
+    modules record into the ledger of the GPU module whose rows they run, and a section holds the figures of its own run only."""
     path = os.environ.get("XV_BOUNDS_OUT")
     if not path:
         return
+    ledger, shares = LEDGER if ledger is None else ledger, SHARES if shares is None else shares
+    tag = tag if title is None else "%s, %s" % (title, tag)
     with open(path, "a") as f:
         f.write("# %s: largest |got - ref| / bound per form and output; wall time of the rows %.1f s\n" % (tag, seconds))
-        f.write("\n".join(LEDGER.lines()) + "\n")
+        f.write("\n".join(ledger.lines()) + "\n")
         f.write("# %s: largest share of mask-ambiguous elements of a row, per form (cap %.0e)\n" % (tag, R.MAX_AMBIGUOUS_SHARE))
-        f.write("\n".join("%-64s %.3g" % kv for kv in sorted(SHARES.items())) + "\n")
+        f.write("\n".join("%-64s %.3g" % kv for kv in sorted(shares.items())) + "\n")
+    if title is not None:
+        ledger.worst.clear()
+        shares.clear()
 
 
 def statistics(be, z, gamma, beta):

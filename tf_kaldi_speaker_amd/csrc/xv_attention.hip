@@ -196,10 +196,14 @@ __global__ void add_inplace_kernel(float* __restrict__ y, const float* __restric
 
 }  // namespace
 
+// vector form: whole column quads in every row (n and the pitch multiples of 4 floats) and both operands on a 16-byte boundary
+static bool att_score_vec(int n, long ldz, uintptr_t zk, uintptr_t query) { return n % 4 == 0 && ldz % 4 == 0 && zk % 16 == 0 && query % 16 == 0; }
+extern "C" int xv_debug_att_score_form(int n, int ldz, uintptr_t zk, uintptr_t query) { return att_score_vec(n, ldz, zk, query) ? 1 : 0; }
+
 extern "C" int xv_att_score(void* stream, const float* zk, int rows, int n, int ldz, int act, const float* query, float scale,
                             float* score) {
     XV_REQUIRE(zk && query && score && rows > 0 && n > 0 && ldz >= n && (act == 0 || act == 1 || act == 3), "att_score: bad arguments (act=%d)", act);
-    const bool vec = n % 4 == 0 && ldz % 4 == 0 && ((uintptr_t)zk % 16) == 0 && ((uintptr_t)query % 16) == 0;
+    const bool vec = att_score_vec(n, ldz, (uintptr_t)zk, (uintptr_t)query);
     if (vec) hipLaunchKernelGGL(att_score_kernel<true>, dim3(xv_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, zk, rows, n, (long)ldz, act, query, scale, score);
     else hipLaunchKernelGGL(att_score_kernel<false>, dim3(xv_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, zk, rows, n, (long)ldz, act, query, scale, score);
     XV_LAUNCH_CHECK();

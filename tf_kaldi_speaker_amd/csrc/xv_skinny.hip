@@ -293,24 +293,43 @@ int sk_target_wgs() { return 256; }      // workgroup target of the split policy
 
 size_t xv_skinny_tickets(int max_n) { return (size_t)xv_cdiv(max_n, SK_COLS); }
 
+// The split rule, stated once (xv_launch_skinny runs it, xv_debug_segment_plan reports it): two stages (64 k) per workgroup at least, as
+// many splits as fill the chip once, no more than the workspace holds slabs for; then a 32-aligned chunk and the splits that chunk leaves.
+struct SkPlan { int tiles_n, splits, k_chunk; };
+static int sk_plan(int M, int N, int K, long lda, long ldb, size_t ws_bytes, SkPlan* plan) {
+    XV_REQUIRE(M > 0 && M <= SK_ROWS && N > 0 && K > 0, "segment gemm: bad shape (M=%d N=%d K=%d, M <= %d)", M, N, K, SK_ROWS);
+    XV_REQUIRE(K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0, "segment gemm: K/lda/ldb must be multiples of 4 (K=%d lda=%ld ldb=%ld)", K, lda, ldb);
+    plan->tiles_n = xv_cdiv(N, SK_COLS);
+    int splits = sk_target_wgs() / plan->tiles_n;
+    const int max_splits = std::max(1, K / (2 * SK_KS));
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    while (splits > 1 && (size_t)splits * plan->tiles_n * SK_ROWS * SK_COLS * sizeof(float) > ws_bytes) --splits;
+    plan->k_chunk = (int)xv_align((size_t)xv_cdiv(K, splits), SK_KS);
+    plan->splits = xv_cdiv(K, plan->k_chunk);
+    return 0;
+}
+
+extern "C" int xv_debug_segment_plan(int m, int n, int k, size_t ws_bytes, int out[3]) {
+    XV_REQUIRE(out, "xv_debug_segment_plan: out is NULL");
+    SkPlan plan;
+    if (const int rc = sk_plan(m, n, k, k, k, ws_bytes, &plan)) return rc;      // contiguous operands: the pitches take no part in the rule
+    out[0] = plan.tiles_n; out[1] = plan.splits; out[2] = plan.k_chunk;
+    return 0;
+}
+
 int xv_launch_skinny(hipStream_t s, const XvSkinny& g) {
-    XV_REQUIRE(g.M > 0 && g.M <= SK_ROWS && g.N > 0 && g.K > 0, "segment gemm: bad shape (M=%d N=%d K=%d, M <= %d)", g.M, g.N, g.K, SK_ROWS);
-    XV_REQUIRE(g.K % 4 == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0, "segment gemm: K/lda/ldb must be multiples of 4 (K=%d lda=%ld ldb=%ld)", g.K, g.lda, g.ldb);
+    SkPlan plan;
+    if (const int rc = sk_plan(g.M, g.N, g.K, g.lda, g.ldb, g.ws_bytes, &plan)) return rc;
     XV_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.Bt % 16) == 0, "segment gemm: operands must be 16-byte aligned");
     XV_REQUIRE(g.epi >= XV_SK_PLAIN && g.epi <= XV_SK_BN_BWD, "segment gemm: bad epilogue %d", g.epi);
     SkArgs p;
     p.g = g;
     p.zero = xv_zero_page((size_t)g.K);
     if (!p.zero) return 1;
-    p.tiles_n = xv_cdiv(g.N, SK_COLS);
-    // two stages (64 k) per workgroup at least; as many splits as fill the chip once
-    int splits = sk_target_wgs() / p.tiles_n;
-    const int max_splits = std::max(1, g.K / (2 * SK_KS));
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    while (splits > 1 && (size_t)splits * p.tiles_n * SK_ROWS * SK_COLS * sizeof(float) > g.ws_bytes) --splits;
-    p.k_chunk = (int)xv_align((size_t)xv_cdiv(g.K, splits), SK_KS);
-    p.splits = xv_cdiv(g.K, p.k_chunk);
+    p.tiles_n = plan.tiles_n;
+    p.splits = plan.splits;
+    p.k_chunk = plan.k_chunk;
     p.slab = (float*)g.ws;
     XV_REQUIRE(p.splits == 1 || (g.tickets && g.ws), "segment gemm: split reduction needs a workspace and tickets");
     dim3 grid(p.tiles_n, p.splits, 1);
