@@ -95,6 +95,21 @@ int xv_debug_segment_plan(int m, int n, int k, size_t ws_bytes, int out[3]);
 /* Diagnostics: the form xv_att_score runs for rows of n columns at a pitch of ldz floats with zk and query at those addresses: 1 (column
  * quads: n % 4 == 0, ldz % 4 == 0, both addresses 16-byte aligned) or 0 (the scalar form).  Host arithmetic. */
 int xv_debug_att_score_form(int n, int ldz, uintptr_t zk, uintptr_t query);
+/* Diagnostics: the form xv_affine_forward_f16x3 / xv_affine_dgrad_f16x3 / xv_affine_dgrad_bnstats_f16x3 run for C[M][N] = A . Bt^T over K
+ * halfs with A rows of lda halfs in segments of a_rps rows at a pitch of a_pitch rows (the weight planes at a pitch of K).  stats: the launch
+ * emits BatchNorm statistics; bwd: it emits the BatchNorm-backward partials; conv_wr: the value of XV_CONV_WR (0 unset, 2 or 4), passed in so
+ * that the answer does not depend on the process environment.  out[0] the kernel: 0 generic (xv_gemm16_nt_kernel), 1 context-window
+ * (xv_gemm16_nt_conv_kernel: lda % 32 == 0, K = taps * lda, taps >= 2, no bwd, and the x rows of any tile fit its A image:
+ * (bm - 1) + (a_pitch - a_rps) * ((bm - 1) / a_rps + 1) + (taps - 1) < bm + 32); out[1] rows of a tile (128 | 256); out[2] taps and out[3]
+ * 32-channel chunks (0, 0: generic); out[4], out[5] row and column tiles; out[6] K-steps of 32 halfs; out[7] halfs of the last K-step inside
+ * K rounded up to 8.  Fails with the launcher's message for a shape the launcher refuses.  Host arithmetic, nothing is launched. */
+int xv_debug_gemm16_nt_form(int M, int N, int K, int lda, int a_rps, int a_pitch, int stats, int bwd, int conv_wr, int out[8]);
+/* Diagnostics: the plan xv_affine_wgrad_f16x3 runs for P[M][N] = sum_r A[r][M] . B[r][N] over R reduction rows in segments of rps rows at
+ * pitches of a_pitch / b_pitch rows.  out[0] tiles of 128 x 128; out[1] splits (slabs summed by the reduce launch): 512 / tiles, at most
+ * half the 32-row stages, at least one, then what the chunk leaves; out[2] reduction rows per split, a multiple of 32; out[3] 1 when the rows
+ * are gap-free (both pitches == rps) and the kernel sees one segment of R rows; out[4] 1 when whole stages advance lane offsets (the rps
+ * the kernel sees >= 32), 0 when every stage takes the per-row form.  Host arithmetic, nothing is launched. */
+int xv_debug_gemm16_tn_plan(int M, int N, int R, int rps, int a_pitch, int b_pitch, int out[5]);
 
 /* dst[r][0..cols) = src[r][0..cols) for r < rows (device to device, pitches in floats). */
 int xv_copy_2d(void* stream, float* dst, size_t ldd, const float* src, size_t lds, int rows, int cols);

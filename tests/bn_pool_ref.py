@@ -168,10 +168,11 @@ def col_stats(z, dt=np.float64):
     return out
 
 
-def col_stats_bound(z):
+def col_stats_bound(z, L=COL_STATS_L):
     """Sum: terms are exact, L u S.  Squares: the kernel centres on its float32 tile mean m^, off the true mean m by at most
     dm = bound(sum) / count + u |m| (the division); sum (z - m^)^2 = sum (z - m)^2 + count (m - m^)^2 exactly (the cross term vanishes about the
-    true mean), and a term (z - m^)^2 carries 3 roundings: (L + 3) u Q + count dm^2.  -> (bound [2][tiles][n], dm [tiles][n])"""
+    true mean), and a term (z - m^)^2 carries 3 roundings: (L + 3) u Q + count dm^2.  -> (bound [2][tiles][n], dm [tiles][n])
+    L: the longest addition chain of the kernel that forms the statistics (xv_col_stats by default; the GEMM epilogues state their own)."""
     z = f64(z)
     rows, n = z.shape
     T = tiles_of(rows)
@@ -180,9 +181,9 @@ def col_stats_bound(z):
         blk = z[t * TILE_M:(t + 1) * TILE_M]
         cnt = blk.shape[0]
         m = blk.mean(axis=0)
-        b[0, t] = COL_STATS_L * U * np.abs(blk).sum(axis=0)
+        b[0, t] = L * U * np.abs(blk).sum(axis=0)
         dm[t] = b[0, t] / cnt + U * np.abs(m)
-        b[1, t] = (COL_STATS_L + 3) * U * ((blk - m) ** 2).sum(axis=0) * (1 + 1e-3) + cnt * dm[t] ** 2
+        b[1, t] = (L + 3) * U * ((blk - m) ** 2).sum(axis=0) * (1 + 1e-3) + cnt * dm[t] ** 2
     return b, dm
 
 

@@ -141,6 +141,8 @@ SIGNATURES = {
     "xv_debug_bn_bwd_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "xv_debug_segment_plan": (_I, [_I, _I, _I, _SZ, C.POINTER(_I)]),
     "xv_debug_att_score_form": (_I, [_I, _I, C.c_size_t, C.c_size_t]),
+    "xv_debug_gemm16_nt_form": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "xv_debug_gemm16_tn_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "xv_debug_engine_clip_sumsq": (_I, [_VP, C.POINTER(_VP)]),
     "xv_copy_2d": (_I, [_VP, _VP, _SZ, _VP, _SZ, _I, _I]),
     "xv_op_workspace_bytes": (_SZ, [_I, _I, _I]),

@@ -562,12 +562,66 @@ static bool conv_form_applies(const XvGemm16NT& g, int bm, int* taps_out) {
 #define XV16_CONV_WR 2
 #endif
 
+// The launch form of an NT problem, stated once: xv_launch_gemm16_nt runs it, xv_debug_gemm16_nt_form reports it.
+struct NT16Form {
+    int conv;                  // 1: the context-window kernel, 0: the generic one
+    int bm;                    // rows of a tile (128; 256 for the context-window kernel with 4 row-waves)
+    int taps, chunks;          // context-window kernel: K = taps * lda, chunks = lda / 32 (0, 0 for the generic kernel)
+    int tiles_m, tiles_n;
+    int nk;                    // K-steps of 32 halfs (context-window kernel: taps * chunks)
+    int last_valid;            // halfs of the last K-step that lie inside K rounded up to 8 (8 ... 32)
+};
+
+// what both the launcher and the hook refuse about the shape of a problem (pointers are the launcher's own business)
+static int nt16_check_shape(const XvGemm16NT& g) {
+    XV_REQUIRE(g.lda % 8 == 0 && g.ldb % 8 == 0, "gemm16_nt: lda/ldb must be multiples of 8 (lda=%ld ldb=%ld)", g.lda, g.ldb);
+    XV_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.a_rps > 0, "gemm16_nt: empty problem");
+    // xv_dma16 addresses every row of a plane as a 32-bit byte offset from the plane's base
+    XV_REQUIRE(((long)xv_cdiv(g.M, g.a_rps) * g.a_pitch + 1) * g.lda * 2 < (1L << 32) && ((long)g.N + 1) * g.ldb * 2 < (1L << 32),
+               "gemm16_nt: a plane spans 4 GB or more (M=%d a_pitch=%d lda=%ld N=%d ldb=%ld): split the batch", g.M, g.a_pitch, g.lda, g.N, g.ldb);
+    return 0;
+}
+
+// conv_wr: XvEnv::conv_wr (XV_CONV_WR=4 (experiments, tests) forces 256-row tiles wherever they apply; as a build default they would be
+// limited to problems with at least one tile per CU).  bwd: the BN-backward epilogue (an off-by-default experiment) is written for the
+// 32x32x16 accumulator layout: with the 16x16x32 build of the context-window kernel such a launch takes the generic kernel.
+static NT16Form nt16_form(const XvGemm16NT& g, bool bwd, int conv_wr) {
+    NT16Form f;
+    const int Kp = (int)xv_align(g.K, 8);
+    const bool wr4 = conv_wr ? conv_wr == 4 : (XV16_CONV_WR == 4 && g.M >= 256 * 256);
+    const bool conv_ok = !bwd;
+    int taps = 0;
+    f.conv = 1;
+    if (conv_ok && wr4 && conv_form_applies(g, 256, &taps)) f.bm = 256;
+    else if (conv_ok && conv_form_applies(g, 128, &taps)) f.bm = 128;
+    else { f.conv = 0; f.bm = 128; taps = 0; }
+    f.taps = taps;
+    f.chunks = f.conv ? (int)(g.lda / 32) : 0;
+    f.tiles_m = xv_cdiv(g.M, f.bm);
+    f.tiles_n = xv_cdiv(g.N, 128);
+    f.nk = f.conv ? f.taps * f.chunks : xv_cdiv(Kp, BK16);
+    f.last_valid = f.conv ? 32 : Kp - (f.nk - 1) * BK16;
+    return f;
+}
+
+extern "C" int xv_debug_gemm16_nt_form(int M, int N, int K, int lda, int a_rps, int a_pitch, int stats, int bwd, int conv_wr, int out[8]) {
+    XV_REQUIRE(out, "xv_debug_gemm16_nt_form: out is NULL");
+    XV_REQUIRE(conv_wr == 0 || conv_wr == 2 || conv_wr == 4, "xv_debug_gemm16_nt_form: conv_wr must be 0, 2 or 4");
+    XV_REQUIRE(!(stats && bwd), "gemm16_nt: one epilogue at a time");
+    XvGemm16NT g = {};
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.a_rps = a_rps; g.a_pitch = a_pitch;      // (ldb = K: the op-level wrappers' weight planes)
+    if (int rc = nt16_check_shape(g)) return rc;
+    const NT16Form f = nt16_form(g, bwd != 0, conv_wr == 4 ? 4 : 0);
+    out[0] = f.conv; out[1] = f.bm; out[2] = f.taps; out[3] = f.chunks; out[4] = f.tiles_m; out[5] = f.tiles_n; out[6] = f.nk; out[7] = f.last_valid;
+    return 0;
+}
+
 template <int WR>
-static int launch_conv(hipStream_t s, const XvGemm16NT& g, NT16Args p, int taps, bool bwd) {
+static int launch_conv(hipStream_t s, const XvGemm16NT& g, NT16Args p, const NT16Form& f, bool bwd) {
     typedef ConvGeom<WR> G;
     NT16ConvArgs q;
-    p.tiles_m = xv_cdiv(g.M, G::BM);
-    q.g = p; q.taps = taps; q.chunks = (int)(g.lda / 32);
+    p.tiles_m = f.tiles_m;
+    q.g = p; q.taps = f.taps; q.chunks = f.chunks;
     q.a_rows = (long)xv_cdiv(g.M, g.a_rps) * g.a_pitch;
     const size_t lds = (size_t)G::LDS_HALFS * sizeof(u16);
     static bool attr_done = false;
@@ -589,35 +643,25 @@ int xv_launch_gemm16_nt(hipStream_t s, const XvGemm16NT& g) {
     XV_REQUIRE(g.lda % 8 == 0 && g.ldb % 8 == 0, "gemm16_nt: lda/ldb must be multiples of 8 (lda=%ld ldb=%ld)", g.lda, g.ldb);
     XV_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.Bt % 16) == 0 && g.a_plane % 8 == 0 && g.b_plane % 8 == 0,
                "gemm16_nt: planes must be 16-byte aligned");
-    XV_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.a_rps > 0, "gemm16_nt: empty problem");
-    // xv_dma16 addresses every row of a plane as a 32-bit byte offset from the plane's base
-    XV_REQUIRE(((long)xv_cdiv(g.M, g.a_rps) * g.a_pitch + 1) * g.lda * 2 < (1L << 32) && ((long)g.N + 1) * g.ldb * 2 < (1L << 32),
-               "gemm16_nt: a plane spans 4 GB or more (M=%d a_pitch=%d lda=%ld N=%d ldb=%ld): split the batch", g.M, g.a_pitch, g.lda, g.N, g.ldb);
-    if (ensure_zero16()) return 1;
-    NT16Args p;
-    p.A = (const u16*)g.A; p.lda = g.lda; p.a_plane = g.a_plane; p.a_rps = g.a_rps; p.a_pitch = g.a_pitch;
-    p.Bt = (const u16*)g.Bt; p.ldb = g.ldb; p.b_plane = g.b_plane;
-    p.C = g.C; p.ldc = g.ldc; p.M = g.M; p.N = g.N; p.K = (int)xv_align(g.K, 8);
-    p.tiles_m = xv_cdiv(g.M, 128); p.tiles_n = xv_cdiv(g.N, 128);
-    p.bias = g.bias; p.part = g.bn_part; p.a_amax = g.a_amax; p.b_amax = g.b_amax; p.zero = g_zero16;
+    if (int rc = nt16_check_shape(g)) return rc;
     const bool bwd = g.bwd_part != nullptr;
     XV_REQUIRE(!(bwd && g.bn_part), "gemm16_nt: one epilogue at a time");
     XV_REQUIRE(!bwd || (g.bwd_z && g.bwd_scale && g.bwd_shift && g.bwd_mean && g.bwd_invstd && XV16_WAVES == 4),
                "gemm16_nt: incomplete BN-backward epilogue arguments");
-    p.bwd = XvBwdStats{g.bwd_z, g.bwd_scale, g.bwd_shift, g.bwd_mean, g.bwd_invstd, g.bwd_part};
-    dim3 grid(p.tiles_m * p.tiles_n);
-    XvProfScope prof(s, g.bn_part ? 3 : 4, 2.0 * g.M * g.N * g.K);
-    int taps = 0;
-    // XV_CONV_WR=4 (experiments, tests) forces 256-row tiles wherever they apply; as a build default they would be
-    // limited to problems with at least one tile per CU
     const XvEnv* env = xv_env();
     if (!env) return 2;
-    const bool wr4 = env->conv_wr ? env->conv_wr == 4 : (XV16_CONV_WR == 4 && g.M >= 256 * 256);
-    // the BN-backward epilogue (an off-by-default experiment) is written for the 32x32x16 accumulator layout: with the 16x16x32
-    // build of the context-window kernel such a launch takes the generic kernel
-    const bool conv_ok = !bwd;
-    if (conv_ok && wr4 && conv_form_applies(g, 256, &taps)) return launch_conv<4>(s, g, p, taps, bwd);
-    if (conv_ok && conv_form_applies(g, 128, &taps)) return launch_conv<2>(s, g, p, taps, bwd);
+    if (ensure_zero16()) return 1;
+    const NT16Form f = nt16_form(g, bwd, env->conv_wr);
+    NT16Args p;
+    p.A = (const u16*)g.A; p.lda = g.lda; p.a_plane = g.a_plane; p.a_rps = g.a_rps; p.a_pitch = g.a_pitch;
+    p.Bt = (const u16*)g.Bt; p.ldb = g.ldb; p.b_plane = g.b_plane;
+    p.C = g.C; p.ldc = g.ldc; p.M = g.M; p.N = g.N; p.K = (int)xv_align(g.K, 8);
+    p.tiles_m = f.tiles_m; p.tiles_n = f.tiles_n;
+    p.bias = g.bias; p.part = g.bn_part; p.a_amax = g.a_amax; p.b_amax = g.b_amax; p.zero = g_zero16;
+    p.bwd = XvBwdStats{g.bwd_z, g.bwd_scale, g.bwd_shift, g.bwd_mean, g.bwd_invstd, g.bwd_part};
+    XvProfScope prof(s, g.bn_part ? 3 : 4, 2.0 * g.M * g.N * g.K);
+    if (f.conv) return f.bm == 256 ? launch_conv<4>(s, g, p, f, bwd) : launch_conv<2>(s, g, p, f, bwd);
+    dim3 grid(p.tiles_m * p.tiles_n);
     if (g.bn_part) hipLaunchKernelGGL(xv_gemm16_nt_kernel<1>, grid, dim3(64 * XV16_WAVES), 0, s, p);
     else if (bwd) hipLaunchKernelGGL(xv_gemm16_nt_kernel<2>, grid, dim3(64 * XV16_WAVES), 0, s, p);
     else hipLaunchKernelGGL(xv_gemm16_nt_kernel<0>, grid, dim3(64 * XV16_WAVES), 0, s, p);
@@ -645,8 +689,10 @@ struct TN16Args {
     const u16* zero;
 };
 
+#define TN16_BR 32      // reduction rows per stage
+
 __global__ __launch_bounds__(256, 2) void xv_gemm16_tn_kernel(TN16Args p) {
-    constexpr int BR = 32;
+    constexpr int BR = TN16_BR;
     constexpr int PH = BR * 128;                  // halfs per plane image
     constexpr int BH = 4 * PH;                    // per buffer: A planes, B planes
     __shared__ __attribute__((aligned(16))) u16 smem[2 * BH];
@@ -791,15 +837,24 @@ __global__ __launch_bounds__(256, 2) void xv_gemm16_tn_kernel(TN16Args p) {
 
 int xv_tn16_splits(int M, int N, int R) {
     int tiles = xv_cdiv(M, 128) * xv_cdiv(N, 128);
-    int ksteps = xv_cdiv(R, 32);
+    int ksteps = xv_cdiv(R, TN16_BR);
     int splits = 512 / tiles;                      // 2 resident workgroups per CU (64 KB LDS each): one co-resident round
     if (splits > ksteps / 2) splits = ksteps / 2;
     if (splits < 1) splits = 1;
-    int chunk = xv_cdiv(ksteps, splits) * 32;
+    int chunk = xv_cdiv(ksteps, splits) * TN16_BR;
     return xv_cdiv(R, chunk);
 }
 
-int xv_launch_gemm16_tn(hipStream_t s, const XvGemm16TN& g) {
+// The launch plan of a TN problem, stated once: xv_launch_gemm16_tn runs it, xv_debug_gemm16_tn_plan reports it.
+struct TN16Plan {
+    int tiles_m, tiles_n;
+    int rps, a_pitch, b_pitch;      // as the kernel sees them: gap-free rows are one segment of R rows
+    int collapsed;                  // 1: the rows were gap-free
+    int r_chunk;                    // reduction rows per split, a multiple of TN16_BR
+    int steady;                     // 1: whole stages advance lane offsets (rps >= TN16_BR); 0: every stage takes the per-row form
+};
+
+static int tn16_check_shape(const XvGemm16TN& g) {
     XV_REQUIRE(g.lda % 8 == 0 && g.ldb % 8 == 0 && g.M % 8 == 0 && g.N % 8 == 0, "gemm16_tn: lda/ldb/M/N must be multiples of 8 (M=%d N=%d)", g.M, g.N);
     XV_REQUIRE(g.R > 0 && g.R < (1 << 24) && g.rps > 0 && g.splits >= 1, "gemm16_tn: bad reduction shape");
     {   // xv_dma16 addresses every row of a plane as a 32-bit byte offset from the plane's base
@@ -807,19 +862,49 @@ int xv_launch_gemm16_tn(hipStream_t s, const XvGemm16TN& g) {
         XV_REQUIRE((segs * g.a_pitch + 1) * g.lda * 2 < (1L << 32) && (segs * g.b_pitch + 1) * g.ldb * 2 < (1L << 32),
                    "gemm16_tn: a plane spans 4 GB or more (%ld segments, lda=%ld ldb=%ld): split the batch", segs, g.lda, g.ldb);
     }
+    return 0;
+}
+
+static int tn16_plan(const XvGemm16TN& g, TN16Plan* t) {
+    t->rps = g.rps; t->a_pitch = g.a_pitch; t->b_pitch = g.b_pitch;
+    // gap-free rows (every dense layer: one-frame "segments") are one segment of R rows, so the K-steps take the cheap form (xv_launch_gemm_tn)
+    t->collapsed = (g.a_pitch == g.rps && g.b_pitch == g.rps) ? 1 : 0;
+    if (t->collapsed) { t->rps = g.R; t->a_pitch = g.R; t->b_pitch = g.R; }
+    t->tiles_m = xv_cdiv(g.M, 128); t->tiles_n = xv_cdiv(g.N, 128);
+    int ksteps = xv_cdiv(g.R, TN16_BR);
+    t->r_chunk = xv_cdiv(ksteps, g.splits) * TN16_BR;
+    XV_REQUIRE(xv_cdiv(g.R, t->r_chunk) == g.splits, "gemm16_tn: splits must come from xv_tn16_splits");
+    t->steady = t->rps >= TN16_BR ? 1 : 0;
+    return 0;
+}
+
+extern "C" int xv_debug_gemm16_tn_plan(int M, int N, int R, int rps, int a_pitch, int b_pitch, int out[5]) {
+    XV_REQUIRE(out, "xv_debug_gemm16_tn_plan: out is NULL");
+    XV_REQUIRE(M > 0 && N > 0, "gemm16_tn: bad reduction shape");
+    XvGemm16TN g = {};
+    g.M = M; g.N = N; g.R = R; g.rps = rps; g.a_pitch = a_pitch; g.b_pitch = b_pitch; g.lda = M; g.ldb = N;
+    g.splits = 1;
+    if (int rc = tn16_check_shape(g)) return rc;
+    g.splits = xv_tn16_splits(M, N, R);
+    TN16Plan t;
+    if (int rc = tn16_plan(g, &t)) return rc;
+    out[0] = t.tiles_m * t.tiles_n; out[1] = g.splits; out[2] = t.r_chunk; out[3] = t.collapsed; out[4] = t.steady;
+    return 0;
+}
+
+int xv_launch_gemm16_tn(hipStream_t s, const XvGemm16TN& g) {
+    if (int rc = tn16_check_shape(g)) return rc;
+    TN16Plan t;
+    if (int rc = tn16_plan(g, &t)) return rc;
     if (ensure_zero16()) return 1;
     TN16Args p;
-    p.A = (const u16*)g.A; p.lda = g.lda; p.a_plane = g.a_plane; p.a_pitch = g.a_pitch;
-    p.B = (const u16*)g.B; p.ldb = g.ldb; p.b_plane = g.b_plane; p.b_pitch = g.b_pitch;
-    p.rps = g.rps;
-    // gap-free rows (every dense layer: one-frame "segments") are one segment of R rows, so the K-steps take the cheap form (xv_launch_gemm_tn)
-    if (g.a_pitch == g.rps && g.b_pitch == g.rps) { p.rps = g.R; p.a_pitch = g.R; p.b_pitch = g.R; }
+    p.A = (const u16*)g.A; p.lda = g.lda; p.a_plane = g.a_plane; p.a_pitch = t.a_pitch;
+    p.B = (const u16*)g.B; p.ldb = g.ldb; p.b_plane = g.b_plane; p.b_pitch = t.b_pitch;
+    p.rps = t.rps;
     p.inv_rps = 1.0f / (float)p.rps;
     p.P = g.P; p.M = g.M; p.N = g.N; p.R = g.R;
-    p.tiles_m = xv_cdiv(g.M, 128); p.tiles_n = xv_cdiv(g.N, 128);
-    int ksteps = xv_cdiv(g.R, 32);
-    p.r_chunk = xv_cdiv(ksteps, g.splits) * 32;
-    XV_REQUIRE(xv_cdiv(g.R, p.r_chunk) == g.splits, "gemm16_tn: splits must come from xv_tn16_splits");
+    p.tiles_m = t.tiles_m; p.tiles_n = t.tiles_n;
+    p.r_chunk = t.r_chunk;
     p.a_amax = g.a_amax; p.b_amax = g.b_amax; p.zero = g_zero16;
     dim3 grid(p.tiles_m * p.tiles_n * g.splits);
     XvProfScope prof(s, 5, 2.0 * g.M * g.N * g.R);

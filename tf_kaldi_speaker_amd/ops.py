@@ -783,13 +783,14 @@ def bn_relu_backward_pooled_split(pool_out, dpool, b, t, z, gamma, mean, invstd,
     return Planes(data, rows, ld, amax), dgamma, dbeta, dbias
 
 
-def affine_forward_f16x3(xp, segs, t_in, k, wtp, bias, o, with_stats=False):
-    """xp: Planes of x [segs*t_in][c_ld]; wtp: Planes of Wt [o][k*c_ld]."""
+def affine_forward_f16x3(xp, segs, t_in, k, wtp, bias, o, with_stats=False, ldz=None):
+    """xp: Planes of x [segs*t_in][c_ld]; wtp: Planes of Wt [o][k*c_ld]; ldz: the row pitch of z in floats (default o: contiguous)."""
     rows = segs * (t_in - k + 1)
-    z = torch.empty((rows, o), dtype=torch.float32, device=xp.data.device)
+    ldz = o if ldz is None else ldz
+    z = torch.empty((rows, ldz), dtype=torch.float32, device=xp.data.device)[:, :o]
     part = torch.empty((4, (rows + TILE_M - 1) // TILE_M, o), dtype=torch.float32, device=z.device) if with_stats else None
     _lib.call("xv_affine_forward_f16x3", _s(), _p(xp.data), C.c_size_t(xp.stride), _p(xp.amax), segs, t_in, xp.ld, k, _p(wtp.data),
-              C.c_size_t(wtp.stride), _p(wtp.amax), _p(bias), _p(z), o, o, _p(part))
+              C.c_size_t(wtp.stride), _p(wtp.amax), _p(bias), _p(z), o, ldz, _p(part))
     return (z, part) if with_stats else z
 
 
