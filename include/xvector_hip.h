@@ -37,7 +37,8 @@ extern "C" {
  * built against another header must fail at load (xv_abi_version) or at xv_engine_create (struct_bytes), never read fields past the end
  * of a shorter struct.  xv_frontend came later and left it at 3: a new entry point beside the old ones, xv_config untouched - a host
  * built against the earlier header runs unchanged against this library.  The same holds for xv_mfcc_num_frames, xv_mfcc_table_floats,
- * xv_mfcc_tables, xv_mfcc and xv_energy_vad, which bring their own struct (xv_mfcc_config, size-checked like xv_config). */
+ * xv_mfcc_tables, xv_mfcc and xv_energy_vad, which bring their own struct (xv_mfcc_config, size-checked like xv_config), and for
+ * xv_debug_augment_plan, xv_augment_workspace_bytes and xv_augment with theirs (xv_augment_config). */
 #define XV_ABI_VERSION 3
 
 const char* xv_last_error(void);
@@ -221,6 +222,67 @@ int xv_mfcc(void* stream, const xv_mfcc_config* cfg, const float* tables_dev, co
  * mask_offsets[i] = i * t.  rows: device int32 [b].  One workgroup per piece.  The VoxCeleb vad.conf: 5.5, 0.5, 2, 0.12. */
 int xv_energy_vad(void* stream, const float* x, const int32_t* rows, int b, int t, int d, float threshold, float mean_scale,
                   int frames_context, float proportion, uint8_t* masks);
+
+/* Reverberation and additive-noise augmentation of waveforms: what the training list of the recipe pipes through wav-reverberate
+ * (egs/voxceleb/v1/run.sh:68-130: the reverberated, noise, music and babble copies of the clean list), with --normalize-output=true as
+ * its default.  Kaldi is not available where this project is built and tested: parity is BY RESTATEMENT, as for xv_mfcc - the rules
+ * below are the specification ("as restated", not "as Kaldi", wherever the two could differ: DESIGN.md section 6d lists what is
+ * unpinned), tests/augment_ref.py restates them in fp64 and the kernels are held against that.
+ *
+ * One output utterance: source x (int16, n >= 1 samples, used as floats, unscaled), optional impulse response h (int16, L >= 1 taps,
+ * unscaled), noises j = 0 .. J - 1 in list order (int16 v_j of len_j samples, snr_j dB, start sample o_j >= 0, span m_j >= 1).
+ *   1. P0 = sum x^2 / n.
+ *   2. With h: p = the first index of max(h); the early part is h[es:ee], es = max(p - trunc(0.001f * fs), 0), ee = min(p + trunc(0.05f
+ *      * fs), L), the products taken in fp32 by the host, which passes es, ee and p in the tables; E = sum (x * h[es:ee])^2 / (n + (ee - es) - 1), the mean
+ *      square of the FULL convolution over its whole length; y = x * h, M = n + L - 1 samples.
+ *   3. Without h: E = P0, y = x, M = n, p = 0.
+ *   4. Noise j is v_j[i mod len_j] for i < m_j (m_j = len_j: a foreground noise, added once at o_j; m_j = M with o_j = 0: the background
+ *      form, the noise repeated over the utterance).  Pn_j = sum_{i < m_j} v_j[i mod len_j]^2 / m_j, g_j = sqrt(10^(-snr_j / 10) * E /
+ *      Pn_j), y[o_j + i] += g_j * v_j[i mod len_j] for i < min(m_j, M - o_j).  A noise with Pn_j = 0 or o_j >= M adds nothing.
+ *   5. Pa = sum y^2 / M.  s = (normalize_output && Pa > 0 ? sqrt(P0 / Pa) : 1) * (volume > 0 ? volume : 1); y *= s.
+ *   6. out[i] = y[(i + shift) mod M] for i < n_out; shift_output: shift = p, n_out = n; otherwise shift = 0, n_out = M.
+ *   7. PCM-16: truncate toward zero, then clamp to [-32768, 32767].
+ * Numerics: P0, E, Pn_j and Pa are summed in double in a fixed order, no floating-point atomics; g_j and s are computed in double and
+ * rounded to fp32 once; the convolution, the additions of step 4 and the product of step 5 run in fp32, the first two with one fma per
+ * term.  The convolution is a direct-form FIR: taps in blocks of XV_AUG_KB anchored at tap 0, a block summed sequentially from zero in
+ * tap order, the block sums added sequentially in block order - the longest add chain of an output is chain(L) = XV_AUG_KB +
+ * ceil(L / XV_AUG_KB) roundings, never one chain over all L taps.  The output bits depend on the shape of the call only. */
+#define XV_AUG_TILE 1024              /* consecutive outputs of one utterance per workgroup */
+#define XV_AUG_KB 32                  /* taps per block of the add chain */
+typedef struct xv_augment_config {
+    int32_t struct_bytes;             /* = sizeof(xv_augment_config) of the header the host was built against; anything else is refused */
+    float sample_frequency;           /* 16000; enters es / ee only, which the host computes: carried so that one struct says it all */
+    int32_t shift_output;             /* 1 (the recipe's setting) */
+    int32_t normalize_output;         /* 1 */
+    float volume;                     /* 0: none */
+} xv_augment_config;
+/* Diagnostics: the plan of one utterance of n samples under L taps (L = 0: no impulse response): out[0] tiles = ceil(M / XV_AUG_TILE),
+ * out[1] XV_AUG_TILE, out[2] XV_AUG_KB, out[3] chain(L) (0 for L = 0).  Host arithmetic, nothing is launched. */
+int xv_debug_augment_plan(int64_t n, int64_t L, int out[4]);
+/* Bytes of workspace of an xv_augment call over b utterances with n_entries noise entries and n_tiles tiles in all (the sum of the plan's
+ * tiles): y in fp32, a tile's XV_AUG_TILE samples at its index, and one double per tile for each of E and Pa, per utterance for P0, per
+ * entry for Pn.  0 for negative counts.  Host arithmetic. */
+size_t xv_augment_workspace_bytes(int b, int n_entries, int64_t n_tiles);
+/* The three pools hold int16 samples back to back on the device (rir_pcm / noise_pcm may be NULL when nothing refers to them).  tables:
+ * ONE device int64 array - the call's only index upload - of XV_AUG_UTT_WORDS * b + XV_AUG_NOISE_WORDS * n_entries + 2 * n_tiles words:
+ *   per utterance i  [b][10]:  source offset, n, rir offset (-1: no impulse response), L, es, ee, p, first noise entry, number of noise
+ *                              entries, output offset (in samples, of out_pcm and out_f32 alike)
+ *   per noise entry  [n_entries][5]: offset, len, snr (the fp32 bit pattern in the low 32 bits), start o, span m - utterance after
+ *                              utterance in list order
+ *   per tile         [n_tiles][2]: utterance, first output - for each utterance in order, the ceil(M / XV_AUG_TILE) tiles of its y
+ * Nothing in it is checked on the device: the caller guarantees that every range lies inside its pool, 0 <= es < ee <= L, 0 <= p < L,
+ * M < 2^31 and that the outputs do not overlap (ops.augment checks the host arrays before the upload, as ops.mfcc does).
+ * out_pcm: int16, utterance i's n_out samples at its output offset - the packed layout xv_mfcc reads, with out_samples [b] = n_out as
+ * its `samples`; samples between the utterances are not written.  out_f32 (NULL: not wanted): the fp32 values of step 6 at the same
+ * offsets.  clipped [b]: how many samples of the utterance the clamp of step 7 changed.
+ * Launches: the powers (one workgroup per signal); the FIR in its `energy` role (the early part; one double per tile) and its `store`
+ * role (y) - both only when an utterance has an impulse response; mix (noises, one double of sum y^2 per tile); finish (steps 5 - 7).
+ * One workgroup per tile in the last four. */
+#define XV_AUG_UTT_WORDS 10
+#define XV_AUG_NOISE_WORDS 5
+int xv_augment(void* stream, const xv_augment_config* cfg, int b, int n_entries, int64_t n_tiles, const int16_t* src_pcm,
+               const int16_t* rir_pcm, const int16_t* noise_pcm, const int64_t* tables, size_t table_words, int any_rir, void* ws,
+               size_t ws_bytes, int16_t* out_pcm, float* out_f32, int32_t* out_samples, int32_t* clipped);
 
 /* Cosine trial scoring with adaptive symmetric score normalisation (AS-norm) on embedding matrices: the stage behind extract.py, for
  * which the reference recipe goes to Kaldi (ivector-mean | ivector-subtract-global-mean | ivector-normalize-length, then

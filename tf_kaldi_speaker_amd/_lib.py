@@ -109,6 +109,26 @@ class XvMfccConfig(C.Structure):
         self.struct_bytes = C.sizeof(XvMfccConfig)
 
 
+class XvAugmentConfig(C.Structure):
+    """Mirror of `struct xv_augment_config` (include/xvector_hip.h) with its defaults - wav-reverberate --shift-output=true
+    --normalize-output=true at 16 kHz; struct_bytes is filled in on construction."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("sample_frequency", C.c_float),
+        ("shift_output", C.c_int32),
+        ("normalize_output", C.c_int32),
+        ("volume", C.c_float),
+    ]
+    DEFAULTS = dict(sample_frequency=16000.0, shift_output=1, normalize_output=1, volume=0.0)
+
+    def __init__(self, *args, **kw):
+        if args:
+            raise TypeError("XvAugmentConfig takes keyword arguments only (its first field is struct_bytes, filled in here)")
+        super(XvAugmentConfig, self).__init__(**dict(self.DEFAULTS, **kw))
+        self.struct_bytes = C.sizeof(XvAugmentConfig)
+
+
 LOSS_KINDS = {
     "softmax": 0,
     "asoftmax": 1,
@@ -203,6 +223,9 @@ SIGNATURES = {
     "xv_mfcc_tables": (_I, [_VP, _VP, _SZ]),
     "xv_mfcc": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "xv_energy_vad": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _F, _I, _F, _VP]),
+    "xv_debug_augment_plan": (_I, [C.c_int64, C.c_int64, C.POINTER(_I)]),
+    "xv_augment_workspace_bytes": (_SZ, [_I, _I, C.c_int64]),
+    "xv_augment": (_I, [_VP, _VP, _I, _I, C.c_int64, _VP, _VP, _VP, _VP, _SZ, _I, _VP, _SZ, _VP, _VP, _VP, _VP]),
     "xv_score_prepare": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I]),
     "xv_score_trials": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "xv_score_cohort_workspace_bytes": (_SZ, [_I, _I, _I]),
@@ -250,6 +273,8 @@ SIGNATURES = {
     "xv_engine_invalidate_weights": (_I, [_VP]),
 }
 
+XV_AUG_UTT_WORDS = 10       # include/xvector_hip.h: words per utterance / per noise entry of xv_augment's tables
+XV_AUG_NOISE_WORDS = 5
 XV_BWD_STAGES = 4
 XV_MAX_FRAME_LAYERS = 12
 _lib = None

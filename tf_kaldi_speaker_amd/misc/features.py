@@ -201,21 +201,36 @@ class FeatureExtractor(object):
 
     def extract(self, waves):
         """waves: int16 arrays -> [(features float32 [T, num_ceps], decisions float32 [T] of 1.0 / 0.0)] in order; T may be 0."""
-        torch, ops = self.torch, self.ops
         waves = [np.ascontiguousarray(w, dtype=np.int16).reshape(-1) for w in waves]
         lengths = [len(w) for w in waves]
         frames = [self.num_frames(n) for n in lengths]
         out = [None] * len(waves)
-        v = self.vad
         for batch in self._batches(frames, lengths):
             offsets = np.concatenate([[0], np.cumsum([lengths[i] for i in batch])]).astype(np.int64)
             if offsets[-1] == 0:
                 for i in batch:
                     out[i] = (np.zeros((0, self.mfcc.num_ceps), np.float32), np.zeros(0, np.float32))
                 continue
-            pcm = torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
+            pcm = self.torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
+            for i, r in zip(batch, self.extract_packed(pcm, offsets[:-1], [lengths[i] for i in batch])):      # one call: the batch fits
+                out[i] = r
+        return out
+
+    def extract_packed(self, pcm, offsets, lengths):
+        """The same for utterances that are on the device already: pcm an int16 device tensor, utterance i its samples offsets[i] ..
+        offsets[i] + lengths[i] (host arrays) - what misc.augment.Augmenter.run returns.  Nothing is copied; the calls are cut as by
+        extract()."""
+        ops, v = self.ops, self.vad
+        offsets, lengths = np.asarray(offsets, np.int64), [int(n) for n in lengths]
+        frames = [self.num_frames(n) for n in lengths]
+        out = [None] * len(lengths)
+        for batch in self._batches(frames, lengths):
+            if sum(lengths[i] for i in batch) == 0:
+                for i in batch:
+                    out[i] = (np.zeros((0, self.mfcc.num_ceps), np.float32), np.zeros(0, np.float32))
+                continue
             t_out = max(max(frames[i] for i in batch), 1)
-            x, rows = ops.mfcc(self.cfg, self.tables, pcm, offsets[:-1], np.asarray([lengths[i] for i in batch], np.int64), t_out)
+            x, rows = ops.mfcc(self.cfg, self.tables, pcm, offsets[batch], np.asarray([lengths[i] for i in batch], np.int64), t_out)
             masks = ops.energy_vad(x, rows, v.threshold, v.mean_scale, v.frames_context, v.proportion)
             x_h, m_h, r_h = x.cpu().numpy(), masks.cpu().numpy(), rows.cpu().numpy()
             for j, i in enumerate(batch):

@@ -50,7 +50,24 @@ ARGUMENTS = {
     "compress": (("--compress",), dict(type=str, default="true", choices=("true", "false"),
                                        help="true: 'CM ' compressed feature matrices (copy-feats --compress=true); false: 'FM '.")),
     "write_utt2num_frames": (("--write-utt2num-frames",), dict(type=str, default="", help="Write `key frames` lines to this file.")),
+    "augment_plan": (("--augment-plan",), dict(type=str, default="", help="A plan file (misc/augment.py): `out_key src_key [rir=ID] "
+                                                                          "[noise=ID:snr:start_seconds[:bg]] ...` per line.  The keys written are "
+                                                                          "the plan's output keys, the sources come from wav.scp, the augmented "
+                                                                          "waveforms go to the MFCC kernels on the device.  Empty: no augmentation.")),
+    "rir_scp": (("--rir-scp",), dict(type=str, default="", help="`id rxfilename` table of the impulse responses the plan names (RIFF PCM-16).")),
+    "noise_scp": (("--noise-scp",), dict(type=str, default="", help="`id rxfilename` table of the noises the plan names (RIFF PCM-16).")),
+    "augment_config": (("--augment-config",), dict(type=str, default="", help="Kaldi conf file of wav-reverberate options (--shift-output, "
+                                                                              "--normalize-output, --volume, --impulse-response-channel, "
+                                                                              "--noise-channel).  Empty: the recipe's (true, true, none, 0, 0).")),
+    "aug_config": (("--config",), dict(type=str, default="", help="Kaldi conf file of wav-reverberate options; see --augment-config of make_mfcc.py.")),
+    "sample_frequency": (("--sample-frequency",), dict(type=float, default=16000.0, help="The sample rate of every file; there is no resampling.")),
+    "make_plan": (("--make-plan",), dict(type=str, default="", choices=("", "reverb", "noise", "music", "babble"),
+                                         help="Write one of the recipe's four lists to the `plan` file instead of augmenting.")),
+    "seed": (("--seed",), dict(type=int, default=0, help="The seed of --make-plan (numpy.random.RandomState).")),
+    "fg_interval": (("--fg-interval",), dict(type=float, default=1.0, help="--make-plan noise: seconds between two foreground noises.")),
     # positionals
+    "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),
+    "augment_out_dir": (("out_dir",), dict(type=str, nargs="?", default="", help="Receives wav/<key>.wav and wav.scp (not needed with --make-plan).")),
     "wav_scp": (("wav_scp",), dict(type=str, help="Kaldi wav.scp: `key rxfilename` per line, the rxfilename a RIFF PCM-16 file or `command |`.")),
     "feats_wspecifier": (("feats_wspecifier",), dict(type=str, help="`ark,scp:feats.ark,feats.scp` (or `ark:feats.ark`): the feature table.")),
     "vad_wspecifier": (("vad_wspecifier",), dict(type=str, help="`ark,scp:vad.ark,vad.scp` (or `ark:vad.ark`): the table of VAD decisions.")),

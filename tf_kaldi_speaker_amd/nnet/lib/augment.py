@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Reverberated and noisy copies of a wav.scp on the GPU:
+
+    python nnet/lib/augment.py [-g GPU] [--config conf/augment.conf] [--sample-frequency 16000] --rir-scp rir.scp --noise-scp noise.scp
+                               plan wav.scp out_dir
+    python nnet/lib/augment.py --make-plan {reverb,noise,music,babble} [--seed N] [--fg-interval S] --rir-scp rir.scp --noise-scp noise.scp
+                               plan wav.scp
+
+The augmentation stage of the recipe, for which the reference goes to Kaldi (egs/voxceleb/v1/run.sh:68-130: the reverberated, noise, music
+and babble copies of the training list are `wav-reverberate` pipes inside wav.scp entries).  plan: one line per output utterance,
+`out_key src_key [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...` (misc/augment.py).  wav.scp: the sources, `key rxfilename` lines, the
+rxfilename a RIFF PCM-16 file or a `command |` that writes one; rir.scp / noise.scp: the same for the impulse responses and noises the plan
+names.  Every file must have --sample-frequency: there is no resampling.  Writes out_dir/wav/<out_key>.wav (mono RIFF PCM-16) and
+out_dir/wav.scp, and logs per key its samples, impulse response, number of noises and clipped samples.  The arithmetic is
+wav-reverberate's with --normalize-output=true as include/xvector_hip.h restates it; --duration, --multi-channel-output and
+--input-wave-channel are refused by name (misc/augment.py says why).
+--make-plan writes one of the recipe's four lists to `plan` instead; the durations it needs are read from the files.  Its random choices
+are this project's own (numpy.random.RandomState(--seed)), not those of Kaldi's reverberate_data_dir.py / augment_data_dir.py.
+"""
+import os
+import sys
+import time
+
+import _cli
+from misc import augment, features
+
+# utterances augmented together (Augmenter cuts them into calls that fit its workspace)
+WINDOW_UTTERANCES = 256
+WINDOW_SAMPLES = 64 << 20
+
+
+def main():
+    log = _cli.logger()
+    args = _cli.parser_for("gpu", "aug_config", "sample_frequency", "rir_scp", "noise_scp", "make_plan", "seed", "fg_interval", "plan", "wav_scp",
+                           "augment_out_dir").parse_args()
+    fs = args.sample_frequency
+    try:
+        options = augment.AugmentOptions.from_conf(args.config) if args.config else augment.AugmentOptions()
+        rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response") if args.rir_scp else {}
+        noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise") if args.noise_scp else {}
+        wavs = augment.read_scp(args.wav_scp)
+    except ValueError as e:
+        sys.exit(str(e))
+    mono = features.MfccOptions(sample_frequency=fs)
+    if args.make_plan:
+        try:
+            utterances = [(key, len(features.read_wav(rx, mono, key)) / fs) for key, rx in wavs]
+            entries = augment.make_plan(args.make_plan, utterances, [(k, len(v) / fs) for k, v in rirs.items()],
+                                        [(k, len(v) / fs) for k, v in noises.items()], args.seed, args.fg_interval, fs)
+        except ValueError as e:
+            sys.exit(str(e))
+        augment.write_plan(entries, args.plan, fs)
+        log.info("[INFO] Wrote the %s plan of %d utterances to %s (seed %d)." % (args.make_plan, len(entries), args.plan, args.seed))
+        return
+    if not args.out_dir:
+        sys.exit("out_dir is needed (unless --make-plan writes the plan)")
+    try:
+        entries = augment.read_plan(args.plan, fs, rirs, noises)
+    except ValueError as e:
+        sys.exit(str(e))
+    rx_of = dict(wavs)
+    for e in entries:
+        if e.src_key not in rx_of:
+            sys.exit("%s: Key %s: source %s is not in %s" % (args.plan, e.out_key, e.src_key, args.wav_scp))
+    import torch
+    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    aug = augment.Augmenter(options, rirs, noises, fs, device)
+    wav_dir = os.path.join(args.out_dir, "wav")
+    os.makedirs(wav_dir, exist_ok=True)
+    stats = {"utts": 0, "samples": 0, "clipped": 0, "t0": time.time()}
+    window, window_samples = [], 0
+    with open(os.path.join(args.out_dir, "wav.scp"), "w") as scp:
+        def flush():
+            if not window:
+                return
+            outs, clipped = aug.augment([w for _, w in window], [e for e, _ in window])
+            for (e, _), out, c in zip(window, outs, clipped):
+                path = os.path.join(wav_dir, e.out_key + ".wav")
+                augment.write_wav(path, out, fs)
+                scp.write("%s %s\n" % (e.out_key, path))
+                log.info("[INFO] Key %s: %d samples, rir %s, %d noises, %d clipped." % (e.out_key, len(out), e.rir if e.rir is not None else "-",
+                                                                                       len(e.noises), int(c)))
+                stats["utts"] += 1
+                stats["samples"] += len(out)
+                stats["clipped"] += int(c)
+            del window[:]
+
+        last = (None, None)
+        for e in entries:
+            if last[0] != e.src_key:
+                try:
+                    last = (e.src_key, features.read_wav(rx_of[e.src_key], mono, e.src_key))
+                except ValueError as err:
+                    sys.exit(str(err))
+            if len(last[1]) == 0:
+                sys.exit("Key %s: the source %s holds no samples" % (e.out_key, e.src_key))
+            window.append((e, last[1]))
+            window_samples += len(last[1])
+            if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
+                flush()
+                window_samples = 0
+        flush()
+    log.info("[INFO] Augmented %d utterances (%d samples, %d clipped) in %.2f s." % (stats["utts"], stats["samples"], stats["clipped"],
+                                                                                    time.time() - stats["t0"]))
+
+
+if __name__ == "__main__":
+    main()

@@ -2,7 +2,8 @@
 """MFCC features and energy VAD decisions from a wav.scp on the GPU:
 
     python nnet/lib/make_mfcc.py [-g GPU] [--mfcc-config conf/mfcc.conf] [--vad-config conf/vad.conf] [--compress {true,false}]
-                                 [--write-utt2num-frames FILE] wav.scp ark,scp:feats.ark,feats.scp ark,scp:vad.ark,vad.scp
+                                 [--write-utt2num-frames FILE] [--augment-plan PLAN --rir-scp F --noise-scp F [--augment-config conf]]
+                                 wav.scp ark,scp:feats.ark,feats.scp ark,scp:vad.ark,vad.scp
 
 The first stage of the recipe, for which the reference goes to Kaldi (egs/voxceleb/v1/run.sh:59-63: steps/make_mfcc.sh --mfcc-config
 conf/mfcc.conf = compute-mfcc-feats | copy-feats --compress=true, then sid/compute_vad_decision.sh = compute-vad-decision).  wav.scp:
@@ -13,6 +14,10 @@ header points per column, not copy-feats' quartiles: the same format for every r
 the column whatever its distribution (dataset/kaldi_io.py write_compressed_mat, header="uniform").
 This is the --dither=0 program: the conf may say --dither=0, any other value is refused (misc/features.py says why); so is every other
 option of the two Kaldi programs that is not implemented, by name.  An utterance too short for one frame is logged and skipped.
+--augment-plan: the features of the AUGMENTED training list (egs/voxceleb/v1/run.sh:68-130) without a wav file in between - the keys
+written are the plan's output keys (misc/augment.py: `out_key src_key [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...`), the sources come
+from wav.scp, and the reverberated / noisy PCM goes from the augmentation kernels to the MFCC kernels on the device: the same bytes as
+nnet/lib/augment.py followed by this program on its wav.scp.  Without the option nothing changes.
 """
 import sys
 import time
@@ -20,7 +25,7 @@ import time
 import numpy as np
 
 import _cli
-from misc import features
+from misc import augment, features
 from dataset import kaldi_io
 
 # utterances read before they go to the GPU together (FeatureExtractor cuts them into calls that fit its workspace)
@@ -57,8 +62,8 @@ class _Table(object):
 
 def main():
     log = _cli.logger()
-    args = _cli.parser_for("gpu", "mfcc_config", "vad_config", "compress", "write_utt2num_frames", "wav_scp", "feats_wspecifier",
-                           "vad_wspecifier").parse_args()
+    args = _cli.parser_for("gpu", "mfcc_config", "vad_config", "compress", "write_utt2num_frames", "augment_plan", "rir_scp", "noise_scp",
+                           "augment_config", "wav_scp", "feats_wspecifier", "vad_wspecifier").parse_args()
     try:
         mfcc = features.MfccOptions.from_conf(args.mfcc_config) if args.mfcc_config else features.MfccOptions()
         vad = features.VadOptions.from_conf(args.vad_config) if args.vad_config else features.VadOptions()
@@ -80,40 +85,84 @@ def main():
     stats = {"utts": 0, "frames": 0, "voiced": 0, "skipped": 0, "t0": time.time()}
     window, window_samples = [], 0
 
+    def write(key, samples, feats, decisions):
+        if feats.shape[0] == 0:
+            log.info("[INFO] Key %s has %d samples, too few for one frame, skip." % (key, samples))
+            stats["skipped"] += 1
+            return
+        log.info("[INFO] Key %s: %d samples, %d frames, %d voiced." % (key, samples, feats.shape[0], int(decisions.sum())))
+        feats_out.write(key, lambda fd, k: write_mat(fd, feats, key=k))
+        vad_out.write(key, lambda fd, k: kaldi_io.write_vec_flt(fd, decisions, key=k))
+        if counts is not None:
+            counts.write("%s %d\n" % (key, feats.shape[0]))
+        stats["utts"] += 1
+        stats["frames"] += feats.shape[0]
+        stats["voiced"] += int(decisions.sum())
+
     def flush():
         results = fx.extract([w for _, w in window])
         for (key, w), (feats, decisions) in zip(window, results):
-            if feats.shape[0] == 0:
-                log.info("[INFO] Key %s has %d samples, too few for one frame, skip." % (key, len(w)))
-                stats["skipped"] += 1
-                continue
-            log.info("[INFO] Key %s: %d samples, %d frames, %d voiced." % (key, len(w), feats.shape[0], int(decisions.sum())))
-            feats_out.write(key, lambda fd, k: write_mat(fd, feats, key=k))
-            vad_out.write(key, lambda fd, k: kaldi_io.write_vec_flt(fd, decisions, key=k))
-            if counts is not None:
-                counts.write("%s %d\n" % (key, feats.shape[0]))
-            stats["utts"] += 1
-            stats["frames"] += feats.shape[0]
-            stats["voiced"] += int(decisions.sum())
+            write(key, len(w), feats, decisions)
         del window[:]
 
-    with open(args.wav_scp, "r") as scp:
-        for line in scp:
-            if not line.strip():
-                continue
-            parts = line.strip().split(None, 1)
-            if len(parts) != 2:
-                sys.exit("%s: `key rxfilename` is expected, got `%s`" % (args.wav_scp, line.strip()))
-            try:
-                wav = features.read_wav(parts[1], mfcc, parts[0])
-            except ValueError as e:
-                sys.exit(str(e))
-            window.append((parts[0], wav))
-            window_samples += len(wav)
+    def flush_augmented(aug):
+        pcm, offsets, lengths, clipped = aug.run([w for _, w in window], [e for e, _ in window])
+        results = fx.extract_packed(pcm, offsets, lengths)
+        for (e, _), n, c, (feats, decisions) in zip(window, lengths, clipped, results):
+            log.info("[INFO] Key %s: augmented from %s, rir %s, %d noises, %d clipped." % (e.out_key, e.src_key, e.rir if e.rir is not None else "-",
+                                                                                          len(e.noises), int(c)))
+            write(e.out_key, int(n), feats, decisions)
+        del window[:]
+
+    if not args.augment_plan and (args.rir_scp or args.noise_scp or args.augment_config):
+        sys.exit("--rir-scp, --noise-scp and --augment-config belong to --augment-plan")
+    if args.augment_plan:
+        try:
+            options = augment.AugmentOptions.from_conf(args.augment_config) if args.augment_config else augment.AugmentOptions()
+            fs = mfcc.sample_frequency
+            rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response") if args.rir_scp else {}
+            noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise") if args.noise_scp else {}
+            entries = augment.read_plan(args.augment_plan, fs, rirs, noises)
+            rx_of = dict(augment.read_scp(args.wav_scp))
+        except ValueError as e:
+            sys.exit(str(e))
+        aug = augment.Augmenter(options, rirs, noises, fs, device)
+        last = (None, None)
+        for e in entries:
+            if e.src_key not in rx_of:
+                sys.exit("%s: Key %s: source %s is not in %s" % (args.augment_plan, e.out_key, e.src_key, args.wav_scp))
+            if last[0] != e.src_key:
+                try:
+                    last = (e.src_key, features.read_wav(rx_of[e.src_key], mfcc, e.src_key))
+                except ValueError as err:
+                    sys.exit(str(err))
+            if len(last[1]) == 0:
+                sys.exit("Key %s: the source %s holds no samples" % (e.out_key, e.src_key))
+            window.append((e, last[1]))
+            window_samples += len(last[1])
             if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
-                flush()
+                flush_augmented(aug)
                 window_samples = 0
-    flush()
+        if window:
+            flush_augmented(aug)
+    else:
+        with open(args.wav_scp, "r") as scp:
+            for line in scp:
+                if not line.strip():
+                    continue
+                parts = line.strip().split(None, 1)
+                if len(parts) != 2:
+                    sys.exit("%s: `key rxfilename` is expected, got `%s`" % (args.wav_scp, line.strip()))
+                try:
+                    wav = features.read_wav(parts[1], mfcc, parts[0])
+                except ValueError as e:
+                    sys.exit(str(e))
+                window.append((parts[0], wav))
+                window_samples += len(wav)
+                if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
+                    flush()
+                    window_samples = 0
+        flush()
     feats_out.close()
     vad_out.close()
     if counts is not None:

@@ -141,6 +141,147 @@ def energy_vad(x, rows, threshold=5.5, mean_scale=0.5, frames_context=2, proport
     return masks
 
 
+def augment_config(**kw):
+    """xv_augment_config with wav-reverberate's recipe settings (16 kHz, shift_output, normalize_output, no volume); keyword arguments
+    name the fields to change."""
+    return _lib.XvAugmentConfig(**kw)
+
+
+def augment_plan(n, taps=0):
+    """xv_debug_augment_plan: {tiles, tile, kb, chain} of an utterance of n samples under `taps` taps (0: no impulse response)."""
+    out = (C.c_int * 4)()
+    _lib.check(_lib.load().xv_debug_augment_plan(C.c_int64(int(n)), C.c_int64(int(taps)), out), "xv_debug_augment_plan")
+    return dict(tiles=out[0], tile=out[1], kb=out[2], chain=out[3])
+
+
+def augment_workspace_bytes(b, n_entries, n_tiles):
+    return int(_lib.load().xv_augment_workspace_bytes(int(b), int(n_entries), C.c_int64(int(n_tiles))))
+
+
+def augment_early(h, sample_frequency):
+    """(es, ee, p) of an impulse response (host array): p the first index of its maximum, the early part h[es:ee] from 1 ms in front of
+    the peak to 50 ms behind it, the products taken in fp32 and truncated (include/xvector_hip.h, step 2)."""
+    import numpy as np
+    h = np.asarray(h).reshape(-1)
+    if h.size == 0:
+        raise ValueError("augment_early: an impulse response needs at least one tap")
+    p, fs = int(np.argmax(h)), np.float32(sample_frequency)
+    return max(p - int(np.float32(0.001) * fs), 0), min(p + int(np.float32(0.05) * fs), h.size), p
+
+
+def _aug_ints(a, what, n=None):
+    import numpy as np
+    a = np.asarray(a)
+    if a.ndim != 1 or a.dtype.kind not in "iu" or (n is not None and a.size != n):
+        raise ValueError("augment: %s must be a 1-D integer array%s" % (what, "" if n is None else " of %d" % n))
+    return a.astype(np.int64)
+
+
+def _aug_pool(t, what):
+    if t is None:
+        return 0
+    if t.dtype != torch.int16 or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("augment: %s must be a contiguous 1-D int16 tensor" % what)
+    return t.numel()
+
+
+def augment(cfg, src, src_off, src_len, rir=None, rir_off=None, rir_len=None, rir_early=None, utt_rir=None, noise=None, noise_off=None,
+            noise_len=None, nz_first=None, nz_id=None, nz_snr=None, nz_start=None, nz_span=None, out_offsets=None, out_pcm=None,
+            out_f32=False):
+    """Reverberation and additive noise on a batch of waveforms (xv_augment; include/xvector_hip.h states the arithmetic).
+    src / rir / noise: int16 device tensors, the pools' signals back to back; every other argument is a HOST array, checked here before
+    the one upload (the kernels check nothing).  Utterance i is src[src_off[i] : src_off[i] + src_len[i]]; utt_rir[i] names its impulse
+    response (-1 or utt_rir=None: none), rir k being rir[rir_off[k] : rir_off[k] + rir_len[k]] with rir_early[k] = augment_early(...) =
+    (es, ee, p); its noises are the entries nz_first[i] .. nz_first[i + 1] (CSR, [b + 1]) in list order: noise nz_id[e] at nz_snr[e] dB
+    from sample nz_start[e] over nz_span[e] samples (-1: the background form, the utterance's M).  out_offsets (default: back to back) /
+    out_pcm (default: a new tensor that just holds them): where the outputs go; out_f32: True for a new float32 tensor of out_pcm's
+    size, or such a tensor.  -> (out_pcm int16, out_offsets int64 host array, out_samples int32 [b], clipped int32 [b], out_f32 | None)."""
+    import numpy as np
+    n_src, n_rir_pool, n_noise_pool = _aug_pool(src, "src"), _aug_pool(rir, "rir"), _aug_pool(noise, "noise")
+    src_off, src_len = _aug_ints(src_off, "src_off"), _aug_ints(src_len, "src_len")
+    b = src_off.size
+    if b == 0 or src_len.size != b:
+        raise ValueError("augment: src_off and src_len must be two non-empty arrays of one length")
+    if src_off.min() < 0 or src_len.min() < 1 or (src_off + src_len).max() > n_src:
+        raise IndexError("augment: a source is empty or lies outside the %d samples of src" % n_src)
+    utt_rir = np.full(b, -1, np.int64) if utt_rir is None else _aug_ints(utt_rir, "utt_rir", b)
+    any_rir = bool((utt_rir >= 0).any())
+    taps = np.zeros(b, np.int64)
+    rir_words = np.zeros((b, 5), np.int64)
+    rir_words[:, 0] = -1
+    if any_rir:
+        rir_off, rir_len = _aug_ints(rir_off, "rir_off"), _aug_ints(rir_len, "rir_len", np.asarray(rir_off).size)
+        early = np.asarray(rir_early, dtype=np.int64).reshape(-1, 3)
+        if early.shape[0] != rir_off.size:
+            raise ValueError("augment: rir_early must hold (es, ee, p) of each of the %d impulse responses" % rir_off.size)
+        if rir_off.size == 0 or rir_off.min() < 0 or rir_len.min() < 1 or (rir_off + rir_len).max() > n_rir_pool:
+            raise IndexError("augment: an impulse response is empty or lies outside the %d samples of rir" % n_rir_pool)
+        if (early[:, 0] < 0).any() or (early[:, 0] >= early[:, 1]).any() or (early[:, 1] > rir_len).any() or (early[:, 2] < 0).any() \
+                or (early[:, 2] >= rir_len).any():
+            raise ValueError("augment: rir_early must satisfy 0 <= es < ee <= L and 0 <= p < L")
+        if utt_rir.max() >= rir_off.size or utt_rir.min() < -1:
+            raise IndexError("augment: utt_rir names an impulse response outside 0 .. %d" % (rir_off.size - 1))
+        has = utt_rir >= 0
+        k = utt_rir[has]
+        taps[has] = rir_len[k]
+        rir_words[has] = np.stack([rir_off[k], rir_len[k], early[k, 0], early[k, 1], early[k, 2]], axis=1)
+    m_len = np.where(taps > 0, src_len + taps - 1, src_len)
+    if m_len.max() >= 2 ** 31:
+        raise ValueError("augment: an utterance would hold 2^31 samples or more")
+    nz_first = np.zeros(b + 1, np.int64) if nz_first is None else _aug_ints(nz_first, "nz_first", b + 1)
+    n_entries = int(nz_first[-1])
+    if nz_first[0] != 0 or (np.diff(nz_first) < 0).any():
+        raise ValueError("augment: nz_first must rise from 0 (CSR)")
+    noise_words = np.zeros((n_entries, 5), np.int64)
+    if n_entries:
+        noise_off, noise_len = _aug_ints(noise_off, "noise_off"), _aug_ints(noise_len, "noise_len", np.asarray(noise_off).size)
+        if noise_off.size == 0 or noise_off.min() < 0 or noise_len.min() < 1 or (noise_off + noise_len).max() > n_noise_pool:
+            raise IndexError("augment: a noise is empty or lies outside the %d samples of noise" % n_noise_pool)
+        nz_id, nz_start, nz_span = _aug_ints(nz_id, "nz_id", n_entries), _aug_ints(nz_start, "nz_start", n_entries), _aug_ints(nz_span, "nz_span", n_entries)
+        snr = np.asarray(nz_snr, dtype=np.float32).reshape(-1)
+        if snr.size != n_entries or not np.isfinite(snr).all() or np.abs(snr).max() > 200:
+            raise ValueError("augment: nz_snr must hold one finite SNR within +-200 dB per noise entry")
+        if nz_id.min() < 0 or nz_id.max() >= noise_off.size:
+            raise IndexError("augment: nz_id names a noise outside 0 .. %d" % (noise_off.size - 1))
+        owner = np.repeat(np.arange(b), np.diff(nz_first))
+        nz_span = np.where(nz_span == -1, m_len[owner], nz_span)
+        if nz_start.min() < 0 or nz_span.min() < 1 or nz_start.max() >= 2 ** 31 or nz_span.max() >= 2 ** 31:
+            raise ValueError("augment: nz_start must lie in 0 .. 2^31 and nz_span in 1 .. 2^31 (or be -1: the background form)")
+        noise_words = np.stack([noise_off[nz_id], noise_len[nz_id], snr.view(np.uint32).astype(np.int64), nz_start, nz_span], axis=1)
+    n_out = src_len if cfg.shift_output else m_len
+    if out_offsets is None:
+        out_offsets = np.concatenate([[0], np.cumsum(n_out)[:-1]]).astype(np.int64)
+    out_offsets = _aug_ints(out_offsets, "out_offsets", b)
+    if out_pcm is None:
+        out_pcm = torch.empty(int((out_offsets + n_out).max()), dtype=torch.int16, device=src.device)
+    total = _aug_pool(out_pcm, "out_pcm")
+    order = np.argsort(out_offsets, kind="stable")
+    if out_offsets.min() < 0 or (out_offsets + n_out).max() > total or (out_offsets[order][1:] < (out_offsets + n_out)[order][:-1]).any():
+        raise IndexError("augment: the outputs overlap or lie outside the %d samples of out_pcm" % total)
+    if out_f32 is True:
+        out_f32 = torch.empty(total, dtype=torch.float32, device=src.device)
+    elif out_f32 is False:
+        out_f32 = None
+    elif out_f32.dtype != torch.float32 or out_f32.dim() != 1 or not out_f32.is_contiguous() or out_f32.numel() < total:
+        raise ValueError("augment: out_f32 must be a contiguous 1-D float32 tensor of out_pcm's size")
+    tile = augment_plan(1)["tile"]
+    tiles = (m_len + tile - 1) // tile
+    n_tiles = int(tiles.sum())
+    tile_utt = np.repeat(np.arange(b, dtype=np.int64), tiles)
+    tile_first = (np.arange(n_tiles, dtype=np.int64) - np.repeat(np.cumsum(tiles) - tiles, tiles)) * tile
+    utt_words = np.concatenate([np.stack([src_off, src_len], axis=1), rir_words, np.stack([nz_first[:-1], np.diff(nz_first), out_offsets], axis=1)], axis=1)
+    assert utt_words.shape == (b, _lib.XV_AUG_UTT_WORDS) and noise_words.shape == (n_entries, _lib.XV_AUG_NOISE_WORDS)
+    tables = np.concatenate([utt_words.reshape(-1), noise_words.reshape(-1), np.stack([tile_utt, tile_first], axis=1).reshape(-1)]).astype(np.int64)
+    tables_d = torch.from_numpy(np.ascontiguousarray(tables)).to(src.device)
+    ws_bytes = augment_workspace_bytes(b, n_entries, n_tiles)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=src.device)
+    out_samples = torch.empty(b, dtype=torch.int32, device=src.device)
+    clipped = torch.empty(b, dtype=torch.int32, device=src.device)
+    _lib.call("xv_augment", _s(), C.byref(cfg), b, n_entries, C.c_int64(n_tiles), _p(src), _p(rir), _p(noise), _p(tables_d), C.c_size_t(tables.size),
+              int(any_rir), _p(ws), C.c_size_t(ws_bytes), _p(out_pcm), _p(out_f32), _p(out_samples), _p(clipped))
+    return out_pcm, out_offsets, out_samples, clipped, out_f32
+
+
 def _pitched(t, what):
     """(rows, pitch in floats) of a 2-D float32 device view with contiguous rows."""
     if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):

@@ -14,6 +14,8 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
   python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
+  python tools/bench_kernel.py augment [utterances=256] [notrace] reverberation + one background noise (xv_augment.hip) on the same synthetic PCM under impulse
+                                                                responses of 4 000 / 8 000 / 16 000 taps: us per kernel role, G taps x samples / s
 
 Environment: XV_DATA_SCALE=0 (all-zero operands: DVFS check), XV_B (chunks, gemm16), ITERS (segment), XV_LIB (another build of the library).
 """
@@ -374,7 +376,64 @@ def cmd_mfcc(argv):
     print("  xv_mfcc + xv_energy_vad %9.1f us  %.2f M frames/s = %.0f x real time" % (us_both, frames.sum() / us_both, frames.sum() / us_both * 1e6 / 100.0), flush=True)
 
 
-COMMANDS = {"mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+def cmd_augment(argv):
+    """xv_augment on one batch per impulse-response length: every utterance reverberated by the same L taps plus one background noise at 10 dB,
+    shift_output and normalize_output on.  Whole calls are timed with device events around ops.augment (table building and the one index
+    upload included); the split over the kernel roles comes from torch.profiler's device-side kernel records of one more call (`notrace`
+    leaves that out: for a run under rocprofv3 --kernel-trace --stats, which gives the same split from outside).  The FIR's
+    rate is priced in taps x samples (one fma each) against the 157.3 TF fp32 vector rate, for the `store` role over n x L and the `energy`
+    role over n x (ee - es); the work the kernels skip (taps that meet no sample of a tile) is not subtracted."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+    from tf_kaldi_speaker_amd import ops
+    trace = "notrace" not in argv
+    argv = [a for a in argv if a != "notrace"]
+    n_utts = int(argv[0]) if argv else 256
+    sf = 16000
+    lens = rs.randint(4 * sf, 20 * sf + 1, n_utts)
+    t = np.arange(int(lens.max())) / float(sf)
+    tone = 3000.0 * np.sin(2.0 * np.pi * 220.0 * t) + 1500.0 * np.sin(2.0 * np.pi * 1830.0 * t)
+    pcm = np.concatenate([np.rint(tone[:n] * (0.02 if i % 3 == 2 else 1.0) + rs.randn(n) * 40.0).astype(np.int16) for i, n in enumerate(lens)])
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    noise = np.rint(rs.randn(5 * sf) * 800.0).astype(np.int16)
+    cfg = ops.augment_config()
+    pcm_d, noise_d = torch.from_numpy(pcm).cuda(), torch.from_numpy(noise).cuda()
+    out = torch.empty(pcm.size, dtype=torch.int16, device="cuda")
+    kw = dict(noise=noise_d, noise_off=[0], noise_len=[noise.size], nz_first=np.arange(n_utts + 1), nz_id=np.zeros(n_utts, np.int64),
+              nz_snr=np.full(n_utts, 10.0), nz_start=np.zeros(n_utts, np.int64), nz_span=np.full(n_utts, -1), out_pcm=out)
+    print("%d utterances of %.1f - %.1f s (16 kHz): %.1f M samples, one background noise each" % (n_utts, lens.min() / sf, lens.max() / sf, pcm.size / 1e6),
+          flush=True)
+    for L in (0, 4000, 8000, 16000):
+        args = dict(kw)
+        early = 0
+        if L:
+            h = np.rint(12000.0 * np.exp(-np.arange(L) / (L / 4.0)) * rs.uniform(-1.0, 1.0, L)).astype(np.int16)
+            h[40] = 29000
+            es, ee, p = ops.augment_early(h, sf)
+            early = ee - es
+            args.update(rir=torch.from_numpy(h).cuda(), rir_off=[0], rir_len=[L], rir_early=[(es, ee, p)], utt_rir=np.zeros(n_utts, np.int64))
+        call = lambda: ops.augment(cfg, pcm_d, offsets, lens, **args)
+        us = timeit(call, 5, 2)
+        print("L = %5d taps (early part %3d): whole call %10.1f us = %.0f x real time" % (L, early, us, pcm.size / sf / (us * 1e-6)), flush=True)
+        if not trace:
+            continue
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            call()
+            torch.cuda.synchronize()
+        roles = {}
+        for ev in prof.events():
+            if "aug_" in ev.name and ev.device_type == DeviceType.CUDA:
+                name = ev.name.split("(")[0].replace("void ", "")
+                roles[name] = roles.get(name, 0.0) + float(getattr(ev, "device_time_total", 0.0) or getattr(ev, "cuda_time_total", 0.0))
+        for name, k_us in sorted(roles.items()):
+            work = pcm.size * (L if "<false>" in name or "<(bool)0>" in name else early) if "fir" in name else 0
+            rate = "  %8.1f G taps x samples / s = %.3f of 157.3 TF" % (work / k_us / 1e3, 2.0 * work / k_us / 1e6 / 157.3) if work else ""
+            print("    %-28s %10.1f us%s" % (name, k_us, rate), flush=True)
+        if not roles:
+            print("    (no kernel records from the profiler: no split over the roles)", flush=True)
+
+
+COMMANDS = {"augment": cmd_augment, "mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
