@@ -1,0 +1,118 @@
+"""What the host side of every op has in common: device buffers as ctypes arguments, the checks of host index arrays that the kernels
+leave to the caller, pitches and offsets, and how the drivers in misc/ cut their work into calls.  ops.py, pipeline_ops.py and misc/
+build on this module; it imports none of them at load time."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+try:
+    from . import _lib
+except ImportError:
+    import _lib
+
+DEFAULT_WORKSPACE_BYTES = 1 << 30      # what the drivers in misc/ let one call take, unless told otherwise
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _s():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _f32(shape, like):
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+
+_WS = {}
+
+
+def workspace(device, nbytes=256 << 20):
+    key = (str(device), nbytes)
+    if key not in _WS:
+        _WS[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return _WS[key]
+
+
+def _ws(t):
+    w = workspace(t.device)
+    return _p(w), C.c_size_t(w.numel() * 4)
+
+
+def device_ops(device):
+    """(torch, ops, torch.device(device)) for a driver in misc/, in either import style: tf_kaldi_speaker_amd.X, or flat from the package directory."""
+    try:
+        from . import ops
+    except ImportError:
+        import ops
+    return torch, ops, torch.device(device)
+
+
+def upload(a, dtype, device):      # a host array as a contiguous device tensor of `dtype` (np.int32 / np.int64 for index arrays)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
+
+
+def host_ints(a, what="", n=None, min_size=0, lo=None, hi=None, msg=None, dtype=None):
+    """A 1-D host integer array as a NumPy array (of `dtype` when given, else its own) - the kernels check no index, so index arrays pass here before
+    their upload.  n: the exact length; min_size: 1 refuses an empty one; lo, hi: values lie in [lo, hi) (IndexError).  `what` starts the messages, `msg` is the first."""
+    a = np.asarray(a)
+    if a.ndim != 1 or a.dtype.kind not in "iu" or a.size < min_size or (n is not None and a.size != n):
+        raise ValueError(msg or "%s must be a %s1-D integer array%s" % (what, "non-empty " if min_size else "", "" if n is None else " of %d" % n))
+    if lo is not None and a.size and (a.min() < lo or a.max() >= hi):
+        raise IndexError("%s holds a value outside %d .. %d" % (what, lo, hi - 1))
+    return a if dtype is None else a.astype(dtype)
+
+
+def f32_values(t, d, what):
+    if t.dtype != torch.float32 or t.numel() != d or not t.is_contiguous():
+        raise ValueError("%s must be %d contiguous float32 values" % (what, d))
+
+
+def pitched(t, what, whole=False):
+    """(rows, pitch in floats) of a 2-D float32 device view with contiguous rows; whole: it must be all of a [rows, pitch] buffer (an
+    output of the kernels that write the padding columns too)."""
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("%s: a 2-D float32 tensor with contiguous rows is expected" % what)
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if whole and t.shape[1] != ld:
+        raise ValueError("%s must be the whole [rows, pitch] buffer (its padding columns are written)" % what)
+    return t.shape[0], ld
+
+
+def pitch4(d):      # d rounded up to 4 floats: the row pitch of a GEMM operand
+    return (d + 3) // 4 * 4
+
+
+def exclusive_offsets(lengths):      # where each of a non-empty list of signals starts when they lie back to back (int64)
+    return np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+
+
+def greedy_batches(n_items, grow, cost_of, limit, max_items=None, too_big=None):
+    """Cuts items 0 .. n_items - 1, in order, into lists that each cost `limit` at the most and hold at most max_items.  The caller keeps
+    running totals of a batch as a tuple: grow(i, *totals) -> the totals with item i added (grow(i): of item i alone), cost_of(*totals) ->
+    the cost of such a batch.  An item that does not fit alone is refused with too_big(i, its cost), when the batches come to it."""
+    batch, totals = [], ()
+    for i in range(n_items):
+        alone = grow(i)
+        if cost_of(*alone) > limit:
+            raise ValueError(too_big(i, cost_of(*alone)))
+        grown = grow(i, *totals) if batch else alone
+        if cost_of(*grown) > limit or len(batch) == max_items:
+            yield batch
+            batch, grown = [], alone
+        batch.append(i)
+        totals = grown
+    if batch:
+        yield batch
+
+
+def steps(n, step):      # (j0, j1) of 0 .. n in runs of `step`, the last one shorter
+    return ((j0, min(j0 + step, n)) for j0 in range(0, n, step))
+
+
+def cat(parts):      # the results of a loop over steps() as one array or tensor; a single part is passed on as it is
+    if len(parts) == 1:
+        return parts[0]
+    return torch.cat(parts) if parts and isinstance(parts[0], torch.Tensor) else np.concatenate(parts)

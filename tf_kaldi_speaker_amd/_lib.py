@@ -22,14 +22,19 @@ class XvError(RuntimeError):
 ABI_VERSION = 3
 
 
-class XvConfig(C.Structure):
-    """Mirror of `struct xv_config` (include/xvector_hip.h); struct_bytes is filled in on construction."""
+class _SizedConfig(C.Structure):
+    """Base of the mirrors of the header's config structures: keyword arguments only, on top of DEFAULTS; struct_bytes is filled in here."""
+    DEFAULTS = {}
 
     def __init__(self, *args, **kw):
         if args:      # struct_bytes is the first field: a positional XvConfig(feat_dim, ...) would shift every value by one, silently
-            raise TypeError("XvConfig takes keyword arguments only (its first field is struct_bytes, filled in here)")
-        super(XvConfig, self).__init__(**kw)
-        self.struct_bytes = C.sizeof(XvConfig)
+            raise TypeError("%s takes keyword arguments only (its first field is struct_bytes, filled in here)" % type(self).__name__)
+        super(_SizedConfig, self).__init__(**dict(self.DEFAULTS, **kw))
+        self.struct_bytes = C.sizeof(type(self))
+
+
+class XvConfig(_SizedConfig):
+    """Mirror of `struct xv_config` (include/xvector_hip.h); no defaults: engine.make_config states every field it relies on."""
 
     _fields_ = [
         ("struct_bytes", C.c_int32),
@@ -77,9 +82,8 @@ class XvConfig(C.Structure):
     ]
 
 
-class XvMfccConfig(C.Structure):
-    """Mirror of `struct xv_mfcc_config` (include/xvector_hip.h) with its defaults - the VoxCeleb conf/mfcc.conf, dither 0; struct_bytes is
-    filled in on construction."""
+class XvMfccConfig(_SizedConfig):
+    """Mirror of `struct xv_mfcc_config` (include/xvector_hip.h) with its defaults - the VoxCeleb conf/mfcc.conf, dither 0."""
 
     _fields_ = [
         ("struct_bytes", C.c_int32),
@@ -102,16 +106,10 @@ class XvMfccConfig(C.Structure):
                     high_freq=7600.0, snip_edges=0, preemphasis=0.97, remove_dc_offset=1, cepstral_lifter=22.0, use_energy=1, raw_energy=1,
                     energy_floor=0.0)
 
-    def __init__(self, *args, **kw):
-        if args:
-            raise TypeError("XvMfccConfig takes keyword arguments only (its first field is struct_bytes, filled in here)")
-        super(XvMfccConfig, self).__init__(**dict(self.DEFAULTS, **kw))
-        self.struct_bytes = C.sizeof(XvMfccConfig)
 
-
-class XvAugmentConfig(C.Structure):
+class XvAugmentConfig(_SizedConfig):
     """Mirror of `struct xv_augment_config` (include/xvector_hip.h) with its defaults - wav-reverberate --shift-output=true
-    --normalize-output=true at 16 kHz; struct_bytes is filled in on construction."""
+    --normalize-output=true at 16 kHz."""
 
     _fields_ = [
         ("struct_bytes", C.c_int32),
@@ -121,12 +119,6 @@ class XvAugmentConfig(C.Structure):
         ("volume", C.c_float),
     ]
     DEFAULTS = dict(sample_frequency=16000.0, shift_output=1, normalize_output=1, volume=0.0)
-
-    def __init__(self, *args, **kw):
-        if args:
-            raise TypeError("XvAugmentConfig takes keyword arguments only (its first field is struct_bytes, filled in here)")
-        super(XvAugmentConfig, self).__init__(**dict(self.DEFAULTS, **kw))
-        self.struct_bytes = C.sizeof(XvAugmentConfig)
 
 
 LOSS_KINDS = {
@@ -145,8 +137,8 @@ _SZ = C.c_size_t
 _I = C.c_int
 _F = C.c_float
 
-# name -> (restype, argtypes).  Kept in header order; tests/test_abi.py checks that every
-# prototype of include/xvector_hip.h is listed here and exported by the .so.
+# name -> (restype, argtypes).  Kept in header order; tests/test_abi.py checks every entry against the prototype of
+# include/xvector_hip.h, type by type, and that the .so exports it.
 SIGNATURES = {
     "xv_last_error": (C.c_char_p, []),
     "xv_abi_version": (_I, []),

@@ -12,9 +12,8 @@ augment_data_dir.py reaches through wav-reverberate --duration).  The arithmetic
 RESTATED in the header; there is no resampling: every file must have the sample rate of the sources."""
 import numpy as np
 
-from .features import _Options, _bool, _f, _i
+from .features import DEFAULT_WORKSPACE_BYTES, _Options, _bool, _f, _i, _lib, device_ops, exclusive_offsets, greedy_batches
 
-DEFAULT_WORKSPACE_BYTES = 1 << 30
 PRESETS = {"reverb": None, "noise": (15.0, 10.0, 5.0, 0.0), "music": (15.0, 10.0, 8.0, 5.0), "babble": (20.0, 17.0, 15.0, 13.0)}
 
 
@@ -42,10 +41,6 @@ class AugmentOptions(_Options):
 
     def config(self, sample_frequency):
         """The xv_augment_config of these options."""
-        try:
-            from .. import _lib
-        except (ImportError, ValueError):
-            import _lib
         return _lib.XvAugmentConfig(sample_frequency=sample_frequency, shift_output=self.shift_output, normalize_output=self.normalize_output,
                                     volume=self.volume)
 
@@ -205,20 +200,15 @@ class Augmenter(object):
     workspace and sources stay within workspace_bytes."""
 
     def __init__(self, options=None, rirs=None, noises=None, sample_frequency=16000.0, device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
-        import torch
-        try:
-            from .. import ops
-        except (ImportError, ValueError):
-            import ops
-        self.torch, self.ops, self.device = torch, ops, torch.device(device)
+        self.torch, self.ops, self.device = device_ops(device)
         self.options = options or AugmentOptions()
         self.sample_frequency = float(sample_frequency)
         self.cfg = self.options.config(self.sample_frequency)
         self.workspace_bytes = int(workspace_bytes)
-        self.tile = ops.augment_plan(1)["tile"]
+        self.tile = self.ops.augment_plan(1)["tile"]
         self.rir_index, self.rir_pool, self.rir_off, self.rir_len = self._pool(rirs or {}, "impulse response")
         self.noise_index, self.noise_pool, self.noise_off, self.noise_len = self._pool(noises or {}, "noise")
-        self.rir_early = [ops.augment_early(rirs[k], self.sample_frequency) for k in self.rir_index] if rirs else []
+        self.rir_early = [self.ops.augment_early(rirs[k], self.sample_frequency) for k in self.rir_index] if rirs else []
 
     def _pool(self, signals, what):
         keys = list(signals)
@@ -227,7 +217,7 @@ class Augmenter(object):
             if a.size == 0:
                 raise ValueError("Augmenter: %s %s holds no samples" % (what, k))
         lengths = np.asarray([a.size for a in arrays], np.int64)
-        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64) if keys else np.zeros(0, np.int64)
+        offsets = exclusive_offsets(lengths) if keys else np.zeros(0, np.int64)
         pool = self.torch.from_numpy(np.concatenate(arrays)).to(self.device) if keys else None
         return {k: i for i, k in enumerate(keys)}, pool, offsets, lengths
 
@@ -242,19 +232,11 @@ class Augmenter(object):
         return self.ops.augment_workspace_bytes(utts, entries, tiles) + 2 * samples
 
     def _batches(self, n, m, entries):
-        batch, tiles, noises, samples = [], 0, 0, 0
-        for i, e in enumerate(entries):
-            t, j = int((m[i] + self.tile - 1) // self.tile), len(e.noises)
-            if self._cost(t, j, int(n[i]), 1) > self.workspace_bytes:
-                raise ValueError("Augmenter: a workspace of %d bytes does not hold utterance %d (%s: %d samples under %d taps: %d bytes)"
-                                 % (self.workspace_bytes, i, e.out_key, n[i], m[i] - n[i] + 1 if e.rir is not None else 0, self._cost(t, j, int(n[i]), 1)))
-            if batch and self._cost(tiles + t, noises + j, samples + int(n[i]), len(batch) + 1) > self.workspace_bytes:
-                yield batch
-                batch, tiles, noises, samples = [], 0, 0, 0
-            batch.append(i)
-            tiles, noises, samples = tiles + t, noises + j, samples + int(n[i])
-        if batch:
-            yield batch
+        grow = lambda i, tiles=0, noises=0, samples=0, utts=0: (tiles + int((m[i] + self.tile - 1) // self.tile), noises + len(entries[i].noises),
+                                                                samples + int(n[i]), utts + 1)
+        too_big = lambda i, cost: ("Augmenter: a workspace of %d bytes does not hold utterance %d (%s: %d samples under %d taps: %d bytes)"
+                                   % (self.workspace_bytes, i, entries[i].out_key, n[i], m[i] - n[i] + 1 if entries[i].rir is not None else 0, cost))
+        return greedy_batches(len(entries), grow, self._cost, self.workspace_bytes, too_big=too_big)
 
     def run(self, sources, entries):
         """sources[i]: the int16 samples of entries[i].src_key -> (pcm int16 device tensor, offsets int64 [b], lengths int64 [b], clipped
@@ -273,7 +255,7 @@ class Augmenter(object):
                     raise KeyError("Augmenter: Key %s: noise %s is not in the table of noises" % (e.out_key, nid))
         n = np.asarray([len(s) for s in sources], np.int64)
         m, n_out = self.lengths(sources, entries)
-        offsets = np.concatenate([[0], np.cumsum(n_out)[:-1]]).astype(np.int64)
+        offsets = exclusive_offsets(n_out)
         pcm = torch.empty(int(n_out.sum()), dtype=torch.int16, device=self.device)
         clipped = np.zeros(len(entries), np.int64)
         for batch in self._batches(n, m, entries):
@@ -289,7 +271,7 @@ class Augmenter(object):
                     spans.append(-1 if background else int(self.noise_len[k]))
                 first.append(len(ids))
             _, _, samples, clip, _ = ops.augment(
-                self.cfg, src, np.concatenate([[0], np.cumsum(src_len)[:-1]]).astype(np.int64), src_len, rir=self.rir_pool, rir_off=self.rir_off,
+                self.cfg, src, exclusive_offsets(src_len), src_len, rir=self.rir_pool, rir_off=self.rir_off,
                 rir_len=self.rir_len, rir_early=self.rir_early,
                 utt_rir=[self.rir_index[entries[i].rir] if entries[i].rir is not None else -1 for i in batch], noise=self.noise_pool,
                 noise_off=self.noise_off, noise_len=self.noise_len, nz_first=first, nz_id=ids, nz_snr=snrs, nz_start=starts, nz_span=spans,

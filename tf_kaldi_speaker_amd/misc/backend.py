@@ -14,8 +14,10 @@ import os
 import numpy as np
 
 try:
+    from .._host import cat, device_ops, pitch4, steps, upload
     from .scoring import DEFAULT_WORKSPACE_BYTES, center_mean
 except (ImportError, ValueError):
+    from _host import cat, device_ops, pitch4, steps, upload
     from misc.scoring import DEFAULT_WORKSPACE_BYTES, center_mean
 
 _LOG = logging.getLogger("tf_kaldi_speaker_amd")
@@ -154,7 +156,7 @@ def plda_coefficients(psi, distinct_n):
     k0 float32 [len(distinct_n)] = -0.5 sum log v + 0.5 sum log(psi + 1); ldc = d rounded up to 4, the padding zero."""
     psi = np.asarray(psi, dtype=np.float64)
     d = psi.shape[0]
-    ldc = (d + 3) // 4 * 4
+    ldc = pitch4(d)
     n = np.asarray(distinct_n, dtype=np.float64)[:, None]
     if n.size == 0 or n.min() < 1:
         raise ValueError("plda_coefficients: utterance counts must be positive")
@@ -184,15 +186,10 @@ class _Chain(object):
     """The device form of a Backend: centre -> LDA -> length normalisation (-> PLDA transform -> PLDA normalisation), in row batches."""
 
     def __init__(self, backend, device):
-        import torch
-        try:
-            from .. import ops
-        except (ImportError, ValueError):
-            import ops
-        self.torch, self.ops, self.device = torch, ops, torch.device(device)
+        self.torch, self.ops, self.device = device_ops(device)
         self.d, self.dim = backend.d, backend.dim
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
-        d4, k4 = (self.d + 3) // 4 * 4, (self.dim + 3) // 4 * 4
+        up = lambda a: upload(a, np.float32, self.device)
+        d4, k4 = pitch4(self.d), pitch4(self.dim)
         self.mean = up(backend.mean)
         self.lda_w = self.lda_b = self.plda_w = self.plda_b = self.psi = None
         if backend.lda is not None:
@@ -222,10 +219,10 @@ class _Chain(object):
 
     def run(self, x, plda, n_utts=None):
         parts = []
-        for r0 in range(0, x.shape[0], PREPARE_ROWS):
-            y = self.unit(x[r0:r0 + PREPARE_ROWS])
-            parts.append(self.plda(y, None if n_utts is None else n_utts[r0:r0 + PREPARE_ROWS]) if plda else y)
-        return parts[0] if len(parts) == 1 else self.torch.cat(parts)
+        for r0, r1 in steps(x.shape[0], PREPARE_ROWS):
+            y = self.unit(x[r0:r1])
+            parts.append(self.plda(y, None if n_utts is None else n_utts[r0:r1]) if plda else y)
+        return cat(parts)
 
 
 class Backend(object):
@@ -270,11 +267,7 @@ class Backend(object):
     def train(cls, matrix, keys, spk2utt, lda_dim=200, device="cuda:0", num_em_iters=10, log=None):
         """Train on the table (keys, matrix float32 [n, d]) grouped by spk2utt (read_spk2utt's list); lda_dim None / 0: no LDA.  The
         statistics come from the GPU (xv_backend_group_means, xv_backend_scatter, the transform chain), the estimators run here in fp64."""
-        import torch
-        try:
-            from .. import ops
-        except (ImportError, ValueError):
-            import ops
+        torch, ops, _ = device_ops(device)
         log = log or _LOG
         matrix = np.ascontiguousarray(matrix, dtype=np.float32)
         groups = GroupIndex(keys, spk2utt, log)
@@ -307,8 +300,7 @@ class Backend(object):
             log.info("[INFO] LDA: kept eigenvalues %.6g .. %.6g (the next one: %s)." % (l[0], l[lda_dim - 1], "%.6g" % l[lda_dim] if lda_dim < d else "none"))
         self = cls(mean, lda, None)
         chain = _Chain(self, device)
-        parts = [chain.unit(x_stats[r0:r0 + PREPARE_ROWS]) for r0 in range(0, x_stats.shape[0], PREPARE_ROWS)]
-        y = parts[0] if len(parts) == 1 else torch.cat(parts)
+        y = cat([chain.unit(x_stats[r0:r1]) for r0, r1 in steps(x_stats.shape[0], PREPARE_ROWS)])
         # y is at unit length; the model is trained at ivector-normalize-length's scale sqrt(dim): both statistics are scaled here, in fp64
         scatter = ops.backend_scatter(y, d=self.dim).cpu().numpy() * float(self.dim)
         m64 = ops.backend_group_means(y, self.dim, groups.offsets, rows, want32=False)[0].cpu().numpy() * np.sqrt(float(self.dim))
@@ -367,8 +359,6 @@ class BackendScorer(object):
             if n.shape != (enrol.shape[0],):
                 raise ValueError("BackendScorer.score: enrol_n must hold one count per enrolment row")
             distinct, nidx = np.unique(n, return_inverse=True)
-            up = lambda a: self.torch.from_numpy(a).to(self.device)
-            coef, g, k0 = (up(a) for a in plda_coefficients(self.backend.plda["psi"], distinct))
+            coef, g, k0 = (upload(a, np.float32, self.device) for a in plda_coefficients(self.backend.plda["psi"], distinct))
             run = lambda a, b: self.ops.backend_plda_trials(enrol, test, self.dim, a, b, nidx, coef, g, k0)
-        out = [run(ei[j0:j0 + step], ti[j0:j0 + step]).cpu().numpy() for j0 in range(0, ei.shape[0], step)]
-        return out[0] if len(out) == 1 else np.concatenate(out)
+        return cat([run(ei[j0:j1], ti[j0:j1]).cpu().numpy() for j0, j1 in steps(ei.shape[0], step)])

@@ -14,7 +14,11 @@ import wave
 
 import numpy as np
 
-DEFAULT_WORKSPACE_BYTES = 1 << 30
+try:
+    from .._host import DEFAULT_WORKSPACE_BYTES, _lib, device_ops, exclusive_offsets, greedy_batches
+except (ImportError, ValueError):
+    from _host import DEFAULT_WORKSPACE_BYTES, _lib, device_ops, exclusive_offsets, greedy_batches
+
 _TRUE, _FALSE = ("true", "t", "1"), ("false", "f", "0")
 
 
@@ -94,9 +98,7 @@ def _s(name, text):
 class MfccOptions(_Options):
     """The options of compute-mfcc-feats this program takes; fields are those of xv_mfcc_config plus `channel` (-1: the file must be mono)."""
     PROGRAM = "compute-mfcc-feats"
-    DEFAULTS = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, num_mel_bins=30, num_ceps=30, low_freq=20.0,
-                    high_freq=7600.0, snip_edges=0, preemphasis=0.97, remove_dc_offset=1, cepstral_lifter=22.0, use_energy=1, raw_energy=1,
-                    energy_floor=0.0, channel=-1)
+    DEFAULTS = dict(_lib.XvMfccConfig.DEFAULTS, channel=-1)
     SUPPORTED = {"sample-frequency": ("sample_frequency", _f), "frame-length": ("frame_length_ms", _f), "frame-shift": ("frame_shift_ms", _f),
                  "num-mel-bins": ("num_mel_bins", _i), "num-ceps": ("num_ceps", _i), "low-freq": ("low_freq", _f), "high-freq": ("high_freq", _f),
                  "snip-edges": ("snip_edges", _bool), "preemphasis-coefficient": ("preemphasis", _f), "remove-dc-offset": ("remove_dc_offset", _bool),
@@ -112,10 +114,6 @@ class MfccOptions(_Options):
 
     def config(self):
         """The xv_mfcc_config of these options."""
-        try:
-            from .. import _lib
-        except (ImportError, ValueError):
-            import _lib
         return _lib.XvMfccConfig(**{k: getattr(self, k) for k in self.DEFAULTS if k != "channel"})
 
 
@@ -168,15 +166,10 @@ class FeatureExtractor(object):
     extract() cuts its list into batches such that the padded outputs and the samples of one call stay within workspace_bytes."""
 
     def __init__(self, mfcc=None, vad=None, device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
-        import torch
-        try:
-            from .. import ops
-        except (ImportError, ValueError):
-            import ops
-        self.torch, self.ops, self.device = torch, ops, torch.device(device)
+        self.torch, self.ops, self.device = device_ops(device)
         self.mfcc, self.vad = mfcc or MfccOptions(), vad or VadOptions()
         self.cfg = self.mfcc.config()
-        self.tables = torch.from_numpy(ops.mfcc_tables(self.cfg)).to(self.device)
+        self.tables = self.torch.from_numpy(self.ops.mfcc_tables(self.cfg)).to(self.device)
         self.workspace_bytes = int(workspace_bytes)
 
     def num_frames(self, samples):
@@ -186,18 +179,10 @@ class FeatureExtractor(object):
         return b * max(t_max, 1) * (4 * self.mfcc.num_ceps + 1) + 2 * total
 
     def _batches(self, frames, lengths):
-        batch, t_max, total = [], 0, 0
-        for i, (t, n) in enumerate(zip(frames, lengths)):
-            if self._cost(1, t, n) > self.workspace_bytes:
-                raise ValueError("FeatureExtractor: a workspace of %d bytes does not hold utterance %d (%d samples, %d frames: %d bytes)"
-                                 % (self.workspace_bytes, i, n, t, self._cost(1, t, n)))
-            if batch and (self._cost(len(batch) + 1, max(t_max, t), total + n) > self.workspace_bytes or len(batch) == 65535):
-                yield batch
-                batch, t_max, total = [], 0, 0
-            batch.append(i)
-            t_max, total = max(t_max, t), total + n
-        if batch:
-            yield batch
+        grow = lambda i, b=0, t_max=0, total=0: (b + 1, max(t_max, frames[i]), total + lengths[i])
+        too_big = lambda i, cost: ("FeatureExtractor: a workspace of %d bytes does not hold utterance %d (%d samples, %d frames: %d bytes)"
+                                   % (self.workspace_bytes, i, lengths[i], frames[i], cost))
+        return greedy_batches(len(frames), grow, self._cost, self.workspace_bytes, max_items=65535, too_big=too_big)
 
     def extract(self, waves):
         """waves: int16 arrays -> [(features float32 [T, num_ceps], decisions float32 [T] of 1.0 / 0.0)] in order; T may be 0."""
@@ -206,13 +191,13 @@ class FeatureExtractor(object):
         frames = [self.num_frames(n) for n in lengths]
         out = [None] * len(waves)
         for batch in self._batches(frames, lengths):
-            offsets = np.concatenate([[0], np.cumsum([lengths[i] for i in batch])]).astype(np.int64)
-            if offsets[-1] == 0:
+            n = [lengths[i] for i in batch]
+            if sum(n) == 0:
                 for i in batch:
                     out[i] = (np.zeros((0, self.mfcc.num_ceps), np.float32), np.zeros(0, np.float32))
                 continue
             pcm = self.torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
-            for i, r in zip(batch, self.extract_packed(pcm, offsets[:-1], [lengths[i] for i in batch])):      # one call: the batch fits
+            for i, r in zip(batch, self.extract_packed(pcm, exclusive_offsets(n), n)):      # one call: the batch fits
                 out[i] = r
         return out
 

@@ -6,9 +6,13 @@ LDA / PLDA and multi-utterance enrolment (spk2utt averaging): misc/backend.py.  
 """
 import numpy as np
 
+try:
+    from .._host import DEFAULT_WORKSPACE_BYTES, cat, device_ops, steps, upload
+except (ImportError, ValueError):
+    from _host import DEFAULT_WORKSPACE_BYTES, cat, device_ops, steps, upload
+
 # (p_target, c_miss, c_fa) of the two detection costs in the reference's result tables: NIST SRE 2008 and 2010
 MIN_DCF_PRESETS = {"minDCF08": (0.01, 10.0, 1.0), "minDCF10": (0.001, 1.0, 1.0)}
-DEFAULT_WORKSPACE_BYTES = 1 << 30
 
 
 def read_trials(path):
@@ -109,15 +113,10 @@ class CosineScorer(object):
     workspace_bytes of scratch (index arrays and scores of a trial batch; the score slab of a row batch)."""
 
     def __init__(self, device="cuda:0", center=None, workspace_bytes=DEFAULT_WORKSPACE_BYTES):
-        import torch
-        try:
-            from .. import ops
-        except (ImportError, ValueError):
-            import ops
-        self.torch, self.ops, self.device = torch, ops, torch.device(device)
+        self.torch, self.ops, self.device = device_ops(device)
         self.workspace_bytes = int(workspace_bytes)
         self.d = None
-        self.center = None if center is None else torch.from_numpy(np.ascontiguousarray(center, dtype=np.float32)).to(self.device)
+        self.center = None if center is None else upload(center, np.float32, self.device)
         self._cohort, self.top_k = None, 0
 
     def prepare(self, matrix):
@@ -144,10 +143,9 @@ class CosineScorer(object):
             raise ValueError("CosineScorer: a workspace of %d bytes does not hold one 128-row tile of %d cohort scores (%d bytes)"
                              % (self.workspace_bytes, n_cohort, tile))
         step = self.workspace_bytes // tile * 128
-        parts = [self.ops.score_cohort_stats(x[r0:r0 + step], self._cohort, self.d, self.top_k,
-                                             ws_bytes=self.ops.score_cohort_workspace_bytes(min(step, x.shape[0] - r0), n_cohort, self.d))
-                 for r0 in range(0, x.shape[0], step)]
-        return parts[0] if len(parts) == 1 else self.torch.cat(parts)
+        return cat([self.ops.score_cohort_stats(x[r0:r1], self._cohort, self.d, self.top_k,
+                                                      ws_bytes=self.ops.score_cohort_workspace_bytes(r1 - r0, n_cohort, self.d))
+                          for r0, r1 in steps(x.shape[0], step)])
 
     def score(self, enrol, test, ei, ti):
         ei, ti = np.asarray(ei), np.asarray(ti)
@@ -156,6 +154,5 @@ class CosineScorer(object):
             e_stats = self._stats(enrol)
             t_stats = e_stats if test is enrol else self._stats(test)
         step = max(self.workspace_bytes // 12, 1)      # two int32 indices and one score per trial
-        out = [self.ops.score_trials(enrol, test, self.d, ei[j0:j0 + step], ti[j0:j0 + step], e_stats, t_stats).cpu().numpy()
-               for j0 in range(0, ei.shape[0], step)]
-        return out[0] if len(out) == 1 else np.concatenate(out)
+        return cat([self.ops.score_trials(enrol, test, self.d, ei[j0:j1], ti[j0:j1], e_stats, t_stats).cpu().numpy()
+                          for j0, j1 in steps(ei.shape[0], step)])
