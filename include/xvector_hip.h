@@ -137,6 +137,41 @@ int xv_cm_decode(void* stream, const uint8_t* packed, int b, int t, int d, size_
  * out[i][0 .. rows[i]) of the [b][t][d] tensor and the padding rows behind it are zeroed.  offsets / rows: device arrays [b]. */
 int xv_cm_decode_ragged(void* stream, const uint8_t* packed, const int64_t* offsets, const int32_t* rows, int b, int t, int d, float* out);
 
+/* Kaldi 'CM ' compressed-matrix ENCODE: what copy-feats --compress=true does at the end of the reference's feature preparation
+ * (egs/voxceleb/v1/run.sh stage 4, prepare_feats_for_egs.sh; matrix/compressed-matrix.cc ComputeGlobalHeader / ComputeColHeader /
+ * FloatToChar).  THE SPECIFICATION IS dataset/kaldi_io.py write_compressed_mat, BYTE FOR BYTE, in both of its header forms.
+ * x: [b][t][d] float32 as xv_mfcc and xv_frontend leave it, piece i holding rows[i] frames, 1 <= rows[i] <= t, d <= 128; rows behind
+ * rows[i] are padding and enter no statistic.  Piece i's image - what a 'CM ' matrix is in an archive behind the "CM " token,
+ *   [min f32][range f32][rows i32][cols i32][d x (p0, p25, p75, p100) u16][d x rows[i] u8, column after column]
+ * (16 + 8 d + d rows[i] bytes), exactly what xv_cm_decode_ragged reads - is written at byte out_offsets[i] of `out`, at ANY alignment
+ * (images packed back to back are unaligned as soon as d rows[i] is odd).  rows, out_offsets: device arrays [b]; neither is checked
+ * on the device, the caller checks them (ops.cm_encode does).  Every fp32 step below is one operation, rounded once, in the order
+ * written, with no contraction; divisions are correctly rounded.
+ *   Global header: min and max of the valid elements, exact.  range = fp32(double(max) - double(min)), or, if they are equal,
+ *     fp32(double(min) + 1 + |min| - double(min)).
+ *   header = XV_CM_HEADER_QUARTILES (Kaldi's choice): per column the order statistics s[k] of its rows[i] values, found exactly.
+ *     rows >= 5: s[0], s[rows / 4], s[3 rows / 4], s[rows - 1] (integer division), each mapped by
+ *       u16(v) = clamp(floor(((v - min) / range) * 65535 + 0.499), 0, 65535), all fp32, 0.499 rounded to fp32.
+ *     rows < 5 (the small-matrix branch): p0 = u16(s[0]); p25 = u16(s[1]) if rows > 1, else p0 + 1; p75 = u16(s[2]) if rows > 2, else
+ *       p25 + 1; p100 = u16(s[3]) if rows > 3, else p75 + 1 - the + 1 in uint16 arithmetic: 65535 + 1 = 0, as the host writer's wraps.
+ *   header = XV_CM_HEADER_UNIFORM (evenly spaced points; what make_mfcc.py writes): from the column's minimum a and maximum z alone, IN
+ *     DOUBLE: p0 = clamp(floor((a - min) / range * 65535)), p100 = clamp(ceil((z - min) / range * 65535)), p25 = rint(p0 + 0.25 (p100 -
+ *     p0)), p75 = rint(p0 + 0.75 (p100 - p0)), rint rounding halves to even.
+ *   Both: the strictly-increasing fix-up p0 = min(p0, 65532), p25 = min(max(p25, p0 + 1), 65533), p75 = min(max(p75, p25 + 1), 65534),
+ *     p100 = max(p100, p75 + 1); the four float points f = min + ((range * fp32(1 / 65535)) * p); per element v: if v < f25 the code is
+ *     clamp(floor(((v - f0) / (f25 - f0)) * 64 + 0.5), 0, 64), else if v < f75 64 + floor(((v - f25) / (f75 - f25)) * 128 + 0.5) clamped
+ *     to 64 .. 192, else 192 + floor(((v - f75) / (f100 - f75)) * 63 + 0.5) clamped to 192 .. 255.
+ * OUTSIDE THE BYTE CONTRACT: (1) where two of a column's four float points coincide in fp32 (its header steps fall below the fp32
+ * spacing at the values' magnitude) the host writer divides by zero and casts NaN to uint8, which is platform-defined: for such a column
+ * only the header bytes are specified, every code lies inside the range of the branch chosen, nothing faults; (2) inputs are finite;
+ * (3) a matrix whose minimum is a zero that occurs with both signs (either zero may come back as the minimum).
+ * One launch, one workgroup per piece; integer LDS atomics only, no floating-point atomics, no cross-workgroup hand-over: the bytes
+ * depend on the shape of the call only. */
+#define XV_CM_HEADER_QUARTILES 0
+#define XV_CM_HEADER_UNIFORM 1
+int xv_cm_encode(void* stream, const float* x, const int32_t* rows, int b, int t, int d, int header, const int64_t* out_offsets,
+                 uint8_t* out);
+
 /* The feature front end of extraction on a decoded batch: sliding-window cepstral mean normalisation, then voiced-frame selection - the
  * two Kaldi programs the reference recipe pipes in front of extract.py (egs/voxceleb/v1/nnet/run_extract_embeddings.sh:47):
  *   apply-cmvn-sliding --norm-vars=false --center=true --cmn-window=W   (featbin/apply-cmvn-sliding.cc, SlidingWindowCmn in

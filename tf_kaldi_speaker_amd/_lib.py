@@ -209,6 +209,7 @@ SIGNATURES = {
     "xv_margin_softmax_rows": (_I, [_VP, _I, _VP, _I, _I, _I, _VP, _I, _VP, _F, _F, _VP, _VP, _VP, _VP]),
     "xv_cm_decode": (_I, [_VP, _VP, _I, _I, _I, _SZ, _VP]),
     "xv_cm_decode_ragged": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "xv_cm_encode": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
     "xv_frontend": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _SZ, _VP, _VP, _VP, _I, _VP, _VP, _VP, _SZ]),
     "xv_mfcc_num_frames": (C.c_int64, [_VP, C.c_int64]),
     "xv_mfcc_table_floats": (_SZ, [_VP]),
@@ -267,6 +268,7 @@ SIGNATURES = {
 
 XV_AUG_UTT_WORDS = 10       # include/xvector_hip.h: words per utterance / per noise entry of xv_augment's tables
 XV_AUG_NOISE_WORDS = 5
+XV_CM_HEADERS = {"quartiles": 0, "uniform": 1}      # XV_CM_HEADER_QUARTILES / XV_CM_HEADER_UNIFORM
 XV_BWD_STAGES = 4
 XV_MAX_FRAME_LAYERS = 12
 _lib = None

@@ -10,6 +10,7 @@
 #include "xv_common.h"
 #include "xv_ew.h"
 #include "xv_rowsum.h"      // sc_row_dot and chain(d), SC_ROWS_PER_WG, sc_aligned16, sc_overlap
+#include "xv_radix_key.h"   // sc_key / sc_unkey: the unsigned key whose order is the float's
 
 #define SC_SEL_THREADS 256
 #define SC_TILE_ROWS 128          // the score slab holds a whole number of GEMM row tiles
@@ -64,13 +65,6 @@ __global__ __launch_bounds__(256) void score_trials_kernel(const float* __restri
     if (e_stats) s = 0.5f * ((s - e_stats[2 * (long)a]) / e_stats[2 * (long)a + 1] + (s - t_stats[2 * (long)b]) / t_stats[2 * (long)b + 1]);
     if (lane == 0) out[j] = s;
 }
-
-// the unsigned key whose order is the float's: negative values have every bit flipped, the others the sign bit set
-__device__ __forceinline__ unsigned sc_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sc_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // a double summed over the workgroup in a fixed order: butterfly inside each wave, the four wave totals added first to last
 __device__ __forceinline__ double sc_block_sum(double v, double* wtot, int tid) {

@@ -175,33 +175,40 @@ class FeatureExtractor(object):
     def num_frames(self, samples):
         return self.ops.mfcc_num_frames(self.cfg, samples)
 
-    def _cost(self, b, t_max, total):
-        return b * max(t_max, 1) * (4 * self.mfcc.num_ceps + 1) + 2 * total
+    def _cost(self, b, t_max, total, coded=False):      # coded: the 'CM ' images as well, a byte per value
+        return b * max(t_max, 1) * ((5 if coded else 4) * self.mfcc.num_ceps + 1) + 2 * total
 
-    def _batches(self, frames, lengths):
+    def _batches(self, frames, lengths, coded=False):
         grow = lambda i, b=0, t_max=0, total=0: (b + 1, max(t_max, frames[i]), total + lengths[i])
         too_big = lambda i, cost: ("FeatureExtractor: a workspace of %d bytes does not hold utterance %d (%d samples, %d frames: %d bytes)"
                                    % (self.workspace_bytes, i, lengths[i], frames[i], cost))
-        return greedy_batches(len(frames), grow, self._cost, self.workspace_bytes, max_items=65535, too_big=too_big)
+        cost_of = lambda b, t_max, total: self._cost(b, t_max, total, coded)
+        return greedy_batches(len(frames), grow, cost_of, self.workspace_bytes, max_items=65535, too_big=too_big)
 
-    def extract(self, waves):
-        """waves: int16 arrays -> [(features float32 [T, num_ceps], decisions float32 [T] of 1.0 / 0.0)] in order; T may be 0."""
+    def _nothing(self, cm_header):      # what an utterance too short for one frame gives
+        return (np.zeros((0, self.mfcc.num_ceps), np.float32) if cm_header is None else b"", np.zeros(0, np.float32))
+
+    def extract(self, waves, cm_header=None):
+        """waves: int16 arrays -> [(features float32 [T, num_ceps], decisions float32 [T] of 1.0 / 0.0)] in order; T may be 0.
+        cm_header ("uniform" or "quartiles"): the features come back 'CM '-compressed on the device instead (ops.cm_encode: the bytes
+        dataset.kaldi_io.write_compressed_mat(header=cm_header) gives for the float features) - [(the image behind the "CM " token, a bytes-like
+        object, empty when T is 0; decisions)]: a byte per value crosses to the host instead of four."""
         waves = [np.ascontiguousarray(w, dtype=np.int16).reshape(-1) for w in waves]
         lengths = [len(w) for w in waves]
         frames = [self.num_frames(n) for n in lengths]
         out = [None] * len(waves)
-        for batch in self._batches(frames, lengths):
+        for batch in self._batches(frames, lengths, cm_header is not None):
             n = [lengths[i] for i in batch]
             if sum(n) == 0:
                 for i in batch:
-                    out[i] = (np.zeros((0, self.mfcc.num_ceps), np.float32), np.zeros(0, np.float32))
+                    out[i] = self._nothing(cm_header)
                 continue
             pcm = self.torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
-            for i, r in zip(batch, self.extract_packed(pcm, exclusive_offsets(n), n)):      # one call: the batch fits
+            for i, r in zip(batch, self.extract_packed(pcm, exclusive_offsets(n), n, cm_header)):      # one call: the batch fits
                 out[i] = r
         return out
 
-    def extract_packed(self, pcm, offsets, lengths):
+    def extract_packed(self, pcm, offsets, lengths, cm_header=None):
         """The same for utterances that are on the device already: pcm an int16 device tensor, utterance i its samples offsets[i] ..
         offsets[i] + lengths[i] (host arrays) - what misc.augment.Augmenter.run returns.  Nothing is copied; the calls are cut as by
         extract()."""
@@ -209,16 +216,107 @@ class FeatureExtractor(object):
         offsets, lengths = np.asarray(offsets, np.int64), [int(n) for n in lengths]
         frames = [self.num_frames(n) for n in lengths]
         out = [None] * len(lengths)
-        for batch in self._batches(frames, lengths):
+        for batch in self._batches(frames, lengths, cm_header is not None):
             if sum(lengths[i] for i in batch) == 0:
                 for i in batch:
-                    out[i] = (np.zeros((0, self.mfcc.num_ceps), np.float32), np.zeros(0, np.float32))
+                    out[i] = self._nothing(cm_header)
                 continue
             t_out = max(max(frames[i] for i in batch), 1)
             x, rows = ops.mfcc(self.cfg, self.tables, pcm, offsets[batch], np.asarray([lengths[i] for i in batch], np.int64), t_out)
             masks = ops.energy_vad(x, rows, v.threshold, v.mean_scale, v.frames_context, v.proportion)
-            x_h, m_h, r_h = x.cpu().numpy(), masks.cpu().numpy(), rows.cpu().numpy()
+            m_h, r_h = masks.cpu().numpy(), rows.cpu().numpy()
             for j, i in enumerate(batch):
                 assert r_h[j] == frames[i], (i, r_h[j], frames[i])
-                out[i] = (x_h[j, :frames[i]].copy(), m_h[j, :frames[i]].astype(np.float32))
+            if cm_header is None:
+                x_h = x.cpu().numpy()
+                for j, i in enumerate(batch):
+                    out[i] = (x_h[j, :frames[i]].copy(), m_h[j, :frames[i]].astype(np.float32))
+                continue
+            kept = [j for j, i in enumerate(batch) if frames[i] > 0]      # a 'CM ' matrix has at least one row
+            if len(kept) < len(batch):
+                x = x[self.torch.as_tensor(kept, device=x.device)] if kept else None
+            images = iter(encoded_images(ops, x, [frames[batch[j]] for j in kept], cm_header) if kept else ())
+            for j, i in enumerate(batch):
+                out[i] = (next(images) if frames[i] > 0 else b"", m_h[j, :frames[i]].astype(np.float32))
         return out
+
+
+def encoded_images(ops, x, rows, cm_header):
+    """ops.cm_encode on a padded batch, copied back: [the image of piece i behind its "CM " token, a view into the one host buffer]."""
+    buf, offsets = ops.cm_encode(x, np.asarray(rows, np.int64), header=cm_header)
+    raw = memoryview(buf.cpu().numpy())
+    return [raw[int(o):int(o + n)] for o, n in zip(offsets, ops.cm_image_bytes(rows, x.shape[2]))]
+
+
+def write_cm_image(fd, image, key=""):
+    """`key `, the "\\0BCM " token and an image as ops.cm_encode leaves it: what dataset.kaldi_io.write_compressed_mat writes for the matrix."""
+    if key != "":
+        fd.write((key + " ").encode("latin1"))
+    fd.write(b"\0BCM ")
+    fd.write(image)
+
+
+class FeaturePreparer(object):
+    """The training features of the recipe from raw ones, on the device: what prepare_feats_for_egs.sh pipes through Kaldi
+    (egs/voxceleb/v1/run.sh stage 4: apply-cmvn-sliding --norm-vars=false --center=true --cmn-window=300 | select-voiced-frames |
+    copy-feats --compress=true) as decode -> ops.frontend -> ops.cm_encode.  prepare() cuts its list into calls whose buffers - the
+    archive bytes, the decoded and the normalised batch, the selected indices, the masks and the images - stay within workspace_bytes."""
+
+    def __init__(self, cmn_window=300, cm_header="uniform", device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        self.torch, self.ops, self.device = device_ops(device)
+        if cmn_window < 0:
+            raise ValueError("FeaturePreparer: cmn_window must be 0 (off) or a number of frames")
+        self.ops.cm_encode_plan((1, 1, 1), [1], cm_header)      # the header's name, before any work
+        self.cmn_window, self.cm_header, self.workspace_bytes = int(cmn_window), cm_header, int(workspace_bytes)
+
+    @staticmethod
+    def _cost(b, t_max, v_max, d, packed):
+        return packed + b * (max(t_max, 1) * (4 * d + 1) + max(v_max, 1) * (4 * d + 4 + d) + 16 + 8 * d)
+
+    def prepare(self, items, masks):
+        """items: the RAW utterances, dataset.kaldi_io.PackedMatrix ('CM ' as it sits in the archive: decoded on the device) or float32
+        matrices; masks: per utterance one uint8 per frame, non-zero = voiced, with at least one voiced frame - or None: every frame is kept.
+        -> [the 'CM ' image of the normalised, selected utterance, behind its token] in order; its rows = the voiced count."""
+        n_in = [int(f.shape[0]) for f in items]
+        masks = [None if m is None else np.ascontiguousarray(np.asarray(m) != 0).view(np.uint8) for m in masks]
+        n_out = [n if m is None else int(np.count_nonzero(m)) for n, m in zip(n_in, masks)]
+        for i, (f, m) in enumerate(zip(items, masks)):
+            if (m is not None and m.shape != (n_in[i],)) or n_out[i] < 1 or f.shape[1] != items[0].shape[1]:
+                raise ValueError("FeaturePreparer: utterance %d: %d frames of %d columns, %s decisions, %d voiced (one mask byte per frame, a "
+                                 "voiced frame and one dimension for all are expected)" % (i, n_in[i], f.shape[1], "no" if m is None else m.size, n_out[i]))
+        if not items:
+            return []
+        d = int(items[0].shape[1])
+        size = lambda i: len(items[i].payload) if hasattr(items[i], "payload") else 0
+        grow = lambda i, b=0, t=0, v=0, packed=0: (b + 1, max(t, n_in[i]), max(v, n_out[i]), packed + size(i))
+        cost_of = lambda b, t, v, packed: self._cost(b, t, v, d, packed)
+        too_big = lambda i, cost: ("FeaturePreparer: a workspace of %d bytes does not hold utterance %d (%d frames: %d bytes)"
+                                   % (self.workspace_bytes, i, n_in[i], cost))
+        out = [None] * len(items)
+        for batch in greedy_batches(len(items), grow, cost_of, self.workspace_bytes, max_items=65535, too_big=too_big):
+            for i, image in zip(batch, self._call([items[i] for i in batch], [masks[i] for i in batch], [n_out[i] for i in batch], d)):
+                out[i] = image
+        return out
+
+    def _call(self, items, masks, n_out, d):
+        torch, ops = self.torch, self.ops
+        n_in = np.asarray([f.shape[0] for f in items], np.int64)
+        t_in = int(n_in.max())
+        if all(hasattr(f, "payload") for f in items):      # the archive bytes go up as they are
+            sizes = [len(f.payload) for f in items]
+            packed = torch.from_numpy(np.concatenate([np.frombuffer(f.payload, np.uint8) for f in items])).to(self.device)
+            x = ops.cm_decode_ragged(packed, exclusive_offsets(sizes), n_in, t_in, d)
+        else:
+            x_h = np.zeros((len(items), t_in, d), np.float32)
+            for j, f in enumerate(items):
+                x_h[j, :n_in[j]] = f.decode() if hasattr(f, "payload") else f
+            x = torch.from_numpy(x_h).to(self.device)
+        rows_in = torch.from_numpy(n_in.astype(np.int32)).to(self.device)
+        if any(m is not None for m in masks):
+            masks = [np.ones(n, np.uint8) if m is None else m for n, m in zip(n_in, masks)]
+            m_d = torch.from_numpy(np.concatenate(masks)).to(self.device)
+            mo_d = torch.from_numpy(exclusive_offsets([len(m) for m in masks])).to(self.device)
+            y, _ = ops.frontend(x, rows_in, self.cmn_window, masks=m_d, mask_offsets=mo_d, t_out=max(n_out))
+        else:
+            y, _ = ops.frontend(x, rows_in, self.cmn_window, t_out=max(n_out))
+        return encoded_images(ops, y, n_out, self.cm_header)

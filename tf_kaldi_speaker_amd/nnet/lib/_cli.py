@@ -49,6 +49,13 @@ ARGUMENTS = {
                                                                       "conf/vad.conf values.")),
     "compress": (("--compress",), dict(type=str, default="true", choices=("true", "false"),
                                        help="true: 'CM ' compressed feature matrices (copy-feats --compress=true); false: 'FM '.")),
+    "prep_cmn_window": (("--cmn-window",), dict(type=int, default=300, help="Sliding-window CMN over this many frames on the GPU (apply-cmvn-sliding "
+                                                                          "--norm-vars=false --center=true --cmn-window=N); 0: none.")),
+    "cm_header": (("--cm-header",), dict(type=str, default="uniform", choices=("uniform", "quartiles"),
+                                         help="Where the four header points of a 'CM ' column lie: uniform (evenly spaced, what make_mfcc.py writes) "
+                                              "or quartiles (what copy-feats --compress=true chooses).  Every 'CM ' reader decodes both.")),
+    "min_len": (("--min-len",), dict(type=int, default=0, help="Utterances of this many frames or fewer are dropped (the recipe keeps "
+                                                               "frames > min_len); 0: none.")),
     "write_utt2num_frames": (("--write-utt2num-frames",), dict(type=str, default="", help="Write `key frames` lines to this file.")),
     "augment_plan": (("--augment-plan",), dict(type=str, default="", help="A plan file (misc/augment.py): `out_key src_key [rir=ID] "
                                                                           "[noise=ID:snr:start_seconds[:bg]] ...` per line.  The keys written are "
@@ -71,6 +78,8 @@ ARGUMENTS = {
     "wav_scp": (("wav_scp",), dict(type=str, help="Kaldi wav.scp: `key rxfilename` per line, the rxfilename a RIFF PCM-16 file or `command |`.")),
     "feats_wspecifier": (("feats_wspecifier",), dict(type=str, help="`ark,scp:feats.ark,feats.scp` (or `ark:feats.ark`): the feature table.")),
     "vad_wspecifier": (("vad_wspecifier",), dict(type=str, help="`ark,scp:vad.ark,vad.scp` (or `ark:vad.ark`): the table of VAD decisions.")),
+    "raw_rspecifier": (("raw_rspecifier",), dict(type=str, help="`ark:raw_feats.ark` (an archive or an input pipe): the raw features.")),
+    "prepared_wspecifier": (("prepared_wspecifier",), dict(type=str, help="`ark,scp:out.ark,out.scp` (or `ark:out.ark`): the prepared features.")),
     "train_rspecifier": (("train_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the training vectors.")),
     "spk2utt": (("spk2utt",), dict(type=str, help="Kaldi spk2utt of the training vectors: `speaker utt1 utt2 ...` per line.")),
     "out_dir": (("out_dir",), dict(type=str, help="The back-end directory to write (mean.vec, transform.mat, plda).")),
@@ -100,6 +109,34 @@ def parser_for(*names, **kw):
         flags, spec = ARGUMENTS[n]
         p.add_argument(*flags, **spec)
     return p
+
+
+class Table(object):
+    """A Kaldi table writer for `ark:FILE` or `ark,scp:ARK,SCP`: write(key, emit) calls emit(fd, key) and records the offset behind "key "."""
+
+    def __init__(self, wspecifier, what):
+        import sys
+        kind, _, rest = wspecifier.partition(":")
+        kinds = kind.split(",")
+        if not rest or "ark" not in kinds or any(k not in ("ark", "scp") for k in kinds):
+            sys.exit("%s: `ark:FILE` or `ark,scp:ARK,SCP` is expected (got %s)" % (what, wspecifier))
+        names = rest.split(",")
+        if len(names) != len(kinds):
+            sys.exit("%s: %s names %d file(s) for %d table type(s)" % (what, wspecifier, len(names), len(kinds)))
+        self.ark_path = names[kinds.index("ark")]
+        self.ark = open(self.ark_path, "wb")
+        self.scp = open(names[kinds.index("scp")], "w") if "scp" in kinds else None
+
+    def write(self, key, emit):
+        at = self.ark.tell() + len(key) + 1
+        emit(self.ark, key)
+        if self.scp is not None:
+            self.scp.write("%s %s:%d\n" % (key, self.ark_path, at))
+
+    def close(self):
+        self.ark.close()
+        if self.scp is not None:
+            self.scp.close()
 
 
 class _BatchedStderr(logging.Handler):

@@ -11,7 +11,8 @@ conf/mfcc.conf = compute-mfcc-feats | copy-feats --compress=true, then sid/compu
 --compress=true, the default; 'FM ' otherwise) and the archive of VAD decisions (float vectors of 1 / 0 per frame) are what
 extract.py --cmn-window 300 --vad scp:vad.scp and the loaders read.  `ark:FILE` alone writes no scp.  The 'CM ' matrices carry evenly spaced
 header points per column, not copy-feats' quartiles: the same format for every reader, and a rounding error below (max - min) / 255 of
-the column whatever its distribution (dataset/kaldi_io.py write_compressed_mat, header="uniform").
+the column whatever its distribution (dataset/kaldi_io.py write_compressed_mat, header="uniform"; the compression itself runs on the
+device, xv_cm_encode, which gives that function's bytes, so one byte per value comes back to the host instead of four).
 This is the --dither=0 program: the conf may say --dither=0, any other value is refused (misc/features.py says why); so is every other
 option of the two Kaldi programs that is not implemented, by name.  An utterance too short for one frame is logged and skipped.
 --augment-plan: the features of the AUGMENTED training list (egs/voxceleb/v1/run.sh:68-130) without a wav file in between - the keys
@@ -33,33 +34,6 @@ WINDOW_UTTERANCES = 256
 WINDOW_SAMPLES = 64 << 20
 
 
-class _Table(object):
-    """A Kaldi table writer for `ark:FILE` or `ark,scp:ARK,SCP`: write(key, emit) calls emit(fd, key) and records the offset behind "key "."""
-
-    def __init__(self, wspecifier, what):
-        kind, _, rest = wspecifier.partition(":")
-        kinds = kind.split(",")
-        if not rest or "ark" not in kinds or any(k not in ("ark", "scp") for k in kinds):
-            sys.exit("%s: `ark:FILE` or `ark,scp:ARK,SCP` is expected (got %s)" % (what, wspecifier))
-        names = rest.split(",")
-        if len(names) != len(kinds):
-            sys.exit("%s: %s names %d file(s) for %d table type(s)" % (what, wspecifier, len(names), len(kinds)))
-        self.ark_path = names[kinds.index("ark")]
-        self.ark = open(self.ark_path, "wb")
-        self.scp = open(names[kinds.index("scp")], "w") if "scp" in kinds else None
-
-    def write(self, key, emit):
-        at = self.ark.tell() + len(key) + 1
-        emit(self.ark, key)
-        if self.scp is not None:
-            self.scp.write("%s %s:%d\n" % (key, self.ark_path, at))
-
-    def close(self):
-        self.ark.close()
-        if self.scp is not None:
-            self.scp.close()
-
-
 def main():
     log = _cli.logger()
     args = _cli.parser_for("gpu", "mfcc_config", "vad_config", "compress", "write_utt2num_frames", "augment_plan", "rir_scp", "noise_scp",
@@ -73,41 +47,40 @@ def main():
     device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
     log.info("[INFO] MFCC without dither (--dither=0): on digital silence the features sit at the FLT_EPSILON floors; --energy-floor lifts the energy.")
     fx = features.FeatureExtractor(mfcc, vad, device)
-    feats_out, vad_out = _Table(args.feats_wspecifier, "feats_wspecifier"), _Table(args.vad_wspecifier, "vad_wspecifier")
+    feats_out, vad_out = _cli.Table(args.feats_wspecifier, "feats_wspecifier"), _cli.Table(args.vad_wspecifier, "vad_wspecifier")
     counts = open(args.write_utt2num_frames, "w") if args.write_utt2num_frames else None
     # 'CM ' with evenly spaced header points: the rounding error stays below (max - min) / 255 of a column whatever its distribution
-    # (Kaldi's quartile points let it reach (max - min) / 126); every 'CM ' reader decodes it (kaldi_io.write_compressed_mat)
-    if args.compress == "true":
-        def write_mat(fd, m, key):
-            kaldi_io.write_compressed_mat(fd, m, key=key, header="uniform")
-    else:
-        write_mat = kaldi_io.write_mat
+    # (Kaldi's quartile points let it reach (max - min) / 126); every 'CM ' reader decodes it.  The matrices are compressed on the device
+    # (ops.cm_encode: the bytes kaldi_io.write_compressed_mat(header="uniform") gives) and come back as the images the archive holds
+    cm_header = "uniform" if args.compress == "true" else None
+    write_mat = features.write_cm_image if cm_header else kaldi_io.write_mat
     stats = {"utts": 0, "frames": 0, "voiced": 0, "skipped": 0, "t0": time.time()}
     window, window_samples = [], 0
 
     def write(key, samples, feats, decisions):
-        if feats.shape[0] == 0:
+        frames = len(decisions)
+        if frames == 0:
             log.info("[INFO] Key %s has %d samples, too few for one frame, skip." % (key, samples))
             stats["skipped"] += 1
             return
-        log.info("[INFO] Key %s: %d samples, %d frames, %d voiced." % (key, samples, feats.shape[0], int(decisions.sum())))
+        log.info("[INFO] Key %s: %d samples, %d frames, %d voiced." % (key, samples, frames, int(decisions.sum())))
         feats_out.write(key, lambda fd, k: write_mat(fd, feats, key=k))
         vad_out.write(key, lambda fd, k: kaldi_io.write_vec_flt(fd, decisions, key=k))
         if counts is not None:
-            counts.write("%s %d\n" % (key, feats.shape[0]))
+            counts.write("%s %d\n" % (key, frames))
         stats["utts"] += 1
-        stats["frames"] += feats.shape[0]
+        stats["frames"] += frames
         stats["voiced"] += int(decisions.sum())
 
     def flush():
-        results = fx.extract([w for _, w in window])
+        results = fx.extract([w for _, w in window], cm_header)
         for (key, w), (feats, decisions) in zip(window, results):
             write(key, len(w), feats, decisions)
         del window[:]
 
     def flush_augmented(aug):
         pcm, offsets, lengths, clipped = aug.run([w for _, w in window], [e for e, _ in window])
-        results = fx.extract_packed(pcm, offsets, lengths)
+        results = fx.extract_packed(pcm, offsets, lengths, cm_header)
         for (e, _), n, c, (feats, decisions) in zip(window, lengths, clipped, results):
             log.info("[INFO] Key %s: augmented from %s, rir %s, %d noises, %d clipped." % (e.out_key, e.src_key, e.rir if e.rir is not None else "-",
                                                                                           len(e.noises), int(c)))

@@ -27,6 +27,61 @@ def frontend(x, rows_in, cmn_window=0, masks=None, mask_offsets=None, first=None
     return out, rows_out
 
 
+CM_MAX_D = 128      # the columns the 'CM ' kernels take (CMD_MAX_D / CME_MAX_D)
+
+
+def cm_decode_ragged(packed, offsets, rows, t, d):
+    """'CM ' matrices as they sit in an archive behind the "CM " token, decoded on the device (xv_cm_decode_ragged; no Engine needed).
+    packed: uint8 device tensor; offsets / rows: HOST integer arrays [b] - image i starts at byte offsets[i] and holds rows[i] <= t frames of d
+    columns; they are checked here, before the upload.  -> float32 [b, t, d], the rows behind rows[i] zero."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("cm_decode_ragged: packed must be a contiguous 1-D uint8 tensor")
+    t, d = int(t), int(d)
+    if not 1 <= d <= CM_MAX_D:
+        raise ValueError("cm_decode_ragged: d must lie in 1 .. %d (got %d)" % (CM_MAX_D, d))
+    pair = "cm_decode_ragged: offsets and rows must be two non-empty 1-D integer arrays of one length"
+    offsets = host_ints(offsets, min_size=1, msg=pair, dtype=np.int64)
+    rows = host_ints(rows, "cm_decode_ragged: rows", n=offsets.size, lo=0, hi=t + 1, msg=pair, dtype=np.int64)
+    if offsets.min() < 0 or (offsets + cm_image_bytes(rows, d)).max() > packed.numel():
+        raise IndexError("cm_decode_ragged: an image lies outside the %d bytes of packed" % packed.numel())
+    out = torch.empty((offsets.size, t, d), dtype=torch.float32, device=packed.device)
+    off_d, rows_d = upload(offsets, np.int64, packed.device), upload(rows, np.int32, packed.device)
+    _lib.call("xv_cm_decode_ragged", _s(), _p(packed), _p(off_d), _p(rows_d), offsets.size, t, d, _p(out))
+    return out
+
+
+def cm_image_bytes(rows, d):      # bytes of a 'CM ' matrix behind its token: global header, d column headers, d x rows codes
+    return 16 + 8 * int(d) + int(d) * np.asarray(rows, np.int64)
+
+
+def cm_encode_plan(shape, rows, header="quartiles"):
+    """The checks and the offset arithmetic of cm_encode, on the host: shape = (b, t, d) of x -> (rows int32 [b], offsets int64 [b] of the
+    images packed back to back, total bytes, the header's code).  Refuses by name: an unknown header, d > 128, rows[i] outside 1 .. t."""
+    if header not in _lib.XV_CM_HEADERS:
+        raise ValueError("cm_encode: header must be 'quartiles' or 'uniform' (got %r)" % (header,))
+    b, t, d = (int(n) for n in shape)
+    if not 1 <= d <= CM_MAX_D:
+        raise ValueError("cm_encode: d must lie in 1 .. %d (got %d)" % (CM_MAX_D, d))
+    rows = host_ints(rows, "cm_encode: rows", n=b, min_size=1, lo=1, hi=t + 1)
+    sizes = cm_image_bytes(rows, d)
+    return rows.astype(np.int32), exclusive_offsets(sizes), int(sizes.sum()), _lib.XV_CM_HEADERS[header]
+
+
+def cm_encode(x, rows, header="quartiles"):
+    """'CM ' compression of a padded batch on the device (xv_cm_encode: dataset.kaldi_io.write_compressed_mat byte for byte, in both header
+    forms).  x: float32 [b, t, d] device tensor, piece i holding rows[i] frames; rows: a HOST integer array, checked here before the upload
+    (1 <= rows[i] <= t; d <= 128; the header's name).  -> (uint8 device tensor: the images behind the "CM " token, packed back to back; their
+    int64 host offsets [b]); image i has cm_image_bytes(rows[i], d) bytes."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("cm_encode: x must be a contiguous float32 [b, t, d] tensor")
+    rows, offsets, total, code = cm_encode_plan(x.shape, rows, header)
+    b, t, d = x.shape
+    out = torch.empty(total, dtype=torch.uint8, device=x.device)
+    rows_d, off_d = upload(rows, np.int32, x.device), upload(offsets, np.int64, x.device)
+    _lib.call("xv_cm_encode", _s(), _p(x), _p(rows_d), b, t, d, code, _p(off_d), _p(out))
+    return out, offsets
+
+
 def _pcm(t, what):      # the samples of a pool of signals: a contiguous 1-D int16 device tensor, or None (no pool)
     if t is None:
         return 0

@@ -14,6 +14,8 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
   python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
+  python tools/bench_kernel.py cm_encode [utterances=256]        'CM ' compression (xv_cm_encode.hip) of 400 - 2000 frames x 30 per utterance, both header forms,
+                                                                against the bytes it must move and against the host writer
   python tools/bench_kernel.py augment [utterances=256] [notrace] reverberation + one background noise (xv_augment.hip) on the same synthetic PCM under impulse
                                                                 responses of 4 000 / 8 000 / 16 000 taps: us per kernel role, G taps x samples / s
 
@@ -376,6 +378,49 @@ def cmd_mfcc(argv):
     print("  xv_mfcc + xv_energy_vad %9.1f us  %.2f M frames/s = %.0f x real time" % (us_both, frames.sum() / us_both, frames.sum() / us_both * 1e6 / 100.0), flush=True)
 
 
+def cmd_cm_encode(argv):
+    """xv_cm_encode on one padded batch of MFCC-like utterances (400 - 2000 frames x 30), both header forms: device events around the bare
+    entry point (index arrays uploaded once) and around ops.cm_encode (its checks, two uploads and the output allocation included).  The
+    bytes the kernel has to move - 4 rows d read per pass over the piece (quartiles: 1 for the column ranges + 2 ranks x 4 radix passes + 1
+    for the codes = 10; uniform: 2) plus rows d written - against the 8 TB/s HBM peak, next to the 0.82 of it a flat streaming kernel
+    reaches here; and the host writer dataset.kaldi_io.write_compressed_mat over the same matrices, which is what the kernel replaces."""
+    import ctypes as C
+    import io
+    from tf_kaldi_speaker_amd import _lib, ops
+    from tf_kaldi_speaker_amd.dataset import kaldi_io
+    n_utts, d = int(argv[0]) if argv else 256, 30
+    rows = rs.randint(400, 2001, n_utts)
+    t = int(rows.max())
+    x_h = np.zeros((n_utts, t, d), np.float32)
+    for i, n in enumerate(rows):
+        x_h[i, :n] = rs.randn(n, d) * 20.0
+        x_h[i, :n, 0] -= 30.0
+    x = torch.from_numpy(x_h).cuda()
+    values = float(rows.sum()) * d
+    print("%d utterances of %d - %d frames x %d: %.2f M frames, %.1f MB of fp32 values" % (n_utts, rows.min(), rows.max(), d, rows.sum() / 1e6, 4 * values / 1e6),
+          flush=True)
+    p, s = (lambda a: C.c_void_p(a.data_ptr())), (lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    for header, passes in (("quartiles", 10), ("uniform", 2)):
+        rows32, offsets, total, code = ops.cm_encode_plan(x.shape, rows, header)
+        rows_d, off_d = torch.from_numpy(rows32).cuda(), torch.from_numpy(offsets).cuda()
+        out = torch.empty(total, dtype=torch.uint8, device="cuda")
+        us = timeit(lambda: _lib.call("xv_cm_encode", s(), p(x), p(rows_d), n_utts, t, d, code, p(off_d), p(out)), 10, 2)
+        us_op = timeit(lambda: ops.cm_encode(x, rows, header), 10, 2)
+        mb = (4.0 * values * passes + values) / 1e6
+        print("  %-9s xv_cm_encode %9.1f us  %.1f M frames/s  (%d passes: %.0f MB read + written = %.3f TB/s = %.3f of the 8 TB/s peak; a flat "
+              "streaming kernel: 0.82)   ops.cm_encode %9.1f us" % (header, us, rows.sum() / us, passes, mb, mb / us, mb / us / 8.0, us_op), flush=True)
+        t0 = time.perf_counter()
+        images = []
+        for i, n in enumerate(rows):
+            sink = io.BytesIO()
+            kaldi_io.write_compressed_mat(sink, x_h[i, :n], header=header)
+            images.append(sink.getvalue()[5:])      # behind "\0BCM "
+        host_us = (time.perf_counter() - t0) * 1e6
+        same = b"".join(images) == out.cpu().numpy().tobytes()
+        print("  %-9s write_compressed_mat on the host, one thread: %9.1f us  %.2f M frames/s = %.0f x the kernel's time; the same bytes: %s"
+              % (header, host_us, rows.sum() / host_us, host_us / us, same), flush=True)
+
+
 def cmd_augment(argv):
     """xv_augment on one batch per impulse-response length: every utterance reverberated by the same L taps plus one background noise at 10 dB,
     shift_output and normalize_output on.  Whole calls are timed with device events around ops.augment (table building and the one index
@@ -433,7 +478,7 @@ def cmd_augment(argv):
             print("    (no kernel records from the profiler: no split over the roles)", flush=True)
 
 
-COMMANDS = {"augment": cmd_augment, "mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+COMMANDS = {"augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
