@@ -1,4 +1,4 @@
-"""The launch plans of the fp32 GEMMs (csrc/xv_gemm.hip xv_nt_plan / xv_tn_plan) restated in Python and checked against the library's own
+"""The launch plans of the fp32 GEMMs (csrc/xv_gemm_nt.hip xv_nt_plan, csrc/xv_gemm_tn.hip xv_tn_plan) restated in Python and checked against the library's own
 answer (xv_debug_nt_schedule / xv_debug_tn_plan: host arithmetic, no GPU needed) over every layer problem of the S1-S5 shapes and a grid of
 ragged ones.  A plan constant changed in the C file without its restatement fails here, naming the shape and the branch; the GPU tests
 that run each branch against the float64 oracle (tests/test_gpu_gemm_plans.py) use these restatements to pin the branch of every row."""
@@ -27,7 +27,7 @@ def cdiv(a, b):
 
 
 def nt_plan(M, N, K, stats, co_running, ws_bytes=DEBUG_WS, have_ws=True, forced=0):
-    """csrc/xv_gemm.hip xv_nt_plan, restated (forced: XV_NT_SCHED, 1 = dp, 2 = sk).  Returns dict(kind, p_sk, shared_tiles, shares, splits)."""
+    """csrc/xv_gemm_nt.hip xv_nt_plan, restated (forced: XV_NT_SCHED, 1 = dp, 2 = sk).  Returns dict(kind, p_sk, shared_tiles, shares, splits)."""
     tiles, ksteps = cdiv(M, BM) * cdiv(N, BN), cdiv(K, BK)
     total = tiles * ksteps
     p_sk = min(min(256 * NT_SK_WPC, max(1, total // 4)), 8 * tiles)
@@ -61,7 +61,7 @@ def nt_plan(M, N, K, stats, co_running, ws_bytes=DEBUG_WS, have_ws=True, forced=
 
 
 def tn_plan(M, N, R, direct=False):
-    """csrc/xv_gemm.hip xv_tn_plan, restated: (kernel, splits, chunk, ahead) - what xv_debug_tn_plan reports."""
+    """csrc/xv_gemm_tn.hip xv_tn_plan, restated: (kernel, splits, chunk, ahead) - what xv_debug_tn_plan reports."""
     tiles, ksteps = cdiv(M, BM) * cdiv(N, BN), cdiv(R, BK)
     if BM < M <= 160:                                      # xv_gemm_tn160_kernel
         splits = max(1, min(TNW_WGS // cdiv(N, BN), ksteps // 4))
@@ -79,7 +79,7 @@ def tn_plan(M, N, R, direct=False):
 
 
 def wgrad_reduce_zsplit(splits, k, c, o):
-    """csrc/xv_gemm.hip xv_launch_wgrad_reduce: the ZSPLIT form (4 groups per output row) or the per-row form"""
+    """csrc/xv_gemm_tn.hip xv_launch_wgrad_reduce: the ZSPLIT form (4 groups per output row) or the per-row form"""
     return splits >= 32 and k * c * cdiv(o // 4, 64) < 1024
 
 

@@ -6,7 +6,7 @@ Tolerances (EPS = 2^-24, chain(d) = 4 * ceil(d / 256) + 6 as stated in csrc/xv_r
                      flag); mean32 == float32(mean64)
   scatter            2 * (c_blk + 2) * EPS * sum_r |v_ri v_rj| per element, from the fp64 products.  c_blk = the reduction rows one
                      workgroup of the TN GEMM accumulates in fp32: out[2] of xv_debug_tn_plan(d4, d4, block rows) - the plan
-                     xv_launch_gemm_tn runs (csrc/xv_gemm.hip, xv_tn_plan: "`chunk` reduction rows per workgroup"), the larger of the
+                     xv_launch_gemm_tn runs (csrc/xv_gemm_tn.hip, xv_tn_plan: "`chunk` reduction rows per workgroup"), the larger of the
                      full block's and the tail block's.  An accumulator takes chunk / 2 MFMA steps of two products each: at most c_blk
                      roundings; the products are exact in the sum's precision only after one rounding each (+ 1); v itself is reproduced
                      exactly by the reference (an fp32 subtraction); the slabs and blocks are added in double (+ 1 covers it generously).

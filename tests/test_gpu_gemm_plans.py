@@ -1,4 +1,4 @@
-"""Every launch plan of the fp32 GEMMs against the float64 oracle, one row per branch (csrc/xv_gemm.hip xv_nt_plan / xv_tn_plan).
+"""Every launch plan of the fp32 GEMMs against the float64 oracle, one row per branch (csrc/xv_gemm_nt.hip xv_nt_plan, csrc/xv_gemm_tn.hip xv_tn_plan).
 
 Each row names the plan it must land on; the test first asserts that plan through the library's own diagnostics (xv_debug_nt_schedule,
 xv_debug_tn_plan) and the Python restatement (tests/test_gemm_plans.py) - a row whose shape has drifted off its branch after a plan change

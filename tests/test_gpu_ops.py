@@ -581,7 +581,7 @@ SEGMENT_CASES = [(128, 512, 3000), (64, 512, 512), (128, 7351, 512), (128, 512, 
 
 
 # (segs, t_in, c, k, o) and SHARE_PLANS (forward plan, data-gradient plan): tile counts between one and four per CU with a remainder -> whole tiles + shares
-# (csrc/xv_gemm.hip xv_nt_shares) in the forward launch; the data gradient runs beside the weight-gradient stream, where shares need tiles of
+# (csrc/xv_gemm_nt.hip xv_nt_shares) in the forward launch; the data gradient runs beside the weight-gradient stream, where shares need tiles of
 # >= 100 K-steps and >= 512 tiles are dealt one workgroup per tile.  Plans: 0 one workgroup per tile, 1 even schedule, 2 shares, 3 split-K
 # (xv_debug_nt_schedule; tests/test_gpu_gemm_plans.py runs every plan against the oracle)
 SHARE_CASES = [
@@ -645,7 +645,7 @@ def test_whole_tiles_plus_shares(ops, segs, t_in, c, k, o):
 
 def test_split_handoff_stress(ops):
     """The split-K hand-over of the one-launch segment kernels (relaxed agent-scope stores / ticket / loads: the xv_handoff_* contract of
-    csrc/xv_common.h, an architecture property of gfx950 rather than a HIP memory-model guarantee - ADVICE r02) replayed many times
+    csrc/xv_handoff.h, an architecture property of gfx950 rather than a HIP memory-model guarantee - ADVICE r02) replayed many times
     back to back, the consumer L1-warm, under UNEVEN load (a large GEMM on another stream occupies part of the chip): every launch must
     reproduce the first result bit for bit - a stale slab word would show as a different sum - and leave its tickets at zero."""
     import torch

@@ -1,4 +1,4 @@
-"""The even ("stream-K") schedule of the fp32 NT GEMM (csrc/xv_gemm.hip, xv_gemm_nt_sk_kernel / xv_launch_gemm_nt) restated in Python and
+"""The even ("stream-K") schedule of the fp32 NT GEMM (csrc/xv_gemm_nt.hip, xv_gemm_nt_sk_kernel / xv_launch_gemm_nt) restated in Python and
 checked exhaustively on the layer shapes: the kernel's integer formulas must tile the (tile, K-step) units exactly once, agree on who
 shares a tile, and never hand two shares of one workgroup the same slab slot.  (Host logic only; the kernel itself is compared with the
 oracle in tests/test_gpu_ops.py.)"""
@@ -112,7 +112,7 @@ def test_wrap_first_order_covers_the_same_units(rows, cols, K):
 
 # ---- "whole tiles + shares" in the one-workgroup-per-tile kernel (xv_nt_shares / xv_gemm_nt_kernel) -------------------------------------
 def nt_shares(tiles, ksteps, stats, beside_wgrad, ws_bytes=1 << 40):
-    """csrc/xv_gemm.hip xv_nt_shares, restated"""
+    """csrc/xv_gemm_nt.hip xv_nt_shares, restated"""
     rem, whole = tiles % 256, tiles // 256
     if rem < 1 or rem > 128:
         return 0

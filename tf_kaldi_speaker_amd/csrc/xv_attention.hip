@@ -7,6 +7,7 @@
 // for statistics pooling: neither v nor dv is ever written; dv enters tdnn5's BN backward through PoolGrad.w.
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_pool.h"
 
 #include <algorithm>
 
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void att_pool_dw_kernel(const float* __restric
             f32x4 zz = zq[u];
             f32x4 a = zz;
             if (scale) a = zz * *(const f32x4*)(scale + c) + *(const f32x4*)(shift + c);
-            if (relu && slope) a = act4(a, *(const f32x4*)(slope + c));      // prelu / leaky ReLU value tensor (act context, xv_common.h)
+            if (relu && slope) a = act4(a, *(const f32x4*)(slope + c));      // prelu / leaky ReLU value tensor (act context, xv_ew.h)
             else if (relu) a = relu4(a);
             f32x4 mean = *(const f32x4*)(o + c), sd = *(const f32x4*)(o + n + c);
             f32x4 dm = *(const f32x4*)(g + c), dsd = *(const f32x4*)(g + n + c);

@@ -17,6 +17,7 @@
 
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_gemm.h"
 #include "xv_rowsum.h"
 
 #define BE_BLOCK_ROWS 8192        // rows per scatter block: the longest fp32 add chain of a scatter element, whatever n is

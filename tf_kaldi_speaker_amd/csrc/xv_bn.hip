@@ -5,6 +5,8 @@
 // frame-level tensors is in xv_bn_bwd.hip.  gfx950 only.
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_bn.h"
+#include "xv_gemm.h"      // XV_TILE_M: the rows behind one partial of a GEMM epilogue
 
 // bn_part layout: [2][tiles][n] with tiles = ceil(rows / XV_TILE_M): sum, then centred sum of squares.
 // block = 256 threads = 32 columns x 8 row lanes over one 128-row tile; two passes (sum/min/max, then
@@ -351,7 +353,7 @@ extern "C" int xv_bn_apply(void* stream, const float* z, int rows, int n, int ld
 }
 
 // ------------------------------------------------------------------------------------
-// small-row BatchNorm, one launch (xv_common.h).  block = 256 threads = 16 channels x 16 row lanes; fixed-order combines.
+// small-row BatchNorm, one launch (xv_bn.h).  block = 256 threads = 16 channels x 16 row lanes; fixed-order combines.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ float small_reduce16(float v, float (*red)[16], int rl, int cx) {
     __syncthreads();

@@ -6,6 +6,7 @@
 
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_bn.h"
 #include "xv_epilogue.h"
 
 // The launch plan of the backward (bn_bwd_plan below; xv_debug_bn_bwd_plan reports it).  Reduction forms, the template flags of the pooled
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(256) void bn_bwd_pooled_stats_kernel(PoolGrad pg, i
     }
 }
 
-// The kernels' view of an upstream-gradient descriptor (xv_common.h)
+// The kernels' view of an upstream-gradient descriptor (xv_bn.h)
 static PoolGrad pool_grad_of(const XvBnUpstream& up) {
     return up.pool_out ? PoolGrad{up.pool_out, up.dpool, up.pool_t, up.weights, up.wpos, up.pamax} : PoolGrad{nullptr, nullptr, 1, nullptr, nullptr, nullptr};
 }
@@ -628,7 +629,7 @@ static int bn_bwd_reductions(hipStream_t s, const char* who, const BnBwdPlan& pl
     return 0;
 }
 
-// dz in fp32, segment-padded layout (xv_common.h).  ldz: leading dimension of z and dz when their rows are padded (the pooled layer: rows on
+// dz in fp32, segment-padded layout (xv_bn.h).  ldz: leading dimension of z and dz when their rows are padded (the pooled layer: rows on
 // the 128-byte grid), 0 = n; closed-form pooled path only.
 int xv_bn_backward_f32(hipStream_t s, const XvBnUpstream& up, const float* z, int segs, int t, int n, const float* gamma, const float* mean,
                        const float* invstd, const float* scale, const float* shift, int relu, int pad, float* dz_pad, int ldz, float* dgamma,
@@ -662,7 +663,7 @@ int xv_bn_backward_f32(hipStream_t s, const XvBnUpstream& up, const float* z, in
     return 0;
 }
 
-// dz as two fp16 planes scaled by the power of two of *dz_amax, which the reduction stage bounds (xv_common.h).  zero_amax = false:
+// dz as two fp16 planes scaled by the power of two of *dz_amax, which the reduction stage bounds (xv_bn.h).  zero_amax = false:
 // *dz_amax was zeroed by the caller.
 int xv_bn_backward_split(hipStream_t s, const XvBnUpstream& up, const float* z, int segs, int t, int n, const float* gamma, const float* mean,
                          const float* invstd, const float* scale, const float* shift, const float* zmin, const float* zmax, int relu, int pad,

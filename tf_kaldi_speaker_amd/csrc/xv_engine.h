@@ -4,7 +4,7 @@
 //   xv_engine_fwd.hip   weight preparation, forward, loss forward, the regularisation loss
 //   xv_engine_bwd.hip   streams, dz ring, join, stage events, layer backward in both precisions, the four backward stages
 //   xv_engine_step.hip  the RCCL exchange, the update, loss pointers, endpoint views
-// No engine unit holds device code: every launch goes through a launcher of the kernel units (xv_common.h, include/xvector_hip.h).
+// No engine unit holds device code: every launch goes through a launcher of the kernel units (the unit headers below, include/xvector_hip.h).
 //
 // HBM layout (all fp32, channel axis contiguous):
 //   variables  : caller-owned flat buffer, TF variable order, trainable first then BN moving
@@ -14,7 +14,7 @@
 //   activations: per frame layer z_l (pre-BN) and a_l (post BN+ReLU), [chunks*frames_l][C_l].
 //   backward   : one da buffer and one dz buffer, ping-ponged down the stack; dz is stored with
 //                k-1 zero frames around each chunk so the data gradient is the SAME spliced-view
-//                GEMM as the forward pass (xv_gemm.hip).
+//                GEMM as the forward pass (xv_gemm_nt.hip).
 //   weights    : kernel-layout copies (transposed / tap-flipped / channel-padded) rebuilt once
 //                per optimiser step.
 #pragma once
@@ -22,6 +22,13 @@
 #include <vector>
 
 #include "xv_common.h"
+#include "xv_bn.h"
+#include "xv_ew.h"
+#include "xv_gemm.h"
+#include "xv_loss.h"
+#include "xv_pool.h"
+#include "xv_prep.h"
+#include "xv_skinny.h"
 
 struct XvVar {
     std::string name;
@@ -175,7 +182,7 @@ inline float* vptr(xv_engine* e, int idx) { return e->V + e->vars[idx].offset; }
 inline float* gptr(xv_engine* e, int idx) { return e->G + e->vars[idx].offset; }
 
 // network_relu_type (tdnn.py:24-30): while in scope, the entry points that take a `relu` flag apply y > 0 ? y : slope[c] * y for this
-// layer - prelu: slope = the layer's alpha variable (d alpha goes to its gradient slot), lrelu: the constant 0.2 vector (xv_common.h)
+// layer - prelu: slope = the layer's alpha variable (d alpha goes to its gradient slot), lrelu: the constant 0.2 vector (xv_ew.h)
 struct ActScope {
     ActScope(xv_engine* e, const XvAffine& a) {
         if (!a.has_relu || e->cfg.relu_type == XV_RELU_RELU) return;

@@ -7,6 +7,7 @@
 // Deterministic: fixed-order combines through LDS, no atomics.
 #pragma once
 #include "xv_common.h"
+#include "xv_gemm.h"      // XV_TILE_M
 
 template <int NB>
 __device__ __forceinline__ void xv_tile_stats_epilogue(const f32x16 (&acc)[2][NB], float* red /* >= 1024 floats of LDS, free */,

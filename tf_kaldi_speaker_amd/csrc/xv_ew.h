@@ -1,9 +1,22 @@
 // Helpers shared by the element-wise units (xv_runtime, xv_prep, xv_bn, xv_bn_bwd, xv_pool, xv_update) and by the activation
 // sites of xv_gemm16.hip and xv_attention.hip: the launch grid of a grid-stride kernel, the wave sum, and the activation behind a
-// BatchNorm (act context, xv_common.h) on a channel quad, forward and backward.  Device helpers are all __forceinline__: every kernel
+// BatchNorm (act context, below) on a channel quad, forward and backward.  Device helpers are all __forceinline__: every kernel
 // keeps the instruction sequence it had with the expression written out.
 #pragma once
 #include "xv_common.h"
+
+// Activation behind a BatchNorm in the layer being processed (network_relu_type, tdnn.py:24-30): y > 0 ? y : slope[c] * y.
+// slope == nullptr: ReLU.  Set by the engine around a layer's calls (prelu: the layer's alpha variable, with dalpha = its gradient;
+// lrelu: a constant 0.2 vector); every entry point that takes a `relu` flag reads it (xv_bn.hip owns it).
+struct XvActContext { const float* slope; float* dalpha; };
+void xv_set_act_context(const float* slope, float* dalpha);
+XvActContext xv_act_context();
+
+// *out += scale * sum(w[0 .. count)^2) by a fixed-order two-stage reduction (xv_update.hip); part: XV_SUMSQ_PARTS floats of scratch
+#define XV_SUMSQ_PARTS 512
+int xv_sumsq_ordered(hipStream_t s, const float* w, size_t count, float scale, float* out, float* part);
+// g[0 .. count) *= grad_scale * clip / max(grad_scale * sqrt(*sumsq), clip)   (tf.clip_by_global_norm; xv_update.hip)
+int xv_clip_scale(hipStream_t s, float* g, size_t count, const float* sumsq, float grad_scale, float clip);
 
 // Geometry of the two kernels that finalise per-channel statistics from partials (bn_finalize_kernel, bn_bwd_finalize_kernel): a block of
 // 256 threads = FIN_CH channels x FIN_LANES partial lanes, FIN_BATCH partials' loads in flight per lane

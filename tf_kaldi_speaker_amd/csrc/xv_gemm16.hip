@@ -12,13 +12,16 @@
 // BN+ReLU from the GEMM epilogue's column min/max; a bound for the BN backward; a reduction for inputs and
 // weights) and travels as the uint bits of a float in device memory - no host round trip.
 // Measured on MI355X (tests/test_gpu_ops_f16x3.py, tools/bench_kernel.py gemm16): max error vs float64 5e-7..8e-7 of the output scale (fp32-input MFMA:
-// 1.7e-7), 2.6-3.0x the speed of the fp32-input MFMA kernels of xv_gemm.hip.
+// 1.7e-7), 2.6-3.0x the speed of the fp32-input MFMA kernels of xv_gemm_nt.hip / xv_gemm_tn.hip.
 //
 // Plane layout: [2][rows][ld] 16-bit, channel axis contiguous, ld a multiple of 8 (16-byte chunks), zero padded.
-// The spliced (context-window) row map of xv_gemm.hip applies unchanged to both kernels.
+// The spliced (context-window) row map of xv_gemm_nt.hip applies unchanged to both kernels.
 #include "xv_common.h"
 #include "xv_epilogue.h"
 #include "xv_ew.h"
+#include "xv_gemm.h"
+#include "xv_gemm_tile.h"      // xcd_swizzle
+#include "xv_handoff.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -31,11 +34,6 @@ static int ensure_zero16() {
     XV_CHECK_HIP(hipMalloc((void**)&g_zero16, 256));
     XV_CHECK_HIP(hipMemset(g_zero16, 0, 256));
     return 0;
-}
-
-__device__ __forceinline__ int xcd_swizzle16(int bid, int nwg) {
-    int xcd = bid & 7, idx = bid >> 3, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
 __device__ __forceinline__ void split_f16(float x, float s, u16& h, u16& l) {
@@ -149,7 +147,7 @@ __global__ void bn_apply_split_kernel(const float* __restrict__ z, long rows, in
             f32x4 y = {0, 0, 0, 0};
             if (c < n) {
                 y = *(const f32x4*)(z + r * ldz + c) * *(const f32x4*)(scale + c) + *(const f32x4*)(shift + c);
-                if (relu && slope) y = act4(y, *(const f32x4*)(slope + c));      // prelu / leaky ReLU (act context, xv_common.h)
+                if (relu && slope) y = act4(y, *(const f32x4*)(slope + c));      // prelu / leaky ReLU (act context, xv_ew.h)
                 else if (relu) y = relu4(y);
             }
             v[4 * q] = y.x; v[4 * q + 1] = y.y; v[4 * q + 2] = y.z; v[4 * q + 3] = y.w;
@@ -224,13 +222,13 @@ __global__ __launch_bounds__(64 * XV16_WAVES, XV16_WGS) void xv_gemm16_nt_kernel
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     const int wr = wave / WN16, wc = wave % WN16;
     const int li = lane & 31, lh = lane >> 5;
-    const int t = xcd_swizzle16(blockIdx.x, gridDim.x);
+    const int t = xcd_swizzle(blockIdx.x, gridDim.x);
     const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
     const int m0 = tile_m * 128, n0 = tile_n * 128;
     const int nk = (p.K + BK16 - 1) / BK16;
 
     const int lrow = lane / CQ16, lpos = lane % CQ16;
-    // per-lane byte offsets from the plane bases, swizzled chunk folded in (xv_dma16: scalar base + 32-bit offset, xv_common.h; both planes
+    // per-lane byte offsets from the plane bases, swizzled chunk folded in (xv_dma16: scalar base + 32-bit offset, xv_handoff.h; both planes
     // share them).  Rows outside the matrix read row 0 - their products are never stored or counted; k beyond K must read zeros and
     // takes the zero page through the builtin's 64-bit form (a ragged last K-step only).
     unsigned aoff[IPW], boff[IPW];
@@ -403,7 +401,7 @@ __global__ __launch_bounds__(128 * WR, 2) void xv_gemm16_nt_conv_kernel(NT16Conv
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
-    const int t = xcd_swizzle16(blockIdx.x, gridDim.x);
+    const int t = xcd_swizzle(blockIdx.x, gridDim.x);
     const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
     const int m0 = tile_m * G::BM, n0 = tile_n * 128;
     const int taps = q.taps, nc = q.chunks;
@@ -700,7 +698,7 @@ __global__ __launch_bounds__(256, 2) void xv_gemm16_tn_kernel(TN16Args p) {
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
-    const int v = xcd_swizzle16(blockIdx.x, gridDim.x);
+    const int v = xcd_swizzle(blockIdx.x, gridDim.x);
     const int tiles = p.tiles_m * p.tiles_n;
     const int split = v / tiles, t = v - split * tiles;
     const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
@@ -738,7 +736,7 @@ __global__ __launch_bounds__(256, 2) void xv_gemm16_tn_kernel(TN16Args p) {
         }
     };
     // Full stages: scalar plane bases + 32-bit lane offsets that advance by BR rows per stage (xv_dma16; the fp32 weight-gradient kernel's
-    // scheme, xv_gemm.hip): a row of the spliced view is (segment, frame), frame += BR, and on crossing a segment's last frame the offset
+    // scheme, xv_gemm_tn.hip): a row of the spliced view is (segment, frame), frame += BR, and on crossing a segment's last frame the offset
     // skips the rows between two segments.  Columns outside the matrix read column 0: their products are never stored.
     const bool steady = p.rps >= BR;
     int tt_i[2];

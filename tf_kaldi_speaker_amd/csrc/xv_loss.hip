@@ -1,8 +1,10 @@
 // Softmax loss family of model/loss.py:9-355 on gfx950: weight normalisation, the per-chunk
 // margin transform + annealing blend + mean sparse cross entropy with its gradients, and the
 // gradient through tf.nn.l2_normalize.  The [rows x N] logits GEMMs themselves run on the MFMA
-// kernels of xv_gemm.hip; everything here is HBM/L2-bound row or column work.
+// kernels of xv_gemm_nt.hip / xv_gemm_tn.hip; everything here is HBM/L2-bound row or column work.
 #include "xv_common.h"
+#include "xv_handoff.h"
+#include "xv_loss.h"
 
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(256) void margin_softmax_rows_kernel(int kind, cons
         dnorm[r] = margin ? s_dn * (py - 1.f) * inv_rows : 0.f;
         if (ticket) {
             // the mean over the rows in the same launch: the last workgroup to finish sums row_loss in index order (mean_kernel's
-            // arithmetic).  Hand-over by agent-scope atomics (the xv_handoff_* contract of xv_common.h), not __threadfence() (a
+            // arithmetic).  Hand-over by agent-scope atomics (the xv_handoff_* contract of xv_handoff.h), not __threadfence() (a
             // whole-L2 write-back per workgroup on gfx950)
             __hip_atomic_store(row_loss + r, rl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -3,6 +3,8 @@
 // (The BatchNorm backward that evaluates the pooling backward on the fly is in xv_bn_bwd.hip.)  gfx950 only.
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_bn.h"      // XvBnUpstream
+#include "xv_pool.h"
 
 // ------------------------------------------------------------------------------------
 // statistics pooling (pooling.py:9-34)
@@ -133,7 +135,7 @@ extern "C" int xv_stat_pool_forward(void* stream, const float* x, int b, int t, 
     return 0;
 }
 
-// wpos, amax (optional, [b][c]): see XvBnUpstream (xv_common.h)
+// wpos, amax (optional, [b][c]): see XvBnUpstream (xv_bn.h)
 int xv_stat_pool_forward_bn_ex(hipStream_t s, const float* z, int b, int t, int c, const float* scale, const float* shift, int relu,
                                const float* weights, float* out, float* wpos, float* amax, const int32_t* frames, int shrink, int ldz) {
     XV_REQUIRE(b > 0 && t > 0 && c > 0 && c % 4 == 0 && scale && shift, "stat_pool_forward_bn: bad shape (c=%d must be a multiple of 4)", c);

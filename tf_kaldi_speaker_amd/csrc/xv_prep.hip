@@ -4,6 +4,7 @@
 #include "xv_common.h"
 #include "xv_ew.h"
 #include "xv_epilogue.h"
+#include "xv_prep.h"
 
 // ------------------------------------------------------------------------------------
 // Kaldi 'CM ' compressed-matrix decode on the GPU (kaldi_io.py:768-867 / compressed-matrix.h) for batches the native loader delivers
@@ -142,7 +143,7 @@ extern "C" int xv_prep_weight_dgrad(void* stream, const float* kernel, int k, in
 }
 
 // ------------------------------------------------------------------------------------
-// multi-job weight preparation (xv_common.h): one launch for every layout copy of every layer
+// multi-job weight preparation (xv_prep.h): one launch for every layout copy of every layer
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void weight_prep_multi_kernel(XvPrepJobs J) {
     XV_EW_FILLER();

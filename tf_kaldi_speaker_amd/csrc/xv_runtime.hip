@@ -1,9 +1,12 @@
 // Process-wide plumbing of the library: the per-thread error string behind xv_last_error, the XV_* environment switches (xv_env),
-// the ABI version / device count queries and the two plain copies of the C-ABI (xv_copy_2d, xv_pad_channels).  gfx950 only.
+// the ABI version / device count queries, live launch timing (xv_profile_*) and the two plain copies of the C-ABI (xv_copy_2d, xv_pad_channels).  gfx950 only.
 #include <stdarg.h>
+
+#include <vector>
 
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_gemm.h"      // XvProfScope
 
 // ------------------------------------------------------------------------------------
 // error plumbing
@@ -89,6 +92,58 @@ extern "C" int xv_copy_2d(void* stream, float* dst, size_t ldd, const float* src
     XV_REQUIRE(dst && src && rows > 0 && cols > 0 && ldd >= (size_t)cols && lds >= (size_t)cols, "copy_2d: bad arguments");
     XV_CHECK_HIP(hipMemcpy2DAsync(dst, ldd * sizeof(float), src, lds * sizeof(float), (size_t)cols * sizeof(float), rows,
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// live launch timing of the GEMM launchers (XvProfScope, xv_gemm.h; bench.py roofline leg)
+// ------------------------------------------------------------------------------------
+namespace {
+struct ProfRec { hipEvent_t a, b; int kind; double flops; };
+bool g_prof_on = false;
+uint32_t g_prof_mask = ~0u;
+std::vector<ProfRec> g_prof;
+size_t g_prof_cap = 0;
+std::vector<hipEvent_t> g_prof_events;   // pool, two per record slot
+}  // namespace
+
+XvProfScope::XvProfScope(hipStream_t st, int kind, double flops) : s(st), idx(-1) {
+    if (!g_prof_on || !((g_prof_mask >> kind) & 1u) || g_prof.size() >= g_prof_cap) return;
+    idx = (int)g_prof.size();
+    ProfRec r = {g_prof_events[2 * idx], g_prof_events[2 * idx + 1], kind, flops};
+    g_prof.push_back(r);
+    (void)hipEventRecord(r.a, s);
+}
+XvProfScope::~XvProfScope() { if (idx >= 0) (void)hipEventRecord(g_prof[idx].b, s); }
+
+extern "C" int xv_profile_begin(int max_launches) { return xv_profile_begin_kinds(max_launches, ~0u); }
+
+extern "C" int xv_profile_begin_kinds(int max_launches, uint32_t kind_mask) {
+    XV_REQUIRE(max_launches > 0, "profile_begin: max_launches must be positive");
+    g_prof_mask = kind_mask;
+    while (g_prof_events.size() < (size_t)2 * max_launches) {
+        hipEvent_t ev;
+        // device-scope release: the pair brackets one launch on its own stream; a system-scope fence per record (the default) would be
+        // measurement overhead inside the region bench.py times
+        XV_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventReleaseToDevice));
+        g_prof_events.push_back(ev);
+    }
+    g_prof.clear();
+    g_prof_cap = (size_t)max_launches;
+    g_prof_on = true;
+    return 0;
+}
+
+extern "C" int xv_profile_end(int64_t launches[XV_PROFILE_KINDS], double ms[XV_PROFILE_KINDS], double flops[XV_PROFILE_KINDS]) {
+    g_prof_on = false;
+    for (int k = 0; k < XV_PROFILE_KINDS; ++k) { launches[k] = 0; ms[k] = 0.0; flops[k] = 0.0; }
+    for (auto& r : g_prof) {
+        XV_CHECK_HIP(hipEventSynchronize(r.b));
+        float t = 0.f;
+        XV_CHECK_HIP(hipEventElapsedTime(&t, r.a, r.b));
+        launches[r.kind] += 1; ms[r.kind] += (double)t; flops[r.kind] += r.flops;
+    }
+    g_prof.clear();
     return 0;
 }
 

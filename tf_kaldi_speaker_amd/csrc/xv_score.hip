@@ -9,6 +9,7 @@
 
 #include "xv_common.h"
 #include "xv_ew.h"
+#include "xv_gemm.h"
 #include "xv_rowsum.h"      // sc_row_dot and chain(d), SC_ROWS_PER_WG, sc_aligned16, sc_overlap
 #include "xv_radix_key.h"   // sc_key / sc_unkey: the unsigned key whose order is the float's
 

@@ -18,6 +18,10 @@
 //     moving averages, scale/shift, activation - bn_small_fwd_kernel's arithmetic) or the BatchNorm backward of the layer
 //     BELOW the gradient GEMM (bn_small_bwd_kernel's) runs on its registers before anything is written.
 #include "xv_common.h"
+#include "xv_ew.h"      // act context
+#include "xv_gemm.h"    // xv_zero_page
+#include "xv_handoff.h"
+#include "xv_skinny.h"
 
 #include <algorithm>
 #include <stdlib.h>
@@ -28,7 +32,7 @@ constexpr int SK_COLS = 32;      // columns per workgroup
 constexpr int SK_ROWS = 128;     // rows per workgroup = the whole batch
 constexpr int SK_KS = 32;        // k per stage: one 128-byte line per operand row
 constexpr int SK_STAGE = (SK_ROWS + SK_COLS) * SK_KS;      // floats per LDS stage: A [128][32] then B [32][32] (20 KB), double-buffered
-#define SK_SWZ(row) (((row) >> 1) & 7)                    // 16-byte chunk c of row r sits at chunk c ^ SK_SWZ(r) (xv_gemm.hip, BK = 32)
+#define SK_SWZ(row) (((row) >> 1) & 7)                    // 16-byte chunk c of row r sits at chunk c ^ SK_SWZ(r) (xv_gemm_tile.h, BK = 32)
 
 struct SkArgs {
     XvSkinny g;
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void xv_skinny_kernel(SkArgs p) {
     const int k_end = min(g.K, k_begin + p.k_chunk);
     const int nk = (k_end - k_begin + SK_KS - 1) / SK_KS;
 
-    // ---- global -> VGPR -> LDS, three stages of loads in flight.  (LDS-DMA as in xv_gemm.hip does not pipeline here: hipcc drains
+    // ---- global -> VGPR -> LDS, three stages of loads in flight.  (LDS-DMA as in xv_gemm_nt.hip does not pipeline here: hipcc drains
     // vmcnt(0) in front of every ds_read that follows a global_load_lds, which the big GEMMs hide behind 4 co-resident workgroups and
     // this kernel, at 1-2 workgroups per CU, cannot.  With register staging the compiler waits for exactly the stage it writes.)
     // Thread (lrow = tid / 8, lpos = tid % 8) owns the 16-byte chunk lpos of rows lrow + 32 i of A (i < 4) and of row lrow of B: a
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(256) void xv_skinny_kernel(SkArgs p) {
     // accumulator r of lane (li, lh) is C[row(r)][n0 + li], row(r) = 32 wave + (r & 3) + 8 (r >> 2) + 4 lh
     const int row0 = wave * 32 + 4 * lh;
     if (p.splits > 1) {
-        // Slab hand-over without a device-wide fence (the xv_handoff_* contract of xv_common.h, gfx950 only).  __threadfence() here is "buffer_wbl2 sc1": every wave writes back its XCD's
+        // Slab hand-over without a device-wide fence (the xv_handoff_* contract of xv_handoff.h, gfx950 only).  __threadfence() here is "buffer_wbl2 sc1": every wave writes back its XCD's
         // whole L2 - measured 12 us per split on this kernel.  Instead the slab values are stored and loaded as relaxed agent-scope
         // atomics (sc1: written through to / read from the level all XCDs share), the stores are drained (vmcnt(0)) in front of the
         // workgroup barrier, and only then does thread 0 take the ticket.

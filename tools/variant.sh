@@ -2,14 +2,14 @@
 # Build alternative libxvector_hip.so builds HERE (hipcc cross-compiles gfx950 without a GPU) into build_variants/<name>/ (git-ignored, travels
 # with the gpurun snapshot); on the box they are selected with XV_LIB=$GRAFT_REPO_ROOT/build_variants/<name>/libxvector_hip.so
 # (tools/ab.sh, tools/probe.sh, any bench).  Same ABI version as the working tree required.
-#   tools/variant.sh unit xv_gemm.hip "base:" "diag:-DXV_DIAG=1" ...   one translation unit rebuilt with -D flags, the others from csrc/build
+#   tools/variant.sh unit xv_gemm_nt.hip "base:" "diag:-DXV_DIAG=1" ...   one translation unit rebuilt with -D flags, the others from csrc/build
 #   tools/variant.sh full prio0 -DXV_EW_PRIO=0                          every translation unit with the flags
 #   tools/variant.sh commit head [HEAD~3]                               the library of a commit (default HEAD)
 # (tools/gemm_probe is rebuilt when its source is newer.)
 mode=$1; shift
 R=$(cd $(dirname $0)/.. && pwd)
 src=$R/tf_kaldi_speaker_amd/csrc
-UNITS="xv_gemm xv_gemm16 xv_skinny xv_runtime xv_prep xv_bn xv_bn_bwd xv_pool xv_update xv_loss xv_attention xv_engine xv_engine_fwd xv_engine_bwd xv_engine_step"
+UNITS=$(make -s --no-print-directory -C $src print-units) || exit 1      # the Makefile's list: a variant holds every unit the library has
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$R/include -I$src -Wall -Wno-unused-function"
 throttle() { while [ $(jobs -r | wc -l) -ge 4 ]; do sleep 0.5; done; }      # at most 4 compilers at a time (8 CPUs, 64 GB)
 case $mode in
