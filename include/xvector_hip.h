@@ -38,7 +38,8 @@ extern "C" {
  * of a shorter struct.  xv_frontend came later and left it at 3: a new entry point beside the old ones, xv_config untouched - a host
  * built against the earlier header runs unchanged against this library.  The same holds for xv_mfcc_num_frames, xv_mfcc_table_floats,
  * xv_mfcc_tables, xv_mfcc and xv_energy_vad, which bring their own struct (xv_mfcc_config, size-checked like xv_config), and for
- * xv_debug_augment_plan, xv_augment_workspace_bytes and xv_augment with theirs (xv_augment_config). */
+ * xv_debug_augment_plan, xv_augment_workspace_bytes and xv_augment with theirs (xv_augment_config), and for xv_resample_num_samples,
+ * xv_resample_table_floats, xv_resample_tables, xv_debug_resample_plan and xv_resample with theirs (xv_resample_config). */
 #define XV_ABI_VERSION 3
 
 const char* xv_last_error(void);
@@ -318,6 +319,62 @@ size_t xv_augment_workspace_bytes(int b, int n_entries, int64_t n_tiles);
 int xv_augment(void* stream, const xv_augment_config* cfg, int b, int n_entries, int64_t n_tiles, const int16_t* src_pcm,
                const int16_t* rir_pcm, const int16_t* noise_pcm, const int64_t* tables, size_t table_words, int any_rir, void* ws,
                size_t ws_bytes, int16_t* out_pcm, float* out_f32, int32_t* out_samples, int32_t* clipped);
+
+/* Sample-rate conversion of waveforms: the `sox -r 8k` stages of the 8 kHz recipes (egs/sre/v1/local/make_musan.sh, run.sh:135-142),
+ * compute-mfcc-feats --allow-downsample / --allow-upsample, and speed perturbation (a factor F at rate fs is the resample F * fs -> fs,
+ * F * fs a whole number: 0.9 at 16 kHz is 14400 -> 16000).  A polyphase windowed-sinc FIR: Kaldi's LinearResample with the cutoff of
+ * ResampleWaveform (feat/resample.{h,cc}).  Kaldi is not available where this project is built and tested: parity is BY RESTATEMENT, as
+ * for xv_mfcc and xv_augment - the rules below are the specification ("as restated", not "as Kaldi" or "as sox"; DESIGN.md section 6f
+ * lists what is unpinned), tests/resample_ref.py restates them in fp64 and the kernel is held against that.
+ *
+ * Integer rates fin != fout (Hz), num_zeros (6), cutoff (0.99 * 0.5 * min(fin, fout)).  Every table value is computed in DOUBLE and
+ * rounded to fp32 once (Kaldi's FilterFunc works in float: a deliberate difference).
+ *   g = gcd(fin, fout), in_unit = fin / g, out_unit = fout / g, ww = num_zeros / (2.0 * cutoff).
+ *   Phase i < out_unit: t = i / (double)fout, first[i] = ceil((t - ww) * fin), last[i] = floor((t + ww) * fin), taps[i] = last - first + 1.
+ *   Weight of input index k = first[i] + j: d = k / (double)fin - t, w[i][j] = filter(d) * window(d) / fin with
+ *     window(d) = 0.5 * (1 + cos(2 pi * cutoff / num_zeros * d)) if |d| < ww, else 0;
+ *     filter(d) = sin(2 pi * cutoff * d) / (pi * d) if d != 0, else 2 * cutoff.
+ *   Rows are padded with zeros to taps_max = max_i taps[i].
+ *   n samples give n_out = ceil(n * out_unit / in_unit) (whole numbers; LinearResample's GetNumOutputSamples with flush = true); n <= 0: 0.
+ *   Output o: q = o / out_unit, i = o mod out_unit, f = first[i] + q * in_unit, y[o] = sum_j w[i][j] * x[f + j] over the j with
+ *   0 <= f + j < n, the int16 samples used as floats, unscaled.  The sum is ONE sequential chain of fmaf from zero in increasing j, at
+ *   most taps_max long: the bits of y depend on x and the table only - not on the tile, the batch or the launch.
+ *   PCM-16: rintf (to nearest, ties to even), then a clamp to [-32768, 32767]; clamped samples are counted per utterance.  (To nearest,
+ *   not xv_augment's truncation: this stands where the recipe has a sox stage that writes a wav.)
+ * Refused by name on the host, before any launch: fin == fout (callers skip the call), rates < 1, out_unit * taps_max > 16384 floats
+ * (the table lives in LDS beside the staged samples: 16000 -> 15999 has 15 999 phases), a table and staging area beyond 128 KiB. */
+typedef struct xv_resample_config {
+    int32_t struct_bytes;             /* = sizeof(xv_resample_config) of the header the host was built against; anything else is refused */
+    int32_t fin;                      /* Hz, >= 1 */
+    int32_t fout;                     /* Hz, >= 1, != fin */
+    int32_t num_zeros;                /* 0: the default, 6 */
+    float cutoff;                     /* Hz; 0: the default, 0.99 * 0.5 * min(fin, fout), formed in double */
+} xv_resample_config;
+/* n_out of an utterance of `samples` samples; -1 (xv_last_error) for a configuration that is refused.  Host arithmetic. */
+int64_t xv_resample_num_samples(const xv_resample_config* cfg, int64_t samples);
+/* The constant table of xv_resample - host arithmetic, no GPU call.  xv_resample_table_floats: its size (0 for a refused
+ * configuration); xv_resample_tables writes it into host_out (`floats` must be that size).  Layout, in floats:
+ *   first [out_unit]              first[i]  (whole numbers stored as floats, like xv_mfcc's mel_bins)
+ *   taps  [out_unit]              taps[i]
+ *   w     [out_unit][taps_max]    the weight rows, zeros behind taps[i] */
+size_t xv_resample_table_floats(const xv_resample_config* cfg);
+int xv_resample_tables(const xv_resample_config* cfg, float* host_out, size_t floats);
+/* Diagnostics: out[0] in_unit, out[1] out_unit, out[2] taps_max, out[3] consecutive outputs of one utterance per tile, out[4] input
+ * samples staged per tile (tile * in_unit / out_unit + taps_max, rounded up to whole periods), out[5] bytes of dynamic LDS of a
+ * workgroup (weight rows on an odd pitch, first[], the staged samples).  Host arithmetic, nothing is launched. */
+int xv_debug_resample_plan(const xv_resample_config* cfg, int out[6]);
+/* pcm: device int16, the samples of all utterances back to back; utterance i starts at sample offsets[i] (device int64 [b], any 2-byte
+ * alignment) and has samples[i] samples (device int32 [b]; <= 0: no output) - the layout xv_mfcc and xv_augment read.  tables_dev: what
+ * xv_resample_tables wrote for the same cfg, on the device.  out_pcm: int16, utterance i's n_out samples at out_offsets[i] (device int64
+ * [b]) - the packed layout xv_mfcc reads, with out_samples [b] = n_out as its `samples`; samples between the utterances are not written.
+ * out_f32 (NULL: not wanted): y before the rounding, at the same offsets.  clipped [b]: how many samples of the utterance the clamp
+ * changed.  Nothing is checked on the device: the caller guarantees that every range lies inside its buffer, that n_out < 2^31 and that
+ * the outputs do not overlap (ops.resample checks the host arrays before the upload).  b <= 65535.
+ * One launch: a workgroup copies the table into LDS once and walks tiles of one utterance; per tile the input span is staged as fp32
+ * with zeros outside [0, n). */
+int xv_resample(void* stream, const xv_resample_config* cfg, const float* tables_dev, const int16_t* pcm, const int64_t* offsets,
+                const int32_t* samples, int b, const int64_t* out_offsets, int16_t* out_pcm, float* out_f32, int32_t* out_samples,
+                int32_t* clipped);
 
 /* Cosine trial scoring with adaptive symmetric score normalisation (AS-norm) on embedding matrices: the stage behind extract.py, for
  * which the reference recipe goes to Kaldi (ivector-mean | ivector-subtract-global-mean | ivector-normalize-length, then

@@ -121,6 +121,20 @@ class XvAugmentConfig(_SizedConfig):
     DEFAULTS = dict(sample_frequency=16000.0, shift_output=1, normalize_output=1, volume=0.0)
 
 
+class XvResampleConfig(_SizedConfig):
+    """Mirror of `struct xv_resample_config` (include/xvector_hip.h): fin and fout must be given; zeros mean the defaults (6 zeros, the
+    cutoff 0.99 * 0.5 * min(fin, fout))."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("fin", C.c_int32),
+        ("fout", C.c_int32),
+        ("num_zeros", C.c_int32),
+        ("cutoff", C.c_float),
+    ]
+    DEFAULTS = dict(fin=0, fout=0, num_zeros=0, cutoff=0.0)
+
+
 LOSS_KINDS = {
     "softmax": 0,
     "asoftmax": 1,
@@ -219,6 +233,11 @@ SIGNATURES = {
     "xv_debug_augment_plan": (_I, [C.c_int64, C.c_int64, C.POINTER(_I)]),
     "xv_augment_workspace_bytes": (_SZ, [_I, _I, C.c_int64]),
     "xv_augment": (_I, [_VP, _VP, _I, _I, C.c_int64, _VP, _VP, _VP, _VP, _SZ, _I, _VP, _SZ, _VP, _VP, _VP, _VP]),
+    "xv_resample_num_samples": (C.c_int64, [_VP, C.c_int64]),
+    "xv_resample_table_floats": (_SZ, [_VP]),
+    "xv_resample_tables": (_I, [_VP, _VP, _SZ]),
+    "xv_debug_resample_plan": (_I, [_VP, C.POINTER(_I)]),
+    "xv_resample": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "xv_score_prepare": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I]),
     "xv_score_trials": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "xv_score_cohort_workspace_bytes": (_SZ, [_I, _I, _I]),

@@ -2,16 +2,20 @@
 `wav-reverberate` pipes in the augmented wav.scp entries of the reference recipe do (egs/voxceleb/v1/run.sh:68-130).
 
     options = AugmentOptions.from_conf("conf/augment.conf")      # Kaldi --name=value lines; what is not supported is refused by name
-    entries = read_plan("plan", 16000.0)                         # out_key src_key [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...
+    entries = read_plan("plan", 16000.0)                         # out_key src_key [speed=F] [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...
     aug = Augmenter(options, rirs, noises, 16000.0, "cuda:0")    # rirs / noises: {id: int16 array}
     pcm, offsets, lengths, clipped = aug.run(sources, entries)   # the packed int16 device tensor FeatureExtractor.extract_packed reads
 
 A plan line names one output utterance: its source, at most one impulse response and any number of noises in the order they are added - a
 foreground noise is added once at start_seconds, `:bg` marks a background noise, repeated over the whole utterance (what
-augment_data_dir.py reaches through wav-reverberate --duration).  The arithmetic is wav-reverberate's with --normalize-output=true AS
-RESTATED in the header; there is no resampling: every file must have the sample rate of the sources."""
+augment_data_dir.py reaches through wav-reverberate --duration).  `speed=F` (at most one a line) perturbs the source first: it is resampled
+F * fs -> fs (misc/resample.py; 0.9 makes it longer and lower) before the impulse response and the noises meet it.  The arithmetic is
+wav-reverberate's with --normalize-output=true AS RESTATED in the header.  Every file must have the sample rate of the sources, unless
+read_signals is told to pass the impulse responses and noises with their rates (--resample-signals true): the Augmenter then resamples those
+that differ when it builds its pools."""
 import numpy as np
 
+from . import resample
 from .features import DEFAULT_WORKSPACE_BYTES, _Options, _bool, _f, _i, _lib, device_ops, exclusive_offsets, greedy_batches
 
 PRESETS = {"reverb": None, "noise": (15.0, 10.0, 5.0, 0.0), "music": (15.0, 10.0, 8.0, 5.0), "babble": (20.0, 17.0, 15.0, 13.0)}
@@ -46,14 +50,18 @@ class AugmentOptions(_Options):
 
 
 class PlanEntry(object):
-    """One output utterance: noises = [(id, snr dB, start sample, background)]."""
-    __slots__ = ("out_key", "src_key", "rir", "noises")
+    """One output utterance: noises = [(id, snr dB, start sample, background)]; speed: None, or the factor as the decimal text of the plan
+    (`0.9`) - the source is resampled speed * fs -> fs BEFORE the impulse response and the noises, so n, the noise starts and
+    --shift-output refer to the perturbed length."""
+    __slots__ = ("out_key", "src_key", "rir", "noises", "speed")
 
-    def __init__(self, out_key, src_key, rir=None, noises=()):
+    def __init__(self, out_key, src_key, rir=None, noises=(), speed=None):
         self.out_key, self.src_key, self.rir, self.noises = out_key, src_key, rir, list(noises)
+        self.speed = None if speed is None else _speed_text(speed)
 
     def line(self, sample_frequency):
-        parts = [self.out_key, self.src_key] + (["rir=%s" % self.rir] if self.rir is not None else [])
+        parts = [self.out_key, self.src_key] + (["speed=%s" % self.speed] if self.speed is not None else [])
+        parts += ["rir=%s" % self.rir] if self.rir is not None else []
         for nid, snr, start, bg in self.noises:
             seconds = start / float(sample_frequency)
             if start_sample(seconds, sample_frequency) != start:      # the fp32 product fell just below the whole number: aim at its middle
@@ -61,6 +69,10 @@ class PlanEntry(object):
             assert start_sample(seconds, sample_frequency) == start
             parts.append("noise=%s:%r:%s%s" % (nid, float(snr), repr(seconds) if start else "0", ":bg" if bg else ""))
         return " ".join(parts)
+
+
+def _speed_text(speed):      # a factor as the plan writes it: 0.9 -> `0.9`, "1.10" -> `1.10`
+    return repr(speed) if isinstance(speed, float) else str(speed)
 
 
 def start_sample(seconds, sample_frequency):
@@ -109,8 +121,16 @@ def read_plan(path, sample_frequency=16000.0, rir_ids=None, noise_ids=None):
                     if noise_ids is not None and bits[0] not in noise_ids:
                         raise ValueError("%s: noise %s is not in the table of noises" % (where, bits[0]))
                     entry.noises.append((bits[0], snr, start_sample(seconds, sample_frequency), background))
+                elif name == "speed" and eq and value:
+                    if entry.speed is not None:
+                        raise ValueError("%s: a second speed `%s` (one per utterance)" % (where, field))
+                    try:
+                        resample.speed_rates(value, sample_frequency)
+                    except ValueError as e:
+                        raise ValueError("%s: `%s`: %s" % (where, field, e))
+                    entry.speed = value
                 else:
-                    raise ValueError("%s: unknown field `%s` (rir=ID and noise=ID:snr:start_seconds[:bg] are known)" % (where, field))
+                    raise ValueError("%s: unknown field `%s` (rir=ID, noise=ID:snr:start_seconds[:bg] and speed=F are known)" % (where, field))
             entries.append(entry)
     return entries
 
@@ -156,6 +176,23 @@ def make_plan(preset, utterances, rirs=(), noises=(), seed=0, fg_interval=1.0, s
     return entries
 
 
+def make_speed_plan(utterances, factors, sample_frequency=16000.0):
+    """The speed-perturbed copies of a list: for each factor F, in order, a line `sp<F>-<key> <key> speed=<F>` per utterance.  utterances:
+    keys, or (key, seconds) as make_plan takes them; factors: decimal texts or floats (0.9, 1.1).  F * sample_frequency must be a whole
+    number and F lie in 0.5 .. 2."""
+    entries = []
+    for factor in factors:
+        text = _speed_text(factor)
+        try:
+            resample.speed_rates(text, sample_frequency)
+        except ValueError as e:
+            raise ValueError("make_speed_plan: %s" % e)
+        for u in utterances:
+            key = u if isinstance(u, str) else u[0]
+            entries.append(PlanEntry("sp%s-%s" % (text, key), key, speed=text))
+    return entries
+
+
 def read_scp(path):
     """[(key, rxfilename)] of a Kaldi scp file."""
     out = []
@@ -170,19 +207,26 @@ def read_scp(path):
     return out
 
 
-def read_signals(scp_path, sample_frequency, channel, what):
-    """{id: int16 array} of a rir.scp / noise.scp style table: `id rxfilename` lines, RIFF PCM-16 at the sources' sample rate (there is no
-    resampling; a mismatch is refused as by read_wav), `channel` of each file."""
+def read_signals(scp_path, sample_frequency, channel, what, resample_signals=False):
+    """{id: int16 array} of a rir.scp / noise.scp style table: `id rxfilename` lines, RIFF PCM-16 at the sources' sample rate (without
+    resample_signals there is no resampling; a mismatch is refused as by read_wav), `channel` of each file.  resample_signals: every rate
+    passes and the table is {id: (int16 array, its rate in Hz)} - the Augmenter converts those that differ when it builds its pools."""
     from . import features
     opts = features.MfccOptions(sample_frequency=sample_frequency, channel=channel)
     out = {}
     for key, rx in read_scp(scp_path):
         if key in out:
             raise ValueError("%s: %s %s is listed twice" % (scp_path, what, key))
-        out[key] = features.read_wav(rx, opts, key)
-        if len(out[key]) == 0:
+        samples, rate = features.read_wav_rate(rx, opts, key, any_rate=bool(resample_signals))
+        out[key] = (samples, rate) if resample_signals else samples
+        if len(samples) == 0:
             raise ValueError("%s: %s %s holds no samples" % (scp_path, what, key))
     return out
+
+
+def signal_seconds(signals, sample_frequency):
+    """[(id, seconds)] of a read_signals table in either form (what make_plan takes)."""
+    return [(k, len(v[0]) / float(v[1])) if isinstance(v, tuple) else (k, len(v) / float(sample_frequency)) for k, v in signals.items()]
 
 
 def write_wav(path, samples, sample_frequency):
@@ -206,9 +250,44 @@ class Augmenter(object):
         self.cfg = self.options.config(self.sample_frequency)
         self.workspace_bytes = int(workspace_bytes)
         self.tile = self.ops.augment_plan(1)["tile"]
-        self.rir_index, self.rir_pool, self.rir_off, self.rir_len = self._pool(rirs or {}, "impulse response")
-        self.noise_index, self.noise_pool, self.noise_off, self.noise_len = self._pool(noises or {}, "noise")
+        self._resamplers = {}
+        rirs, noises = self._at_rate(rirs or {}), self._at_rate(noises or {})
+        self.rir_index, self.rir_pool, self.rir_off, self.rir_len = self._pool(rirs, "impulse response")
+        self.noise_index, self.noise_pool, self.noise_off, self.noise_len = self._pool(noises, "noise")
         self.rir_early = [self.ops.augment_early(rirs[k], self.sample_frequency) for k in self.rir_index] if rirs else []
+
+    def resampler(self, fin):
+        """The Resampler fin -> sample_frequency of this Augmenter, kept: its table goes to the device once."""
+        if fin not in self._resamplers:
+            self._resamplers[fin] = resample.Resampler(fin, self.sample_frequency, self.device, self.workspace_bytes)
+        return self._resamplers[fin]
+
+    def _at_rate(self, signals):
+        """A read_signals table in either form as {id: int16 array at sample_frequency}: the (array, rate) entries whose rate differs are
+        resampled on the device, once, grouped by rate (xv_resample; rounded to int16, as the wav of a `sox -r` stage is)."""
+        out = {k: (v[0] if isinstance(v, tuple) else v) for k, v in signals.items()}
+        groups = {}
+        for k, v in signals.items():
+            if isinstance(v, tuple) and int(v[1]) != self.sample_frequency:
+                groups.setdefault(int(v[1]), []).append(k)
+        for rate, keys in groups.items():
+            converted, _ = self.resampler(rate).resample([signals[k][0] for k in keys])
+            out.update(zip(keys, converted))
+        return out
+
+    def perturbed(self, sources, entries):
+        """The sources of the entries with speed=F resampled F * fs -> fs on the device, grouped by factor, and brought back as int16 (the
+        intermediate a piped wav would be); the others as they are."""
+        sources = list(sources)
+        groups = {}
+        for i, e in enumerate(entries):
+            if e.speed is not None:
+                groups.setdefault(resample.speed_rates(e.speed, self.sample_frequency)[0], []).append(i)
+        for fin, members in groups.items():
+            converted, _ = self.resampler(fin).resample([sources[i] for i in members])
+            for i, w in zip(members, converted):
+                sources[i] = w
+        return sources
 
     def _pool(self, signals, what):
         keys = list(signals)
@@ -223,7 +302,17 @@ class Augmenter(object):
 
     def lengths(self, sources, entries):
         """(M, n_out) per entry: the samples of y and of the output (step 6)."""
-        n = np.asarray([len(s) for s in sources], np.int64)
+        return self._lengths([self.source_samples(len(s), e) for s, e in zip(sources, entries)], entries)
+
+    def source_samples(self, n, entry):
+        """The samples of a source of n samples as the entry's impulse response and noises meet it: ceil(n / speed) under speed=F."""
+        if entry.speed is None:
+            return n
+        fin, fout = resample.speed_rates(entry.speed, self.sample_frequency)
+        return 0 if n <= 0 else -(-n * fout // fin)      # ceil(n * out_unit / in_unit): the common divisor cancels
+
+    def _lengths(self, n, entries):
+        n = np.asarray(n, np.int64)
         taps = np.asarray([self.rir_len[self.rir_index[e.rir]] if e.rir is not None else 0 for e in entries], np.int64)
         m = np.where(taps > 0, n + taps - 1, n)
         return m, (n if self.options.shift_output else m)
@@ -253,8 +342,10 @@ class Augmenter(object):
             for nid, _, _, _ in e.noises:
                 if nid not in self.noise_index:
                     raise KeyError("Augmenter: Key %s: noise %s is not in the table of noises" % (e.out_key, nid))
+        if any(e.speed is not None for e in entries):
+            sources = self.perturbed(sources, entries)
         n = np.asarray([len(s) for s in sources], np.int64)
-        m, n_out = self.lengths(sources, entries)
+        m, n_out = self._lengths(n, entries)
         offsets = exclusive_offsets(n_out)
         pcm = torch.empty(int(n_out.sum()), dtype=torch.int16, device=self.device)
         clipped = np.zeros(len(entries), np.int64)

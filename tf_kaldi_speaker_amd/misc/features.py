@@ -96,25 +96,28 @@ def _s(name, text):
 
 
 class MfccOptions(_Options):
-    """The options of compute-mfcc-feats this program takes; fields are those of xv_mfcc_config plus `channel` (-1: the file must be mono)."""
+    """The options of compute-mfcc-feats this program takes; fields are those of xv_mfcc_config plus `channel` (-1: the file must be mono) and
+    allow_downsample / allow_upsample (0: a file at another rate is refused; 1: it is resampled on the device, misc/resample.py)."""
     PROGRAM = "compute-mfcc-feats"
-    DEFAULTS = dict(_lib.XvMfccConfig.DEFAULTS, channel=-1)
+    HOST_ONLY = ("channel", "allow_downsample", "allow_upsample")      # what is not a field of xv_mfcc_config
+    DEFAULTS = dict(_lib.XvMfccConfig.DEFAULTS, channel=-1, allow_downsample=0, allow_upsample=0)
     SUPPORTED = {"sample-frequency": ("sample_frequency", _f), "frame-length": ("frame_length_ms", _f), "frame-shift": ("frame_shift_ms", _f),
                  "num-mel-bins": ("num_mel_bins", _i), "num-ceps": ("num_ceps", _i), "low-freq": ("low_freq", _f), "high-freq": ("high_freq", _f),
                  "snip-edges": ("snip_edges", _bool), "preemphasis-coefficient": ("preemphasis", _f), "remove-dc-offset": ("remove_dc_offset", _bool),
                  "cepstral-lifter": ("cepstral_lifter", _f), "use-energy": ("use_energy", _bool), "raw-energy": ("raw_energy", _bool),
-                 "energy-floor": ("energy_floor", _f), "channel": ("channel", _i)}
+                 "energy-floor": ("energy_floor", _f), "channel": ("channel", _i), "allow-downsample": ("allow_downsample", _bool),
+                 "allow-upsample": ("allow_upsample", _bool)}
     FIXED = {"dither": (0.0, _f), "window-type": ("povey", _s), "htk-compat": (0, _bool), "round-to-power-of-two": (1, _bool),
              "vtln-warp": (1.0, _f), "vtln-map": ("", _s), "utt2spk": ("", _s), "vtln-low": (100.0, _f), "vtln-high": (-500.0, _f),
-             "subtract-mean": (0, _bool), "blackman-coeff": (0.42, _f), "allow-downsample": (0, _bool), "allow-upsample": (0, _bool),
+             "subtract-mean": (0, _bool), "blackman-coeff": (0.42, _f),
              "debug-mel": (0, _bool), "min-duration": (0.0, _f), "output-format": ("kaldi", _s), "max-feature-vectors": (-1, _i)}
     WHY = {"dither": "dither is random and not reproducible; on digital silence use --energy-floor", "window-type": "the window is Povey's",
-           "allow-downsample": "no resampling", "allow-upsample": "no resampling", "vtln-warp": "no VTLN", "vtln-map": "no VTLN", "utt2spk": "no VTLN",
+           "vtln-warp": "no VTLN", "vtln-map": "no VTLN", "utt2spk": "no VTLN",
            "vtln-low": "no VTLN", "vtln-high": "no VTLN", "subtract-mean": "extract.py --cmn-window normalises"}
 
     def config(self):
         """The xv_mfcc_config of these options."""
-        return _lib.XvMfccConfig(**{k: getattr(self, k) for k in self.DEFAULTS if k != "channel"})
+        return _lib.XvMfccConfig(**{k: getattr(self, k) for k in self.DEFAULTS if k not in self.HOST_ONLY})
 
 
 class VadOptions(_Options):
@@ -130,6 +133,13 @@ def read_wav(rxfilename, options=None, key=""):
     """The samples of a RIFF PCM-16 file as an int16 array: a path or a `cmd |` entry of a wav.scp (dataset.kaldi_io.open_or_fd), read with the
     stdlib wave module.  options (MfccOptions): the sample rate must be options.sample_frequency, and options.channel picks the channel
     (-1: the file must be mono).  Anything else is refused, naming `key`."""
+    return read_wav_rate(rxfilename, options, key, any_rate=False)[0]
+
+
+def read_wav_rate(rxfilename, options=None, key="", any_rate=None):
+    """(samples, sample rate in Hz) of a file as read_wav reads it.  any_rate None: a file at another rate than options.sample_frequency
+    passes if options allows the conversion - a higher rate needs allow_downsample, a lower one allow_upsample (compute-mfcc-feats'
+    rule); True: every rate passes (the caller resamples); False: read_wav's refusal.  The samples come back at the FILE's rate."""
     try:
         from ..dataset import kaldi_io
     except (ImportError, ValueError):
@@ -148,17 +158,24 @@ def read_wav(rxfilename, options=None, key=""):
     with w:
         if w.getsampwidth() != 2:
             raise ValueError("%s: %d-bit samples; only PCM-16 is read" % (who, 8 * w.getsampwidth()))
-        if w.getframerate() != int(options.sample_frequency) or int(options.sample_frequency) != options.sample_frequency:
-            raise ValueError("%s: sample rate %d Hz, but --sample-frequency=%g (there is no resampling)" % (who, w.getframerate(), options.sample_frequency))
+        rate = w.getframerate()
+        if rate != int(options.sample_frequency) or int(options.sample_frequency) != options.sample_frequency:
+            allowed = any_rate
+            if any_rate is None:
+                allowed = bool(options.allow_downsample if rate > options.sample_frequency else options.allow_upsample)
+            if not allowed or rate < 1 or int(options.sample_frequency) != options.sample_frequency:
+                raise ValueError("%s: sample rate %d Hz, but --sample-frequency=%g (there is no resampling%s)"
+                                 % (who, rate, options.sample_frequency, "" if any_rate is False else
+                                    " without --allow-downsample=true" if rate > options.sample_frequency else " without --allow-upsample=true"))
         channels = w.getnchannels()
         x = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, channels)
     if options.channel < 0:
         if channels != 1:
             raise ValueError("%s: %d channels; choose one with --channel" % (who, channels))
-        return np.ascontiguousarray(x[:, 0])
+        return np.ascontiguousarray(x[:, 0]), rate
     if options.channel >= channels:
         raise ValueError("%s: --channel=%d, but the file has %d channel(s)" % (who, options.channel, channels))
-    return np.ascontiguousarray(x[:, options.channel])
+    return np.ascontiguousarray(x[:, options.channel]), rate
 
 
 class FeatureExtractor(object):
@@ -205,6 +222,40 @@ class FeatureExtractor(object):
                 continue
             pcm = self.torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
             for i, r in zip(batch, self.extract_packed(pcm, exclusive_offsets(n), n, cm_header)):      # one call: the batch fits
+                out[i] = r
+        return out
+
+    def resampler(self, rate):
+        """The Resampler rate -> sample_frequency of this extractor, kept: its table goes to the device once."""
+        try:
+            from .resample import Resampler
+        except (ImportError, ValueError):
+            from misc.resample import Resampler
+        if not hasattr(self, "_resamplers"):
+            self._resamplers = {}
+        if rate not in self._resamplers:
+            self._resamplers[rate] = Resampler(rate, self.mfcc.sample_frequency, self.device, self.workspace_bytes)
+        return self._resamplers[rate]
+
+    def extract_at_rates(self, waves, rates, cm_header=None):
+        """extract() for waveforms at their own sample rates (Hz, whole numbers): those at sample_frequency go through as they are, the
+        others are resampled on the device, grouped by rate, and reach xv_mfcc as int16 without leaving it (compute-mfcc-feats keeps
+        floats there: unpinned).  A higher rate needs mfcc.allow_downsample, a lower one mfcc.allow_upsample."""
+        fs = self.mfcc.sample_frequency
+        groups = {}
+        for i, rate in enumerate(rates):
+            groups.setdefault(int(rate), []).append(i)
+        out = [None] * len(waves)
+        for rate, members in groups.items():
+            if rate == fs:
+                results = self.extract([waves[i] for i in members], cm_header)
+            else:
+                if not (self.mfcc.allow_downsample if rate > fs else self.mfcc.allow_upsample):
+                    raise ValueError("sample rate %d Hz, but --sample-frequency=%g (there is no resampling without --allow-%s=true)"
+                                     % (rate, fs, "downsample" if rate > fs else "upsample"))
+                pcm, offsets, lengths, _ = self.resampler(rate).run([waves[i] for i in members])
+                results = self.extract_packed(pcm, offsets, lengths, cm_header)
+            for i, r in zip(members, results):
                 out[i] = r
         return out
 

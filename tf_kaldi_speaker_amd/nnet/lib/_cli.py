@@ -70,6 +70,15 @@ ARGUMENTS = {
     "sample_frequency": (("--sample-frequency",), dict(type=float, default=16000.0, help="The sample rate of every file; there is no resampling.")),
     "make_plan": (("--make-plan",), dict(type=str, default="", choices=("", "reverb", "noise", "music", "babble"),
                                          help="Write one of the recipe's four lists to the `plan` file instead of augmenting.")),
+    "resample_signals": (("--resample-signals",), dict(type=str, default="false", choices=("true", "false"),
+                                                       help="true: impulse responses and noises at another sample rate than the sources are "
+                                                            "resampled on the device when the pools are built (misc/resample.py); false: refused.")),
+    "make_speed_plan": (("--make-speed-plan",), dict(type=str, default="", help="F[,F...] (0.9,1.1): write the speed-perturbed copies of wav.scp, "
+                                                                                "`sp<F>-<key> <key> speed=<F>` per line, to the `plan` file.")),
+    "to_rate": (("--to-rate",), dict(type=int, default=0, help="Resample every file to this sample rate in Hz.")),
+    "speed": (("--speed",), dict(type=str, default="", help="Speed factor F (0.9, 1.1): every file is resampled F * rate -> rate, its rate kept.")),
+    "channel": (("--channel",), dict(type=int, default=-1, help="The channel to read (-1: every file must be mono).")),
+    "resample_out_dir": (("out_dir",), dict(type=str, help="Receives wav/<key>.wav and wav.scp.")),
     "seed": (("--seed",), dict(type=int, default=0, help="The seed of --make-plan (numpy.random.RandomState).")),
     "fg_interval": (("--fg-interval",), dict(type=float, default=1.0, help="--make-plan noise: seconds between two foreground noises.")),
     # positionals

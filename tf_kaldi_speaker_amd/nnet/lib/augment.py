@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """Reverberated and noisy copies of a wav.scp on the GPU:
 
-    python nnet/lib/augment.py [-g GPU] [--config conf/augment.conf] [--sample-frequency 16000] --rir-scp rir.scp --noise-scp noise.scp
-                               plan wav.scp out_dir
+    python nnet/lib/augment.py [-g GPU] [--config conf/augment.conf] [--sample-frequency 16000] [--resample-signals true]
+                               --rir-scp rir.scp --noise-scp noise.scp plan wav.scp out_dir
     python nnet/lib/augment.py --make-plan {reverb,noise,music,babble} [--seed N] [--fg-interval S] --rir-scp rir.scp --noise-scp noise.scp
                                plan wav.scp
+    python nnet/lib/augment.py --make-speed-plan 0.9,1.1 plan wav.scp
 
 The augmentation stage of the recipe, for which the reference goes to Kaldi (egs/voxceleb/v1/run.sh:68-130: the reverberated, noise, music
 and babble copies of the training list are `wav-reverberate` pipes inside wav.scp entries).  plan: one line per output utterance,
-`out_key src_key [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...` (misc/augment.py).  wav.scp: the sources, `key rxfilename` lines, the
+`out_key src_key [speed=F] [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...` (misc/augment.py; speed=F resamples the source F * fs -> fs
+before anything else meets it).  wav.scp: the sources, `key rxfilename` lines, the
 rxfilename a RIFF PCM-16 file or a `command |` that writes one; rir.scp / noise.scp: the same for the impulse responses and noises the plan
-names.  Every file must have --sample-frequency: there is no resampling.  Writes out_dir/wav/<out_key>.wav (mono RIFF PCM-16) and
+names.  Every file must have --sample-frequency: without --resample-signals true there is no resampling; with it the impulse responses
+and noises at another rate are resampled on the device when the pools are built (the `sox -r 8k` stages of egs/sre/v1/local/make_musan.sh;
+the sources still must have --sample-frequency).  Writes out_dir/wav/<out_key>.wav (mono RIFF PCM-16) and
 out_dir/wav.scp, and logs per key its samples, impulse response, number of noises and clipped samples.  The arithmetic is
 wav-reverberate's with --normalize-output=true as include/xvector_hip.h restates it; --duration, --multi-channel-output and
 --input-wave-channel are refused by name (misc/augment.py says why).
 --make-plan writes one of the recipe's four lists to `plan` instead; the durations it needs are read from the files.  Its random choices
 are this project's own (numpy.random.RandomState(--seed)), not those of Kaldi's reverberate_data_dir.py / augment_data_dir.py.
+--make-speed-plan F[,F...] writes the speed-perturbed copies, `sp<F>-<key> <key> speed=<F>` per line and factor; no file is read.
 """
 import os
 import sys
@@ -31,22 +36,28 @@ WINDOW_SAMPLES = 64 << 20
 
 def main():
     log = _cli.logger()
-    args = _cli.parser_for("gpu", "aug_config", "sample_frequency", "rir_scp", "noise_scp", "make_plan", "seed", "fg_interval", "plan", "wav_scp",
-                           "augment_out_dir").parse_args()
+    args = _cli.parser_for("gpu", "aug_config", "sample_frequency", "rir_scp", "noise_scp", "resample_signals", "make_plan", "make_speed_plan", "seed",
+                           "fg_interval", "plan", "wav_scp", "augment_out_dir").parse_args()
     fs = args.sample_frequency
+    any_rate = args.resample_signals == "true"
     try:
         options = augment.AugmentOptions.from_conf(args.config) if args.config else augment.AugmentOptions()
-        rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response") if args.rir_scp else {}
-        noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise") if args.noise_scp else {}
         wavs = augment.read_scp(args.wav_scp)
+        if args.make_speed_plan:
+            entries = augment.make_speed_plan([key for key, _ in wavs], [f for f in args.make_speed_plan.split(",") if f], fs)
+            augment.write_plan(entries, args.plan, fs)
+            log.info("[INFO] Wrote the speed plan of %d utterances to %s." % (len(entries), args.plan))
+            return
+        rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response", any_rate) if args.rir_scp else {}
+        noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise", any_rate) if args.noise_scp else {}
     except ValueError as e:
         sys.exit(str(e))
     mono = features.MfccOptions(sample_frequency=fs)
     if args.make_plan:
         try:
             utterances = [(key, len(features.read_wav(rx, mono, key)) / fs) for key, rx in wavs]
-            entries = augment.make_plan(args.make_plan, utterances, [(k, len(v) / fs) for k, v in rirs.items()],
-                                        [(k, len(v) / fs) for k, v in noises.items()], args.seed, args.fg_interval, fs)
+            entries = augment.make_plan(args.make_plan, utterances, augment.signal_seconds(rirs, fs), augment.signal_seconds(noises, fs),
+                                        args.seed, args.fg_interval, fs)
         except ValueError as e:
             sys.exit(str(e))
         augment.write_plan(entries, args.plan, fs)
@@ -78,8 +89,8 @@ def main():
                 path = os.path.join(wav_dir, e.out_key + ".wav")
                 augment.write_wav(path, out, fs)
                 scp.write("%s %s\n" % (e.out_key, path))
-                log.info("[INFO] Key %s: %d samples, rir %s, %d noises, %d clipped." % (e.out_key, len(out), e.rir if e.rir is not None else "-",
-                                                                                       len(e.noises), int(c)))
+                log.info("[INFO] Key %s: %d samples, %srir %s, %d noises, %d clipped." % (e.out_key, len(out), "speed %s, " % e.speed if e.speed else "",
+                                                                                         e.rir if e.rir is not None else "-", len(e.noises), int(c)))
                 stats["utts"] += 1
                 stats["samples"] += len(out)
                 stats["clipped"] += int(c)

@@ -2,7 +2,8 @@
 """MFCC features and energy VAD decisions from a wav.scp on the GPU:
 
     python nnet/lib/make_mfcc.py [-g GPU] [--mfcc-config conf/mfcc.conf] [--vad-config conf/vad.conf] [--compress {true,false}]
-                                 [--write-utt2num-frames FILE] [--augment-plan PLAN --rir-scp F --noise-scp F [--augment-config conf]]
+                                 [--write-utt2num-frames FILE]
+                                 [--augment-plan PLAN --rir-scp F --noise-scp F [--augment-config conf] [--resample-signals true]]
                                  wav.scp ark,scp:feats.ark,feats.scp ark,scp:vad.ark,vad.scp
 
 The first stage of the recipe, for which the reference goes to Kaldi (egs/voxceleb/v1/run.sh:59-63: steps/make_mfcc.sh --mfcc-config
@@ -19,6 +20,10 @@ option of the two Kaldi programs that is not implemented, by name.  An utterance
 written are the plan's output keys (misc/augment.py: `out_key src_key [rir=ID] [noise=ID:snr:start_seconds[:bg]] ...`), the sources come
 from wav.scp, and the reverberated / noisy PCM goes from the augmentation kernels to the MFCC kernels on the device: the same bytes as
 nnet/lib/augment.py followed by this program on its wav.scp.  Without the option nothing changes.
+--allow-downsample=true / --allow-upsample=true in the MFCC conf (compute-mfcc-feats' options): files at a higher / lower rate than
+--sample-frequency are read at their own rate and resampled on the device in front of the MFCC kernels, grouped by rate (misc/resample.py:
+the same bytes as nnet/lib/resample.py --to-rate followed by this program on its wav.scp; the samples are rounded to int16 in between, where
+compute-mfcc-feats keeps floats).  Without them a file at another rate is refused, as before.
 """
 import sys
 import time
@@ -37,7 +42,7 @@ WINDOW_SAMPLES = 64 << 20
 def main():
     log = _cli.logger()
     args = _cli.parser_for("gpu", "mfcc_config", "vad_config", "compress", "write_utt2num_frames", "augment_plan", "rir_scp", "noise_scp",
-                           "augment_config", "wav_scp", "feats_wspecifier", "vad_wspecifier").parse_args()
+                           "augment_config", "resample_signals", "wav_scp", "feats_wspecifier", "vad_wspecifier").parse_args()
     try:
         mfcc = features.MfccOptions.from_conf(args.mfcc_config) if args.mfcc_config else features.MfccOptions()
         vad = features.VadOptions.from_conf(args.vad_config) if args.vad_config else features.VadOptions()
@@ -55,7 +60,7 @@ def main():
     cm_header = "uniform" if args.compress == "true" else None
     write_mat = features.write_cm_image if cm_header else kaldi_io.write_mat
     stats = {"utts": 0, "frames": 0, "voiced": 0, "skipped": 0, "t0": time.time()}
-    window, window_samples = [], 0
+    window, rates, window_samples = [], [], 0
 
     def write(key, samples, feats, decisions):
         frames = len(decisions)
@@ -73,10 +78,16 @@ def main():
         stats["voiced"] += int(decisions.sum())
 
     def flush():
-        results = fx.extract([w for _, w in window], cm_header)
-        for (key, w), (feats, decisions) in zip(window, results):
+        if all(rate == mfcc.sample_frequency for rate in rates):
+            results = fx.extract([w for _, w in window], cm_header)
+        else:
+            results = fx.extract_at_rates([w for _, w in window], rates, cm_header)
+        for (key, w), rate, (feats, decisions) in zip(window, rates, results):
+            if rate != mfcc.sample_frequency:
+                log.info("[INFO] Key %s: resampled from %d Hz." % (key, rate))
             write(key, len(w), feats, decisions)
         del window[:]
+        del rates[:]
 
     def flush_augmented(aug):
         pcm, offsets, lengths, clipped = aug.run([w for _, w in window], [e for e, _ in window])
@@ -87,14 +98,15 @@ def main():
             write(e.out_key, int(n), feats, decisions)
         del window[:]
 
-    if not args.augment_plan and (args.rir_scp or args.noise_scp or args.augment_config):
-        sys.exit("--rir-scp, --noise-scp and --augment-config belong to --augment-plan")
+    any_rate = args.resample_signals == "true"
+    if not args.augment_plan and (args.rir_scp or args.noise_scp or args.augment_config or any_rate):
+        sys.exit("--rir-scp, --noise-scp, --augment-config and --resample-signals belong to --augment-plan")
     if args.augment_plan:
         try:
             options = augment.AugmentOptions.from_conf(args.augment_config) if args.augment_config else augment.AugmentOptions()
             fs = mfcc.sample_frequency
-            rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response") if args.rir_scp else {}
-            noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise") if args.noise_scp else {}
+            rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response", any_rate) if args.rir_scp else {}
+            noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise", any_rate) if args.noise_scp else {}
             entries = augment.read_plan(args.augment_plan, fs, rirs, noises)
             rx_of = dict(augment.read_scp(args.wav_scp))
         except ValueError as e:
@@ -127,10 +139,11 @@ def main():
                 if len(parts) != 2:
                     sys.exit("%s: `key rxfilename` is expected, got `%s`" % (args.wav_scp, line.strip()))
                 try:
-                    wav = features.read_wav(parts[1], mfcc, parts[0])
+                    wav, rate = features.read_wav_rate(parts[1], mfcc, parts[0])
                 except ValueError as e:
                     sys.exit(str(e))
                 window.append((parts[0], wav))
+                rates.append(rate)
                 window_samples += len(wav)
                 if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
                     flush()

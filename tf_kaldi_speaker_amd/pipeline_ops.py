@@ -273,6 +273,85 @@ def augment(cfg, src, src_off, src_len, rir=None, rir_off=None, rir_len=None, ri
     return out_pcm, out_offsets, out_samples, clipped, out_f32
 
 
+def resample_config(fin, fout, num_zeros=0, cutoff=0.0):
+    """xv_resample_config of the conversion fin -> fout Hz (whole numbers); zeros: the defaults (6 zeros, 0.99 * 0.5 * min(fin, fout))."""
+    if int(fin) != fin or int(fout) != fout:
+        raise ValueError("resample: the rates must be whole numbers of Hz (got %r -> %r)" % (fin, fout))
+    return _lib.XvResampleConfig(fin=int(fin), fout=int(fout), num_zeros=int(num_zeros), cutoff=float(cutoff))
+
+
+def resample_plan(cfg):
+    """xv_debug_resample_plan: {in_unit, out_unit, taps_max, tile, span, lds_bytes} of cfg (host arithmetic)."""
+    out = (C.c_int * 6)()
+    _lib.check(_lib.load().xv_debug_resample_plan(C.byref(cfg), out), "xv_debug_resample_plan")
+    return dict(in_unit=out[0], out_unit=out[1], taps_max=out[2], tile=out[3], span=out[4], lds_bytes=out[5])
+
+
+def resample_num_samples(cfg, samples):
+    n = int(_lib.load().xv_resample_num_samples(C.byref(cfg), C.c_int64(int(samples))))
+    if n < 0:
+        _lib.check(2, "xv_resample_num_samples")
+    return n
+
+
+def resample_tables(cfg):
+    """The constant table of xv_resample for cfg as a host float32 array (xv_resample_tables: host arithmetic, no GPU call)."""
+    lib = _lib.load()
+    n = int(lib.xv_resample_table_floats(C.byref(cfg)))
+    if n == 0:
+        _lib.check(2, "xv_resample_table_floats")
+    flat = np.empty(n, np.float32)
+    _lib.check(lib.xv_resample_tables(C.byref(cfg), C.c_void_p(flat.ctypes.data), C.c_size_t(n)), "xv_resample_tables")
+    return flat
+
+
+def resample(cfg, tables, pcm, offsets, samples, out_offsets=None, out_pcm=None, out_f32=False):
+    """Sample-rate conversion of a batch of waveforms (xv_resample).  tables: resample_tables(cfg) on the device; pcm: int16 device tensor,
+    the utterances back to back; offsets / samples: HOST integer arrays [b] - utterance i is pcm[offsets[i] : offsets[i] + samples[i]] (the
+    kernel checks nothing, so they are checked here, before the upload).  out_offsets (default: back to back) / out_pcm (default: a new
+    tensor that just holds them): where the outputs go; out_f32: True for a new float32 tensor of out_pcm's size, or such a tensor.
+    -> (out_pcm int16, out_offsets int64 host array, out_samples int32 [b], clipped int32 [b], out_f32 | None)."""
+    n_pcm = _pcm(pcm, "resample: pcm")
+    pair = "resample: offsets and samples must be two non-empty 1-D integer arrays of one length"
+    offsets = host_ints(offsets, min_size=1, msg=pair, dtype=np.int64)
+    samples = host_ints(samples, n=offsets.size, msg=pair, dtype=np.int64)
+    b = offsets.size
+    if b > 65535:
+        raise ValueError("resample: at most 65535 utterances a call (got %d)" % b)
+    if offsets.min() < 0 or samples.min() < 0 or (offsets + samples).max() > n_pcm:
+        raise IndexError("resample: an utterance lies outside the %d samples of pcm" % n_pcm)
+    if samples.max() >= 2 ** 31:
+        raise ValueError("resample: an utterance holds 2^31 samples or more")
+    floats = int(_lib.load().xv_resample_table_floats(C.byref(cfg)))
+    if floats == 0:
+        _lib.check(2, "xv_resample_table_floats")
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != floats:
+        raise ValueError("resample: tables must be resample_tables(cfg) as a contiguous float32 device tensor of %d values" % floats)
+    plan = resample_plan(cfg)
+    n_out = (samples * plan["out_unit"] + plan["in_unit"] - 1) // plan["in_unit"]
+    if n_out.max() >= 2 ** 31:
+        raise ValueError("resample: an utterance would hold 2^31 samples or more")
+    out_offsets = host_ints(exclusive_offsets(n_out) if out_offsets is None else out_offsets, "resample: out_offsets", n=b, dtype=np.int64)
+    if out_pcm is None:
+        out_pcm = torch.empty(max(int((out_offsets + n_out).max()), 1), dtype=torch.int16, device=pcm.device)
+    total = _pcm(out_pcm, "resample: out_pcm")
+    order = np.argsort(out_offsets, kind="stable")
+    if out_offsets.min() < 0 or (out_offsets + n_out).max() > total or (out_offsets[order][1:] < (out_offsets + n_out)[order][:-1]).any():
+        raise IndexError("resample: the outputs overlap or lie outside the %d samples of out_pcm" % total)
+    if out_f32 is True:
+        out_f32 = torch.empty(total, dtype=torch.float32, device=pcm.device)
+    elif out_f32 is False:
+        out_f32 = None
+    elif out_f32.dtype != torch.float32 or out_f32.dim() != 1 or not out_f32.is_contiguous() or out_f32.numel() < total:
+        raise ValueError("resample: out_f32 must be a contiguous 1-D float32 tensor of out_pcm's size")
+    off_d, n_d, oo_d = upload(offsets, np.int64, pcm.device), upload(samples, np.int32, pcm.device), upload(out_offsets, np.int64, pcm.device)
+    out_samples = torch.empty(b, dtype=torch.int32, device=pcm.device)
+    clipped = torch.empty(b, dtype=torch.int32, device=pcm.device)
+    _lib.call("xv_resample", _s(), C.byref(cfg), _p(tables), _p(pcm), _p(off_d), _p(n_d), b, _p(oo_d), _p(out_pcm), _p(out_f32), _p(out_samples),
+              _p(clipped))
+    return out_pcm, out_offsets, out_samples, clipped, out_f32
+
+
 def _centered(name, entry, x, d, mean, out):      # score_prepare and backend_center: one row-wise kernel each, on the same arguments
     rows, ldx = pitched(x, "%s: x" % name)
     d = x.shape[1] if d is None else int(d)

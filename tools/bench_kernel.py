@@ -18,6 +18,8 @@ sub-command per question (they used to be eight scripts):
                                                                 against the bytes it must move and against the host writer
   python tools/bench_kernel.py augment [utterances=256] [notrace] reverberation + one background noise (xv_augment.hip) on the same synthetic PCM under impulse
                                                                 responses of 4 000 / 8 000 / 16 000 taps: us per kernel role, G taps x samples / s
+  python tools/bench_kernel.py resample [utterances=256]        sample-rate conversion (xv_resample.hip) of synthetic utterances of 4 - 20 s: 16000 -> 8000,
+                                                                44100 -> 16000 and speed 0.9; the bare entry point and ops.resample, G fma / s, GB / s
 
 Environment: XV_DATA_SCALE=0 (all-zero operands: DVFS check), XV_B (chunks, gemm16), ITERS (segment), XV_LIB (another build of the library).
 """
@@ -478,7 +480,46 @@ def cmd_augment(argv):
             print("    (no kernel records from the profiler: no split over the roles)", flush=True)
 
 
-COMMANDS = {"augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+def cmd_resample(argv):
+    """xv_resample on one ragged batch per conversion.  Device events around the bare entry point (tables and index arrays on the device
+    already: the kernel and its memset alone) and around ops.resample (the host checks and the three index uploads included).  The rate is
+    priced in fmas (outputs x taps_max, the padding columns included: the kernel runs them) and in the bytes that cross HBM (2 in, 2 out
+    per sample)."""
+    import ctypes as C
+    from tf_kaldi_speaker_amd import _lib, ops
+    from tf_kaldi_speaker_amd._host import _p, _s, exclusive_offsets, upload
+    from tf_kaldi_speaker_amd.misc.resample import speed_rates
+    n_utts = int(argv[0]) if argv else 256
+    seconds = rs.uniform(4.0, 20.0, n_utts)
+    for label, (fin, fout) in (("16000 -> 8000", (16000, 8000)), ("44100 -> 16000", (44100, 16000)), ("speed 0.9 at 16 kHz", speed_rates("0.9", 16000))):
+        cfg = ops.resample_config(fin, fout)
+        plan = ops.resample_plan(cfg)
+        lens = (seconds * fin).astype(np.int64)
+        t = np.arange(int(lens.max())) / float(fin)
+        tone = 3000.0 * np.sin(2.0 * np.pi * 220.0 * t) + 1500.0 * np.sin(2.0 * np.pi * 1830.0 * t)
+        pcm = np.concatenate([np.rint(tone[:n] + rs.randn(n) * 40.0).astype(np.int16) for n in lens])
+        offsets = exclusive_offsets(lens)
+        n_out = (lens * plan["out_unit"] + plan["in_unit"] - 1) // plan["in_unit"]
+        out_off = exclusive_offsets(n_out)
+        pcm_d, tables = torch.from_numpy(pcm).cuda(), torch.from_numpy(ops.resample_tables(cfg)).cuda()
+        out = torch.empty(int(n_out.sum()), dtype=torch.int16, device="cuda")
+        off_d, n_d, oo_d = upload(offsets, np.int64, out.device), upload(lens, np.int32, out.device), upload(out_off, np.int64, out.device)
+        samples, clipped = torch.empty(n_utts, dtype=torch.int32, device="cuda"), torch.empty(n_utts, dtype=torch.int32, device="cuda")
+        bare = lambda: _lib.call("xv_resample", _s(), C.byref(cfg), _p(tables), _p(pcm_d), _p(off_d), _p(n_d), n_utts, _p(oo_d), _p(out), _p(None),
+                                 _p(samples), _p(clipped))
+        whole = lambda: ops.resample(cfg, tables, pcm_d, offsets, lens, out_offsets=out_off, out_pcm=out)
+        us_bare, us_whole = timeit(bare, 10, 3), timeit(whole, 10, 3)
+        assert np.array_equal(samples.cpu().numpy(), n_out)
+        fmas, moved = float(n_out.sum()) * plan["taps_max"], 2.0 * (pcm.size + float(n_out.sum()))
+        print("%-20s %d utterances of %.1f - %.1f s: %.1f M samples in, %.1f M out; %d phases x %d taps, tile %d, %d staged samples, %d bytes of LDS"
+              % (label, n_utts, seconds.min(), seconds.max(), pcm.size / 1e6, n_out.sum() / 1e6, plan["out_unit"], plan["taps_max"], plan["tile"],
+                 plan["span"], plan["lds_bytes"]), flush=True)
+        print("    bare entry point %9.1f us = %7.0f x real time, %7.1f G fma / s = %.4f of 157.3 TF, %6.1f GB / s; ops.resample %9.1f us; %d clipped"
+              % (us_bare, pcm.size / fin / (us_bare * 1e-6), fmas / us_bare / 1e3, 2.0 * fmas / us_bare / 1e6 / 157.3, moved / us_bare / 1e3, us_whole,
+                 int(clipped.sum())), flush=True)
+
+
+COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
