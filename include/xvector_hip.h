@@ -411,6 +411,13 @@ int xv_score_trials(void* stream, const float* e, int lde, int ne, const float* 
 size_t xv_score_cohort_workspace_bytes(int rows, int n_cohort, int d);
 int xv_score_cohort_stats(void* stream, const float* x, int ldx, int rows, const float* cohort, int ldc, int n_cohort, int d, int top_k,
                           float* stats, void* ws, size_t ws_bytes);
+/* score_normalize (the AS-norm of scores that are on the device already: the PLDA log-likelihood ratios of egs/sre/v1/run.sh:477-490,
+ * normalised as score_trials normalises a cosine): out[j] = 0.5 * ((s - e_stats[ei[j]][0]) / e_stats[ei[j]][1] + (s - t_stats[ti[j]][0]) /
+ * t_stats[ti[j]][1]), s = scores[j], j < m - the expression of score_trials, compiled once for both, so the same bits for the same s and
+ * statistics.  In place (out == scores) is allowed, any other overlap is refused.  ei, ti: device int32 [m], NOT checked on the device
+ * (ops.score_normalize checks the host arrays before the upload). */
+int xv_score_normalize(void* stream, const float* scores, const int32_t* ei, const int32_t* ti, int64_t m, const float* e_stats,
+                       const float* t_stats, float* out);
 
 /* The LDA / PLDA back end behind extraction, device side: what ivector-mean (with and without spk2utt), ivector-compute-lda,
  * ivector-compute-plda, ivector-subtract-global-mean and ivector-plda-scoring --normalize-length=true do on the embedding tables
@@ -459,6 +466,24 @@ int xv_backend_plda_normalize(void* stream, const float* u, int rows, int d, int
 int xv_backend_plda_trials(void* stream, const float* e, int lde, int ne, const float* t, int ldt, int nt, int d, const int32_t* ei,
                            const int32_t* ti, int64_t m, const int32_t* nidx, const float* coef, int ldc, int n_distinct, const float* g,
                            const float* k0, float* out);
+/* plda_cohort_stats (the cohort statistics of AS-norm behind the PLDA scores of egs/sre/v1/run.sh:477-490): stats[r] = (mean,
+ * sqrt(max(var, 1e-12))) of the k = min(top_k, n_cohort) largest log-likelihood ratios of row r of x [rows][ldx] - a PLDA-normalised row
+ * in the model role, q = nidx[r] its entry in the table of distinct utterance counts (nidx = NULL: 0 for every row) - against the rows of
+ * cohort [n_cohort][ldc], normalised with one utterance, in the test role.  coef, g, k0: the tables of plda_trials.  The ratio is taken
+ * in its factored form LLR(e, t) = R(e) + C_q(t) + sum_c (iv_q[c] a_q[c] e_c) t_c with R(e) = k0[q] - 0.5 sum_c iv_q[c] a_q[c]^2 e_c^2 and
+ * C_q(t) = 0.5 sum_c (g[c] - iv_q[c]) t_c^2: one kernel writes C_q(t_j) for every (q, j), once per call; per tile of rows one kernel
+ * writes the GEMM operand xs = (iv a) x on the pitch d rounded up to 4 (zero padding) and R, the fp32 GEMM of score_cohort_stats writes
+ * xs . cohort^T into the slab, and the selection of score_cohort_stats - the same code - runs over v(r, j) = (slab[r][j] + C_q[j]) +
+ * R[r], two plain fp32 adds.  For n = 1 the ratio is symmetric in (e, t), so a test row is passed as a one-utterance model.  ws, in
+ * floats: [n_distinct][P] column terms, then per round [tile][P] slab, [tile][K] operand, [tile] row terms, P = n_cohort and K = d rounded
+ * up to 4, tile = the largest multiple of 128 rows ws_bytes holds; xv_backend_plda_cohort_workspace_bytes is the size at which one round
+ * covers all rows.  Refused by name: top_k <= 0, n_cohort <= 0, d <= 0, ldx or ldc below d rounded up to 4 (columns d .. K of the cohort
+ * rows are read and must be zero: plda_normalize writes them), ldcoef below d, a workspace below the column terms plus one 128-row tile or
+ * off the 16-byte grid, and what the GEMM refuses.  nidx is NOT checked on the device (ops.backend_plda_cohort_stats checks the host array). */
+size_t xv_backend_plda_cohort_workspace_bytes(int rows, int n_cohort, int d, int n_distinct);
+int xv_backend_plda_cohort_stats(void* stream, const float* x, int ldx, int rows, const int32_t* nidx, const float* cohort, int ldc,
+                                 int n_cohort, int d, const float* coef, int ldcoef, int n_distinct, const float* g, const float* k0,
+                                 int top_k, float* stats, void* ws, size_t ws_bytes);
 
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);

@@ -1,8 +1,9 @@
 // Cosine trial scoring with adaptive symmetric score normalisation (AS-norm): what ivector-subtract-global-mean | ivector-normalize-length,
 // ivector-compute-dot-products and the cohort statistics of an AS-norm back end do behind the reference's extract.py, on embedding
-// matrices that live on the device.  Three ops: rows centred and scaled to unit length (score_prepare), trial dot products with the
-// optional normalisation (score_trials), and per row the mean / deviation of its top-k cohort scores (score_cohort_stats: the project's
-// fp32 NT GEMM into a score slab, then an exact radix select per row).  No floating-point atomics and no cross-workgroup hand-over in
+// matrices that live on the device.  Four ops: rows centred and scaled to unit length (score_prepare), trial dot products with the
+// optional normalisation (score_trials), that normalisation alone on scores already on the device (score_normalize), and per row the
+// mean / deviation of its top-k cohort scores (score_cohort_stats: the project's fp32 NT GEMM into a score slab, then an exact radix
+// select per row, xv_select.h).  No floating-point atomics and no cross-workgroup hand-over in
 // these kernels (the select's histogram is integer LDS atomics: a count does not depend on the order of its increments): a result
 // depends on the shape of the call only, so it is the same bits every time.  gfx950 only.
 #include <algorithm>
@@ -11,10 +12,7 @@
 #include "xv_ew.h"
 #include "xv_gemm.h"
 #include "xv_rowsum.h"      // sc_row_dot and chain(d), SC_ROWS_PER_WG, sc_aligned16, sc_overlap
-#include "xv_radix_key.h"   // sc_key / sc_unkey: the unsigned key whose order is the float's
-
-#define SC_SEL_THREADS 256
-#define SC_TILE_ROWS 128          // the score slab holds a whole number of GEMM row tiles
+#include "xv_select.h"      // sc_select_kernel: the exact top-k selection and its statistics; SC_TILE_ROWS, sc_slab_pitch
 
 // y[r][c] = v * rsqrt(max(Σ v², 1e-12)), v = x[r][c] - mean[c], for c < d; y[r][d .. ldy) = 0.  One wave per row.  In place (y == x,
 // ldy == ldx) a lane reads back exactly the elements it then overwrites, and the padding belongs to the row.
@@ -50,6 +48,12 @@ __global__ __launch_bounds__(256) void score_prepare_kernel(const float* x, int 
     }
 }
 
+// AS-norm of a score s with the cohort statistics (μ, σ) of its enrolment row a and its test row b: one expression, so score_trials_kernel
+// and score_normalize_kernel give the same bits for the same s
+__device__ __forceinline__ float sc_as_norm(float s, const float* __restrict__ e_stats, int a, const float* __restrict__ t_stats, int b) {
+    return 0.5f * ((s - e_stats[2 * (long)a]) / e_stats[2 * (long)a + 1] + (s - t_stats[2 * (long)b]) / t_stats[2 * (long)b + 1]);
+}
+
 // out[j] = s = Σ_c e[ei[j]][c] * t[ti[j]][c], or with the row statistics 0.5 * ((s - μe) / σe + (s - μt) / σt).  One wave per trial;
 // the sum is sc_row_dot's (chain(d) above).
 template <bool VEC>
@@ -63,117 +67,20 @@ __global__ __launch_bounds__(256) void score_trials_kernel(const float* __restri
     if (j >= m) return;
     const int a = ei[j], b = ti[j];
     float s = sc_row_dot<VEC, false>(e + (long)a * lde, t + (long)b * ldt, nullptr, d, lane);
-    if (e_stats) s = 0.5f * ((s - e_stats[2 * (long)a]) / e_stats[2 * (long)a + 1] + (s - t_stats[2 * (long)b]) / t_stats[2 * (long)b + 1]);
+    if (e_stats) s = sc_as_norm(s, e_stats, a, t_stats, b);
     if (lane == 0) out[j] = s;
 }
 
-// a double summed over the workgroup in a fixed order: butterfly inside each wave, the four wave totals added first to last
-__device__ __forceinline__ double sc_block_sum(double v, double* wtot, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();      // (wtot may still be read from the call before)
-    if ((tid & 63) == 0) wtot[tid >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < SC_SEL_THREADS / XV_WAVE; ++w) s += wtot[w];
-    return s;
-}
+// (score_cohort_stats selects with sc_select_kernel<ScSlabRow> of xv_select.h: the plain slab element)
 
-// stats[r] = (mean, sqrt(max(var, 1e-12))) of the k largest of the n scores of row r of the slab (k <= n).  One workgroup per row.
-// Radix select of the k-th largest key, most significant byte first: each pass counts, among the elements that share the bytes already
-// fixed, the next byte's 256 values in LDS; wave 0 walks the counts from the top until `want` more elements are covered, which fixes the
-// byte and leaves `want` = the rank inside that bucket.  After four passes the key is the k-th largest score exactly and `want` is how
-// many copies of it the top k holds (k - want elements lie strictly above).  The sums take the elements strictly above plus `want` copies
-// of the threshold, so a cut through a run of equal scores is well defined; they are accumulated in double (a thread's elements in index
-// order, then sc_block_sum), the variance around the mean in a second pass.  The row is streamed from the slab six times; nothing of it
-// is kept in LDS, so n is not bounded here.
-__global__ __launch_bounds__(SC_SEL_THREADS) void score_select_kernel(const float* __restrict__ slab, long lds, int n, int k, float* __restrict__ stats) {
+// out[j] = sc_as_norm of scores[j] with the statistics of rows ei[j] / ti[j]: the normalisation of score_trials_kernel on scores that are
+// on the device already (the PLDA log-likelihood ratios).  One thread per trial; out == scores is in place.
+__global__ __launch_bounds__(256) void score_normalize_kernel(const float* scores, const int* __restrict__ ei, const int* __restrict__ ti, long m,
+                                                              const float* __restrict__ e_stats, const float* __restrict__ t_stats, float* out) {
     XV_EW_PRIORITY();
-    __shared__ int hist[256];
-    __shared__ unsigned sh_prefix;
-    __shared__ int sh_want;
-    __shared__ double wtot[SC_SEL_THREADS / XV_WAVE];
-    const int tid = threadIdx.x;
-    const float* row = slab + (long)blockIdx.x * lds;
-    const int n4 = n / 4;      // (every slab row starts on a 16-byte boundary: the slab is 16-byte aligned and lds a multiple of 4)
-    unsigned prefix = 0, mask = 0;
-    int want = k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;
-        __syncthreads();
-        for (int q = tid; q < n4; q += SC_SEL_THREADS) {
-            const f32x4 v = *(const f32x4*)(row + 4 * q);
-            const unsigned k0 = sc_key(v.x), k1 = sc_key(v.y), k2 = sc_key(v.z), k3 = sc_key(v.w);
-            if ((k0 & mask) == prefix) atomicAdd(&hist[(k0 >> shift) & 255u], 1);
-            if ((k1 & mask) == prefix) atomicAdd(&hist[(k1 >> shift) & 255u], 1);
-            if ((k2 & mask) == prefix) atomicAdd(&hist[(k2 >> shift) & 255u], 1);
-            if ((k3 & mask) == prefix) atomicAdd(&hist[(k3 >> shift) & 255u], 1);
-        }
-        if (tid < n - 4 * n4) {
-            const unsigned kk = sc_key(row[4 * n4 + tid]);
-            if ((kk & mask) == prefix) atomicAdd(&hist[(kk >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (tid < XV_WAVE) {      // lane l owns the buckets 255 - 4l ... 252 - 4l, walked downwards
-            int c[4], own = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { c[j] = hist[255 - 4 * tid - j]; own += c[j]; }
-            int incl = own;
-#pragma unroll
-            for (int o = 1; o < XV_WAVE; o <<= 1) {
-                const int up = __shfl_up(incl, o);
-                if (tid >= o) incl += up;
-            }
-            int above = incl - own;      // elements in the buckets of the lanes in front
-            if (above < want && want <= incl) {      // exactly one lane: the buckets hold at least `want` elements together
-                int digit = 255 - 4 * tid - 3;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (want <= above + c[j]) { digit = 255 - 4 * tid - j; break; }
-                    above += c[j];
-                }
-                sh_prefix = prefix | ((unsigned)digit << shift);
-                sh_want = want - above;
-            }
-        }
-        __syncthreads();
-        prefix = sh_prefix;
-        want = sh_want;
-        mask |= 255u << shift;
-    }
-    const float thr = sc_unkey(prefix);
-    const double dthr = (double)thr;
-    double acc = 0.0;
-    for (int q = tid; q < n4; q += SC_SEL_THREADS) {
-        const f32x4 v = *(const f32x4*)(row + 4 * q);
-        if (sc_key(v.x) > prefix) acc += (double)v.x;
-        if (sc_key(v.y) > prefix) acc += (double)v.y;
-        if (sc_key(v.z) > prefix) acc += (double)v.z;
-        if (sc_key(v.w) > prefix) acc += (double)v.w;
-    }
-    if (tid < n - 4 * n4) {
-        const float v = row[4 * n4 + tid];
-        if (sc_key(v) > prefix) acc += (double)v;
-    }
-    const double mean = (sc_block_sum(acc, wtot, tid) + (double)want * dthr) / (double)k;
-    acc = 0.0;
-    for (int q = tid; q < n4; q += SC_SEL_THREADS) {
-        const f32x4 v = *(const f32x4*)(row + 4 * q);
-        if (sc_key(v.x) > prefix) acc += ((double)v.x - mean) * ((double)v.x - mean);
-        if (sc_key(v.y) > prefix) acc += ((double)v.y - mean) * ((double)v.y - mean);
-        if (sc_key(v.z) > prefix) acc += ((double)v.z - mean) * ((double)v.z - mean);
-        if (sc_key(v.w) > prefix) acc += ((double)v.w - mean) * ((double)v.w - mean);
-    }
-    if (tid < n - 4 * n4) {
-        const float v = row[4 * n4 + tid];
-        if (sc_key(v) > prefix) acc += ((double)v - mean) * ((double)v - mean);
-    }
-    const double var = (sc_block_sum(acc, wtot, tid) + (double)want * (dthr - mean) * (dthr - mean)) / (double)k;
-    if (tid == 0) {
-        stats[2 * (long)blockIdx.x] = (float)mean;
-        stats[2 * (long)blockIdx.x + 1] = (float)sqrt(fmax(var, 1e-12));
-    }
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    out[j] = sc_as_norm(scores[j], e_stats, ei[j], t_stats, ti[j]);
 }
 
 extern "C" int xv_score_prepare(void* stream, const float* x, int rows, int d, int ldx, const float* mean, float* y, int ldy) {
@@ -209,9 +116,6 @@ extern "C" int xv_score_trials(void* stream, const float* e, int lde, int ne, co
     return 0;
 }
 
-// floats per slab row: the cohort size on the 16-byte grid
-static size_t sc_slab_pitch(int n_cohort) { return xv_align((size_t)(n_cohort > 0 ? n_cohort : 1), 4); }
-
 extern "C" size_t xv_score_cohort_workspace_bytes(int rows, int n_cohort, int d) {
     (void)d;
     return xv_align((size_t)(rows > 0 ? rows : 1), SC_TILE_ROWS) * sc_slab_pitch(n_cohort) * sizeof(float);
@@ -246,8 +150,19 @@ extern "C" int xv_score_cohort_stats(void* stream, const float* x, int ldx, int 
         g.M = m; g.N = n_cohort; g.K = kd;
         const int rc = xv_launch_gemm_nt(s, g);
         if (rc) return rc;
-        hipLaunchKernelGGL(score_select_kernel, dim3(m), dim3(SC_SEL_THREADS), 0, s, (const float*)ws, (long)pitch, n_cohort, k, stats + 2 * (size_t)r0);
+        hipLaunchKernelGGL(sc_select_kernel<ScSlabRow>, dim3(m), dim3(SC_SEL_THREADS), 0, s, (const float*)ws, (long)pitch, n_cohort, k, stats + 2 * (size_t)r0);
         XV_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+extern "C" int xv_score_normalize(void* stream, const float* scores, const int32_t* ei, const int32_t* ti, int64_t m, const float* e_stats,
+                                  const float* t_stats, float* out) {
+    XV_REQUIRE(scores && ei && ti && e_stats && t_stats && out && m > 0, "score_normalize: bad arguments");
+    XV_REQUIRE(m <= (int64_t)256 * 0x7fffffff, "score_normalize: too many trials in one call (%lld)", (long long)m);
+    XV_REQUIRE(out == scores || !sc_overlap(scores, (size_t)m, out, (size_t)m), "score_normalize: scores and out overlap (in place needs out == scores)");
+    hipLaunchKernelGGL(score_normalize_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, (const int*)ei, (const int*)ti,
+                       (long)m, e_stats, t_stats, out);
+    XV_LAUNCH_CHECK();
     return 0;
 }

@@ -1,12 +1,14 @@
-"""The LDA / PLDA back end behind extraction (nnet/lib/train_backend.py, nnet/lib/score.py --backend), with multi-utterance enrolment.
+"""The LDA / PLDA back end behind extraction (nnet/lib/train_backend.py, nnet/lib/adapt_backend.py, nnet/lib/score.py --backend), with
+multi-utterance enrolment, unsupervised domain adaptation and AS-norm of the PLDA scores.
 
-What the reference recipes go to Kaldi for (egs/voxceleb/v1/run.sh:370-401, egs/sre/v1/run.sh:397-490): ivector-mean, ivector-compute-lda,
-ivector-compute-plda, ivector-subtract-global-mean | transform-vec | ivector-normalize-length, ivector-plda-scoring.  INTEGRATION.md
+What the reference recipes go to Kaldi for (egs/voxceleb/v1/run.sh:370-401, egs/sre/v1/run.sh:397-492): ivector-mean, ivector-compute-lda,
+ivector-compute-plda, ivector-adapt-plda, ivector-subtract-global-mean | transform-vec | ivector-normalize-length, ivector-plda-scoring.  INTEGRATION.md
 section 6b is the specification (parity by restatement: nothing compared with a Kaldi run).  Host side: spk2utt files, the CSR form of
-groups of keys, the two estimators and the coefficient table of the log-likelihood ratio, all fp64 NumPy on matrices of d x d or smaller.
-Device side: Backend.train runs the statistics that grow with the corpus (per-speaker means, scatter matrices, the transform chain) through
-csrc/xv_backend.hip and the project's GEMMs; BackendScorer keeps prepared tables on the GPU as CosineScorer does.
-Not here: ivector-adapt-plda, AS-norm of PLDA scores, DET plots.
+groups of keys, the three estimators and the coefficient table of the log-likelihood ratio, all fp64 NumPy on matrices of d x d or smaller.
+Device side: Backend.train and Backend.adapt run the statistics that grow with the corpus (per-speaker means, scatter matrices, the
+transform chain) through csrc/xv_backend.hip and the project's GEMMs; BackendScorer keeps prepared tables on the GPU as CosineScorer does,
+the cohort of AS-norm among them (csrc/xv_backend_cohort.hip).
+Not here: DET plots.
 """
 import logging
 import os
@@ -148,6 +150,39 @@ def estimate_plda(scatter, means, counts, num_em_iters=10):
     psi = np.maximum(psi, 0.0)
     transform = u.T @ t1
     return dict(mean=mu, transform=transform, psi=psi, offset=-(transform @ mu), within=w, between=b)
+
+
+def adapt_plda(plda, mean_y, scatter_y, n, within_covar_scale=0.3, between_covar_scale=0.7, mean_diff_scale=1.0):
+    """ivector-adapt-plda from statistics, fp64 (INTEGRATION.md section 6b states the steps): plda = the model to adapt (mean, transform,
+    psi), mean_y [d] = the average of the n adaptation vectors y (at ivector-normalize-length's scale, as Backend.train feeds its PLDA),
+    scatter_y = sum y y^T (not centred).  The adaptation set's total covariance is whitened by the model's own; along each direction in which
+    it exceeds 1, within_covar_scale / between_covar_scale of the excess go to the within- / between-class covariance.
+    -> dict(mean, transform, psi, offset, within, between, eigenvalues = the s of the whitened covariance, descending)."""
+    if within_covar_scale < 0 or between_covar_scale < 0 or mean_diff_scale < 0:
+        raise ValueError("adapt_plda: the scales must not be negative (within %g, between %g, mean-diff %g)"
+                         % (within_covar_scale, between_covar_scale, mean_diff_scale))
+    mean, t, psi = (np.asarray(plda[k], dtype=np.float64) for k in ("mean", "transform", "psi"))
+    m = np.asarray(mean_y, dtype=np.float64)
+    d = m.shape[0]
+    if mean.shape != (d,) or t.shape != (d, d) or psi.shape != (d,) or np.shape(scatter_y) != (d, d) or n <= 0:
+        raise ValueError("adapt_plda: the model and the statistics must share one dimension, n must be positive")
+    diff = m - mean
+    v = np.asarray(scatter_y, dtype=np.float64) / float(n) - np.outer(m, m) + float(mean_diff_scale) * np.outer(diff, diff)
+    mt = t / np.sqrt(1.0 + psi)[:, None]                       # the map under which the model's total covariance is the unit matrix
+    s, p = _sym_eigh_desc(mt @ v @ mt.T)
+    w2 = p.T @ (p / (1.0 + psi)[:, None])
+    b2 = p.T @ (p * (psi / (1.0 + psi))[:, None])
+    excess = np.maximum(s - 1.0, 0.0)
+    w2[np.diag_indices(d)] += float(within_covar_scale) * excess
+    b2[np.diag_indices(d)] += float(between_covar_scale) * excess
+    k = np.linalg.inv(p.T @ mt)
+    w, b = k @ w2 @ k.T, k @ b2 @ k.T
+    w, b = 0.5 * (w + w.T), 0.5 * (b + b.T)
+    t1 = np.linalg.inv(np.linalg.cholesky(w))
+    psi_new, u = _sym_eigh_desc(t1 @ b @ t1.T)
+    psi_new = np.maximum(psi_new, 0.0)
+    transform = u.T @ t1
+    return dict(mean=m, transform=transform, psi=psi_new, offset=-(transform @ m), within=w, between=b, eigenvalues=s)
 
 
 def plda_coefficients(psi, distinct_n):
@@ -308,6 +343,41 @@ class Backend(object):
         log.info("[INFO] PLDA: psi min %.6g, max %.6g (%d EM iterations)." % (plda["psi"].min(), plda["psi"].max(), num_em_iters))
         return cls(mean, lda, plda)
 
+    def recentred(self, matrix):
+        """This back end on the mean of another table (the fp64-accumulated mean.vec of `matrix`), nothing adapted: the recipe's
+        out-of-domain PLDA on the in-domain mean (egs/sre/v1/run.sh:477-483)."""
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+        if matrix.ndim != 2 or matrix.shape[0] == 0 or matrix.shape[1] != self.d:
+            raise ValueError("Backend.recentred: dimension mismatch: a non-empty [n, %d] matrix is expected, got %s" % (self.d, matrix.shape))
+        return Backend(center_mean(matrix).astype(np.float32), self.lda, self.plda)
+
+    def adapt(self, matrix, device="cuda:0", within_covar_scale=0.3, between_covar_scale=0.7, mean_diff_scale=1.0, log=None):
+        """ivector-adapt-plda on the unlabelled table `matrix` [n, d] (egs/sre/v1/run.sh:451-492): the new mean.vec is the table's mean, the
+        LDA is kept, and the PLDA model is adapted to the table's vectors taken through the chain centred on the NEW mean.  Their
+        statistics come from the GPU in PREPARE_ROWS batches (the transform chain, xv_backend_scatter, and xv_backend_group_means with a
+        single group for the row sum in double); adapt_plda runs here in fp64.  -> Backend(new mean, lda, adapted plda)."""
+        if self.plda is None:
+            raise ValueError("Backend.adapt: the back end holds no PLDA model (no `plda` file in its directory)")
+        torch, ops, _ = device_ops(device)
+        log = log or _LOG
+        base = self.recentred(matrix)
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+        chain = _Chain(Backend(base.mean, self.lda, None), device)
+        n, dim = matrix.shape[0], self.dim
+        scatter, total = np.zeros((dim, dim)), np.zeros(dim)
+        for r0, r1 in steps(n, PREPARE_ROWS):
+            y = chain.unit(torch.from_numpy(matrix[r0:r1]).to(device))
+            scatter += ops.backend_scatter(y, d=dim).cpu().numpy()
+            one = ops.backend_group_means(y, dim, np.array([0, r1 - r0], np.int64), np.arange(r1 - r0, dtype=np.int32), want32=False)[0]
+            total += one.cpu().numpy()[0] * float(r1 - r0)
+        # y is at unit length; the model works at ivector-normalize-length's scale sqrt(dim): both statistics are scaled here, in fp64
+        plda = adapt_plda(self.plda, total / n * np.sqrt(float(dim)), scatter * float(dim), n, within_covar_scale, between_covar_scale,
+                          mean_diff_scale)
+        s = plda["eigenvalues"]
+        log.info("[INFO] PLDA adaptation: N = %d vectors, %d of %d eigenvalues above 1 (largest %.6g, smallest %.6g); psi min %.6g, max %.6g."
+                 % (n, int((s > 1.0).sum()), dim, s[0], s[-1], plda["psi"].min(), plda["psi"].max()))
+        return Backend(base.mean, self.lda, plda)
+
 
 class BackendScorer(object):
     """Trial scores behind a trained back end, the tables kept on the GPU as CosineScorer keeps them.
@@ -316,12 +386,17 @@ class BackendScorer(object):
         names, avg, counts = scorer.enrol_average(matrix, keys, spk2utt)   # optional: models = averages of raw vectors (ivector-mean ark:spk2utt)
         enrol = scorer.prepare(avg, n_utts=counts)                   # host [n, d] matrix or device tensor -> prepared device matrix
         test = scorer.prepare(test_matrix)
+        scorer.cohort(cohort_matrix, top_k=300)                      # optional, "plda" mode: AS-norm of the log-likelihood ratios; cohort(None) drops it
         scores = scorer.score(enrol, test, ei, ti, enrol_n=counts)   # NumPy float32 [m]
 
     n_utts / enrol_n (None: 1 per row) enter the "plda" mode only: the normalisation of an enrolment vector and its log-likelihood ratio.
-    score() cuts the trials into batches such that no call asks for more than workspace_bytes of scratch."""
+    With a cohort every score s becomes 0.5 * ((s - mu_e) / sigma_e + (s - mu_t) / sigma_t): mu / sigma the mean and deviation of the top_k
+    largest ratios of the enrolment model (with its utterance count) / of the test vector (as a one-utterance model) against the cohort
+    vectors (xv_backend_plda_cohort_stats).  score() cuts the trials, and the rows whose cohort statistics it needs, into batches such that
+    no call asks for more than workspace_bytes of scratch."""
 
     MODES = ("lda_cos", "plda")
+    _cohort, top_k = None, 0      # no cohort until cohort() sets one
 
     def __init__(self, backend, mode="plda", device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
         if mode not in self.MODES:
@@ -333,6 +408,30 @@ class BackendScorer(object):
         self.torch, self.ops, self.device = self.chain.torch, self.chain.ops, self.chain.device
         self.workspace_bytes = int(workspace_bytes)
         self.d, self.dim = backend.d, backend.dim
+
+    def cohort(self, matrix, top_k=0):
+        """The cohort of AS-norm: prepared with one utterance per row and kept on the device.  matrix None: no cohort any more."""
+        if matrix is None:
+            self._cohort, self.top_k = None, 0
+            return
+        if self.mode != "plda":
+            raise ValueError("BackendScorer.cohort: AS-norm of PLDA scores needs the plda mode (lda_cos: CosineScorer on the prepared tables)")
+        if int(top_k) <= 0:
+            raise ValueError("BackendScorer.cohort: top_k must be positive (got %d)" % top_k)
+        self._cohort, self.top_k = self.prepare(matrix), int(top_k)
+
+    def _stats(self, x, nidx, tables):
+        """Cohort statistics [n, 2] of the prepared rows x (table entries nidx; None: entry 0), in row batches that fit the workspace."""
+        n_cohort, nq = self._cohort.shape[0], tables[0].shape[0]
+        need = lambda rows: self.ops.backend_plda_cohort_workspace_bytes(rows, n_cohort, self.dim, nq)
+        tile = need(256) - need(128)                            # what 128 more rows cost; the rest of need(128) are the column terms
+        if need(128) > self.workspace_bytes:
+            raise ValueError("BackendScorer: a workspace of %d bytes does not hold one 128-row tile of %d cohort scores (%d bytes)"
+                             % (self.workspace_bytes, n_cohort, need(128)))
+        step = (self.workspace_bytes - (need(128) - tile)) // tile * 128
+        return cat([self.ops.backend_plda_cohort_stats(x[r0:r1], self._cohort, self.dim, None if nidx is None else nidx[r0:r1], *tables,
+                                                       top_k=self.top_k, ws_bytes=need(r1 - r0))
+                    for r0, r1 in steps(x.shape[0], step)])
 
     def enrol_average(self, matrix, keys, spk2utt, log=None):
         """(names, device float32 [models, d rounded up to 4], counts int64): per speaker of spk2utt the plain average of its raw vectors,
@@ -358,7 +457,18 @@ class BackendScorer(object):
             n = np.ones(enrol.shape[0], np.int64) if enrol_n is None else np.asarray(enrol_n, dtype=np.int64)
             if n.shape != (enrol.shape[0],):
                 raise ValueError("BackendScorer.score: enrol_n must hold one count per enrolment row")
-            distinct, nidx = np.unique(n, return_inverse=True)
+            if self._cohort is not None:
+                distinct = np.unique(np.concatenate([[1], n]))      # the table always holds n = 1, as entry 0: the test side of AS-norm
+                nidx = np.searchsorted(distinct, n)
+            else:
+                distinct, nidx = np.unique(n, return_inverse=True)
             coef, g, k0 = (upload(a, np.float32, self.device) for a in plda_coefficients(self.backend.plda["psi"], distinct))
             run = lambda a, b: self.ops.backend_plda_trials(enrol, test, self.dim, a, b, nidx, coef, g, k0)
+            if self._cohort is not None:
+                e_stats = self._stats(enrol, nidx, (coef, g, k0))
+                t_stats = e_stats if test is enrol and not nidx.any() else self._stats(test, None, (coef, g, k0))
+
+                def run(a, b, raw=run):      # the raw ratios of a batch, normalised in place
+                    s = raw(a, b)
+                    return self.ops.score_normalize(s, a, b, e_stats, t_stats, out=s)
         return cat([run(ei[j0:j1], ti[j0:j1]).cpu().numpy() for j0, j1 in steps(ei.shape[0], step)])

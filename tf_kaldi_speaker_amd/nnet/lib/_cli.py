@@ -34,15 +34,24 @@ ARGUMENTS = {
     "top_k": (("--top-k",), dict(type=int, default=300, help="Cohort scores per vector that enter its AS-norm statistics (the largest ones).")),
     "backend": (("--backend",), dict(type=str, default="", help="A back-end directory written by train_backend.py (mean.vec, transform.mat, plda): its "
                                                                 "mean is the centre, its transforms run in front of the scores.  Empty: none.")),
-    "scoring": (("--scoring",), dict(type=str, default="cosine", choices=("cosine", "lda_cos", "plda"),
+    "scoring": (("--scoring",), dict(type=str, default="cosine", choices=("cosine", "lda_cos", "plda", "plda_asnorm"),
                                      help="cosine: cosine scores (no back end).  lda_cos: cosine behind the back end's LDA.  plda: PLDA "
-                                          "log-likelihood ratios (ivector-plda-scoring --normalize-length=true).")),
+                                          "log-likelihood ratios (ivector-plda-scoring --normalize-length=true).  plda_asnorm: those ratios "
+                                          "AS-normalised against --cohort.")),
     "enrol_spk2utt": (("--enrol-spk2utt",), dict(type=str, default="", help="spk2utt of the enrolment table: a model is the average of its speaker's "
                                                                             "raw vectors (ivector-mean ark:spk2utt) and the trials name speakers on "
                                                                             "the enrol side; with --scoring plda the counts also enter (--num-utts).")),
     "lda_dim": (("--lda-dim",), dict(type=int, default=200, help="Dimensions the LDA keeps (ivector-compute-lda --dim).")),
     "no_lda": (("--no-lda",), dict(action="store_true", help="Train the PLDA on the centred, length-normalised vectors without an LDA in front.")),
     "num_em_iters": (("--num-em-iters",), dict(type=int, default=10, help="EM iterations of the PLDA estimation (ivector-compute-plda).")),
+    "within_covar_scale": (("--within-covar-scale",), dict(type=float, default=0.3, help="Share of the adaptation set's excess variance that goes "
+                                                                                         "to the within-class covariance (ivector-adapt-plda).")),
+    "between_covar_scale": (("--between-covar-scale",), dict(type=float, default=0.7, help="Share of the excess variance that goes to the "
+                                                                                           "between-class covariance (ivector-adapt-plda).")),
+    "mean_diff_scale": (("--mean-diff-scale",), dict(type=float, default=1.0, help="Weight of the squared distance between the two means in the "
+                                                                                   "adaptation set's covariance (ivector-adapt-plda).")),
+    "mean_only": (("--mean-only",), dict(type=str, default="false", choices=("true", "false"),
+                                         help="true: only mean.vec is replaced by the adaptation table's mean; transform.mat and plda are copied.")),
     "mfcc_config": (("--mfcc-config",), dict(type=str, default="", help="Kaldi conf file of compute-mfcc-feats options (--name=value lines).  Empty: "
                                                                         "the VoxCeleb conf/mfcc.conf values.")),
     "vad_config": (("--vad-config",), dict(type=str, default="", help="Kaldi conf file of compute-vad-decision options.  Empty: the VoxCeleb "
@@ -92,6 +101,9 @@ ARGUMENTS = {
     "train_rspecifier": (("train_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the training vectors.")),
     "spk2utt": (("spk2utt",), dict(type=str, help="Kaldi spk2utt of the training vectors: `speaker utt1 utt2 ...` per line.")),
     "out_dir": (("out_dir",), dict(type=str, help="The back-end directory to write (mean.vec, transform.mat, plda).")),
+    "backend_in": (("backend_in",), dict(type=str, help="The back-end directory to adapt (train_backend.py wrote it).")),
+    "adapt_rspecifier": (("adapt_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the unlabelled in-domain vectors.")),
+    "backend_out": (("backend_out",), dict(type=str, help="The back-end directory to write (mean.vec, transform.mat, plda).")),
     "trials": (("trials",), dict(type=str, help="Kaldi trial list: `enrol test [target|nontarget]` per line.")),
     "enrol_rspecifier": (("enrol_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the enrolment vectors.")),
     "test_rspecifier": (("test_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the test vectors (may equal enrol_rspecifier).")),

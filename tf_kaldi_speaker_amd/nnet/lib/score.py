@@ -3,7 +3,8 @@
 trained LDA / PLDA back end, with optional multi-utterance enrolment:
 
     python nnet/lib/score.py [-g GPU] [--center-on RSPECIFIER] [--cohort RSPECIFIER --top-k N]
-                             [--backend DIR --scoring {cosine,lda_cos,plda}] [--enrol-spk2utt FILE] trials enrol_rspecifier test_rspecifier scores_out
+                             [--backend DIR --scoring {cosine,lda_cos,plda,plda_asnorm}] [--enrol-spk2utt FILE]
+                             trials enrol_rspecifier test_rspecifier scores_out
 
 The stage behind extract.py, for which the reference recipe goes to Kaldi (egs/voxceleb/v1/run.sh, cosine back end: ivector-mean,
 ivector-subtract-global-mean | ivector-normalize-length, ivector-compute-dot-products, compute-eer).  The rspecifiers name float-vector
@@ -16,11 +17,13 @@ logged at the end.  When every kept trial carries a label, EER, minDCF08 and min
 --backend DIR (nnet/lib/train_backend.py wrote it) with --scoring lda_cos | plda: every vector is centred on the back end's mean.vec (giving
 --center-on as well is refused), taken through transform.mat and length-normalised (run.sh stage 10-11: ivector-subtract-global-mean |
 transform-vec | ivector-normalize-length); lda_cos scores the cosine, plda the log-likelihood ratio of ivector-plda-scoring
---normalize-length=true.  --scoring plda with --cohort is refused (AS-norm of PLDA scores: DESIGN.md section 7).
+--normalize-length=true.  --scoring plda_asnorm (needs --backend and --cohort; honours --top-k): the PLDA ratios AS-normalised, mu / sigma
+the statistics of the --top-k largest ratios of the enrolment model (with its utterance count) / of the test vector (as a one-utterance model)
+against the cohort vectors.  --scoring plda with --cohort is refused: the normalised scores have a name of their own.
 --enrol-spk2utt FILE (any scoring mode): a model is the plain average of its speaker's raw enrolment vectors (ivector-mean ark:spk2utt), the
 trials name speakers on the enrol side, and with plda the number of utterances enters the score (--num-utts).
 Without the three new options the output is what it was before they existed, byte for byte.
-Not here: ivector-adapt-plda, AS-norm of PLDA scores, DET plots.
+Not here: DET plots.  (ivector-adapt-plda: nnet/lib/adapt_backend.py.)
 """
 import sys
 
@@ -38,9 +41,10 @@ def backend_scores(args, log, device, trials, enrol_keys, enrol, test_keys, test
         sys.exit("dimension mismatch: enrol_rspecifier holds vectors of %d dimensions, the back end %s works on %d" % (enrol.shape[1], args.backend, be.d))
     if be is None:      # cosine on averaged models: a back end that only centres
         be = B.Backend(np.zeros(enrol.shape[1], np.float32) if center is None else scoring.center_mean(center).astype(np.float32))
-    if args.scoring == "plda" and be.plda is None:
-        sys.exit("--scoring plda: the back end %s holds no plda file" % args.backend)
-    scorer = B.BackendScorer(be, "plda" if args.scoring == "plda" else "lda_cos", device)
+    plda = args.scoring in ("plda", "plda_asnorm")
+    if plda and be.plda is None:
+        sys.exit("--scoring %s: the back end %s holds no plda file" % (args.scoring, args.backend))
+    scorer = B.BackendScorer(be, "plda" if plda else "lda_cos", device)
     model_keys, models, counts = enrol_keys, enrol, None
     if args.enrol_spk2utt:
         model_keys, models, counts = scorer.enrol_average(enrol, enrol_keys, B.read_spk2utt(args.enrol_spk2utt), log)
@@ -50,9 +54,11 @@ def backend_scores(args, log, device, trials, enrol_keys, enrol, test_keys, test
         log.info("[INFO] Trial %s %s: %s, skip." % (a, b, "no vector for a key"))
     if not kept:
         return np.zeros(0, np.float32), kept, skipped
-    e_prep = scorer.prepare(models, n_utts=counts if args.scoring == "plda" else None)
+    e_prep = scorer.prepare(models, n_utts=counts if plda else None)
     t_prep = e_prep if same else scorer.prepare(test)
-    if args.scoring == "plda":
+    if plda:
+        if args.scoring == "plda_asnorm":
+            scorer.cohort(cohort, args.top_k)
         return scorer.score(e_prep, t_prep, ei, ti, enrol_n=counts), kept, skipped
     if cohort is None:
         return scorer.score(e_prep, t_prep, ei, ti), kept, skipped
@@ -76,7 +82,9 @@ def main():
     if args.backend and args.center_on:
         sys.exit("--backend and --center-on exclude each other: with a back end the centre is its mean.vec")
     if args.scoring == "plda" and args.cohort:
-        sys.exit("--cohort with --scoring plda is not supported: AS-norm of PLDA scores is out of scope (DESIGN.md section 7)")
+        sys.exit("--cohort with --scoring plda is not supported: plda writes raw log-likelihood ratios; --scoring plda_asnorm normalises them against the cohort")
+    if args.scoring == "plda_asnorm" and not args.cohort:
+        sys.exit("--scoring plda_asnorm needs --cohort RSPECIFIER (the vectors the PLDA scores are normalised against)")
     import torch
     device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
     trials = scoring.read_trials(args.trials)

@@ -11,7 +11,7 @@ recipe's files: mean.vec, transform.mat (not with --no-lda) and plda, which nnet
 The statistics that grow with the corpus (scatter matrices, per-speaker means, the transform chain) run on the GPU; the
 eigendecompositions and the EM run on the host in fp64 (misc/backend.py).  N, K, the kept LDA eigenvalue range and the PLDA's psi range are
 logged.
-Not here: ivector-adapt-plda.
+Domain adaptation of the trained model (ivector-adapt-plda): nnet/lib/adapt_backend.py.
 """
 import sys
 

@@ -1,5 +1,5 @@
 """Op-level wrappers of the pipeline stages around the network (include/xvector_hip.h): the extraction front end, MFCC and energy VAD,
-augmentation, cosine / AS-norm scoring and the LDA / PLDA back end.  ops.py re-exports every public name here: callers write ops.mfcc.
+augmentation, cosine / AS-norm scoring and the LDA / PLDA back end with its cohort statistics.  ops.py re-exports every public name here: callers write ops.mfcc.
 Their kernels check none of the index arrays they are handed, so much of this is validation (_host.host_ints) in front of one upload."""
 import ctypes as C
 
@@ -487,11 +487,7 @@ def backend_plda_trials(e, t, d, ei, ti, nidx, coef, g, k0):
     ne, lde = pitched(e, "backend_plda_trials: e")
     nt, ldt = pitched(t, "backend_plda_trials: t")
     d = int(d)
-    if coef.dim() != 3 or coef.shape[1] != 2 or coef.dtype != torch.float32 or not coef.is_contiguous() or coef.shape[2] < d:
-        raise ValueError("backend_plda_trials: coef must be a contiguous float32 [n_distinct, 2, >= d] tensor")
-    nq, ldc = coef.shape[0], coef.shape[2]
-    if g.dtype != torch.float32 or g.numel() < d or not g.is_contiguous() or k0.dtype != torch.float32 or k0.numel() != nq or not k0.is_contiguous():
-        raise ValueError("backend_plda_trials: g must hold >= d and k0 n_distinct contiguous float32 values")
+    nq, ldc = _plda_tables("backend_plda_trials", coef, g, k0, d)
     ei = host_ints(ei, "backend_plda_trials: ei", min_size=1, lo=0, hi=ne)
     ti = host_ints(ti, "backend_plda_trials: ti", min_size=1, lo=0, hi=nt)
     nidx = host_ints(nidx, "backend_plda_trials: nidx", min_size=1, lo=0, hi=nq)
@@ -501,4 +497,63 @@ def backend_plda_trials(e, t, d, ei, ti, nidx, coef, g, k0):
     out = torch.empty(ei.size, dtype=torch.float32, device=e.device)
     _lib.call("xv_backend_plda_trials", _s(), _p(e), lde, ne, _p(t), ldt, nt, d, _p(ei_d), _p(ti_d), C.c_int64(ei.size), _p(nidx_d), _p(coef), ldc,
               nq, _p(g), _p(k0), _p(out))
+    return out
+
+
+def _plda_tables(name, coef, g, k0, d):      # the checks plda_trials and plda_cohort_stats share: -> (n_distinct, pitch of coef)
+    if coef.dim() != 3 or coef.shape[1] != 2 or coef.dtype != torch.float32 or not coef.is_contiguous() or coef.shape[2] < d:
+        raise ValueError("%s: coef must be a contiguous float32 [n_distinct, 2, >= d] tensor" % name)
+    nq = coef.shape[0]
+    if g.dtype != torch.float32 or g.numel() < d or not g.is_contiguous() or k0.dtype != torch.float32 or k0.numel() != nq or not k0.is_contiguous():
+        raise ValueError("%s: g must hold >= d and k0 n_distinct contiguous float32 values" % name)
+    return nq, coef.shape[2]
+
+
+def backend_plda_cohort_workspace_bytes(rows, n_cohort, d, n_distinct):
+    return int(_lib.load().xv_backend_plda_cohort_workspace_bytes(int(rows), int(n_cohort), int(d), int(n_distinct)))
+
+
+def backend_plda_cohort_stats(x, cohort, d, nidx, coef, g, k0, top_k, ws_bytes=None):
+    """[rows, 2] = (mean, biased deviation) of each row's min(top_k, n_cohort) largest PLDA log-likelihood ratios against the cohort rows
+    (xv_backend_plda_cohort_stats).  x: PLDA-normalised rows in the model role (backend_plda_normalize with their utterance counts), cohort:
+    rows normalised with one utterance; both on a zero-padded pitch that is a multiple of 4.  coef, g, k0: plda_coefficients' tables on the
+    device; nidx: HOST integer array [rows] into them (None: entry 0 for every row), checked here before the upload.  ws_bytes: size of
+    the workspace (default: the whole call in one round); fewer bytes run the rows in tiles."""
+    rows, ldx = pitched(x, "backend_plda_cohort_stats: x")
+    n_cohort, ldc = pitched(cohort, "backend_plda_cohort_stats: cohort")
+    d = int(d)
+    nq, ldk = _plda_tables("backend_plda_cohort_stats", coef, g, k0, d)
+    nidx_d = None
+    if nidx is not None:
+        nidx = host_ints(nidx, "backend_plda_cohort_stats: nidx", min_size=1, lo=0, hi=nq)
+        if nidx.size != rows:
+            raise ValueError("backend_plda_cohort_stats: nidx must hold one entry per row (%d, got %d)" % (rows, nidx.size))
+        nidx_d = upload(nidx, np.int32, x.device)
+    if ws_bytes is None:
+        ws_bytes = backend_plda_cohort_workspace_bytes(rows, n_cohort, d, nq)
+    ws = torch.empty(max(int(ws_bytes) // 4, 1), dtype=torch.float32, device=x.device)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+    _lib.call("xv_backend_plda_cohort_stats", _s(), _p(x), ldx, rows, _p(nidx_d), _p(cohort), ldc, n_cohort, d, _p(coef), ldk, nq, _p(g), _p(k0),
+              int(top_k), _p(stats), _p(ws), C.c_size_t(int(ws_bytes)))
+    return stats
+
+
+def score_normalize(scores, ei, ti, e_stats, t_stats, out=None):
+    """AS-norm of scores that are on the device already (xv_score_normalize): out[j] = 0.5 * ((s - mu_e) / sigma_e + (s - mu_t) / sigma_t),
+    s = scores[j], the statistics those of rows ei[j] of e_stats [ne, 2] and ti[j] of t_stats [nt, 2] - score_trials' expression, bit for
+    bit.  ei, ti: HOST integer arrays, checked here before the upload.  out: the tensor to write (scores itself: in place); default new."""
+    if scores.dim() != 1 or scores.dtype != torch.float32 or not scores.is_contiguous() or scores.numel() == 0:
+        raise ValueError("score_normalize: scores must be a non-empty contiguous 1-D float32 tensor")
+    for st, name in ((e_stats, "e_stats"), (t_stats, "t_stats")):
+        if st is None or st.dtype != torch.float32 or st.dim() != 2 or st.shape[1] != 2 or not st.is_contiguous() or st.shape[0] == 0:
+            raise ValueError("score_normalize: %s must be a contiguous float32 [n, 2] tensor" % name)
+    m = scores.numel()
+    ei = host_ints(ei, "score_normalize: ei", n=m, lo=0, hi=e_stats.shape[0])
+    ti = host_ints(ti, "score_normalize: ti", n=m, lo=0, hi=t_stats.shape[0])
+    if out is None:
+        out = torch.empty(m, dtype=torch.float32, device=scores.device)
+    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() != m or not out.is_contiguous():
+        raise ValueError("score_normalize: out must be a contiguous 1-D float32 tensor of the scores' length")
+    ei_d, ti_d = upload(ei, np.int32, scores.device), upload(ti, np.int32, scores.device)
+    _lib.call("xv_score_normalize", _s(), _p(scores), _p(ei_d), _p(ti_d), C.c_int64(m), _p(e_stats), _p(t_stats), _p(out))
     return out

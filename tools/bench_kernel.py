@@ -13,6 +13,7 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py staged                           plain step vs the staged (multi-GPU) backward, without / with a one-rank RCCL all-reduce
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
   python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
+  python tools/bench_kernel.py plda_cohort [small|large]        the cohort statistics of PLDA scores (xv_backend_cohort.hip): d = 200, 4 k rows, cohorts of 4 k / 40 k
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
   python tools/bench_kernel.py cm_encode [utterances=256]        'CM ' compression (xv_cm_encode.hip) of 400 - 2000 frames x 30 per utterance, both header forms,
                                                                 against the bytes it must move and against the host writer
@@ -350,6 +351,41 @@ def cmd_backend(argv):
         print("  plda_trials             %9.1f us  %.2f TB/s of gathered rows (includes the index checks and uploads of ops.py)" % (us, mb / us), flush=True)
 
 
+def cmd_plda_cohort(argv):
+    """Time of the cohort statistics of PLDA scores (xv_backend_plda_cohort_stats, d = 200, 4 k rows with the counts 1 / 3 / 8 mixed) against
+    cohorts of 4 k and 40 k rows; the op's GEMM launches alone (the same row tiles through xv_affine_forward without scratch) against the
+    whole op: the rest is the column-term and fold kernels and the selection."""
+    import ctypes as C
+    from tf_kaldi_speaker_amd import _lib, ops
+    from tf_kaldi_speaker_amd.misc import backend as B
+    from tf_kaldi_speaker_amd.ops import _p, _s
+    d, n, top_k = 200, 4096, 300
+    psi = np.sort(rs.uniform(0.05, 5.0, d))[::-1].copy()
+    coef, g, k0 = (torch.from_numpy(a).cuda() for a in B.plda_coefficients(psi, [1, 3, 8]))
+    nidx = torch.from_numpy(rs.randint(0, 3, n).astype(np.int32)).cuda()
+    x = rnd(n, d)
+    sizes = {"small": 4096, "large": 40960}
+    for key in (argv or ["small", "large"]):
+        n_cohort = sizes[key]
+        cohort = rnd(n_cohort, d)
+        ws_bytes = ops.backend_plda_cohort_workspace_bytes(n, n_cohort, d, 3)
+        ws = torch.empty(ws_bytes // 4, device="cuda")
+        stats = torch.empty((n, 2), device="cuda")
+        ldn = (n_cohort + 3) // 4 * 4
+        print("plda_cohort: %d rows, cohort %d, top-k %d, d = %d, 3 counts, workspace %.0f MB" % (n, n_cohort, top_k, d, ws_bytes / 1e6), flush=True)
+
+        def whole():
+            _lib.call("xv_backend_plda_cohort_stats", _s(), _p(x), d, n, _p(nidx), _p(cohort), d, n_cohort, d, _p(coef), d, 3, _p(g), _p(k0), top_k,
+                      _p(stats), _p(ws), C.c_size_t(ws_bytes))
+
+        def gemm():
+            _lib.call("xv_affine_forward", _s(), _p(x), n, 1, d, 1, _p(cohort), None, _p(ws), n_cohort, ldn, None, None, C.c_size_t(0))
+        us_all, us_gemm = timeit(whole, 5, 1), timeit(gemm, 5, 1)
+        fl = 2.0 * n * n_cohort * d
+        print("  cohort statistics       %9.1f us: GEMM %.1f us (%.1f TF) = %.2f of the op, column terms + fold + selection %.1f us = %.2f"
+              % (us_all, us_gemm, fl / us_gemm / 1e6, us_gemm / us_all, us_all - us_gemm, 1.0 - us_gemm / us_all), flush=True)
+
+
 def cmd_mfcc(argv):
     """Frames per second of xv_mfcc alone and of xv_mfcc + xv_energy_vad on one padded batch (VoxCeleb conf: 16 kHz, 25 / 10 ms, 30 bins, 30
     coefficients); the bytes the kernel has to move (2 S bytes of new samples in, 4 num_ceps bytes out per frame, plus the zeroed padding
@@ -519,7 +555,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "backend": cmd_backend, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
