@@ -39,7 +39,8 @@ extern "C" {
  * built against the earlier header runs unchanged against this library.  The same holds for xv_mfcc_num_frames, xv_mfcc_table_floats,
  * xv_mfcc_tables, xv_mfcc and xv_energy_vad, which bring their own struct (xv_mfcc_config, size-checked like xv_config), and for
  * xv_debug_augment_plan, xv_augment_workspace_bytes and xv_augment with theirs (xv_augment_config), and for xv_resample_num_samples,
- * xv_resample_table_floats, xv_resample_tables, xv_debug_resample_plan and xv_resample with theirs (xv_resample_config). */
+ * xv_resample_table_floats, xv_resample_tables, xv_debug_resample_plan and xv_resample with theirs (xv_resample_config), and for xv_fbank_num_frames,
+ * xv_fbank_table_floats, xv_fbank_tables and xv_fbank with theirs (xv_fbank_config). */
 #define XV_ABI_VERSION 3
 
 const char* xv_last_error(void);
@@ -258,6 +259,51 @@ int xv_mfcc(void* stream, const xv_mfcc_config* cfg, const float* tables_dev, co
  * mask_offsets[i] = i * t.  rows: device int32 [b].  One workgroup per piece.  The VoxCeleb vad.conf: 5.5, 0.5, 2, 0.12. */
 int xv_energy_vad(void* stream, const float* x, const int32_t* rows, int b, int t, int d, float threshold, float mean_scale,
                   int frames_context, float proportion, uint8_t* masks);
+
+/* Log-mel filterbank energies from waveforms: compute-fbank-feats with --dither=0, which is compute-mfcc-feats stopped in front of the
+ * DCT.  Parity is BY RESTATEMENT, as for xv_mfcc: the rules are the specification, tests/fbank_ref.py restates them in fp64 on top of
+ * tests/mfcc_ref.py, the kernel is held against that.  The same kernel body runs both feature kinds; no floating-point atomics, the
+ * output bits depend on the shape of the call only.
+ *
+ * L, S, N, T, the frame's first sample, the reflection, the DC removal, logE (raw_energy: in front of the pre-emphasis, otherwise
+ * behind the window), the pre-emphasis, the Povey window, the FFT and the mel energies E[m] are xv_mfcc's, word for word (above), but
+ * for P[k]: use_power ? |X[k]|^2 : sqrtf(|X[k]|^2).  Then column m of a frame is use_log_fbank ? log(max(E[m], FLT_EPSILON)) : E[m];
+ * with use_energy, column 0 is logE, floored at log(energy_floor) when energy_floor > 0, and the mel columns follow it:
+ * d = num_mel_bins + use_energy floats per frame, d <= 128 (what xv_frontend and xv_cm_encode take; more is refused by name). */
+typedef struct xv_fbank_config {
+    int32_t struct_bytes;             /* = sizeof(xv_fbank_config) of the header the host was built against; anything else is refused */
+    float sample_frequency;           /* 16000 */
+    float frame_length_ms;            /* 25 */
+    float frame_shift_ms;             /* 10 */
+    int32_t num_mel_bins;             /* 23 (compute-fbank-feats' own defaults throughout); <= 128 */
+    float low_freq;                   /* 20 */
+    float high_freq;                  /* 0; <= 0: the Nyquist frequency plus this value */
+    int32_t snip_edges;               /* 1 */
+    float preemphasis;                /* 0.97 */
+    int32_t remove_dc_offset;         /* 1 */
+    int32_t use_energy;               /* 0 */
+    int32_t raw_energy;               /* 1 */
+    float energy_floor;               /* 0 */
+    int32_t use_log_fbank;            /* 1 */
+    int32_t use_power;                /* 1 */
+} xv_fbank_config;
+/* T of an utterance of `samples` samples (xv_mfcc_num_frames' rule); -1 (xv_last_error) for a configuration that is refused.  Host
+ * arithmetic. */
+int64_t xv_fbank_num_frames(const xv_fbank_config* cfg, int64_t samples);
+/* The constant tables of xv_fbank - host arithmetic, no GPU call: the layout of xv_mfcc_tables without its last block (window [L],
+ * twiddles [N / 2][2], mel_bins [bins][3], mel_w [sum of counts]), the same numbers for the same fields.  xv_fbank_table_floats: their
+ * size (0 for a refused configuration); xv_fbank_tables writes them into h_out (`floats` must be that size). */
+size_t xv_fbank_table_floats(const xv_fbank_config* cfg);
+int xv_fbank_tables(const xv_fbank_config* cfg, float* h_out, size_t floats);
+/* out[i][f][:] = the d columns of frame f of utterance i for f < rows_out[i] = min(T_i, t_out), zero rows behind - fp32 [b][t_out][d],
+ * the layout xv_mfcc leaves: xv_frontend, xv_cm_encode and xv_engine_forward_lengths take it as it is.  pcm, offsets, samples: as for
+ * xv_mfcc, the caller guaranteeing the ranges (ops.fbank checks the host arrays before the upload).  tables_dev: what xv_fbank_tables
+ * wrote for the same cfg, on the device.  energy_out: NULL, or fp32 [b][t_out]: logE of every frame by the rule above, floor included
+ * (zeros behind rows_out[i]), WHATEVER use_energy says - with the options of an xv_mfcc_config it holds the bits of that call's column
+ * 0, so xv_energy_vad(x = energy_out, d = 1) gives the decisions an MFCC pass with use_energy gives: the second feature pass Kaldi
+ * recipes run for the VAD of an fbank system is not needed.  One launch, xv_mfcc's grid. */
+int xv_fbank(void* stream, const xv_fbank_config* cfg, const float* tables_dev, const int16_t* pcm, const int64_t* offsets,
+             const int32_t* samples, int b, int t_out, float* out, int32_t* rows_out, float* energy_out);
 
 /* Reverberation and additive-noise augmentation of waveforms: what the training list of the recipe pipes through wav-reverberate
  * (egs/voxceleb/v1/run.sh:68-130: the reverberated, noise, music and babble copies of the clean list), with --normalize-output=true as

@@ -107,6 +107,31 @@ class XvMfccConfig(_SizedConfig):
                     energy_floor=0.0)
 
 
+class XvFbankConfig(_SizedConfig):
+    """Mirror of `struct xv_fbank_config` (include/xvector_hip.h) with its defaults - compute-fbank-feats' own, dither 0."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("sample_frequency", C.c_float),
+        ("frame_length_ms", C.c_float),
+        ("frame_shift_ms", C.c_float),
+        ("num_mel_bins", C.c_int32),
+        ("low_freq", C.c_float),
+        ("high_freq", C.c_float),
+        ("snip_edges", C.c_int32),
+        ("preemphasis", C.c_float),
+        ("remove_dc_offset", C.c_int32),
+        ("use_energy", C.c_int32),
+        ("raw_energy", C.c_int32),
+        ("energy_floor", C.c_float),
+        ("use_log_fbank", C.c_int32),
+        ("use_power", C.c_int32),
+    ]
+    DEFAULTS = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, num_mel_bins=23, low_freq=20.0, high_freq=0.0,
+                    snip_edges=1, preemphasis=0.97, remove_dc_offset=1, use_energy=0, raw_energy=1, energy_floor=0.0, use_log_fbank=1,
+                    use_power=1)
+
+
 class XvAugmentConfig(_SizedConfig):
     """Mirror of `struct xv_augment_config` (include/xvector_hip.h) with its defaults - wav-reverberate --shift-output=true
     --normalize-output=true at 16 kHz."""
@@ -230,6 +255,10 @@ SIGNATURES = {
     "xv_mfcc_tables": (_I, [_VP, _VP, _SZ]),
     "xv_mfcc": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "xv_energy_vad": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _F, _I, _F, _VP]),
+    "xv_fbank_num_frames": (C.c_int64, [_VP, C.c_int64]),
+    "xv_fbank_table_floats": (_SZ, [_VP]),
+    "xv_fbank_tables": (_I, [_VP, _VP, _SZ]),
+    "xv_fbank": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "xv_debug_augment_plan": (_I, [C.c_int64, C.c_int64, C.POINTER(_I)]),
     "xv_augment_workspace_bytes": (_SZ, [_I, _I, C.c_int64]),
     "xv_augment": (_I, [_VP, _VP, _I, _I, C.c_int64, _VP, _VP, _VP, _VP, _SZ, _I, _VP, _SZ, _VP, _VP, _VP, _VP]),

@@ -456,6 +456,37 @@ class VoicedRows(object):
         return VoicedRows(self.item, self.voiced, self.first + start, length, total=self.total)
 
 
+class DeviceBatch(object):
+    """Raw features that are on the device already, as one feature call left them (misc.features.FeatureExtractor.on_device): x float32
+    [b, t, d], rows int32 [b] (raw frames per utterance), masks uint8 [b, t] or None (every frame is kept) - device tensors - and the two
+    per-utterance counts the host needs, as lists: frames (raw) and kept (after selection)."""
+    __slots__ = ("x", "rows", "masks", "frames", "kept")
+
+    def __init__(self, x, rows, masks, frames, kept):
+        self.x, self.rows, self.masks, self.frames, self.kept = x, rows, masks, [int(n) for n in frames], [int(n) for n in kept]
+        assert len(self.frames) == len(self.kept) == int(x.shape[0]) and (masks is None or tuple(masks.shape) == tuple(x.shape[:2]))
+
+
+class DeviceRows(object):
+    """VoicedRows for an utterance of a DeviceBatch: utterance `index` of `batch`, of whose kept frames this piece covers
+    [first, first + count).  shape and row_range() count kept frames.  Trainer.predict_batch gathers the raw rows on the device and runs
+    the front end (CMN, selection) there: the features never come to the host."""
+    __slots__ = ("batch", "index", "total", "first", "count")
+
+    def __init__(self, batch, index, first=0, count=None):
+        self.batch, self.index, self.total, self.first = batch, int(index), batch.kept[index], int(first)
+        self.count = self.total - self.first if count is None else int(count)
+        assert 0 <= self.first and 0 <= self.count and self.first + self.count <= self.total
+
+    @property
+    def shape(self):
+        return (self.count, int(self.batch.x.shape[2]))
+
+    def row_range(self, start, length):
+        assert 0 <= start and start + length <= self.count
+        return DeviceRows(self.batch, self.index, self.first + start, length)
+
+
 def read_mat_ark_packed(file_or_fd, block_bytes=8 << 20):
     """read_mat_ark for the batched extraction driver: 'CM ' matrices come back undecoded as PackedMatrix, every other format as the
     float32 matrix read_mat gives.  The archive is pulled in blocks of `block_bytes` and the records are cut out of the block as views -

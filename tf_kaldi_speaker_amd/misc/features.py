@@ -1,5 +1,6 @@
-"""MFCC features and energy VAD decisions from waveforms on the GPU: the host side of xv_mfcc / xv_energy_vad (include/xvector_hip.h), what
-steps/make_mfcc.sh --mfcc-config conf/mfcc.conf and sid/compute_vad_decision.sh do in the reference recipe (egs/voxceleb/v1/run.sh:59-63).
+"""MFCC or filterbank features and energy VAD decisions from waveforms on the GPU: the host side of xv_mfcc / xv_fbank / xv_energy_vad
+(include/xvector_hip.h), what steps/make_mfcc.sh --mfcc-config conf/mfcc.conf (steps/make_fbank.sh --fbank-config conf/fbank.conf) and
+sid/compute_vad_decision.sh do in the reference recipe (egs/voxceleb/v1/run.sh:59-63).
 
     mfcc = MfccOptions.from_conf("conf/mfcc.conf")           # Kaldi --name=value lines; what is not supported is refused by name
     vad = VadOptions.from_conf("conf/vad.conf")
@@ -7,8 +8,8 @@ steps/make_mfcc.sh --mfcc-config conf/mfcc.conf and sid/compute_vad_decision.sh 
     for feats, decisions in fx.extract([read_wav(rx, mfcc, key) for key, rx in entries]): ...
 
 This is the --dither=0 program: Kaldi's default dither of 1.0 adds noise from its own generator and is not reproducible across Kaldi runs
-either.  Defaults are the VoxCeleb conf's (30 bins, 30 coefficients, 20 - 7600 Hz, snip-edges false), NOT compute-mfcc-feats' own: a conf
-file should state what it relies on."""
+either.  MfccOptions' defaults are the VoxCeleb conf's (30 bins, 30 coefficients, 20 - 7600 Hz, snip-edges false), NOT compute-mfcc-feats'
+own: a conf file should state what it relies on.  FbankOptions' defaults are compute-fbank-feats' own."""
 import io
 import wave
 
@@ -115,9 +116,34 @@ class MfccOptions(_Options):
            "vtln-warp": "no VTLN", "vtln-map": "no VTLN", "utt2spk": "no VTLN",
            "vtln-low": "no VTLN", "vtln-high": "no VTLN", "subtract-mean": "extract.py --cmn-window normalises"}
 
+    KIND = "mfcc"      # the ops that take config(): ops.mfcc, ops.mfcc_tables, ops.mfcc_num_frames
+
     def config(self):
         """The xv_mfcc_config of these options."""
         return _lib.XvMfccConfig(**{k: getattr(self, k) for k in self.DEFAULTS if k not in self.HOST_ONLY})
+
+    def feature_dim(self):
+        return int(self.num_ceps)
+
+
+class FbankOptions(_Options):
+    """The options of compute-fbank-feats this program takes; fields are those of xv_fbank_config plus MfccOptions' host-side ones (channel,
+    allow_downsample, allow_upsample).  The defaults are compute-fbank-feats' own (23 bins, 20 Hz .. the Nyquist frequency, snip-edges
+    true, no energy column): Kaldi's fbank confs rely on them.  What is refused, and why, is what MfccOptions refuses."""
+    PROGRAM = "compute-fbank-feats"
+    KIND = "fbank"
+    HOST_ONLY = MfccOptions.HOST_ONLY
+    DEFAULTS = dict(_lib.XvFbankConfig.DEFAULTS, channel=-1, allow_downsample=0, allow_upsample=0)
+    SUPPORTED = dict({name: spec for name, spec in MfccOptions.SUPPORTED.items() if name not in ("num-ceps", "cepstral-lifter")},
+                     **{"use-log-fbank": ("use_log_fbank", _bool), "use-power": ("use_power", _bool)})
+    FIXED, WHY = MfccOptions.FIXED, MfccOptions.WHY
+
+    def config(self):
+        """The xv_fbank_config of these options."""
+        return _lib.XvFbankConfig(**{k: getattr(self, k) for k in self.DEFAULTS if k not in self.HOST_ONLY})
+
+    def feature_dim(self):
+        return int(self.num_mel_bins) + (1 if self.use_energy else 0)
 
 
 class VadOptions(_Options):
@@ -178,22 +204,55 @@ def read_wav_rate(rxfilename, options=None, key="", any_rate=None):
     return np.ascontiguousarray(x[:, options.channel]), rate
 
 
-class FeatureExtractor(object):
-    """MFCCs and VAD decisions of waveforms.  The constant tables are built once (xv_mfcc_tables, host arithmetic) and kept on the device;
-    extract() cuts its list into batches such that the padded outputs and the samples of one call stay within workspace_bytes."""
+def read_wav_scp(path, options):
+    """(key, samples, sample rate) of every `key rxfilename` line of a wav.scp, read by read_wav_rate under options' rate rules - the
+    reader of make_mfcc.py, make_fbank.py and extract.py's wav mode.  ValueError: a malformed line, or what read_wav_rate refuses."""
+    with open(path, "r") as scp:
+        for line in scp:
+            if not line.strip():
+                continue
+            parts = line.strip().split(None, 1)
+            if len(parts) != 2:
+                raise ValueError("%s: `key rxfilename` is expected, got `%s`" % (path, line.strip()))
+            wav, rate = read_wav_rate(parts[1], options, parts[0])
+            yield parts[0], wav, rate
 
-    def __init__(self, mfcc=None, vad=None, device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+
+class FeatureExtractor(object):
+    """Features (MFCCs or filterbank energies) and VAD decisions of waveforms.  mfcc: a MfccOptions or a FbankOptions - the kernel follows
+    the option set.  The constant tables are built once (xv_mfcc_tables / xv_fbank_tables, host arithmetic) and kept on the device;
+    extract() cuts its list into batches such that the padded outputs and the samples of one call stay within workspace_bytes.  The VAD
+    reads the log-energy: column 0 of the MFCCs (the conf must keep --use-energy=true, as Kaldi's does), xv_fbank's energy_out for
+    filterbanks - whatever their --use-energy says, so an fbank system needs no second feature pass for its decisions.  with_vad False:
+    no decisions are computed, None stands in their place."""
+
+    def __init__(self, mfcc=None, vad=None, device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES, with_vad=True):
         self.torch, self.ops, self.device = device_ops(device)
-        self.mfcc, self.vad = mfcc or MfccOptions(), vad or VadOptions()
+        self.mfcc, self.vad = mfcc or MfccOptions(), vad or VadOptions()      # self.mfcc: the feature options of either kind
         self.cfg = self.mfcc.config()
-        self.tables = self.torch.from_numpy(self.ops.mfcc_tables(self.cfg)).to(self.device)
-        self.workspace_bytes = int(workspace_bytes)
+        self.tables = self.torch.from_numpy(getattr(self.ops, self.kind + "_tables")(self.cfg)).to(self.device)
+        self.workspace_bytes, self.with_vad = int(workspace_bytes), bool(with_vad)
+
+    kind = property(lambda self: self.mfcc.KIND)                 # "mfcc" or "fbank": the ops that take cfg
+    dim = property(lambda self: self.mfcc.feature_dim())        # floats per frame
 
     def num_frames(self, samples):
-        return self.ops.mfcc_num_frames(self.cfg, samples)
+        return getattr(self.ops, self.kind + "_num_frames")(self.cfg, samples)
 
-    def _cost(self, b, t_max, total, coded=False):      # coded: the 'CM ' images as well, a byte per value
-        return b * max(t_max, 1) * ((5 if coded else 4) * self.mfcc.num_ceps + 1) + 2 * total
+    def on_device(self, pcm, offsets, lengths, t_out):
+        """One call on utterances that are on the device (extract_packed's arguments, not cut): -> (features [b, t_out, dim], rows int32 [b],
+        masks uint8 [b, t_out] or None without with_vad), device tensors - the layout ops.frontend and the engine read."""
+        ops, v, with_vad = self.ops, self.vad, self.with_vad
+        if self.kind == "fbank":
+            x, rows, energy = ops.fbank(self.cfg, self.tables, pcm, offsets, lengths, t_out, with_energy=with_vad)
+        else:
+            x, rows = ops.mfcc(self.cfg, self.tables, pcm, offsets, lengths, t_out)
+            energy = x
+        masks = ops.energy_vad(energy, rows, v.threshold, v.mean_scale, v.frames_context, v.proportion) if with_vad else None
+        return x, rows, masks
+
+    def _cost(self, b, t_max, total, coded=False):      # coded: the 'CM ' images as well, a byte per value; + 4: fbank's energy column
+        return b * max(t_max, 1) * ((5 if coded else 4) * self.dim + 1 + (4 if self.kind == "fbank" else 0)) + 2 * total
 
     def _batches(self, frames, lengths, coded=False):
         grow = lambda i, b=0, t_max=0, total=0: (b + 1, max(t_max, frames[i]), total + lengths[i])
@@ -203,10 +262,10 @@ class FeatureExtractor(object):
         return greedy_batches(len(frames), grow, cost_of, self.workspace_bytes, max_items=65535, too_big=too_big)
 
     def _nothing(self, cm_header):      # what an utterance too short for one frame gives
-        return (np.zeros((0, self.mfcc.num_ceps), np.float32) if cm_header is None else b"", np.zeros(0, np.float32))
+        return (np.zeros((0, self.dim), np.float32) if cm_header is None else b"", np.zeros(0, np.float32) if self.with_vad else None)
 
     def extract(self, waves, cm_header=None):
-        """waves: int16 arrays -> [(features float32 [T, num_ceps], decisions float32 [T] of 1.0 / 0.0)] in order; T may be 0.
+        """waves: int16 arrays -> [(features float32 [T, dim], decisions float32 [T] of 1.0 / 0.0)] in order; T may be 0.
         cm_header ("uniform" or "quartiles"): the features come back 'CM '-compressed on the device instead (ops.cm_encode: the bytes
         dataset.kaldi_io.write_compressed_mat(header=cm_header) gives for the float features) - [(the image behind the "CM " token, a bytes-like
         object, empty when T is 0; decisions)]: a byte per value crosses to the host instead of four."""
@@ -259,11 +318,43 @@ class FeatureExtractor(object):
                 out[i] = r
         return out
 
+    def device_batches(self, waves, rates):
+        """extract_at_rates for a consumer on the device (extract.py's wav mode): one feature call per sample rate among `rates`, the
+        others resampled first, and NOTHING is read back but one int32 per utterance - how many frames its mask keeps (without with_vad
+        all of them, and nothing at all is read).  Yields (members: the indices into waves, samples per member at sample_frequency,
+        kaldi_io.DeviceBatch or None when no member holds a sample).  The caller bounds the list: one call holds its padded features."""
+        try:
+            from ..dataset.kaldi_io import DeviceBatch
+        except (ImportError, ValueError):
+            from dataset.kaldi_io import DeviceBatch
+        fs = self.mfcc.sample_frequency
+        groups = {}
+        for i, rate in enumerate(rates):
+            groups.setdefault(int(rate), []).append(i)
+        for rate, members in groups.items():
+            if rate == fs:
+                group = [np.ascontiguousarray(waves[i], dtype=np.int16).reshape(-1) for i in members]
+                lengths = [len(w) for w in group]
+                if sum(lengths) == 0:
+                    yield members, lengths, None
+                    continue
+                pcm, offsets = self.torch.from_numpy(np.concatenate(group)).to(self.device), exclusive_offsets(lengths)
+            else:
+                if not (self.mfcc.allow_downsample if rate > fs else self.mfcc.allow_upsample):
+                    raise ValueError("sample rate %d Hz, but --sample-frequency=%g (there is no resampling without --allow-%s=true)"
+                                     % (rate, fs, "downsample" if rate > fs else "upsample"))
+                pcm, offsets, lengths, _ = self.resampler(rate).run([waves[i] for i in members])
+                lengths = [int(n) for n in lengths]
+            frames = [self.num_frames(n) for n in lengths]
+            x, rows, masks = self.on_device(pcm, offsets, np.asarray(lengths, np.int64), max(max(frames), 1))
+            kept = frames if masks is None else masks.sum(dim=1, dtype=self.torch.int32).cpu().tolist()
+            yield members, lengths, DeviceBatch(x, rows, masks, frames, kept)
+
     def extract_packed(self, pcm, offsets, lengths, cm_header=None):
         """The same for utterances that are on the device already: pcm an int16 device tensor, utterance i its samples offsets[i] ..
         offsets[i] + lengths[i] (host arrays) - what misc.augment.Augmenter.run returns.  Nothing is copied; the calls are cut as by
         extract()."""
-        ops, v = self.ops, self.vad
+        ops = self.ops
         offsets, lengths = np.asarray(offsets, np.int64), [int(n) for n in lengths]
         frames = [self.num_frames(n) for n in lengths]
         out = [None] * len(lengths)
@@ -273,22 +364,22 @@ class FeatureExtractor(object):
                     out[i] = self._nothing(cm_header)
                 continue
             t_out = max(max(frames[i] for i in batch), 1)
-            x, rows = ops.mfcc(self.cfg, self.tables, pcm, offsets[batch], np.asarray([lengths[i] for i in batch], np.int64), t_out)
-            masks = ops.energy_vad(x, rows, v.threshold, v.mean_scale, v.frames_context, v.proportion)
-            m_h, r_h = masks.cpu().numpy(), rows.cpu().numpy()
+            x, rows, masks = self.on_device(pcm, offsets[batch], np.asarray([lengths[i] for i in batch], np.int64), t_out)
+            r_h = rows.cpu().numpy()
+            decisions = (lambda j, i: None) if masks is None else (lambda j, i, m_h=masks.cpu().numpy(): m_h[j, :frames[i]].astype(np.float32))
             for j, i in enumerate(batch):
                 assert r_h[j] == frames[i], (i, r_h[j], frames[i])
             if cm_header is None:
                 x_h = x.cpu().numpy()
                 for j, i in enumerate(batch):
-                    out[i] = (x_h[j, :frames[i]].copy(), m_h[j, :frames[i]].astype(np.float32))
+                    out[i] = (x_h[j, :frames[i]].copy(), decisions(j, i))
                 continue
             kept = [j for j, i in enumerate(batch) if frames[i] > 0]      # a 'CM ' matrix has at least one row
             if len(kept) < len(batch):
                 x = x[self.torch.as_tensor(kept, device=x.device)] if kept else None
             images = iter(encoded_images(ops, x, [frames[batch[j]] for j in kept], cm_header) if kept else ())
             for j, i in enumerate(batch):
-                out[i] = (next(images) if frames[i] > 0 else b"", m_h[j, :frames[i]].astype(np.float32))
+                out[i] = (next(images) if frames[i] > 0 else b"", decisions(j, i))
         return out
 
 
@@ -297,6 +388,13 @@ def encoded_images(ops, x, rows, cm_header):
     buf, offsets = ops.cm_encode(x, np.asarray(rows, np.int64), header=cm_header)
     raw = memoryview(buf.cpu().numpy())
     return [raw[int(o):int(o + n)] for o, n in zip(offsets, ops.cm_image_bytes(rows, x.shape[2]))]
+
+
+def rows_of(feats, d):
+    """Frames of what FeatureExtractor.extract returns for an utterance: a float matrix, or a 'CM ' image of d columns (empty: none)."""
+    if isinstance(feats, np.ndarray):
+        return int(feats.shape[0])
+    return (len(feats) - 16 - 8 * d) // d if len(feats) else 0
 
 
 def write_cm_image(fd, image, key=""):

@@ -29,7 +29,7 @@ try:
     from ..parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from ..dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
     from ..misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state, plan_length_batches
-    from ..dataset.kaldi_io import PackedMatrix, VoicedRows
+    from ..dataset.kaldi_io import DeviceRows, PackedMatrix, VoicedRows
     from ..misc import tf_checkpoint
     from .tdnn import tdnn, extended_tdnn, engine_config, collect_endpoints, check_params
     from . import loss as _loss
@@ -39,7 +39,7 @@ except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_RO
     from parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
     from misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state, plan_length_batches
-    from dataset.kaldi_io import PackedMatrix, VoicedRows
+    from dataset.kaldi_io import DeviceRows, PackedMatrix, VoicedRows
     from misc import tf_checkpoint
     from model.tdnn import tdnn, extended_tdnn, engine_config, collect_endpoints, check_params
     from model import loss as _loss
@@ -482,7 +482,9 @@ class Trainer(object):
         cmn_window / voiced: the recipe's feature pipe on the GPU (Engine.frontend) for items that are RAW features - sliding-window
         CMN over cmn_window frames (0 = off), then the frames whose entry in voiced[i] (one uint8 array per item; None = all) is
         non-zero.  An item may also be a kaldi_io.VoicedRows (raw utterance + mask + a range of its kept frames: extract.py's chunks).
-        Lengths - the batch plan, the receptive-field check - then count the frames left after selection."""
+        Lengths - the batch plan, the receptive-field check - then count the frames left after selection.
+        Items of the third kind, kaldi_io.DeviceRows (all of them, then), are raw features and masks that are on the device already -
+        extract.py's wav mode: _predict_device."""
         if not self.is_loaded:
             if os.path.isfile(os.path.join(self.model, "checkpoint")):
                 self.load()
@@ -492,6 +494,10 @@ class Trainer(object):
         if n == 0:
             return np.zeros((0, 0), np.float32)
         cmn_window = int(cmn_window)
+        if any(isinstance(it, DeviceRows) for it in items):
+            if voiced is not None or not all(isinstance(it, DeviceRows) for it in items):
+                raise ValueError("predict_batch: DeviceRows items carry their own masks (voiced must be None) and do not mix with host items")
+            return self._predict_device(items, return_device, cmn_window)
         if voiced is not None and len(voiced) != n:
             raise ValueError("predict_batch: %d voicing masks for %d items" % (len(voiced), n))
         pieces = None      # the front end is on: every item as a VoicedRows (raw utterance, mask, range of kept frames)
@@ -616,6 +622,77 @@ class Trainer(object):
         if return_device:
             # nothing here waits for the GPU (the permutation back to the caller's order is applied on the host after the read-back: an
             # index tensor uploaded from pageable memory would have made this call wait for the whole window's forward passes)
+            return _PendingEmbeddings(dev, inv)
+        emb = dev.cpu().numpy()[inv]
+        self.endpoints = OrderedDict([(node, emb)])
+        return emb
+
+    def _predict_device(self, items, return_device, cmn_window):
+        """predict_batch for kaldi_io.DeviceRows: the pieces are planned by their kept length exactly as host items are - whichever
+        DeviceBatch they sit in - and a batch of the plan gathers its utterances' raw rows on the device (index_select, cut at the batch's
+        longest raw utterance: the padded block a host batch would upload) and runs Engine.frontend on them with the DeviceBatches' masks,
+        so the front end and the network see what they see when the same features come from an archive.  Nothing but the embeddings
+        leaves the device."""
+        n, dim, node, min_frames = len(items), self.dim, self.params.embedding_node, self.engine.min_frames
+        for i, it in enumerate(items):
+            if it.shape[1] != dim:
+                raise ValueError("predict_batch: item %d has shape %s, the model expects [frames, %d]" % (i, tuple(it.shape), dim))
+            if it.count < min_frames:
+                raise ValueError("predict_batch: item %d has %d frames, fewer than the network's receptive field (%d)" % (i, it.count, min_frames))
+        sources, where = [], {}      # the DeviceBatches of this call, in order of appearance
+        for it in items:
+            if id(it.batch) not in where:
+                where[id(it.batch)] = len(sources)
+                sources.append(it.batch)
+        if len({src.masks is None for src in sources}) != 1:
+            raise ValueError("predict_batch: DeviceRows items with and without masks do not mix")
+        src_of = [where[id(it.batch)] for it in items]
+        plan = plan_length_batches([it.count for it in items], self.PREDICT_ROWS, self.PREDICT_CHUNKS)
+        self._ensure_capacity(max(len(idx) for idx, _ in plan), max(t for _, t in plan), rows=max(self.PREDICT_ROWS, max(len(idx) * t for idx, t in plan)))
+        eng = self.engine      # (the engine that has the capacity)
+        # the sources' frame counts and masks back to back (a copy only when a call spans several sources: the end of a feature window)
+        row_base = np.concatenate([[0], np.cumsum([len(src.frames) for src in sources])])
+        mask_base = np.concatenate([[0], np.cumsum([len(src.frames) * int(src.x.shape[1]) for src in sources])])
+        rows_all = sources[0].rows if len(sources) == 1 else torch.cat([src.rows for src in sources])
+        masks_all = None
+        if sources[0].masks is not None:
+            masks_all = sources[0].masks.reshape(-1) if len(sources) == 1 else torch.cat([src.masks.reshape(-1) for src in sources])
+        # per piece, in plan order: its utterance's index in its source and among all sources, the byte offset of its mask, first, count
+        flat = [i for idx, _ in plan for i in idx]
+        meta = torch.empty((5, len(flat)), dtype=torch.int64, pin_memory=True)
+        mv = meta.numpy()
+        mv[0] = [items[i].index for i in flat]
+        mv[1] = [row_base[src_of[i]] + items[i].index for i in flat]
+        mv[2] = [mask_base[src_of[i]] + items[i].index * int(items[i].batch.x.shape[1]) for i in flat]
+        mv[3] = [items[i].first for i in flat]
+        mv[4] = [items[i].count for i in flat]
+        meta_dev = meta.to(eng.device, non_blocking=True)
+        range_dev = meta_dev[3:5].to(torch.int32)
+        outs, cursor = [], 0
+        for idx, t in plan:
+            sl = slice(cursor, cursor + len(idx))
+            cursor += len(idx)
+            t_raw = max(items[i].batch.frames[items[i].index] for i in idx)
+            here = sorted({src_of[i] for i in idx})
+            if len(here) == 1:
+                xr = sources[here[0]].x[:, :t_raw].index_select(0, meta_dev[0, sl])
+            else:
+                xr = torch.zeros((len(idx), t_raw, dim), dtype=torch.float32, device=eng.device)
+                for g in here:
+                    pos = torch.as_tensor([k for k, i in enumerate(idx) if src_of[i] == g], dtype=torch.int64, device=eng.device)
+                    tg = min(t_raw, int(sources[g].x.shape[1]))
+                    xr[pos, :tg] = sources[g].x[:, :tg].index_select(0, meta_dev[0, sl].index_select(0, pos))
+            x, rows = eng.frontend(xr, rows_all.index_select(0, meta_dev[1, sl]), cmn_window, masks_all, meta_dev[2, sl] if masks_all is not None else None,
+                                   range_dev[0, sl], range_dev[1, sl], t)
+            eng.forward_lengths(x, rows)
+            emb = eng.endpoint(node)
+            if emb.shape[0] != len(idx):
+                raise ValueError("predict_batch: embedding node %s is a frame-level endpoint (%d rows for %d utterances)" % (node, emb.shape[0], len(idx)))
+            outs.append(emb)
+        dev = torch.cat(outs, dim=0)
+        inv = np.empty(n, np.int64)
+        inv[np.asarray(flat)] = np.arange(n)
+        if return_device:
             return _PendingEmbeddings(dev, inv)
         emb = dev.cpu().numpy()[inv]
         self.endpoints = OrderedDict([(node, emb)])

@@ -56,6 +56,16 @@ ARGUMENTS = {
                                                                         "the VoxCeleb conf/mfcc.conf values.")),
     "vad_config": (("--vad-config",), dict(type=str, default="", help="Kaldi conf file of compute-vad-decision options.  Empty: the VoxCeleb "
                                                                       "conf/vad.conf values.")),
+    "fbank_config": (("--fbank-config",), dict(type=str, default="", help="Kaldi conf file of compute-fbank-feats options (--name=value lines).  "
+                                                                          "Empty: that program's own defaults.")),
+    "wav_mfcc_config": (("--mfcc-config",), dict(type=str, default="", help="Kaldi conf file of compute-mfcc-feats options: the rspecifier names a "
+                                                                            "wav.scp and the MFCCs are computed on the GPU, in front of "
+                                                                            "--cmn-window.  Not together with --fbank-config.")),
+    "wav_fbank_config": (("--fbank-config",), dict(type=str, default="", help="Kaldi conf file of compute-fbank-feats options: the rspecifier names "
+                                                                              "a wav.scp and the filterbank energies are computed on the GPU.")),
+    "wav_vad_config": (("--vad-config",), dict(type=str, default="", help="Kaldi conf file of compute-vad-decision options, with --mfcc-config or "
+                                                                          "--fbank-config: the decisions are computed on the GPU and the "
+                                                                          "voiced frames selected.  Empty: every frame is kept.")),
     "compress": (("--compress",), dict(type=str, default="true", choices=("true", "false"),
                                        help="true: 'CM ' compressed feature matrices (copy-feats --compress=true); false: 'FM '.")),
     "prep_cmn_window": (("--cmn-window",), dict(type=int, default=300, help="Sliding-window CMN over this many frames on the GPU (apply-cmvn-sliding "
@@ -96,6 +106,8 @@ ARGUMENTS = {
     "wav_scp": (("wav_scp",), dict(type=str, help="Kaldi wav.scp: `key rxfilename` per line, the rxfilename a RIFF PCM-16 file or `command |`.")),
     "feats_wspecifier": (("feats_wspecifier",), dict(type=str, help="`ark,scp:feats.ark,feats.scp` (or `ark:feats.ark`): the feature table.")),
     "vad_wspecifier": (("vad_wspecifier",), dict(type=str, help="`ark,scp:vad.ark,vad.scp` (or `ark:vad.ark`): the table of VAD decisions.")),
+    "vad_wspecifier_optional": (("vad_wspecifier",), dict(type=str, nargs="?", default="", help="`ark,scp:vad.ark,vad.scp` (or `ark:vad.ark`): the table "
+                                                                                               "of VAD decisions.  Left out: none are computed.")),
     "raw_rspecifier": (("raw_rspecifier",), dict(type=str, help="`ark:raw_feats.ark` (an archive or an input pipe): the raw features.")),
     "prepared_wspecifier": (("prepared_wspecifier",), dict(type=str, help="`ark,scp:out.ark,out.scp` (or `ark:out.ark`): the prepared features.")),
     "train_rspecifier": (("train_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the training vectors.")),

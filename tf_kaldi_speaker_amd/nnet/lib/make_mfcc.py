@@ -24,6 +24,8 @@ nnet/lib/augment.py followed by this program on its wav.scp.  Without the option
 --sample-frequency are read at their own rate and resampled on the device in front of the MFCC kernels, grouped by rate (misc/resample.py:
 the same bytes as nnet/lib/resample.py --to-rate followed by this program on its wav.scp; the samples are rounded to int16 in between, where
 compute-mfcc-feats keeps floats).  Without them a file at another rate is refused, as before.
+make_fbank.py is this program with --fbank-config (main("fbank")); extract.py --mfcc-config / --fbank-config reads the same wav.scp with
+the same reader and goes on to the embeddings without writing either table.
 """
 import sys
 import time
@@ -39,20 +41,26 @@ WINDOW_UTTERANCES = 256
 WINDOW_SAMPLES = 64 << 20
 
 
-def main():
+def main(kind="mfcc"):
+    """kind "mfcc": this program.  "fbank": make_fbank.py - --fbank-config in place of --mfcc-config (misc.features.FbankOptions), the VAD
+    wspecifier optional; everything else, `mfcc` the feature options of either kind, is the code below."""
     log = _cli.logger()
-    args = _cli.parser_for("gpu", "mfcc_config", "vad_config", "compress", "write_utt2num_frames", "augment_plan", "rir_scp", "noise_scp",
-                           "augment_config", "resample_signals", "wav_scp", "feats_wspecifier", "vad_wspecifier").parse_args()
+    args = _cli.parser_for("gpu", kind + "_config", "vad_config", "compress", "write_utt2num_frames", "augment_plan", "rir_scp", "noise_scp",
+                           "augment_config", "resample_signals", "wav_scp", "feats_wspecifier",
+                           "vad_wspecifier" if kind == "mfcc" else "vad_wspecifier_optional").parse_args()
+    options_of, conf = (features.FbankOptions if kind == "fbank" else features.MfccOptions), getattr(args, kind + "_config")
     try:
-        mfcc = features.MfccOptions.from_conf(args.mfcc_config) if args.mfcc_config else features.MfccOptions()
+        mfcc = options_of.from_conf(conf) if conf else options_of()
         vad = features.VadOptions.from_conf(args.vad_config) if args.vad_config else features.VadOptions()
     except ValueError as e:
         sys.exit(str(e))
     import torch
     device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
-    log.info("[INFO] MFCC without dither (--dither=0): on digital silence the features sit at the FLT_EPSILON floors; --energy-floor lifts the energy.")
-    fx = features.FeatureExtractor(mfcc, vad, device)
-    feats_out, vad_out = _cli.Table(args.feats_wspecifier, "feats_wspecifier"), _cli.Table(args.vad_wspecifier, "vad_wspecifier")
+    log.info("[INFO] %s without dither (--dither=0): on digital silence the features sit at the FLT_EPSILON floors; --energy-floor lifts the energy."
+             % ("MFCC" if kind == "mfcc" else "Filterbank energies"))
+    fx = features.FeatureExtractor(mfcc, vad, device, with_vad=bool(args.vad_wspecifier))
+    feats_out = _cli.Table(args.feats_wspecifier, "feats_wspecifier")
+    vad_out = _cli.Table(args.vad_wspecifier, "vad_wspecifier") if args.vad_wspecifier else None      # make_fbank.py may leave it out
     counts = open(args.write_utt2num_frames, "w") if args.write_utt2num_frames else None
     # 'CM ' with evenly spaced header points: the rounding error stays below (max - min) / 255 of a column whatever its distribution
     # (Kaldi's quartile points let it reach (max - min) / 126); every 'CM ' reader decodes it.  The matrices are compressed on the device
@@ -63,19 +71,21 @@ def main():
     window, rates, window_samples = [], [], 0
 
     def write(key, samples, feats, decisions):
-        frames = len(decisions)
+        frames = len(decisions) if decisions is not None else features.rows_of(feats, fx.dim)
         if frames == 0:
             log.info("[INFO] Key %s has %d samples, too few for one frame, skip." % (key, samples))
             stats["skipped"] += 1
             return
-        log.info("[INFO] Key %s: %d samples, %d frames, %d voiced." % (key, samples, frames, int(decisions.sum())))
+        voiced = int(decisions.sum()) if decisions is not None else 0
+        log.info("[INFO] Key %s: %d samples, %d frames%s." % (key, samples, frames, ", %d voiced" % voiced if decisions is not None else ""))
         feats_out.write(key, lambda fd, k: write_mat(fd, feats, key=k))
-        vad_out.write(key, lambda fd, k: kaldi_io.write_vec_flt(fd, decisions, key=k))
+        if vad_out is not None:
+            vad_out.write(key, lambda fd, k: kaldi_io.write_vec_flt(fd, decisions, key=k))
         if counts is not None:
             counts.write("%s %d\n" % (key, frames))
         stats["utts"] += 1
         stats["frames"] += frames
-        stats["voiced"] += int(decisions.sum())
+        stats["voiced"] += voiced
 
     def flush():
         if all(rate == mfcc.sample_frequency for rate in rates):
@@ -131,30 +141,24 @@ def main():
         if window:
             flush_augmented(aug)
     else:
-        with open(args.wav_scp, "r") as scp:
-            for line in scp:
-                if not line.strip():
-                    continue
-                parts = line.strip().split(None, 1)
-                if len(parts) != 2:
-                    sys.exit("%s: `key rxfilename` is expected, got `%s`" % (args.wav_scp, line.strip()))
-                try:
-                    wav, rate = features.read_wav_rate(parts[1], mfcc, parts[0])
-                except ValueError as e:
-                    sys.exit(str(e))
-                window.append((parts[0], wav))
+        try:
+            for key, wav, rate in features.read_wav_scp(args.wav_scp, mfcc):
+                window.append((key, wav))
                 rates.append(rate)
                 window_samples += len(wav)
                 if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
                     flush()
                     window_samples = 0
+        except ValueError as e:
+            sys.exit(str(e))
         flush()
     feats_out.close()
-    vad_out.close()
+    if vad_out is not None:
+        vad_out.close()
     if counts is not None:
         counts.close()
-    log.info("[INFO] Computed features of %d utterances (%d frames, %d voiced) in %.2f s, skipped %d."
-             % (stats["utts"], stats["frames"], stats["voiced"], time.time() - stats["t0"], stats["skipped"]))
+    log.info("[INFO] Computed features of %d utterances (%d frames%s) in %.2f s, skipped %d."
+             % (stats["utts"], stats["frames"], ", %d voiced" % stats["voiced"] if vad_out is not None else "", time.time() - stats["t0"], stats["skipped"]))
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""Op-level wrappers of the pipeline stages around the network (include/xvector_hip.h): the extraction front end, MFCC and energy VAD,
-augmentation, cosine / AS-norm scoring and the LDA / PLDA back end with its cohort statistics.  ops.py re-exports every public name here: callers write ops.mfcc.
+"""Op-level wrappers of the pipeline stages around the network (include/xvector_hip.h): the extraction front end, MFCC, filterbank and energy
+VAD, augmentation, cosine / AS-norm scoring and the LDA / PLDA back end with its cohort statistics.  ops.py re-exports every public name here: callers write ops.mfcc.
 Their kernels check none of the index arrays they are handed, so much of this is validation (_host.host_ints) in front of one upload."""
 import ctypes as C
 
@@ -91,24 +91,55 @@ def _pcm(t, what):      # the samples of a pool of signals: a contiguous 1-D int
 
 
 mfcc_config = _lib.XvMfccConfig      # xv_mfcc_config with the VoxCeleb conf/mfcc.conf defaults (dither 0); keyword arguments name the fields to change
+fbank_config = _lib.XvFbankConfig    # xv_fbank_config with compute-fbank-feats' own defaults (dither 0)
+
+
+def _num_frames(kind, cfg, samples):
+    name = "xv_%s_num_frames" % kind
+    n = int(getattr(_lib.load(), name)(C.byref(cfg), C.c_int64(int(samples))))
+    if n < 0:
+        _lib.check(2, name)
+    return n
+
+
+def _tables(kind, cfg):
+    lib = _lib.load()
+    n = int(getattr(lib, "xv_%s_table_floats" % kind)(C.byref(cfg)))
+    if n == 0:
+        _lib.check(2, "xv_%s_table_floats" % kind)
+    flat = np.empty(n, np.float32)
+    _lib.check(getattr(lib, "xv_%s_tables" % kind)(C.byref(cfg), C.c_void_p(flat.ctypes.data), C.c_size_t(n)), "xv_%s_tables" % kind)
+    return flat
+
+
+def _waveform_batch(kind, cfg, tables, pcm, offsets, samples, t_out):
+    """The argument checks xv_mfcc and xv_fbank share - their kernels check neither the offsets nor the tables' size - and the upload:
+    -> (offsets int64 [b], samples int32 [b] on the device, b, t_out)."""
+    n_pcm = _pcm(pcm, "%s: pcm" % kind)
+    pair = "%s: offsets and samples must be two non-empty 1-D integer arrays of one length" % kind
+    offsets = host_ints(offsets, min_size=1, msg=pair)
+    samples = host_ints(samples, n=offsets.size, msg=pair)
+    if offsets.min() < 0 or samples.min() < 0 or (offsets.astype(np.int64) + samples.astype(np.int64)).max() > n_pcm:
+        raise IndexError("%s: an utterance lies outside the %d samples of pcm" % (kind, n_pcm))
+    if samples.max() >= 2 ** 31:
+        raise ValueError("%s: an utterance holds 2^31 samples or more" % kind)
+    floats = int(getattr(_lib.load(), "xv_%s_table_floats" % kind)(C.byref(cfg)))
+    if floats == 0:
+        _lib.check(2, "xv_%s_table_floats" % kind)
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != floats or tables.device != pcm.device:
+        raise ValueError("%s: tables must be %s_tables(cfg) as a contiguous float32 device tensor" % (kind, kind))
+    if t_out is None:
+        t_out = max(max(_num_frames(kind, cfg, n) for n in samples), 1)
+    return upload(offsets, np.int64, pcm.device), upload(samples, np.int32, pcm.device), offsets.size, int(t_out)
 
 
 def mfcc_num_frames(cfg, samples):
-    n = int(_lib.load().xv_mfcc_num_frames(C.byref(cfg), C.c_int64(int(samples))))
-    if n < 0:
-        _lib.check(2, "xv_mfcc_num_frames")
-    return n
+    return _num_frames("mfcc", cfg, samples)
 
 
 def mfcc_tables(cfg):
     """The constant tables of xv_mfcc for cfg as a host float32 array (xv_mfcc_tables: host arithmetic, no GPU call)."""
-    lib = _lib.load()
-    n = int(lib.xv_mfcc_table_floats(C.byref(cfg)))
-    if n == 0:
-        _lib.check(2, "xv_mfcc_table_floats")
-    flat = np.empty(n, np.float32)
-    _lib.check(lib.xv_mfcc_tables(C.byref(cfg), C.c_void_p(flat.ctypes.data), C.c_size_t(n)), "xv_mfcc_tables")
-    return flat
+    return _tables("mfcc", cfg)
 
 
 def mfcc(cfg, tables, pcm, offsets, samples, t_out=None):
@@ -116,25 +147,32 @@ def mfcc(cfg, tables, pcm, offsets, samples, t_out=None):
     offsets / samples: HOST integer arrays [b] - utterance i is pcm[offsets[i] : offsets[i] + samples[i]] (the kernel does not check them, so
     they are checked here, before the upload).  t_out: rows of the output (default: the longest frame count).
     -> (out [b, t_out, num_ceps] float32, rows_out int32 [b] = min(frames, t_out); rows behind are zero)."""
-    n_pcm = _pcm(pcm, "mfcc: pcm")
-    pair = "mfcc: offsets and samples must be two non-empty 1-D integer arrays of one length"
-    offsets = host_ints(offsets, min_size=1, msg=pair)
-    samples = host_ints(samples, n=offsets.size, msg=pair)
-    if offsets.min() < 0 or samples.min() < 0 or (offsets.astype(np.int64) + samples.astype(np.int64)).max() > n_pcm:
-        raise IndexError("mfcc: an utterance lies outside the %d samples of pcm" % n_pcm)
-    if samples.max() >= 2 ** 31:
-        raise ValueError("mfcc: an utterance holds 2^31 samples or more")
-    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != int(_lib.load().xv_mfcc_table_floats(C.byref(cfg))):
-        raise ValueError("mfcc: tables must be mfcc_tables(cfg) as a contiguous float32 device tensor")
-    b = offsets.size
-    if t_out is None:
-        t_out = max(max(mfcc_num_frames(cfg, n) for n in samples), 1)
-    t_out = int(t_out)
-    off_d, n_d = upload(offsets, np.int64, pcm.device), upload(samples, np.int32, pcm.device)
+    off_d, n_d, b, t_out = _waveform_batch("mfcc", cfg, tables, pcm, offsets, samples, t_out)
     out = torch.empty((b, t_out, int(cfg.num_ceps)), dtype=torch.float32, device=pcm.device)
     rows_out = torch.empty(b, dtype=torch.int32, device=pcm.device)
     _lib.call("xv_mfcc", _s(), C.byref(cfg), _p(tables), _p(pcm), _p(off_d), _p(n_d), b, t_out, _p(out), _p(rows_out))
     return out, rows_out
+
+
+def fbank_num_frames(cfg, samples):
+    return _num_frames("fbank", cfg, samples)
+
+
+def fbank_tables(cfg):
+    """The constant tables of xv_fbank for cfg as a host float32 array (xv_fbank_tables: host arithmetic, no GPU call)."""
+    return _tables("fbank", cfg)
+
+
+def fbank(cfg, tables, pcm, offsets, samples, t_out=None, with_energy=True):
+    """(Log-)mel filterbank energies of a batch of waveforms (xv_fbank); the arguments are mfcc's, with fbank_tables(cfg) as tables.
+    -> (out [b, t_out, num_mel_bins + use_energy] float32, rows_out int32 [b], energy [b, t_out, 1] float32 or None without with_energy:
+    the log-energy of every frame, whatever cfg.use_energy says - energy_vad(energy, rows_out) gives the decisions of an MFCC pass)."""
+    off_d, n_d, b, t_out = _waveform_batch("fbank", cfg, tables, pcm, offsets, samples, t_out)
+    out = torch.empty((b, t_out, int(cfg.num_mel_bins) + int(cfg.use_energy != 0)), dtype=torch.float32, device=pcm.device)
+    rows_out = torch.empty(b, dtype=torch.int32, device=pcm.device)
+    energy = torch.empty((b, t_out, 1), dtype=torch.float32, device=pcm.device) if with_energy else None
+    _lib.call("xv_fbank", _s(), C.byref(cfg), _p(tables), _p(pcm), _p(off_d), _p(n_d), b, t_out, _p(out), _p(rows_out), _p(energy))
+    return out, rows_out, energy
 
 
 def energy_vad(x, rows, threshold=5.5, mean_scale=0.5, frames_context=2, proportion=0.12):

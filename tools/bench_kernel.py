@@ -15,6 +15,7 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
   python tools/bench_kernel.py plda_cohort [small|large]        the cohort statistics of PLDA scores (xv_backend_cohort.hip): d = 200, 4 k rows, cohorts of 4 k / 40 k
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
+  python tools/bench_kernel.py fbank [utterances=256]            xv_fbank (30 bins) against xv_mfcc on the same batch, alternated five times: medians and spread
   python tools/bench_kernel.py cm_encode [utterances=256]        'CM ' compression (xv_cm_encode.hip) of 400 - 2000 frames x 30 per utterance, both header forms,
                                                                 against the bytes it must move and against the host writer
   python tools/bench_kernel.py augment [utterances=256] [notrace] reverberation + one background noise (xv_augment.hip) on the same synthetic PCM under impulse
@@ -416,6 +417,44 @@ def cmd_mfcc(argv):
     print("  xv_mfcc + xv_energy_vad %9.1f us  %.2f M frames/s = %.0f x real time" % (us_both, frames.sum() / us_both, frames.sum() / us_both * 1e6 / 100.0), flush=True)
 
 
+def cmd_fbank(argv):
+    """xv_fbank (30 bins, the VoxCeleb framing: 16 kHz, 25 / 10 ms, N = 512, d = 30 - the bytes xv_mfcc writes) against xv_mfcc on the batch
+    of the mfcc leg, ALTERNATED five times each in one run: per kernel the five timings (each the mean of 10 calls), their median and
+    their spread (max - min).  fbank does strictly less work per frame (no DCT, no log-mel slice in LDS), so its median should not lie above
+    xv_mfcc's by more than xv_mfcc's own spread; the third column is xv_fbank with energy_out (4 more bytes per frame)."""
+    from tf_kaldi_speaker_amd import ops
+    n_utts = int(argv[0]) if argv else 256
+    sf = 16000
+    lens = rs.randint(4 * sf, 20 * sf + 1, n_utts)
+    t = np.arange(int(lens.max())) / float(sf)
+    tone = 3000.0 * np.sin(2.0 * np.pi * 220.0 * t) + 1500.0 * np.sin(2.0 * np.pi * 1830.0 * t)
+    pcm = np.concatenate([np.rint(tone[:n] * (0.02 if i % 3 == 2 else 1.0) + rs.randn(n) * 40.0).astype(np.int16) for i, n in enumerate(lens)])
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    mcfg = ops.mfcc_config()
+    fcfg = ops.fbank_config(num_mel_bins=30, high_freq=7600.0, snip_edges=0)
+    mt, ft = torch.from_numpy(ops.mfcc_tables(mcfg)).cuda(), torch.from_numpy(ops.fbank_tables(fcfg)).cuda()
+    pcm_d = torch.from_numpy(pcm).cuda()
+    frames = np.asarray([ops.mfcc_num_frames(mcfg, n) for n in lens])
+    assert [ops.fbank_num_frames(fcfg, n) for n in lens] == list(frames)
+    t_out = int(frames.max())
+    print("%d utterances of %.1f - %.1f s (16 kHz): %.1f M samples, %d frames, padded to [%d, %d, 30]"
+          % (n_utts, lens.min() / sf, lens.max() / sf, pcm.size / 1e6, frames.sum(), n_utts, t_out), flush=True)
+    legs = [("xv_mfcc", lambda: ops.mfcc(mcfg, mt, pcm_d, offsets, lens, t_out)),
+            ("xv_fbank", lambda: ops.fbank(fcfg, ft, pcm_d, offsets, lens, t_out, with_energy=False)),
+            ("xv_fbank + energy_out", lambda: ops.fbank(fcfg, ft, pcm_d, offsets, lens, t_out))]
+    us = {name: [] for name, _ in legs}
+    for _ in range(5):
+        for name, fn in legs:
+            us[name].append(timeit(fn, 10, 2))
+    for name, _ in legs:
+        v = np.asarray(us[name])
+        print("  %-22s %s us  median %8.1f  spread %6.1f  %.2f M frames/s" % (name, " ".join("%8.1f" % x for x in v), np.median(v), v.max() - v.min(),
+                                                                              frames.sum() / np.median(v)), flush=True)
+    m, f = np.asarray(us["xv_mfcc"]), np.asarray(us["xv_fbank"])
+    print("  condition: median(xv_fbank) - median(xv_mfcc) = %+.1f us <= spread(xv_mfcc) = %.1f us: %s"
+          % (np.median(f) - np.median(m), m.max() - m.min(), "holds" if np.median(f) - np.median(m) <= m.max() - m.min() else "DOES NOT HOLD"), flush=True)
+
+
 def cmd_cm_encode(argv):
     """xv_cm_encode on one padded batch of MFCC-like utterances (400 - 2000 frames x 30), both header forms: device events around the bare
     entry point (index arrays uploaded once) and around ops.cm_encode (its checks, two uploads and the output allocation included).  The
@@ -555,7 +594,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
