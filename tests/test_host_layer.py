@@ -309,6 +309,92 @@ def test_pipeline_ops_refuse_host_arrays_as_before():
         ops.augment(cfg, src, [0], [5], out_offsets=[[0]])
 
 
+def test_wave_ops_refuse_as_before():
+    """The refusals of the ops that take PCM, and of cm_decode_ragged, that only GPU tests reached: texts and exception types, byte for
+    byte (tensors on the CPU: nothing is launched)."""
+    import torch
+    pcm, one = torch.zeros(100, dtype=torch.int16), ([0], [10])
+    cfg = ops.resample_config(16000, 8000)
+    tables = torch.from_numpy(ops.resample_tables(cfg))
+    with pytest.raises(ValueError, match="^resample: offsets and samples must be two non-empty 1-D integer arrays of one length$"):
+        ops.resample(cfg, tables, pcm, [], [])
+    with pytest.raises(IndexError, match="^resample: an utterance lies outside the 100 samples of pcm$"):
+        ops.resample(cfg, tables, pcm, [90], [11])
+    with pytest.raises(ValueError, match="^resample: tables must be resample_tables\\(cfg\\) as a contiguous float32 device tensor of 27 values$"):
+        ops.resample(cfg, tables[:-1].clone(), pcm, *one)
+    with pytest.raises(IndexError, match="^resample: the outputs overlap or lie outside the 8 samples of out_pcm$"):
+        ops.resample(cfg, tables, pcm, [0, 10], [10, 10], out_offsets=[0, 3])
+    with pytest.raises(IndexError, match="^resample: the outputs overlap or lie outside the 2 samples of out_pcm$"):
+        ops.resample(cfg, tables, pcm, *one, out_pcm=torch.zeros(2, dtype=torch.int16))
+    with pytest.raises(ValueError, match="^resample: out_f32 must be a contiguous 1-D float32 tensor of out_pcm's size$"):
+        ops.resample(cfg, tables, pcm, *one, out_f32=torch.zeros(2))
+    with pytest.raises(ValueError, match="^resample: pcm must be a contiguous 1-D int16 tensor$"):
+        ops.resample(cfg, tables, pcm.float(), *one)
+    src, acfg = torch.ones(50, dtype=torch.int16), ops.augment_config()
+    with pytest.raises(IndexError, match="^augment: the outputs overlap or lie outside the 13 samples of out_pcm$"):
+        ops.augment(acfg, src, [0, 10], [10, 10], out_offsets=[0, 3])
+    with pytest.raises(ValueError, match="^augment: out_f32 must be a contiguous 1-D float32 tensor of out_pcm's size$"):
+        ops.augment(acfg, src, *one, out_f32=torch.zeros(2))
+    with pytest.raises(IndexError, match="^augment: an impulse response is empty or lies outside the 50 samples of rir$"):
+        ops.augment(acfg, src, *one, rir=src, rir_off=[45], rir_len=[10], rir_early=[(0, 1, 0)], utt_rir=[0])
+    with pytest.raises(IndexError, match="^augment: a noise is empty or lies outside the 50 samples of noise$"):
+        ops.augment(acfg, src, *one, noise=src, noise_off=[45], noise_len=[10], nz_first=[0, 1], nz_id=[0], nz_snr=[10.0], nz_start=[0], nz_span=[-1])
+    fcfg = ops.fbank_config()
+    with pytest.raises(IndexError, match="^fbank: an utterance lies outside the 100 samples of pcm$"):
+        ops.fbank(fcfg, None, pcm, [90], [11])
+    with pytest.raises(ValueError, match="^fbank: tables must be fbank_tables\\(cfg\\) as a contiguous float32 device tensor$"):
+        ops.fbank(fcfg, torch.from_numpy(ops.fbank_tables(fcfg))[:-1].clone(), pcm, *one)
+    with pytest.raises(ValueError, match="^fbank: offsets and samples must be two non-empty 1-D integer arrays of one length$"):
+        ops.fbank(fcfg, None, pcm, [0], [1, 2])
+    with pytest.raises(IndexError, match="^cm_decode_ragged: an image lies outside the 10 bytes of packed$"):
+        ops.cm_decode_ragged(torch.zeros(10, dtype=torch.uint8), [0], [3], 3, 2)
+
+
+class _FakeResampler(object):
+    """What a resampler cache hands out: run() records its rate and the lengths it was given and passes the lengths on."""
+
+    def __init__(self, rate, seen):
+        self.rate, self.seen = rate, seen
+
+    def run(self, waves):
+        n = np.asarray([len(w) for w in waves], np.int64)
+        self.seen.append((self.rate, n.tolist()))
+        return None, _host.exclusive_offsets(n), n, np.zeros(len(n), np.int64)
+
+
+def test_rate_groups_are_first_appearance_and_refused_once():
+    """extract_at_rates and device_batches visit the sample rates in the order they first appear, the members of a rate in list order;
+    a rate the options do not allow is refused with one text."""
+    import torch
+    rates, seen = [16000, 8000, 16000, 44100, 8000], []
+    waves = [np.zeros(100 + i, np.int16) for i in range(5)]             # utterance i is known by its length
+    want = [(16000, [100, 102]), (8000, [101, 104]), (44100, [103])]
+
+    def packed(pcm, offsets, lengths, cm_header=None):      # stands in for extract_packed: a result per utterance, its length
+        if pcm is not None:                                  # the group at sample_frequency (the fake resamplers hand on no samples)
+            seen.append((16000, [int(n) for n in lengths]))
+        return [int(n) for n in lengths]
+
+    def extractor(**allow):
+        fx = object.__new__(features.FeatureExtractor)
+        fx.torch, fx.ops, fx.device, fx.mfcc, fx.workspace_bytes, fx.with_vad = torch, ops, torch.device("cpu"), features.MfccOptions(**allow), 1 << 30, False
+        fx.cfg = fx.mfcc.config()
+        fx._resamplers = {(rate, fx.mfcc.sample_frequency): _FakeResampler(rate, seen) for rate in (8000, 44100)}
+        fx.extract_packed = packed
+        fx.on_device = lambda pcm, offsets, lengths, t_out: (torch.zeros(len(lengths), t_out, 1), None, None)
+        return fx
+
+    fx = extractor(allow_downsample=1, allow_upsample=1)
+    assert fx.extract_at_rates(waves, rates) == [100, 101, 102, 103, 104] and seen == want
+    del seen[:]
+    got = [(members, list(samples)) for members, samples, batch in fx.device_batches(waves, rates)]
+    assert got == [([0, 2], [100, 102]), ([1, 4], [101, 104]), ([3], [103])] and seen == want[1:]
+    refusal = "^sample rate 8000 Hz, but --sample-frequency=16000 \\(there is no resampling without --allow-upsample=true\\)$"
+    for visit in (lambda fx: fx.extract_at_rates(waves, rates), lambda fx: list(fx.device_batches(waves, rates))):
+        with pytest.raises(ValueError, match=refusal):
+            visit(extractor(allow_downsample=1, allow_upsample=0))
+
+
 def test_small_helpers():
     import torch
     assert [_host.pitch4(d) for d in (0, 1, 4, 5, 150, 512)] == [0, 4, 4, 8, 152, 512]
@@ -332,10 +418,10 @@ def test_both_import_styles_need_no_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pkg = os.path.join(root, "tf_kaldi_speaker_amd")
-    check = "assert ops.mfcc is p.mfcc and ops.score_trials is p.score_trials and ops._p is h._p and h.device_ops('cpu')[1] is ops"
-    for path, code in ((root, "import tf_kaldi_speaker_amd.ops as ops, tf_kaldi_speaker_amd.pipeline_ops as p, tf_kaldi_speaker_amd._host as h; "
-                              "from tf_kaldi_speaker_amd.misc import features, augment, scoring, backend; " + check),
-                       (pkg, "import ops, pipeline_ops as p, _host as h; from misc import features, augment, scoring, backend; " + check)):
+    check = "assert ops.mfcc is w.mfcc and ops.score_trials is p.score_trials and ops._p is h._p and h.device_ops('cpu')[1] is ops"
+    for path, code in ((root, "import tf_kaldi_speaker_amd.ops as ops, tf_kaldi_speaker_amd.pipeline_ops as p, tf_kaldi_speaker_amd.wave_ops as w, "
+                              "tf_kaldi_speaker_amd._host as h; from tf_kaldi_speaker_amd.misc import features, augment, scoring, backend; " + check),
+                       (pkg, "import ops, pipeline_ops as p, wave_ops as w, _host as h; from misc import features, augment, scoring, backend; " + check)):
         r = subprocess.run([sys.executable, "-c", code], cwd="/", env=dict(os.environ, PYTHONPATH=path, HIP_VISIBLE_DEVICES=""), capture_output=True,
                            text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]

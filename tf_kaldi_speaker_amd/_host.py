@@ -1,6 +1,7 @@
 """What the host side of every op has in common: device buffers as ctypes arguments, the checks of host index arrays that the kernels
-leave to the caller, pitches and offsets, and how the drivers in misc/ cut their work into calls.  ops.py, pipeline_ops.py and misc/
-build on this module; it imports none of them at load time."""
+leave to the caller (index arrays, spans inside a pool of samples, where waveform outputs go, the size of a constant table), pitches and
+offsets, and how the drivers in misc/ cut their work into calls.  ops.py, wave_ops.py, pipeline_ops.py and misc/ build on this module; it
+imports none of them at load time."""
 import ctypes as C
 
 import numpy as np
@@ -79,6 +80,62 @@ def pitched(t, what, whole=False):
     if whole and t.shape[1] != ld:
         raise ValueError("%s must be the whole [rows, pitch] buffer (its padding columns are written)" % what)
     return t.shape[0], ld
+
+
+def pcm_samples(t, what):      # the samples of a pool of signals: a contiguous 1-D int16 device tensor, or None (no pool)
+    if t is None:
+        return 0
+    if t.dtype != torch.int16 or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous 1-D int16 tensor" % what)
+    return t.numel()
+
+
+def spans_inside(offsets, lengths, size, msg, min_length=0):
+    """Refuses with IndexError(msg) a span offsets[i] .. offsets[i] + lengths[i] (two host integer arrays of one length, host_ints' results)
+    that leaves the `size` elements of its pool, one shorter than min_length (1: no empty span), and a table without a span."""
+    if offsets.size == 0 or offsets.min() < 0 or lengths.min() < min_length or (offsets.astype(np.int64) + lengths.astype(np.int64)).max() > size:
+        raise IndexError(msg)
+
+
+def place_outputs(name, n_out, out_offsets, out_pcm, out_f32, device, min_samples=0):
+    """Where the ops that write waveforms put them: out_offsets (None: the n_out [b] samples of each back to back), out_pcm (None: a new
+    int16 tensor that just holds them, min_samples at the least) and out_f32 (True: a new float32 tensor of out_pcm's size, False: none,
+    or such a tensor), checked - the kernels do not - and refused in `name`.  -> (out_pcm, out_offsets int64 [b], out_f32 | None)."""
+    out_offsets = host_ints(exclusive_offsets(n_out) if out_offsets is None else out_offsets, name + ": out_offsets", n=n_out.size, dtype=np.int64)
+    ends = out_offsets + n_out
+    if out_pcm is None:
+        out_pcm = torch.empty(max(int(ends.max()), min_samples), dtype=torch.int16, device=device)
+    total = pcm_samples(out_pcm, name + ": out_pcm")
+    order = np.argsort(out_offsets, kind="stable")
+    if out_offsets.min() < 0 or ends.max() > total or (out_offsets[order][1:] < ends[order][:-1]).any():
+        raise IndexError("%s: the outputs overlap or lie outside the %d samples of out_pcm" % (name, total))
+    if out_f32 is True:
+        out_f32 = torch.empty(total, dtype=torch.float32, device=device)
+    elif out_f32 is False:
+        out_f32 = None
+    elif out_f32.dtype != torch.float32 or out_f32.dim() != 1 or not out_f32.is_contiguous() or out_f32.numel() < total:
+        raise ValueError("%s: out_f32 must be a contiguous 1-D float32 tensor of out_pcm's size" % name)
+    return out_pcm, out_offsets, out_f32
+
+
+def table_floats(kind, cfg):      # xv_<kind>_table_floats(cfg): the floats of the constant tables of "mfcc", "fbank" or "resample"
+    name = "xv_%s_table_floats" % kind
+    n = int(getattr(_lib.load(), name)(C.byref(cfg)))
+    if n == 0:
+        _lib.check(2, name)
+    return n
+
+
+def config_tables(kind, cfg):
+    """The constant tables of xv_<kind> for cfg as a host float32 array (xv_<kind>_tables: host arithmetic, no GPU call)."""
+    flat = np.empty(table_floats(kind, cfg), np.float32)
+    name = "xv_%s_tables" % kind
+    _lib.check(getattr(_lib.load(), name)(C.byref(cfg), C.c_void_p(flat.ctypes.data), C.c_size_t(flat.size)), name)
+    return flat
+
+
+def holds_tables(t, floats):      # t is config_tables' array as the kernels read it: `floats` contiguous float32 values
+    return t.dtype == torch.float32 and t.is_contiguous() and t.numel() == floats
 
 
 def pitch4(d):      # d rounded up to 4 floats: the row pitch of a GEMM operand

@@ -15,8 +15,10 @@ read_signals is told to pass the impulse responses and noises with their rates (
 that differ when it builds its pools."""
 import numpy as np
 
-from . import resample
-from .features import DEFAULT_WORKSPACE_BYTES, _Options, _bool, _f, _i, _lib, device_ops, exclusive_offsets, greedy_batches
+from . import resample, waves
+from .conf import _Options, _bool, _f, _i
+from .features import DEFAULT_WORKSPACE_BYTES, _lib, device_ops, exclusive_offsets, greedy_batches
+from .waves import read_scp, write_wav      # noqa: F401 (drivers and tests reach them here)
 
 PRESETS = {"reverb": None, "noise": (15.0, 10.0, 5.0, 0.0), "music": (15.0, 10.0, 8.0, 5.0), "babble": (20.0, 17.0, 15.0, 13.0)}
 
@@ -193,50 +195,60 @@ def make_speed_plan(utterances, factors, sample_frequency=16000.0):
     return entries
 
 
-def read_scp(path):
-    """[(key, rxfilename)] of a Kaldi scp file."""
-    out = []
-    with open(path, "r") as f:
-        for number, line in enumerate(f, 1):
-            if not line.strip():
-                continue
-            parts = line.strip().split(None, 1)
-            if len(parts) != 2:
-                raise ValueError("%s:%d: `key rxfilename` is expected, got `%s`" % (path, number, line.strip()))
-            out.append((parts[0], parts[1]))
-    return out
-
-
 def read_signals(scp_path, sample_frequency, channel, what, resample_signals=False):
     """{id: int16 array} of a rir.scp / noise.scp style table: `id rxfilename` lines, RIFF PCM-16 at the sources' sample rate (without
     resample_signals there is no resampling; a mismatch is refused as by read_wav), `channel` of each file.  resample_signals: every rate
     passes and the table is {id: (int16 array, its rate in Hz)} - the Augmenter converts those that differ when it builds its pools."""
-    from . import features
-    opts = features.MfccOptions(sample_frequency=sample_frequency, channel=channel)
+    opts = waves.WavFormat(sample_frequency, channel)
     out = {}
     for key, rx in read_scp(scp_path):
         if key in out:
             raise ValueError("%s: %s %s is listed twice" % (scp_path, what, key))
-        samples, rate = features.read_wav_rate(rx, opts, key, any_rate=bool(resample_signals))
+        samples, rate = waves.read_wav_rate(rx, opts, key, any_rate=bool(resample_signals))
         out[key] = (samples, rate) if resample_signals else samples
         if len(samples) == 0:
             raise ValueError("%s: %s %s holds no samples" % (scp_path, what, key))
     return out
 
 
+def read_setup(options, rir_scp, noise_scp, sample_frequency, resample_signals=False, plan=""):
+    """What a driver reads in front of an augmentation: -> (rirs, noises: the read_signals tables of rir.scp / noise.scp, each on its
+    channel of options, {} for an empty path; the entries of the plan file checked against them, None for an empty path)."""
+    rirs = read_signals(rir_scp, sample_frequency, options.impulse_response_channel, "impulse response", resample_signals) if rir_scp else {}
+    noises = read_signals(noise_scp, sample_frequency, options.noise_channel, "noise", resample_signals) if noise_scp else {}
+    return rirs, noises, (read_plan(plan, sample_frequency, rirs, noises) if plan else None)
+
+
+class SourceError(ValueError):
+    """A source of a plan entry that cannot be used: not listed, not readable, empty."""
+
+
+def check_sources(entries, rx_of, plan_path, scp_path):
+    """Refuses the first entry whose source is not a key of rx_of, the {key: rxfilename} of scp_path."""
+    for e in entries:
+        if e.src_key not in rx_of:
+            raise SourceError("%s: Key %s: source %s is not in %s" % (plan_path, e.out_key, e.src_key, scp_path))
+
+
+def plan_sources(entries, rx_of, options, plan_path, scp_path):
+    """(entry, the samples of its source) per plan entry, in order: read by waves.read_wav under options as the entry is reached, once
+    while consecutive entries name the same source.  SourceError: as check_sources, what read_wav refuses, a source without samples."""
+    last = (None, None)
+    for e in entries:
+        check_sources([e], rx_of, plan_path, scp_path)
+        if last[0] != e.src_key:
+            try:
+                last = (e.src_key, waves.read_wav(rx_of[e.src_key], options, e.src_key))
+            except ValueError as err:
+                raise SourceError(str(err))
+        if len(last[1]) == 0:
+            raise SourceError("Key %s: the source %s holds no samples" % (e.out_key, e.src_key))
+        yield e, last[1]
+
+
 def signal_seconds(signals, sample_frequency):
     """[(id, seconds)] of a read_signals table in either form (what make_plan takes)."""
     return [(k, len(v[0]) / float(v[1])) if isinstance(v, tuple) else (k, len(v) / float(sample_frequency)) for k, v in signals.items()]
-
-
-def write_wav(path, samples, sample_frequency):
-    """A mono RIFF PCM-16 file (stdlib wave)."""
-    import wave
-    with wave.open(path, "wb") as w:
-        w.setnchannels(1)
-        w.setsampwidth(2)
-        w.setframerate(int(sample_frequency))
-        w.writeframes(np.ascontiguousarray(samples, dtype="<i2").tobytes())
 
 
 class Augmenter(object):
@@ -250,7 +262,6 @@ class Augmenter(object):
         self.cfg = self.options.config(self.sample_frequency)
         self.workspace_bytes = int(workspace_bytes)
         self.tile = self.ops.augment_plan(1)["tile"]
-        self._resamplers = {}
         rirs, noises = self._at_rate(rirs or {}), self._at_rate(noises or {})
         self.rir_index, self.rir_pool, self.rir_off, self.rir_len = self._pool(rirs, "impulse response")
         self.noise_index, self.noise_pool, self.noise_off, self.noise_len = self._pool(noises, "noise")
@@ -258,31 +269,24 @@ class Augmenter(object):
 
     def resampler(self, fin):
         """The Resampler fin -> sample_frequency of this Augmenter, kept: its table goes to the device once."""
-        if fin not in self._resamplers:
-            self._resamplers[fin] = resample.Resampler(fin, self.sample_frequency, self.device, self.workspace_bytes)
-        return self._resamplers[fin]
+        return waves.Resamplers.of(self)[fin, self.sample_frequency]
 
     def _at_rate(self, signals):
         """A read_signals table in either form as {id: int16 array at sample_frequency}: the (array, rate) entries whose rate differs are
         resampled on the device, once, grouped by rate (xv_resample; rounded to int16, as the wav of a `sox -r` stage is)."""
         out = {k: (v[0] if isinstance(v, tuple) else v) for k, v in signals.items()}
-        groups = {}
-        for k, v in signals.items():
-            if isinstance(v, tuple) and int(v[1]) != self.sample_frequency:
-                groups.setdefault(int(v[1]), []).append(k)
-        for rate, keys in groups.items():
-            converted, _ = self.resampler(rate).resample([signals[k][0] for k in keys])
-            out.update(zip(keys, converted))
+        keys = list(signals)
+        groups = waves.by_rate(int(v[1]) if isinstance(v, tuple) and int(v[1]) != self.sample_frequency else None for v in signals.values())
+        for rate, members in groups.items():
+            converted, _ = self.resampler(rate).resample([out[keys[i]] for i in members])
+            out.update(zip((keys[i] for i in members), converted))
         return out
 
     def perturbed(self, sources, entries):
         """The sources of the entries with speed=F resampled F * fs -> fs on the device, grouped by factor, and brought back as int16 (the
         intermediate a piped wav would be); the others as they are."""
         sources = list(sources)
-        groups = {}
-        for i, e in enumerate(entries):
-            if e.speed is not None:
-                groups.setdefault(resample.speed_rates(e.speed, self.sample_frequency)[0], []).append(i)
+        groups = waves.by_rate(None if e.speed is None else resample.speed_rates(e.speed, self.sample_frequency)[0] for e in entries)
         for fin, members in groups.items():
             converted, _ = self.resampler(fin).resample([sources[i] for i in members])
             for i, w in zip(members, converted):
@@ -290,15 +294,10 @@ class Augmenter(object):
         return sources
 
     def _pool(self, signals, what):
-        keys = list(signals)
-        arrays = [np.ascontiguousarray(signals[k], dtype=np.int16).reshape(-1) for k in keys]
-        for k, a in zip(keys, arrays):
-            if a.size == 0:
+        for k, a in signals.items():
+            if np.size(a) == 0:
                 raise ValueError("Augmenter: %s %s holds no samples" % (what, k))
-        lengths = np.asarray([a.size for a in arrays], np.int64)
-        offsets = exclusive_offsets(lengths) if keys else np.zeros(0, np.int64)
-        pool = self.torch.from_numpy(np.concatenate(arrays)).to(self.device) if keys else None
-        return {k: i for i, k in enumerate(keys)}, pool, offsets, lengths
+        return ({k: i for i, k in enumerate(signals)},) + waves.pack(signals.values(), self.device)      # no signal: no pool (None)
 
     def lengths(self, sources, entries):
         """(M, n_out) per entry: the samples of y and of the output (step 6)."""
@@ -350,8 +349,7 @@ class Augmenter(object):
         pcm = torch.empty(int(n_out.sum()), dtype=torch.int16, device=self.device)
         clipped = np.zeros(len(entries), np.int64)
         for batch in self._batches(n, m, entries):
-            src = torch.from_numpy(np.concatenate([sources[i] for i in batch])).to(self.device)
-            src_len = n[batch]
+            src, src_off, src_len = waves.pack([sources[i] for i in batch], self.device)
             first, ids, snrs, starts, spans = [0], [], [], [], []
             for i in batch:
                 for nid, snr, start, background in entries[i].noises:
@@ -362,7 +360,7 @@ class Augmenter(object):
                     spans.append(-1 if background else int(self.noise_len[k]))
                 first.append(len(ids))
             _, _, samples, clip, _ = ops.augment(
-                self.cfg, src, exclusive_offsets(src_len), src_len, rir=self.rir_pool, rir_off=self.rir_off,
+                self.cfg, src, src_off, src_len, rir=self.rir_pool, rir_off=self.rir_off,
                 rir_len=self.rir_len, rir_early=self.rir_early,
                 utt_rir=[self.rir_index[entries[i].rir] if entries[i].rir is not None else -1 for i in batch], noise=self.noise_pool,
                 noise_off=self.noise_off, noise_len=self.noise_len, nz_first=first, nz_id=ids, nz_snr=snrs, nz_start=starts, nz_span=spans,
@@ -374,5 +372,4 @@ class Augmenter(object):
     def augment(self, sources, entries):
         """The host convenience: ([int16 array per entry], clipped)."""
         pcm, offsets, lengths, clipped = self.run(sources, entries)
-        host = pcm.cpu().numpy()
-        return [host[o:o + k].copy() for o, k in zip(offsets, lengths)], clipped
+        return waves.unpack(pcm, offsets, lengths), clipped

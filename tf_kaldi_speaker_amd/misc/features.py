@@ -9,91 +9,20 @@ sid/compute_vad_decision.sh do in the reference recipe (egs/voxceleb/v1/run.sh:5
 
 This is the --dither=0 program: Kaldi's default dither of 1.0 adds noise from its own generator and is not reproducible across Kaldi runs
 either.  MfccOptions' defaults are the VoxCeleb conf's (30 bins, 30 coefficients, 20 - 7600 Hz, snip-edges false), NOT compute-mfcc-feats'
-own: a conf file should state what it relies on.  FbankOptions' defaults are compute-fbank-feats' own."""
-import io
-import wave
-
+own: a conf file should state what it relies on.  FbankOptions' defaults are compute-fbank-feats' own.  The readers of wav files and of a
+wav.scp, and what is common to everything that handles waveforms and their rates, are misc/waves.py's; the conf parser is misc/conf.py's."""
 import numpy as np
 
 try:
     from .._host import DEFAULT_WORKSPACE_BYTES, _lib, device_ops, exclusive_offsets, greedy_batches
+    from . import waves as W
+    from .conf import _Options, _bool, _f, _i, _s
+    from .waves import read_wav, read_wav_rate, read_wav_scp      # noqa: F401 (drivers and tests reach the readers of misc/waves.py here)
 except (ImportError, ValueError):
     from _host import DEFAULT_WORKSPACE_BYTES, _lib, device_ops, exclusive_offsets, greedy_batches
-
-_TRUE, _FALSE = ("true", "t", "1"), ("false", "f", "0")
-
-
-def _bool(name, text):
-    if text.lower() in _TRUE:
-        return 1
-    if text.lower() in _FALSE:
-        return 0
-    raise ValueError("--%s=%s: true or false is expected" % (name, text))
-
-
-def _conf_lines(path):
-    """(name, value) of every `--name=value` line of a Kaldi conf file; `#` starts a comment."""
-    out = []
-    with open(path, "r") as f:
-        for number, line in enumerate(f, 1):
-            line = line.split("#", 1)[0].strip()
-            if not line:
-                continue
-            if not line.startswith("--") or "=" not in line:
-                raise ValueError("%s:%d: `--name=value` is expected, got `%s`" % (path, number, line))
-            name, value = line[2:].split("=", 1)
-            out.append((name.strip(), value.strip()))
-    return out
-
-
-class _Options(object):
-    """Options by Kaldi name.  SUPPORTED: name -> (attribute, parser).  FIXED: options of the Kaldi program that this one does not
-    implement, name -> (the one value that changes nothing, parser): that value is accepted, any other is refused by name."""
-    SUPPORTED, FIXED, PROGRAM = {}, {}, ""
-
-    def __init__(self, **kw):
-        for attr, _ in self.SUPPORTED.values():
-            setattr(self, attr, self.DEFAULTS[attr])
-        for k, v in kw.items():
-            if k not in self.DEFAULTS:
-                raise TypeError("%s: no option `%s`" % (type(self).__name__, k))
-            setattr(self, k, v)
-
-    def set(self, name, text):
-        if name in self.SUPPORTED:
-            attr, parse = self.SUPPORTED[name]
-            setattr(self, attr, parse(name, text))
-        elif name in self.FIXED:
-            only, parse = self.FIXED[name]
-            if parse(name, text) != only:
-                raise ValueError("--%s=%s is not supported (only --%s=%s: %s)" % (name, text, name, str(only).lower(), self.WHY.get(name, "not implemented")))
-        else:
-            raise ValueError("--%s is not an option of %s that this program knows" % (name, self.PROGRAM))
-
-    @classmethod
-    def from_conf(cls, path):
-        self = cls()
-        for name, value in _conf_lines(path):
-            self.set(name, value)
-        return self
-
-
-def _f(name, text):
-    try:
-        return float(text)
-    except ValueError:
-        raise ValueError("--%s=%s: a number is expected" % (name, text))
-
-
-def _i(name, text):
-    try:
-        return int(text)
-    except ValueError:
-        raise ValueError("--%s=%s: a whole number is expected" % (name, text))
-
-
-def _s(name, text):
-    return text
+    from misc import waves as W
+    from misc.conf import _Options, _bool, _f, _i, _s
+    from misc.waves import read_wav, read_wav_rate, read_wav_scp      # noqa: F401
 
 
 class MfccOptions(_Options):
@@ -155,69 +84,6 @@ class VadOptions(_Options):
     FIXED, WHY = {}, {}
 
 
-def read_wav(rxfilename, options=None, key=""):
-    """The samples of a RIFF PCM-16 file as an int16 array: a path or a `cmd |` entry of a wav.scp (dataset.kaldi_io.open_or_fd), read with the
-    stdlib wave module.  options (MfccOptions): the sample rate must be options.sample_frequency, and options.channel picks the channel
-    (-1: the file must be mono).  Anything else is refused, naming `key`."""
-    return read_wav_rate(rxfilename, options, key, any_rate=False)[0]
-
-
-def read_wav_rate(rxfilename, options=None, key="", any_rate=None):
-    """(samples, sample rate in Hz) of a file as read_wav reads it.  any_rate None: a file at another rate than options.sample_frequency
-    passes if options allows the conversion - a higher rate needs allow_downsample, a lower one allow_upsample (compute-mfcc-feats'
-    rule); True: every rate passes (the caller resamples); False: read_wav's refusal.  The samples come back at the FILE's rate."""
-    try:
-        from ..dataset import kaldi_io
-    except (ImportError, ValueError):
-        from dataset import kaldi_io
-    options = options or MfccOptions()
-    who = "Key %s (%s)" % (key, rxfilename) if key else rxfilename
-    fd = kaldi_io.open_or_fd(rxfilename, "rb")
-    try:
-        data = fd.read()
-    finally:
-        fd.close()
-    try:
-        w = wave.open(io.BytesIO(data), "rb")
-    except (wave.Error, EOFError) as e:
-        raise ValueError("%s: not a RIFF PCM file (%s)" % (who, e))
-    with w:
-        if w.getsampwidth() != 2:
-            raise ValueError("%s: %d-bit samples; only PCM-16 is read" % (who, 8 * w.getsampwidth()))
-        rate = w.getframerate()
-        if rate != int(options.sample_frequency) or int(options.sample_frequency) != options.sample_frequency:
-            allowed = any_rate
-            if any_rate is None:
-                allowed = bool(options.allow_downsample if rate > options.sample_frequency else options.allow_upsample)
-            if not allowed or rate < 1 or int(options.sample_frequency) != options.sample_frequency:
-                raise ValueError("%s: sample rate %d Hz, but --sample-frequency=%g (there is no resampling%s)"
-                                 % (who, rate, options.sample_frequency, "" if any_rate is False else
-                                    " without --allow-downsample=true" if rate > options.sample_frequency else " without --allow-upsample=true"))
-        channels = w.getnchannels()
-        x = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, channels)
-    if options.channel < 0:
-        if channels != 1:
-            raise ValueError("%s: %d channels; choose one with --channel" % (who, channels))
-        return np.ascontiguousarray(x[:, 0]), rate
-    if options.channel >= channels:
-        raise ValueError("%s: --channel=%d, but the file has %d channel(s)" % (who, options.channel, channels))
-    return np.ascontiguousarray(x[:, options.channel]), rate
-
-
-def read_wav_scp(path, options):
-    """(key, samples, sample rate) of every `key rxfilename` line of a wav.scp, read by read_wav_rate under options' rate rules - the
-    reader of make_mfcc.py, make_fbank.py and extract.py's wav mode.  ValueError: a malformed line, or what read_wav_rate refuses."""
-    with open(path, "r") as scp:
-        for line in scp:
-            if not line.strip():
-                continue
-            parts = line.strip().split(None, 1)
-            if len(parts) != 2:
-                raise ValueError("%s: `key rxfilename` is expected, got `%s`" % (path, line.strip()))
-            wav, rate = read_wav_rate(parts[1], options, parts[0])
-            yield parts[0], wav, rate
-
-
 class FeatureExtractor(object):
     """Features (MFCCs or filterbank energies) and VAD decisions of waveforms.  mfcc: a MfccOptions or a FbankOptions - the kernel follows
     the option set.  The constant tables are built once (xv_mfcc_tables / xv_fbank_tables, host arithmetic) and kept on the device;
@@ -269,52 +135,38 @@ class FeatureExtractor(object):
         cm_header ("uniform" or "quartiles"): the features come back 'CM '-compressed on the device instead (ops.cm_encode: the bytes
         dataset.kaldi_io.write_compressed_mat(header=cm_header) gives for the float features) - [(the image behind the "CM " token, a bytes-like
         object, empty when T is 0; decisions)]: a byte per value crosses to the host instead of four."""
-        waves = [np.ascontiguousarray(w, dtype=np.int16).reshape(-1) for w in waves]
-        lengths = [len(w) for w in waves]
-        frames = [self.num_frames(n) for n in lengths]
+        lengths = [np.size(w) for w in waves]
         out = [None] * len(waves)
-        for batch in self._batches(frames, lengths, cm_header is not None):
-            n = [lengths[i] for i in batch]
-            if sum(n) == 0:
-                for i in batch:
-                    out[i] = self._nothing(cm_header)
-                continue
-            pcm = self.torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
-            for i, r in zip(batch, self.extract_packed(pcm, exclusive_offsets(n), n, cm_header)):      # one call: the batch fits
+        for batch in self._batches([self.num_frames(n) for n in lengths], lengths, cm_header is not None):
+            packed = W.pack([waves[i] for i in batch], self.device)      # one upload and one call: the batch fits
+            for i, r in zip(batch, self.extract_packed(*packed, cm_header=cm_header)):
                 out[i] = r
         return out
 
     def resampler(self, rate):
         """The Resampler rate -> sample_frequency of this extractor, kept: its table goes to the device once."""
-        try:
-            from .resample import Resampler
-        except (ImportError, ValueError):
-            from misc.resample import Resampler
-        if not hasattr(self, "_resamplers"):
-            self._resamplers = {}
-        if rate not in self._resamplers:
-            self._resamplers[rate] = Resampler(rate, self.mfcc.sample_frequency, self.device, self.workspace_bytes)
-        return self._resamplers[rate]
+        return W.Resamplers.of(self)[rate, self.mfcc.sample_frequency]
+
+    def _rate_groups(self, waves, rates):
+        """(members, pcm, offsets, lengths) per sample rate among `rates` (Hz, whole numbers), in the order the rates first appear: the
+        members' waveforms packed on the device at sample_frequency - uploaded as they are, or resampled there (rounded to int16;
+        compute-mfcc-feats keeps floats: unpinned).  A higher rate needs mfcc.allow_downsample, a lower one
+        mfcc.allow_upsample.  pcm is None when a group at sample_frequency holds no sample."""
+        for rate, members in W.by_rate(rates).items():
+            group = [waves[i] for i in members]
+            if rate == self.mfcc.sample_frequency:
+                yield (members,) + W.pack(group, self.device)
+            elif not W.rate_allowed(self.mfcc, rate):
+                raise ValueError(W.rate_refusal(self.mfcc, rate))
+            else:
+                yield (members,) + self.resampler(rate).run(group)[:3]
 
     def extract_at_rates(self, waves, rates, cm_header=None):
-        """extract() for waveforms at their own sample rates (Hz, whole numbers): those at sample_frequency go through as they are, the
-        others are resampled on the device, grouped by rate, and reach xv_mfcc as int16 without leaving it (compute-mfcc-feats keeps
-        floats there: unpinned).  A higher rate needs mfcc.allow_downsample, a lower one mfcc.allow_upsample."""
-        fs = self.mfcc.sample_frequency
-        groups = {}
-        for i, rate in enumerate(rates):
-            groups.setdefault(int(rate), []).append(i)
+        """extract() for waveforms at their own sample rates: those at sample_frequency go through as they are, the others are resampled
+        on the device, grouped by rate, and reach xv_mfcc as int16 without leaving it (_rate_groups)."""
         out = [None] * len(waves)
-        for rate, members in groups.items():
-            if rate == fs:
-                results = self.extract([waves[i] for i in members], cm_header)
-            else:
-                if not (self.mfcc.allow_downsample if rate > fs else self.mfcc.allow_upsample):
-                    raise ValueError("sample rate %d Hz, but --sample-frequency=%g (there is no resampling without --allow-%s=true)"
-                                     % (rate, fs, "downsample" if rate > fs else "upsample"))
-                pcm, offsets, lengths, _ = self.resampler(rate).run([waves[i] for i in members])
-                results = self.extract_packed(pcm, offsets, lengths, cm_header)
-            for i, r in zip(members, results):
+        for members, pcm, offsets, lengths in self._rate_groups(waves, rates):
+            for i, r in zip(members, self.extract_packed(pcm, offsets, lengths, cm_header)):
                 out[i] = r
         return out
 
@@ -327,24 +179,11 @@ class FeatureExtractor(object):
             from ..dataset.kaldi_io import DeviceBatch
         except (ImportError, ValueError):
             from dataset.kaldi_io import DeviceBatch
-        fs = self.mfcc.sample_frequency
-        groups = {}
-        for i, rate in enumerate(rates):
-            groups.setdefault(int(rate), []).append(i)
-        for rate, members in groups.items():
-            if rate == fs:
-                group = [np.ascontiguousarray(waves[i], dtype=np.int16).reshape(-1) for i in members]
-                lengths = [len(w) for w in group]
-                if sum(lengths) == 0:
-                    yield members, lengths, None
-                    continue
-                pcm, offsets = self.torch.from_numpy(np.concatenate(group)).to(self.device), exclusive_offsets(lengths)
-            else:
-                if not (self.mfcc.allow_downsample if rate > fs else self.mfcc.allow_upsample):
-                    raise ValueError("sample rate %d Hz, but --sample-frequency=%g (there is no resampling without --allow-%s=true)"
-                                     % (rate, fs, "downsample" if rate > fs else "upsample"))
-                pcm, offsets, lengths, _ = self.resampler(rate).run([waves[i] for i in members])
-                lengths = [int(n) for n in lengths]
+        for members, pcm, offsets, lengths in self._rate_groups(waves, rates):
+            lengths = [int(n) for n in lengths]
+            if pcm is None:
+                yield members, lengths, None
+                continue
             frames = [self.num_frames(n) for n in lengths]
             x, rows, masks = self.on_device(pcm, offsets, np.asarray(lengths, np.int64), max(max(frames), 1))
             kept = frames if masks is None else masks.sum(dim=1, dtype=self.torch.int32).cpu().tolist()

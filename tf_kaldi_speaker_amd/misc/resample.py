@@ -15,8 +15,10 @@ import numpy as np
 
 try:
     from .._host import DEFAULT_WORKSPACE_BYTES, device_ops, exclusive_offsets, greedy_batches
+    from .waves import pack, unpack
 except (ImportError, ValueError):
     from _host import DEFAULT_WORKSPACE_BYTES, device_ops, exclusive_offsets, greedy_batches
+    from misc.waves import pack, unpack
 
 SPEED_RANGE = (0.5, 2.0)
 
@@ -94,11 +96,10 @@ class Resampler(object):
         out = torch.empty(max(int(n_out.sum()), 1), dtype=torch.int16, device=self.device)
         clipped = np.zeros(len(waves), np.int64)
         for batch in self._batches(n_in, n_out):
-            n = [n_in[i] for i in batch]
-            if sum(n) == 0:
+            src, offsets, n = pack([waves[i] for i in batch], self.device)
+            if src is None:
                 continue
-            src = torch.from_numpy(np.concatenate([waves[i] for i in batch])).to(self.device)
-            _, _, samples, clip, _ = self.ops.resample(self.cfg, self.tables, src, exclusive_offsets(n), n, out_offsets=out_offsets[batch], out_pcm=out)
+            _, _, samples, clip, _ = self.ops.resample(self.cfg, self.tables, src, offsets, n, out_offsets=out_offsets[batch], out_pcm=out)
             assert np.array_equal(samples.cpu().numpy(), n_out[batch])
             clipped[batch] = clip.cpu().numpy()
         return out, out_offsets, n_out, clipped
@@ -106,5 +107,4 @@ class Resampler(object):
     def resample(self, waves):
         """The host convenience: ([int16 array per waveform], clipped)."""
         pcm, offsets, lengths, clipped = self.run(waves)
-        host = pcm.cpu().numpy()
-        return [host[o:o + k].copy() for o, k in zip(offsets, lengths)], clipped
+        return unpack(pcm, offsets, lengths), clipped

@@ -205,6 +205,17 @@ def logger(batched=False):
     return logging.getLogger("tf_kaldi_speaker_amd")
 
 
+def device_index(gpu):
+    """The HIP device of -g GPU among those HIP_VISIBLE_DEVICES leaves visible: GPU modulo their count, so parallel jobs spread over the
+    devices of a node and a node with one device serves every job; -1: the first.  torch is imported here, not by --help."""
+    import torch
+    return gpu % max(torch.cuda.device_count(), 1) if gpu >= 0 else 0
+
+
+def device(gpu):
+    return "cuda:%d" % device_index(gpu)
+
+
 def seed_from(params, offset=0):
     random.seed(params.seed + offset)
     np.random.seed(params.seed + offset)

@@ -43,8 +43,7 @@ def main():
         out = model.recentred(matrix)
         log.info("[INFO] Mean of N = %d vectors; transform.mat and plda are copied." % matrix.shape[0])
     else:
-        import torch
-        device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+        device = _cli.device(args.gpu)
         out = model.adapt(matrix, device=device, within_covar_scale=args.within_covar_scale, between_covar_scale=args.between_covar_scale,
                           mean_diff_scale=args.mean_diff_scale, log=log)
     out.save(args.backend_out)

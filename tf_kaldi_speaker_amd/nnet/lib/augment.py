@@ -22,12 +22,11 @@ wav-reverberate's with --normalize-output=true as include/xvector_hip.h restates
 are this project's own (numpy.random.RandomState(--seed)), not those of Kaldi's reverberate_data_dir.py / augment_data_dir.py.
 --make-speed-plan F[,F...] writes the speed-perturbed copies, `sp<F>-<key> <key> speed=<F>` per line and factor; no file is read.
 """
-import os
 import sys
 import time
 
 import _cli
-from misc import augment, features
+from misc import augment, waves
 
 # utterances augmented together (Augmenter cuts them into calls that fit its workspace)
 WINDOW_UTTERANCES = 256
@@ -48,14 +47,13 @@ def main():
             augment.write_plan(entries, args.plan, fs)
             log.info("[INFO] Wrote the speed plan of %d utterances to %s." % (len(entries), args.plan))
             return
-        rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response", any_rate) if args.rir_scp else {}
-        noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise", any_rate) if args.noise_scp else {}
+        rirs, noises, _ = augment.read_setup(options, args.rir_scp, args.noise_scp, fs, any_rate)
     except ValueError as e:
         sys.exit(str(e))
-    mono = features.MfccOptions(sample_frequency=fs)
+    mono = waves.WavFormat(fs)
     if args.make_plan:
         try:
-            utterances = [(key, len(features.read_wav(rx, mono, key)) / fs) for key, rx in wavs]
+            utterances = [(key, len(waves.read_wav(rx, mono, key)) / fs) for key, rx in wavs]
             entries = augment.make_plan(args.make_plan, utterances, augment.signal_seconds(rirs, fs), augment.signal_seconds(noises, fs),
                                         args.seed, args.fg_interval, fs)
         except ValueError as e:
@@ -65,51 +63,40 @@ def main():
         return
     if not args.out_dir:
         sys.exit("out_dir is needed (unless --make-plan writes the plan)")
+    rx_of = dict(wavs)
     try:
         entries = augment.read_plan(args.plan, fs, rirs, noises)
+        augment.check_sources(entries, rx_of, args.plan, args.wav_scp)      # every key, before the device is opened
     except ValueError as e:
         sys.exit(str(e))
-    rx_of = dict(wavs)
-    for e in entries:
-        if e.src_key not in rx_of:
-            sys.exit("%s: Key %s: source %s is not in %s" % (args.plan, e.out_key, e.src_key, args.wav_scp))
-    import torch
-    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    device = _cli.device(args.gpu)
     aug = augment.Augmenter(options, rirs, noises, fs, device)
-    wav_dir = os.path.join(args.out_dir, "wav")
-    os.makedirs(wav_dir, exist_ok=True)
+    out = waves.WavDir(args.out_dir)
     stats = {"utts": 0, "samples": 0, "clipped": 0, "t0": time.time()}
     window, window_samples = [], 0
-    with open(os.path.join(args.out_dir, "wav.scp"), "w") as scp:
+    with open(out.scp_path, "w") as scp:
         def flush():
             if not window:
                 return
             outs, clipped = aug.augment([w for _, w in window], [e for e, _ in window])
-            for (e, _), out, c in zip(window, outs, clipped):
-                path = os.path.join(wav_dir, e.out_key + ".wav")
-                augment.write_wav(path, out, fs)
-                scp.write("%s %s\n" % (e.out_key, path))
-                log.info("[INFO] Key %s: %d samples, %srir %s, %d noises, %d clipped." % (e.out_key, len(out), "speed %s, " % e.speed if e.speed else "",
+            for (e, _), y, c in zip(window, outs, clipped):
+                scp.write(out.write(e.out_key, y, fs))
+                log.info("[INFO] Key %s: %d samples, %srir %s, %d noises, %d clipped." % (e.out_key, len(y), "speed %s, " % e.speed if e.speed else "",
                                                                                          e.rir if e.rir is not None else "-", len(e.noises), int(c)))
                 stats["utts"] += 1
-                stats["samples"] += len(out)
+                stats["samples"] += len(y)
                 stats["clipped"] += int(c)
             del window[:]
 
-        last = (None, None)
-        for e in entries:
-            if last[0] != e.src_key:
-                try:
-                    last = (e.src_key, features.read_wav(rx_of[e.src_key], mono, e.src_key))
-                except ValueError as err:
-                    sys.exit(str(err))
-            if len(last[1]) == 0:
-                sys.exit("Key %s: the source %s holds no samples" % (e.out_key, e.src_key))
-            window.append((e, last[1]))
-            window_samples += len(last[1])
-            if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
-                flush()
-                window_samples = 0
+        try:
+            for e, samples in augment.plan_sources(entries, rx_of, mono, args.plan, args.wav_scp):
+                window.append((e, samples))
+                window_samples += len(samples)
+                if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
+                    flush()
+                    window_samples = 0
+        except augment.SourceError as err:
+            sys.exit(str(err))
         flush()
     log.info("[INFO] Augmented %d utterances (%d samples, %d clipped) in %.2f s." % (stats["utts"], stats["samples"], stats["clipped"],
                                                                                     time.time() - stats["t0"]))

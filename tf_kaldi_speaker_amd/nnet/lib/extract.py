@@ -66,8 +66,7 @@ def main():
     # leaves visible, job N takes device N modulo their count, so `nj` parallel jobs spread over the GPUs of the node and
     # a node with one device serves every job; -1 (the default) = the first visible device.
     if args.gpu >= 0:
-        import torch
-        os.environ["LOCAL_RANK"] = str(args.gpu % max(torch.cuda.device_count(), 1))
+        os.environ["LOCAL_RANK"] = str(_cli.device_index(args.gpu))
     nnet_dir = os.path.join(args.model_dir, "nnet")
     config_json = os.path.join(args.model_dir, "nnet/config.json")
     if not os.path.isfile(config_json):

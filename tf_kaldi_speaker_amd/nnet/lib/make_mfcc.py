@@ -54,8 +54,7 @@ def main(kind="mfcc"):
         vad = features.VadOptions.from_conf(args.vad_config) if args.vad_config else features.VadOptions()
     except ValueError as e:
         sys.exit(str(e))
-    import torch
-    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    device = _cli.device(args.gpu)
     log.info("[INFO] %s without dither (--dither=0): on digital silence the features sit at the FLT_EPSILON floors; --energy-floor lifts the energy."
              % ("MFCC" if kind == "mfcc" else "Filterbank energies"))
     fx = features.FeatureExtractor(mfcc, vad, device, with_vad=bool(args.vad_wspecifier))
@@ -115,29 +114,20 @@ def main(kind="mfcc"):
         try:
             options = augment.AugmentOptions.from_conf(args.augment_config) if args.augment_config else augment.AugmentOptions()
             fs = mfcc.sample_frequency
-            rirs = augment.read_signals(args.rir_scp, fs, options.impulse_response_channel, "impulse response", any_rate) if args.rir_scp else {}
-            noises = augment.read_signals(args.noise_scp, fs, options.noise_channel, "noise", any_rate) if args.noise_scp else {}
-            entries = augment.read_plan(args.augment_plan, fs, rirs, noises)
+            rirs, noises, entries = augment.read_setup(options, args.rir_scp, args.noise_scp, fs, any_rate, args.augment_plan)
             rx_of = dict(augment.read_scp(args.wav_scp))
         except ValueError as e:
             sys.exit(str(e))
         aug = augment.Augmenter(options, rirs, noises, fs, device)
-        last = (None, None)
-        for e in entries:
-            if e.src_key not in rx_of:
-                sys.exit("%s: Key %s: source %s is not in %s" % (args.augment_plan, e.out_key, e.src_key, args.wav_scp))
-            if last[0] != e.src_key:
-                try:
-                    last = (e.src_key, features.read_wav(rx_of[e.src_key], mfcc, e.src_key))
-                except ValueError as err:
-                    sys.exit(str(err))
-            if len(last[1]) == 0:
-                sys.exit("Key %s: the source %s holds no samples" % (e.out_key, e.src_key))
-            window.append((e, last[1]))
-            window_samples += len(last[1])
-            if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
-                flush_augmented(aug)
-                window_samples = 0
+        try:
+            for e, samples in augment.plan_sources(entries, rx_of, mfcc, args.augment_plan, args.wav_scp):
+                window.append((e, samples))
+                window_samples += len(samples)
+                if len(window) >= WINDOW_UTTERANCES or window_samples >= WINDOW_SAMPLES:
+                    flush_augmented(aug)
+                    window_samples = 0
+        except augment.SourceError as err:
+            sys.exit(str(err))
         if window:
             flush_augmented(aug)
     else:

@@ -39,8 +39,7 @@ def main():
     if "." in args.raw_rspecifier and args.raw_rspecifier.rsplit(".", 1)[1] == "scp":
         sys.exit("The rspecifier must be ark or input pipe")
     out = _cli.Table(args.prepared_wspecifier, "prepared_wspecifier")
-    import torch
-    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    device = _cli.device(args.gpu)
     prep = features.FeaturePreparer(args.cmn_window, args.cm_header, device)
     vad = VecFltTable(args.vad) if args.vad else None
     counts = open(args.write_utt2num_frames, "w") if args.write_utt2num_frames else None

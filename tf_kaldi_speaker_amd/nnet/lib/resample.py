@@ -12,12 +12,11 @@ RIFF PCM-16, rounded to nearest) and out_dir/wav.scp, and logs per key its sampl
 rate: one table per conversion.  The arithmetic is Kaldi's LinearResample with ResampleWaveform's cutoff as include/xvector_hip.h
 restates it - not sox's resampler and not `sox speed`'s.
 """
-import os
 import sys
 import time
 
 import _cli
-from misc import augment, features, resample
+from misc import resample, waves
 
 # samples converted together (Resampler cuts them into calls that fit its workspace)
 WINDOW_UTTERANCES = 256
@@ -32,18 +31,16 @@ def main():
     if args.to_rate < 0:
         sys.exit("--to-rate=%d: a sample rate of at least 1 Hz is expected" % args.to_rate)
     try:
-        wavs = augment.read_scp(args.wav_scp)
+        wavs = waves.read_scp(args.wav_scp)
     except ValueError as e:
         sys.exit(str(e))
-    import torch
-    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
-    any_rate = features.MfccOptions(channel=args.channel)
-    wav_dir = os.path.join(args.out_dir, "wav")
-    os.makedirs(wav_dir, exist_ok=True)
-    resamplers = {}
+    device = _cli.device(args.gpu)
+    any_rate = waves.WavFormat(channel=args.channel)
+    out_dir = waves.WavDir(args.out_dir)
+    resamplers = waves.Resamplers(device)
     stats = {"utts": 0, "samples": 0, "clipped": 0, "t0": time.time()}
     windows = {}      # source rate -> [(key, samples)]
-    done = {}         # key -> path, written to wav.scp in the order of the input
+    done = {}         # key -> its line of wav.scp, written in the order of the input
 
     def flush(rate):
         window = windows.pop(rate, [])
@@ -56,16 +53,13 @@ def main():
         if fin == fout:
             outs, clipped = [w for _, w in window], [0] * len(window)
         else:
-            if (fin, fout) not in resamplers:
-                try:
-                    resamplers[(fin, fout)] = resample.Resampler(fin, fout, device)
-                except Exception as e:      # a conversion the library refuses by name (a table that does not fit)
-                    sys.exit("Key %s: %s" % (window[0][0], e))
-            outs, clipped = resamplers[(fin, fout)].resample([w for _, w in window])
+            try:
+                resampler = resamplers[fin, fout]
+            except Exception as e:      # a conversion the library refuses by name (a table that does not fit)
+                sys.exit("Key %s: %s" % (window[0][0], e))
+            outs, clipped = resampler.resample([w for _, w in window])
         for (key, w), out, c in zip(window, outs, clipped):
-            path = os.path.join(wav_dir, key + ".wav")
-            augment.write_wav(path, out, fout)
-            done[key] = path
+            done[key] = out_dir.write(key, out, fout)
             log.info("[INFO] Key %s: %d samples at %d Hz -> %d samples at %d Hz, %d clipped." % (key, len(w), rate, len(out), fout, int(c)))
             stats["utts"] += 1
             stats["samples"] += len(out)
@@ -75,7 +69,7 @@ def main():
         if key in done or any(key == k for w in windows.values() for k, _ in w):
             sys.exit("%s: key %s is listed twice" % (args.wav_scp, key))
         try:
-            samples, rate = features.read_wav_rate(rx, any_rate, key, any_rate=True)
+            samples, rate = waves.read_wav_rate(rx, any_rate, key, any_rate=True)
         except ValueError as e:
             sys.exit(str(e))
         window = windows.setdefault(rate, [])
@@ -84,9 +78,8 @@ def main():
             flush(rate)
     for rate in sorted(windows):
         flush(rate)
-    with open(os.path.join(args.out_dir, "wav.scp"), "w") as scp:
-        for key, _ in wavs:
-            scp.write("%s %s\n" % (key, done[key]))
+    with open(out_dir.scp_path, "w") as scp:
+        scp.writelines(done[key] for key, _ in wavs)
     log.info("[INFO] Resampled %d utterances (%d samples, %d clipped) in %.2f s." % (stats["utts"], stats["samples"], stats["clipped"],
                                                                                     time.time() - stats["t0"]))
 

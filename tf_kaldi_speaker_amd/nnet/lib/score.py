@@ -85,8 +85,7 @@ def main():
         sys.exit("--cohort with --scoring plda is not supported: plda writes raw log-likelihood ratios; --scoring plda_asnorm normalises them against the cohort")
     if args.scoring == "plda_asnorm" and not args.cohort:
         sys.exit("--scoring plda_asnorm needs --cohort RSPECIFIER (the vectors the PLDA scores are normalised against)")
-    import torch
-    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    device = _cli.device(args.gpu)
     trials = scoring.read_trials(args.trials)
     enrol_keys, enrol = scoring.read_vectors(args.enrol_rspecifier)
     same = args.test_rspecifier == args.enrol_rspecifier

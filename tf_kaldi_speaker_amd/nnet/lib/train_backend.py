@@ -26,8 +26,7 @@ def main():
         sys.exit("--lda-dim must be positive (got %d); --no-lda trains without an LDA" % args.lda_dim)
     if args.num_em_iters <= 0:
         sys.exit("--num-em-iters must be positive (got %d)" % args.num_em_iters)
-    import torch
-    device = "cuda:%d" % (args.gpu % max(torch.cuda.device_count(), 1) if args.gpu >= 0 else 0)
+    device = _cli.device(args.gpu)
     keys, matrix = scoring.read_vectors(args.train_rspecifier)
     if not args.no_lda and args.lda_dim > matrix.shape[1]:
         sys.exit("--lda-dim %d exceeds the %d dimensions of the vectors" % (args.lda_dim, matrix.shape[1]))

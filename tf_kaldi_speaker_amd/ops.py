@@ -3,7 +3,8 @@
 Inputs/outputs are torch CUDA tensors used purely as device buffers; every
 function enqueues HIP kernels on torch's current stream.  No arithmetic is done
 by torch here.  These are what the per-kernel parity tests call.
-The ops of the pipeline stages around the network live in pipeline_ops.py and are re-exported here: callers write ops.mfcc, ops.augment ...
+The ops of the pipeline stages around the network live in wave_ops.py (those that take PCM) and pipeline_ops.py (features, scores, the
+back end) and are re-exported here: callers write ops.mfcc, ops.score_trials ...
 """
 import ctypes as C
 
@@ -12,9 +13,11 @@ import torch
 try:
     from ._host import _f32, _lib, _p, _s, _ws, pitch4, pitched, workspace
     from .pipeline_ops import *       # noqa: F401,F403 (its public names are the pipeline ops)
+    from .wave_ops import *           # noqa: F401,F403 (and those of the ops that take PCM)
 except ImportError:
     from _host import _f32, _lib, _p, _s, _ws, pitch4, pitched, workspace
     from pipeline_ops import *        # noqa: F401,F403
+    from wave_ops import *            # noqa: F401,F403
 
 TILE_M = 128
 
