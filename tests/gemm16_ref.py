@@ -1,4 +1,4 @@
-"""NumPy model of the split-precision (f16x3) representation and GEMMs of csrc/xv_gemm16.hip with the bound of each output, what
+"""NumPy model of the split-precision (f16x3) representation and GEMMs of csrc/xv_gemm16.h (xv_planes16.hip, xv_gemm16_nt.hip, xv_gemm16_tn.hip) with the bound of each output, what
 tests/test_gpu_gemm16_forms.py compares the kernels with.  As in tests/segment_ref.py: float64 is the reference, class NumpyOps is a plain
 float32 NumPy evaluation of the same formulas behind the interface of the GPU backend, which tests/test_gemm16_ref.py holds against the same
 bounds before the kernels run; u = 2^-24; bounds are per element or per channel, never relative to a tensor's largest entry.

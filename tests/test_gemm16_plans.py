@@ -1,4 +1,4 @@
-"""The launch rules of the split-precision (f16x3) GEMMs (csrc/xv_gemm16.hip: nt16_form - generic or context-window kernel, tile height,
+"""The launch rules of the split-precision (f16x3) GEMMs (csrc/xv_gemm16_nt.hip: nt16_form - generic or context-window kernel, tile height,
 taps, chunks, K-steps and the valid halfs of the last one; xv_tn16_splits / tn16_plan - tiles, splits, rows per split, the collapse of
 gap-free rows to one segment, steady or per-row stages) restated in Python and checked against the library's own answers
 (xv_debug_gemm16_nt_form / xv_debug_gemm16_tn_plan: host arithmetic, no GPU needed) at every boundary of the rules, over a grid and over

@@ -1,4 +1,4 @@
-"""Every form of the split-precision (f16x3) kernels of csrc/xv_gemm16.hip - the plane emitters, the generic and the context-window NT
+"""Every form of the split-precision (f16x3) kernels of csrc/xv_planes16.hip, xv_gemm16_nt.hip and xv_gemm16_tn.hip - the plane emitters, the generic and the context-window NT
 kernels with their epilogues, the TN weight-gradient kernel with its stage forms - at the smallest shapes that reach it.  A row first
 asserts its form through the restatement of tests/test_gemm16_plans.py and the library's hook, so a row that drifts to another branch
 fails by name.  A GEMM row then runs twice: on position-coded integer operands (every piece, product and partial sum exactly representable:

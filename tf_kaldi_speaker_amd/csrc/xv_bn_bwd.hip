@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_dense_kernel(const float* __
 }
 
 // Same as bn_bwd_apply_kernel but dz is written as two fp16 planes [2][segs*(t+2pad)][ldd] scaled by the power of two
-// derived from *amax (xv_gemm16.hip); pad rows / columns are zero.
+// derived from *amax (xv_gemm16.h); pad rows / columns are zero.
 // Thread = one 8-channel chunk (16 B per plane) x a strip of rows: the 7 per-channel parameter vectors are loaded
 // once per thread, not once per element (they were 3/4 of the load instructions of the element-per-thread form).
 // block = 64 chunks x 4 row lanes, BAS_ROWS padded rows per block.

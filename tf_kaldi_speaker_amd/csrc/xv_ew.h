@@ -1,5 +1,5 @@
 // Helpers shared by the element-wise units (xv_runtime, xv_prep, xv_bn, xv_bn_bwd, xv_pool, xv_update) and by the activation
-// sites of xv_gemm16.hip and xv_attention.hip: the launch grid of a grid-stride kernel, the wave sum, and the activation behind a
+// sites of xv_planes16.hip and xv_attention.hip: the launch grid of a grid-stride kernel, the wave sum, and the activation behind a
 // BatchNorm (act context, below) on a channel quad, forward and backward.  Device helpers are all __forceinline__: every kernel
 // keeps the instruction sequence it had with the expression written out.
 #pragma once

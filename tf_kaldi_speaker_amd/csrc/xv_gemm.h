@@ -1,4 +1,4 @@
-// Internal interface of the GEMM units (xv_gemm_nt.hip, xv_gemm_tn.hip, xv_gemm16.hip): tile geometry, the zero page, the ticket pool, the
+// Internal interface of the GEMM units (xv_gemm_nt.hip, xv_gemm_tn.hip, xv_gemm16_nt.hip, xv_gemm16_tn.hip): tile geometry, the zero page, the ticket pool, the
 // launch structs and launchers, the split functions the callers size workspaces with, and live launch timing.
 #pragma once
 #include "xv_common.h"
@@ -64,7 +64,7 @@ int xv_launch_gemm_tn(hipStream_t s, const XvGemmTN& g);
 int xv_launch_wgrad_reduce(hipStream_t s, const float* P, int splits, int k, int C, int c_pad, int n_in, int n_out, const float* w,
                            long ldw, float l2, float* out, long ldo);
 
-// ---- split-precision (f16x3) GEMMs on fp16 planes (xv_gemm16.hip) ------------------------------
+// ---- split-precision (f16x3) GEMMs on fp16 planes (xv_gemm16_nt.hip, xv_gemm16_tn.hip; xv_gemm16.h) ---
 struct XvGemm16NT {
     const void* A; long lda; long a_plane; int a_rps; int a_pitch;   // planes [2][rows][lda] fp16
     const void* Bt; long ldb; long b_plane;

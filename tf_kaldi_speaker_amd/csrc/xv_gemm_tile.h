@@ -1,4 +1,4 @@
-// Device pieces shared by the fp32 GEMM kernels (xv_gemm_nt.hip, xv_gemm_tn.hip; xcd_swizzle also by xv_gemm16.hip), each stated once: the LDS
+// Device pieces shared by the fp32 GEMM kernels (xv_gemm_nt.hip, xv_gemm_tn.hip; xcd_swizzle also by xv_gemm16_nt.hip / xv_gemm16_tn.hip), each stated once: the LDS
 // image of the NT kernels, the XCD swizzle, the hardware lane / wave helpers and the two tile epilogues of the NT kernels.  Plain
 // __forceinline__ functions: every kernel keeps the instruction sequence it had (profiles/gemm_split_isa.txt).
 // What is NOT here, although both NT kernels spell it the same way: zeroing the 2 x 2 accumulators, the fragment reads and MFMAs of one
