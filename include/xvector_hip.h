@@ -738,6 +738,33 @@ int xv_key_activation(void* stream, const float* z, size_t count, int act, float
 /* y[i] += x[i]  (the two gradient paths into tdnn4_relu: through tdnn5 and through the attention key network) */
 int xv_add_inplace(void* stream, float* y, const float* x, size_t count);
 
+/* ---- GhostVLAD / NetVLAD pooling (model/pooling.py:195-277), fp32 ----
+ * x [b*t][c] is the value tensor (the last frame layer's ReLU output), kg = k centres + ghost clusters <= 64, c a multiple of 4.
+ * The assignment logits x W + bias (pooling.py:242-246) and W's two gradients run on the dense GEMMs (xv_affine_forward / _wgrad /
+ * _dgrad); these are the pieces around them.  No atomics: a call gives the same bits every time.
+ *   a[r][j]   = softmax_j(logits[r][j]), j < kg; logits rows are ld >= kg floats apart (GEMM padding is never read)      pooling.py:249
+ *   r[b][k]   = sum_t a[t][k] (x_t - centers[k]), n[b][k] = sum_t a[t][k], k < k centres (the ghosts are dropped)       pooling.py:258-266
+ *               frames (optional, device [b]) / shrink: chunk i pools its first frames[i] - shrink rows only (batched extraction)
+ *   out[b]    = [r_k rsqrt(max(|r_k|^2, 1e-12))]_k, and with final_norm the k*c row normalised once more the same way   pooling.py:268-271 */
+int xv_vlad_softmax(void* stream, const float* logits, int rows, int kg, int ld, float* a);
+/* dst[r][j] = j < cols ? src[r][j] : 0 for j < ldd (rows lds / ldd floats apart): the [c][kg] kernel of pooling.py:242-246 as a GEMM operand on
+ * whole column quads (ldd = kg rounded up to 4, zero padding), and its gradient back (ldd = cols = kg < lds). */
+int xv_vlad_repitch(void* stream, const float* src, int rows, int cols, int lds, float* dst, int ldd);
+int xv_vlad_pool_forward(void* stream, const float* x, const float* a, const float* centers, int b, int t, int c, int k, int kg,
+                         const int32_t* frames, int shrink, float* r, float* n);
+int xv_vlad_normalize_forward(void* stream, const float* r, int b, int k, int c, int final_norm, float* out);
+/* Backward of the above (what tf.gradients derives from pooling.py:249-271).
+ *   dr from dout through both normalisations (a clamped norm passes the gradient through the constant 1e6: a zero residual stays finite)
+ *   da[r][k] = (x_r - centers[k]) . dr[b][k] for k < k centres, 0 for the ghosts;  dx[r] = sum_k a[r][k] dr[b][k]  (one pass over x)
+ *   dl[r][j] = a (da - sum_j a da), columns kg .. ld zeroed (ld <= 64)
+ *   dc[k]    = -sum_b n[b][k] dr[b][k] for k < k centres, 0 for the ghosts, + l2 * centers[k] (pooling.py:256 regulariser), [kg][c] */
+int xv_vlad_normalize_backward(void* stream, const float* r, const float* dout, int b, int k, int c, int final_norm, float* dr);
+int xv_vlad_pool_backward(void* stream, const float* x, const float* a, const float* centers, const float* dr, int b, int t, int c, int k,
+                          int kg, float* da, float* dx);
+int xv_vlad_softmax_backward(void* stream, const float* a, const float* da, int rows, int kg, int ld, float* dl);
+int xv_vlad_centers_backward(void* stream, const float* n, const float* dr, const float* centers, int b, int k, int kg, int c, float l2,
+                             float* dc);
+
 /* l2_scaling, common.py:45-58 (feature_norm:true, trainer.py:183-186). */
 int xv_l2_scaling_forward(void* stream, const float* x, int rows, int n, float factor, float* y);
 int xv_l2_scaling_backward(void* stream, const float* x, const float* dy, int rows, int n, float factor, float* dx);
@@ -808,7 +835,8 @@ int xv_sumsq(void* stream, const float* g, size_t count, float* out_accum);
 typedef struct xv_engine xv_engine;
 
 typedef struct xv_config {
-    int32_t struct_bytes;             /* = sizeof(xv_config) of the header the host was built against; anything else is refused */
+    int32_t struct_bytes;             /* = sizeof(xv_config) of the header the host was built against; anything else is refused (but the
+                                       * size this struct had before the vlad_* fields were added at its end: see there) */
     int32_t feat_dim;                 /* dim, train.py:71 */
     int32_t num_speakers;             /* train.py:74 (0 => no loss head, predict only) */
     int32_t num_nodes_pooling_layer;  /* tdnn.py:111-113, default 1500 */
@@ -853,6 +881,11 @@ typedef struct xv_config {
     /* capacity in rows = chunks x frames of one forward; 0 = max_batch * max_frames.  Batched extraction sets it (with a large
      * max_frames): a batch is many short utterances or a few long ones, never max_batch chunks of max_frames frames */
     int32_t max_rows;
+    /* ghost_vlad pooling (pooling.py:195-277).  Added behind the fields of ABI version 3: a host built against the shorter struct
+     * (struct_bytes = the offset of vlad_num_centers) is still accepted and reads as "no VLAD". */
+    int32_t vlad_num_centers;         /* K >= 1 */
+    int32_t vlad_num_ghosts;          /* G >= 0, K + G <= 64 */
+    int32_t vlad_final_l2_norm;       /* pooling.py:270-271 */
 } xv_config;
 #define XV_MAX_FRAME_LAYERS 12
 /* the non-linearity behind every BatchNorm: relu | prelu = relu(x) + alpha (x - |x|) / 2 with a trainable per-channel alpha
@@ -864,6 +897,9 @@ typedef struct xv_config {
 /* self_attention in the shipped single-head form (nnet_conf/..._tdnn4_att.json): key network on tdnn4_relu, value = tdnn5_relu,
  * one head, key not split, no value network, no penalty term, no post non-linearity */
 #define XV_POOL_SELF_ATTENTION 1
+/* ghost_vlad / NetVLAD: key = value = the last frame layer's ReLU output, no key / value networks; fp32 engine only.  The output is
+ * vlad_num_centers * num_nodes_pooling_layer columns wide */
+#define XV_POOL_GHOST_VLAD 2
 /* fp32-input MFMA (v_mfma_f32_32x32x2_f32, exact fp32 products) */
 #define XV_PRECISION_F32 0
 /* split precision: three fp16 MFMA products of (hi,lo) pieces per fp32 product, fp32 accumulate (2^-22 relative) */
@@ -931,7 +967,8 @@ int xv_engine_loss_ptrs(xv_engine* e, float** raw_loss, float** reg_loss);
 /* Diagnostics: device pointer to 1 float, the sum of squares over the gradient buffer [0, trainable count) as the last xv_engine_apply
  * with clip_gradient_norm > 0 took it - before grad_scale: that update's global norm is sqrtf(*sumsq) * grad_scale.  Read-only. */
 int xv_debug_engine_clip_sumsq(xv_engine* e, float** sumsq);
-/* endpoint by reference name ("tdnn1_conv", ..., "pooling", "tdnn6_dense", "output", "logits"):
+/* endpoint by reference name ("tdnn1_conv", ..., "pooling", "tdnn6_dense", "output", "logits"; ghost_vlad: "vlad_key", "vlad_weights",
+ * "vlad_centers"):
  * device pointer, rows, cols, leading dimension of the most recent forward. */
 int xv_engine_endpoint(xv_engine* e, const char* name, float** ptr, int32_t* rows, int32_t* cols, int32_t* ld);
 /* 1 (default): weight gradients run on an internal second HIP stream beside the data-gradient chain;

@@ -79,6 +79,9 @@ class XvConfig(_SizedConfig):
         ("frame_width", C.c_int32 * 12),
         ("relu_type", C.c_int32),
         ("max_rows", C.c_int32),
+        ("vlad_num_centers", C.c_int32),
+        ("vlad_num_ghosts", C.c_int32),
+        ("vlad_final_l2_norm", C.c_int32),
     ]
 
 
@@ -168,7 +171,7 @@ LOSS_KINDS = {
 }
 OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
 PRECISIONS = {"f32": 0, "f16x3": 1}
-POOLINGS = {"statistics_pooling": 0, "self_attention": 1}
+POOLINGS = {"statistics_pooling": 0, "self_attention": 1, "ghost_vlad": 2}
 RELU_TYPES = {"relu": 0, "prelu": 1, "lrelu": 2}
 
 _VP = C.c_void_p
@@ -242,6 +245,14 @@ SIGNATURES = {
     "xv_att_key_backward": (_I, [_VP, _VP, _I, _I, _I, _VP, _F, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "xv_key_activation": (_I, [_VP, _VP, _SZ, _I, _VP]),
     "xv_add_inplace": (_I, [_VP, _VP, _VP, _SZ]),
+    "xv_vlad_softmax": (_I, [_VP, _VP, _I, _I, _I, _VP]),
+    "xv_vlad_repitch": (_I, [_VP, _VP, _I, _I, _I, _VP, _I]),
+    "xv_vlad_pool_forward": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _VP]),
+    "xv_vlad_normalize_forward": (_I, [_VP, _VP, _I, _I, _I, _I, _VP]),
+    "xv_vlad_normalize_backward": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+    "xv_vlad_pool_backward": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
+    "xv_vlad_softmax_backward": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
+    "xv_vlad_centers_backward": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
     "xv_l2_scaling_forward": (_I, [_VP, _VP, _I, _I, _F, _VP]),
     "xv_l2_scaling_backward": (_I, [_VP, _VP, _VP, _I, _I, _F, _VP]),
     "xv_loss_prep_weight": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I, _VP]),

@@ -81,6 +81,18 @@ struct xv_engine {
     int amax_a = 1, amax_wt = 0, amax_dz = 0;   // slot ranges inside `amax`, see amax layout below
     bool att = false;
     int v_query = -1;
+    // ghost_vlad pooling (xv_vlad.hip): K centres + G ghost clusters on the last frame layer's ReLU output, which is then written like any
+    // other frame layer's (a) and whose backward takes a materialised d a.  The assignment GEMMs see W / the logits / d logits with
+    // KGp = K + G rounded up to 4 columns (xv_vlad_repitch writes the copies of the variables with zero padding columns).
+    bool vlad = false;
+    int VK = 0, VG = 0, VKG = 0, VKGp = 0;
+    int v_vlad_w = -1, v_vlad_b = -1, v_vlad_c = -1;
+    float *vl_wp = nullptr, *vl_wt = nullptr, *vl_bp = nullptr, *vl_dwp = nullptr;       // [P][KGp], [KGp][P], [KGp], [P][KGp]
+    float *vl_logits = nullptr, *vl_dl = nullptr;                                        // [B*T_pool][KGp]
+    float *vl_A = nullptr, *vl_dA = nullptr;                                             // [B*T_pool][KG]
+    float *vl_R = nullptr, *vl_dR = nullptr, *vl_n = nullptr;                            // [B][K][P] residuals, [B][K] assignment mass
+    float* vl_dxv = nullptr;                                                             // [B*T_pool][P]: the value path of d x
+    int pool_dim = 0;                     // columns of the pooled vector: 2 P, or K P with ghost_vlad
     float *att_score = nullptr, *att_w = nullptr, *att_dw = nullptr, *att_ds = nullptr;   // [B*T5]
     float* bufA = nullptr;                // d (key input) through the key network, [B*T_pool][width of tdnn(F-1)]
     int min_frames = 15;                  // receptive field of the frame layers

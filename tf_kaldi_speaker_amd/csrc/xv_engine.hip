@@ -31,6 +31,10 @@ void build_variables(xv_engine* e) {
     e->Lout = c.num_nodes_last_layer;
     e->N = c.num_speakers;
     e->att = c.pooling == XV_POOL_SELF_ATTENTION;
+    e->vlad = c.pooling == XV_POOL_GHOST_VLAD;
+    e->VK = e->vlad ? c.vlad_num_centers : 0; e->VG = e->vlad ? c.vlad_num_ghosts : 0;
+    e->VKG = e->VK + e->VG; e->VKGp = (int)xv_align(e->VKG, 4);
+    e->pool_dim = e->vlad ? e->VK * e->P : 2 * e->P;
     const int F = e->F;
     e->NL = e->att ? F + 4 : F + 2;
     e->L.assign(F + 4, XvAffine());
@@ -50,7 +54,7 @@ void build_variables(xv_engine* e) {
         }
     }
     const int Ckey = specs[F - 2].cout;      // the attention key network reads the last-but-one frame layer (tdnn4_relu in the shipped configs)
-    specs.push_back({"tdnn" + std::to_string(F + 1), "dense", "", 1, 2 * e->P, 512, true, true, false, -1, 0});
+    specs.push_back({"tdnn" + std::to_string(F + 1), "dense", "", 1, e->pool_dim, 512, true, true, false, -1, 0});
     specs.push_back({"tdnn" + std::to_string(F + 2), "dense", "", 1, 512, e->Lout, !c.last_layer_no_bn, !c.last_layer_linear, false, F, 0});
     // self-attention key network (pooling.py:78-96): dense+bn+relu on the key input, then dense (+tanh)
     specs.push_back({"att_key0", "dense", "attention/att_key0/", 1, Ckey, c.att_key0_nodes, true, true, false, F - 2, 0});
@@ -63,6 +67,11 @@ void build_variables(xv_engine* e) {
     order.push_back(F + 2); order.push_back(F + 3); order.push_back(F); order.push_back(F + 1);
     for (int i : order) {
         if (i >= e->NL) continue;
+        if (i == F && e->vlad) {      // pooling.py:242-256: the variables of the "vlad" scope sit where the attention variables sit
+            e->v_vlad_w = add_var(e, "tdnn/vlad/vlad_weight_affine/kernel", {e->P, e->VKG}, true);
+            e->v_vlad_b = add_var(e, "tdnn/vlad/vlad_weight_affine/bias", {e->VKG}, true);
+            e->v_vlad_c = add_var(e, "tdnn/vlad/vlad_centers", {e->VKG, e->P}, true);
+        }
         XvAffine& a = e->L[i];
         const Spec& s = specs[i];
         a.prefix = s.prefix; a.kind = s.kind; a.scope = s.scope; a.in_layer = s.in_layer; a.act = s.act;
@@ -73,7 +82,7 @@ void build_variables(xv_engine* e) {
         // The pooled layer's pre-BN tensor and its gradient are the largest tensors of the step and are streamed by HBM-bound kernels (pooling, the
         // pooled BatchNorm backward) and by the GEMMs' LDS-DMA: 1 500 channels = 6 000-byte rows start off the 128-byte grid (nine cache lines
         // per KiB instead of eight).  Plain fp32 path with statistics pooling and a plain ReLU only (the kernels of the other paths take dense rows).
-        a.ldz = (i == F - 1 && !e->f16 && !e->att && c.relu_type == XV_RELU_RELU && s.k == 1) ? (int)xv_align(s.cout, 32) : s.cout;
+        a.ldz = (i == F - 1 && !e->f16 && !e->att && !e->vlad && c.relu_type == XV_RELU_RELU && s.k == 1) ? (int)xv_align(s.cout, 32) : s.cout;
         a.has_bn = s.bn; a.has_relu = s.relu; a.fused_bn = s.fused;
         a.wslot = i < F ? i : i - 2;          // amax slots of the weights: tdnn1..F -> 0..F-1, att_key0/1 -> F, F+1
         a.aslot = i < F ? i : F - 1;          // BN+ReLU output planes: tdnn1..F-1 -> 0..F-2, att_key0 -> F-1
@@ -181,7 +190,15 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         take(e->att_score, rows_pool); take(e->att_w, rows_pool); take(e->att_dw, rows_pool); take(e->att_ds, rows_pool);
         take(e->bufA, rows_pool * e->L[F - 2].c_out);
     }
-    take(e->pool, B * 2 * e->P);
+    if (e->vlad) {
+        const size_t kgp = e->VKGp, kg = e->VKG;
+        take(e->vl_wp, (size_t)e->P * kgp); take(e->vl_wt, kgp * e->P); take(e->vl_bp, kgp); take(e->vl_dwp, (size_t)e->P * kgp);
+        take(e->vl_logits, rows_pool * kgp); take(e->vl_dl, rows_pool * kgp);
+        take(e->vl_A, rows_pool * kg); take(e->vl_dA, rows_pool * kg);
+        take(e->vl_R, B * e->pool_dim); take(e->vl_dR, B * e->pool_dim); take(e->vl_n, B * (size_t)e->VK);
+        if (e->N > 0) take(e->vl_dxv, rows_pool * e->P);      // (backward only: a predict-only engine does not pay for it)
+    }
+    take(e->pool, B * (size_t)e->pool_dim);
     take(e->h7_buf, B * e->Lout);
     take(e->out_buf, B * e->Lout);
     if (e->N > 0 && c.aux_mhe) {
@@ -203,7 +220,7 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         take(e->dzh[0], p.dzh_halfs);
         take(e->dzh[1], p.dzh_halfs);
     }
-    const size_t small = B * (size_t)(2 * e->P > 512 ? 2 * e->P : 512);
+    const size_t small = B * (size_t)(e->pool_dim > 512 ? e->pool_dim : 512);
     take(e->d_small0, small);
     take(e->d_small1, small);
     take(e->scalars, 16);
@@ -241,6 +258,10 @@ size_t workspace_bytes(const xv_engine* e, const ArenaPlan& p) {
     }
     size_t opws = xv_op_workspace_bytes((int)p.rows[1], 2 * e->P, 2 * e->P);
     if (opws > ws) ws = opws;
+    if (e->vlad) {      // the assignment layer's weight gradient [P][KGp] over the pooled rows
+        size_t s = (size_t)xv_tn_splits(e->P, e->VKGp, (int)rows_pool) * e->P * e->VKGp * sizeof(float);
+        if (s > ws) ws = s;
+    }
     if (e->att) {       // xv_att_key_backward: per-chunk partials + the column-sum workspace
         size_t s = 2 * ((size_t)xv_cdiv(rows_pool, 64) * 2 * c.att_key1_nodes * sizeof(float) + xv_op_workspace_bytes((int)rows_pool, c.att_key1_nodes, c.att_key1_nodes)) + 4096;
         if (s > ws) ws = s;
@@ -298,7 +319,7 @@ int alloc_buffers(xv_engine* e) {
     e->zr[0].n = e->f16 ? 2 : e->nz;
     e->zr[1].n = 2;
     p.dzh_halfs = xv_align(max_pad_rows * (size_t)xv_align(p.maxc, 8), 8);
-    p.ntick = xv_skinny_tickets((int)std::max<size_t>(std::max<size_t>(e->N, 2 * (size_t)e->P), std::max<size_t>(p.maxc, (size_t)e->Lout))) + 8;
+    p.ntick = xv_skinny_tickets((int)std::max<size_t>(std::max<size_t>(e->N, (size_t)e->pool_dim), std::max<size_t>(p.maxc, (size_t)e->Lout))) + 8;
     p.ws = workspace_bytes(e, p);
     ArenaCursor measured;
     arena_layout(e, p, measured);
@@ -355,9 +376,16 @@ int alloc_buffers(xv_engine* e) {
 extern "C" int xv_engine_create(const xv_config* cfg, xv_engine** out) {
     XV_REQUIRE(cfg && out, "engine_create: null argument");
     if (!xv_env()) return 2;      // an environment switch this library does not know, or a value it does not understand: refused by name
-    XV_REQUIRE(cfg->struct_bytes == (int32_t)sizeof(xv_config),
+    // the struct of ABI version 3 before the ghost_vlad fields were added behind it is still accepted (those fields then read as 0)
+    const int32_t v3_bytes = (int32_t)offsetof(xv_config, vlad_num_centers);
+    XV_REQUIRE(cfg->struct_bytes == (int32_t)sizeof(xv_config) || cfg->struct_bytes == v3_bytes,
                "engine_create: xv_config.struct_bytes is %d, this library's xv_config has %d bytes (ABI version %d): rebuild the host against include/xvector_hip.h",
                cfg->struct_bytes, (int)sizeof(xv_config), XV_ABI_VERSION);
+    xv_config full;
+    memset(&full, 0, sizeof(full));
+    memcpy(&full, cfg, (size_t)cfg->struct_bytes);
+    full.struct_bytes = (int32_t)sizeof(xv_config);
+    cfg = &full;
     XV_REQUIRE(cfg->feat_dim > 0, "engine_create: feat_dim must be positive");
     XV_REQUIRE(cfg->num_nodes_pooling_layer > 0 && cfg->num_nodes_pooling_layer % 4 == 0,
                "engine_create: num_nodes_pooling_layer must be a positive multiple of 4 (got %d)", cfg->num_nodes_pooling_layer);
@@ -369,7 +397,14 @@ extern "C" int xv_engine_create(const xv_config* cfg, xv_engine** out) {
         XV_REQUIRE(cfg->margin_m == 1.f || cfg->margin_m == 2.f || cfg->margin_m == 4.f, "[ERROR] m=%d is not unsupported.", (int)cfg->margin_m);
     XV_REQUIRE(!cfg->feature_norm || cfg->feature_scaling_factor > 0.f, "If feature normalization is applied, scaling factor is necessary.");
     XV_REQUIRE(cfg->precision == XV_PRECISION_F32 || cfg->precision == XV_PRECISION_F16X3, "engine_create: unknown precision %d", cfg->precision);
-    XV_REQUIRE(cfg->pooling == XV_POOL_STATISTICS || cfg->pooling == XV_POOL_SELF_ATTENTION, "Not implement pooling kind %d", cfg->pooling);
+    XV_REQUIRE(cfg->pooling == XV_POOL_STATISTICS || cfg->pooling == XV_POOL_SELF_ATTENTION || cfg->pooling == XV_POOL_GHOST_VLAD,
+               "Not implement pooling kind %d", cfg->pooling);
+    if (cfg->pooling == XV_POOL_GHOST_VLAD) {
+        XV_REQUIRE(cfg->precision == XV_PRECISION_F32, "engine_create: ghost_vlad pooling runs in precision f32 only (not f16x3)");
+        XV_REQUIRE(cfg->vlad_num_centers >= 1 && cfg->vlad_num_ghosts >= 0 && cfg->vlad_num_centers + cfg->vlad_num_ghosts <= 64,
+                   "engine_create: ghost_vlad needs vlad_num_centers >= 1, vlad_num_ghosts >= 0 and at most 64 clusters in all (got %d + %d)",
+                   cfg->vlad_num_centers, cfg->vlad_num_ghosts);
+    }
     if (cfg->pooling == XV_POOL_SELF_ATTENTION) {
         XV_REQUIRE(cfg->att_key0_nodes > 0 && cfg->att_key0_nodes % 4 == 0 && cfg->att_key1_nodes > 0 && cfg->att_key1_nodes % 4 == 0,
                    "engine_create: att_key_num_nodes must be two positive multiples of 4 (got %d, %d)", cfg->att_key0_nodes, cfg->att_key1_nodes);

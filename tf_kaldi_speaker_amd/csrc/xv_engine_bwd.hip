@@ -427,6 +427,32 @@ int backward_attention(xv_engine* e, hipStream_t s) {
     return layer_backward(e, s, k0, e->bufD, e->L[F - 2].a, rows, 1, e->bufA, nullptr);  // -> d (key input) through the keys (bufA)
 }
 
+// ghost_vlad backward (stage 1): d pool -> d R through the normalisations; the centres; one pass over x for d A and the value path of
+// d x; the softmax; W's bias / weight / data gradients on the column-sum and GEMM launchers; the two paths into x joined in bufD
+int backward_vlad(xv_engine* e, hipStream_t s) {
+    const xv_config& c = e->cfg;
+    XvAffine& a = e->L[e->F - 1];
+    const int b = e->B, Tp = e->Tl[e->F], rows = b * Tp, P = e->P, K = e->VK, KG = e->VKG, KGp = e->VKGp;
+    const float* cen = vptr(e, e->v_vlad_c);
+    int rc = xv_vlad_normalize_backward(s, e->vl_R, e->d_small0, b, K, P, c.vlad_final_l2_norm, e->vl_dR);
+    if (rc) return rc;
+    rc = xv_vlad_centers_backward(s, e->vl_n, e->vl_dR, cen, b, K, KG, P, c.weight_l2_regularizer, gptr(e, e->v_vlad_c));
+    if (rc) return rc;
+    rc = xv_vlad_pool_backward(s, a.a, e->vl_A, cen, e->vl_dR, b, Tp, P, K, KG, e->vl_dA, e->vl_dxv);
+    if (rc) return rc;
+    rc = xv_vlad_softmax_backward(s, e->vl_A, e->vl_dA, rows, KG, KGp, e->vl_dl);
+    if (rc) return rc;
+    rc = xv_colsum(s, e->vl_dl, rows, KG, KGp, gptr(e, e->v_vlad_b), e->ws, e->ws_bytes);
+    if (rc) return rc;
+    rc = xv_affine_wgrad_ld(s, a.a, rows, 1, P, 1, P, e->vl_dl, KGp, 1, 0, KGp, e->vl_wp, c.weight_l2_regularizer, e->vl_dwp, e->ws, e->ws_bytes);
+    if (rc) return rc;
+    rc = xv_vlad_repitch(s, e->vl_dwp, P, KG, KGp, gptr(e, e->v_vlad_w), KG);
+    if (rc) return rc;
+    rc = xv_affine_dgrad_ld(s, e->vl_dl, KGp, rows, 1, KGp, 1, e->vl_wp, e->bufD, P, e->ws, e->ws_bytes);
+    if (rc) return rc;
+    return xv_add_inplace(s, e->bufD, e->vl_dxv, (size_t)rows * P);
+}
+
 // backward of frame layer i: a context layer sees chunks of Tl[i] frames, a dense layer one "chunk" per frame
 int frame_backward(xv_engine* e, hipStream_t s, int i, const float* da) {
     XvAffine& a = e->L[i];
@@ -468,7 +494,8 @@ int engine_backward(xv_engine* e, void* stream, int stage, bool defer) {
     }
     if (stage == -1 || stage == 1) {
         if (e->att) { rc = backward_attention(e, s); if (rc) return rc; }
-        rc = frame_backward(e, s, F - 1, nullptr);                                     // last frame layer (da = pooling backward)
+        if (e->vlad) { rc = backward_vlad(e, s); if (rc) return rc; }
+        rc = frame_backward(e, s, F - 1, e->vlad ? e->bufD : nullptr);                 // last frame layer (da = pooling backward, materialised for ghost_vlad)
         if (rc) return rc;
         if (e->att) rc = xv_add_inplace(s, e->bufD, e->bufA, (size_t)e->B * e->Tl[F] * e->L[F - 2].c_out);   // the two paths into the key input
         if (rc) return rc;

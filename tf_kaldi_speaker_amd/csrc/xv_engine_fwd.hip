@@ -171,7 +171,7 @@ int layer_forward(xv_engine* e, hipStream_t s, int i, int segs, int t_in) {
     XvAffine& a = e->L[i];
     const int rows = segs * (t_in - a.k + 1);
     const XvAffine* in = a.in_layer < 0 ? nullptr : &e->L[a.in_layer];
-    float* dst_a = i == e->F - 1 ? nullptr : a.a;
+    float* dst_a = (i == e->F - 1 && !e->vlad) ? nullptr : a.a;      // (ghost_vlad reads the activation twice: it is written)
     int rc;
     if (e->f16) {
         const unsigned short* xh = in ? in->ah : e->xh;
@@ -241,6 +241,27 @@ int output_forward(xv_engine* e, hipStream_t s) {
     return rc;
 }
 
+// ghost_vlad (pooling.py:225-277) on the last frame layer's ReLU output: the assignment logits on the dense GEMM (W and the bias as
+// copies padded to whole column quads), softmax over the K + G clusters, the residual sums of the K centres, the normalisations
+int vlad_forward(xv_engine* e, hipStream_t s, int b, int Tp, const int32_t* frames, int shrink) {
+    const xv_config& c = e->cfg;
+    XvAffine& a = e->L[e->F - 1];
+    const int rows = b * Tp, P = e->P, K = e->VK, KG = e->VKG, KGp = e->VKGp;
+    int rc = xv_vlad_repitch(s, vptr(e, e->v_vlad_w), P, KG, KG, e->vl_wp, KGp);
+    if (rc) return rc;
+    rc = xv_vlad_repitch(s, vptr(e, e->v_vlad_b), 1, KG, KG, e->vl_bp, KGp);
+    if (rc) return rc;
+    rc = xv_prep_weight_fwd(s, e->vl_wp, 1, P, KGp, e->vl_wt, P);
+    if (rc) return rc;
+    rc = xv_affine_forward(s, a.a, rows, 1, P, 1, e->vl_wt, e->vl_bp, e->vl_logits, KGp, KGp, nullptr, e->ws, e->ws_bytes);
+    if (rc) return rc;
+    rc = xv_vlad_softmax(s, e->vl_logits, rows, KG, KGp, e->vl_A);
+    if (rc) return rc;
+    rc = xv_vlad_pool_forward_ex(s, a.a, e->vl_A, vptr(e, e->v_vlad_c), b, Tp, P, K, KG, frames, shrink, e->vl_R, e->vl_n);
+    if (rc) return rc;
+    return xv_vlad_normalize_forward(s, e->vl_R, b, K, P, c.vlad_final_l2_norm, e->pool);
+}
+
 int engine_forward(xv_engine* e, void* stream, const float* features, int b, int t, int training, const int32_t* frames) {
     XV_REQUIRE(e && e->V, "engine_forward: engine not bound");
     XV_REQUIRE(b >= 1 && b <= e->cfg.max_batch, "engine_forward: batch %d exceeds capacity %d", b, e->cfg.max_batch);
@@ -297,8 +318,10 @@ int engine_forward(xv_engine* e, void* stream, const float* features, int b, int
         if (rc) return rc;
         frame_w = e->att_w;
     }
-    // the last frame layer's BN + ReLU is applied inside the pooling reduction: its [b*t][1500] activation is never written
-    {
+    if (e->vlad) {
+        rc = vlad_forward(e, s, b, Tp, frames, t - Tp);
+    } else {
+        // the last frame layer's BN + ReLU is applied inside the pooling reduction: its [b*t][1500] activation is never written
         XvAffine& a = e->L[F - 1];
         ActScope act(e, a);
         rc = xv_stat_pool_forward_bn_ex(s, a.z, b, Tp, e->P, a.scale, a.shift, 1, frame_w, e->pool, training ? e->pool_wpos : nullptr,
@@ -386,6 +409,12 @@ int xve_reg_loss(xv_engine* e, hipStream_t s) {
     for (int i = 0; i < e->NL; ++i) {
         int rc = xv_sumsq_ordered(s, vptr(e, e->L[i].v_kernel), e->vars[e->L[i].v_kernel].count, 0.5f * c.weight_l2_regularizer, e->scalars + 1, (float*)e->ws);
         if (rc) return rc;
+    }
+    if (e->vlad) {      // pooling.py:245,256: the assignment kernel and every centre (ghosts included), not the bias
+        for (int v : {e->v_vlad_w, e->v_vlad_c}) {
+            int rc = xv_sumsq_ordered(s, vptr(e, v), e->vars[v].count, 0.5f * c.weight_l2_regularizer, e->scalars + 1, (float*)e->ws);
+            if (rc) return rc;
+        }
     }
     if (e->N > 0) {
         int rc = xv_sumsq_ordered(s, vptr(e, e->v_loss_kernel), e->vars[e->v_loss_kernel].count, 0.5f * xve_output_l2(c), e->scalars + 1, (float*)e->ws);

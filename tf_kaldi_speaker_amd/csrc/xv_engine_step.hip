@@ -156,7 +156,7 @@ extern "C" int xv_engine_endpoint(xv_engine* e, const char* name, float** ptr, i
         }
     }
     // debug views of the backward scratch (valid right after backward stage 0)
-    if (n == "debug:da5") {     // evaluated on demand with the standalone pooling backward (valid after backward stage 0, before stage 1)
+    if (n == "debug:da5" && !e->vlad) {     // evaluated on demand with the standalone pooling backward (valid after backward stage 0, before stage 1)
         XvAffine& a5 = e->L[e->F - 1];
         ActScope act(e, a5);
         int rc = xv_bn_apply(e->last_stream, a5.z, a5.rows, a5.c_out, a5.ldz, a5.scale, a5.shift, 1, a5.a, a5.c_out);
@@ -165,7 +165,13 @@ extern "C" int xv_engine_endpoint(xv_engine* e, const char* name, float** ptr, i
         if (rc) return rc;
         return set(e->bufD, e->B * e->Tl[e->F], e->P, e->P);
     }
-    if (n == "debug:dpool") return set(e->d_small0, e->B, 2 * e->P, 2 * e->P);
+    if (n == "debug:dpool") return set(e->d_small0, e->B, e->pool_dim, e->pool_dim);
+    if (e->vlad) {      // pooling.py:250,273-275
+        const int rows = e->B * e->Tl[e->F];
+        if (n == "vlad_key") return set(e->vl_logits, rows, e->VKG, e->VKGp);
+        if (n == "vlad_weights") return set(e->vl_A, rows, e->VKG, e->VKG);
+        if (n == "vlad_centers") return set(vptr(e, e->v_vlad_c), e->VKG, e->P, e->P);
+    }
     if (n == "attention_weights" && e->att) return set(e->att_w, e->B, e->Tl[e->F], e->Tl[e->F]);     // [b, heads = 1, frames]
     if (n == "att_key1_relu" && e->att && e->L[e->K1()].act == 1) {      // relu key (type 1) lives inside the score kernels: rebuild on demand
         XvAffine& k1 = e->L[e->K1()];
@@ -175,7 +181,7 @@ extern "C" int xv_engine_endpoint(xv_engine* e, const char* name, float** ptr, i
         if (rc) return rc;
         return set(sc, k1.rows, k1.c_out, k1.c_out);
     }
-    if (n == "pooling") return set(e->pool, e->B, 2 * e->P, 2 * e->P);
+    if (n == "pooling") return set(e->pool, e->B, e->pool_dim, e->pool_dim);
     if (n == "output") return set(e->out, e->B, e->Lout, e->Lout);
     if (n == "logits" && e->N > 0) return set(e->logits, e->B, e->N, e->ldl);
     xv_set_error("engine_endpoint: unknown endpoint '%s'", name);

@@ -11,5 +11,8 @@
 int xv_stat_pool_forward_bn_ex(hipStream_t s, const float* z, int b, int t, int c, const float* scale, const float* shift, int relu,
                                const float* weights, float* out, float* wpos, float* amax, const int32_t* frames = nullptr, int shrink = 0,
                                int ldz = 0 /* floats per row of z; 0 = c */);
+// xv_vlad_pool_forward on a hipStream_t (xv_vlad.hip)
+int xv_vlad_pool_forward_ex(hipStream_t s, const float* x, const float* a, const float* centers, int b, int t, int c, int k, int kg,
+                            const int32_t* frames, int shrink, float* r, float* n);
 // softmax over the first frames[i] - shrink scores of chunk i (weights beyond are 0); frames == nullptr: all t (xv_attention.hip)
 int xv_softmax_segments_ex(hipStream_t s, const float* score, int b, int t, float* weights, const int32_t* frames, int shrink);

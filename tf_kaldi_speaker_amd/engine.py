@@ -46,7 +46,8 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
                 bn_epsilon=1e-3, fused_bn_unbiased_moving_var=True, optimizer="sgd", momentum=0.9, use_nesterov=False,
                 clip_gradient_norm=0.0, max_batch=128, max_frames=400, precision=None, pooling_type="statistics_pooling",
                 att_key_num_nodes=(1500, 1500), att_key_network_type=3, att_use_scale=True, aux_loss_func=(), ring_loss_init=20.0,
-                ring_loss_lambda=0.01, mhe_lambda=0.01, frame_layers=None, network_relu_type="relu", max_rows=0):
+                ring_loss_lambda=0.01, mhe_lambda=0.01, frame_layers=None, network_relu_type="relu", max_rows=0,
+                vlad_num_centers=0, vlad_num_ghosts=0, vlad_final_l2_norm=False):
     if pooling_type not in POOLINGS:
         raise NotImplementedError("Not implement %s pooling" % pooling_type)
     if loss_func not in LOSS_KINDS:
@@ -114,6 +115,14 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
         c.att_key0_nodes, c.att_key1_nodes = int(att_key_num_nodes[0]), int(att_key_num_nodes[1])
         c.att_key_type = int(att_key_network_type)
         c.att_use_scale = int(bool(att_use_scale))
+    if pooling_type == "ghost_vlad":
+        # pooling.py:195-277 with key = value = the last frame layer's ReLU output (model/tdnn.check_params refuses the other inputs by name)
+        k, g = int(vlad_num_centers), int(vlad_num_ghosts)
+        if k < 1 or g < 0 or k + g > 64:
+            raise NotImplementedError("ghost_vlad: vlad_num_centers >= 1, vlad_num_ghosts >= 0 and at most 64 clusters in all (got %d + %d)" % (k, g))
+        if precision != "f32":
+            raise NotImplementedError("ghost_vlad: precision %s is not supported (f32 only)" % precision)
+        c.vlad_num_centers, c.vlad_num_ghosts, c.vlad_final_l2_norm = k, g, int(bool(vlad_final_l2_norm))
     return c
 
 
@@ -209,6 +218,9 @@ class Engine(object):
                 vals[name] = rs.uniform(-lim, lim, size=shape).astype(np.float32)
             elif name == "softmax_ringloss/r":
                 vals[name] = np.full(shape, self.config.ring_loss_init, np.float32)
+            elif leaf == "vlad_centers":      # tf.contrib.layers.xavier_initializer() on [K + G, dim], pooling.py:253-255
+                lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+                vals[name] = rs.uniform(-lim, lim, size=shape).astype(np.float32)
             elif leaf == "query":      # truncated_normal(stddev=0.1), pooling.py:131-132
                 vals[name] = np.clip(rs.randn(*shape) * 0.1, -0.2, 0.2).astype(np.float32)
             elif leaf in ("gamma", "moving_variance"):

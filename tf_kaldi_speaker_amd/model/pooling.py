@@ -2,15 +2,15 @@
 
     f(features, aux_features, endpoints, params, is_training) -> [batch, 2 * dim]
 
-`statistics_pooling` and `self_attention` run on the GPU through the op-level C-ABI (csrc/xv_pool.hip,
-csrc/xv_attention.hip); inside the training engine the same kernels are driven natively (csrc/xv_engine_fwd.hip, csrc/xv_engine_bwd.hip), so these
+`statistics_pooling`, `self_attention` and `ghost_vlad` run on the GPU through the op-level C-ABI (csrc/xv_pool.hip,
+csrc/xv_attention.hip, csrc/xv_vlad.hip); inside the training engine the same kernels are driven natively (csrc/xv_engine_fwd.hip, csrc/xv_engine_bwd.hip), so these
 callables are the evaluation forms a caller of the reference API reaches.  `self_attention` covers the single-head form
 every shipped attention config uses (key network on `endpoints[att_key_input]`, value = `endpoints[att_value_input]`, key
 not split, no value network, no penalty term, no post non-linearity); the other options of the reference function are
-refused by name.  `ghost_vlad` is outside the hot path.
+refused by name.  `ghost_vlad` takes its key and its value straight from endpoints (no key / value networks).
 
-The attention variables live in a module-level store under the reference's scope names ("attention/att_key0/att_key0_dense/kernel",
-..., "attention/query"), like the loss functions' `softmax/output/kernel` (model/loss.py): the first call creates them,
+The attention and VLAD variables live in a module-level store under the reference's scope names ("attention/att_key0/att_key0_dense/kernel",
+..., "attention/query", "vlad/vlad_weight_affine/kernel", "vlad/vlad_centers"), like the loss functions' `softmax/output/kernel` (model/loss.py): the first call creates them,
 a second creating call raises as tf.get_variable would, `reuse_variables()` re-enters them.
 """
 from collections import OrderedDict
@@ -185,6 +185,55 @@ def self_attention(features, aux_features, endpoints, params, is_training=None):
     return att
 
 
+def check_vlad_params(d, last_relu=None):
+    """The ghost_vlad options the kernels cover, the rest refused by name (shared with model/tdnn.check_params).  last_relu: the only
+    endpoint the engine can pool ("tdnn5_relu"); None (the op-level function) takes any endpoint."""
+    unsupported = []
+    if len(d.get("vlad_key_num_nodes", [])) != 0:
+        unsupported.append("vlad_key_num_nodes (no key network)")
+    if len(d.get("vlad_value_num_nodes", [])) != 0:
+        unsupported.append("vlad_value_num_nodes (no value network)")
+    for key in ("vlad_key_input", "vlad_value_input"):
+        if last_relu is not None and d.get(key) != last_relu:
+            unsupported.append("%s=%r (%s)" % (key, d.get(key), last_relu))
+    if d.get("vlad_key_input") != d.get("vlad_value_input"):
+        unsupported.append("vlad_key_input != vlad_value_input (one tensor is key and value)")
+    k, g = int(d.get("vlad_num_centers", 0)), int(d.get("vlad_num_ghosts", 0))
+    if k < 1 or g < 0 or k + g > 64:
+        unsupported.append("vlad_num_centers=%d, vlad_num_ghosts=%d (at least one centre, at most 64 clusters)" % (k, g))
+    if d.get("precision", "f32") not in (None, "f32"):
+        unsupported.append("precision %s (f32)" % d["precision"])
+    if unsupported:
+        raise NotImplementedError("ghost_vlad on the MI355X kernels: not " + ", ".join(unsupported))
+    return k, g
+
+
 def ghost_vlad(features, aux_features, endpoints, params, is_training=None):
-    raise NotImplementedError("Not implement ghost_vlad pooling on the MI355X engine (no shipped single-task config selects it, "
-                              "SURVEY.md section 2)")
+    """NetVLAD / GhostVLAD, reference pooling.py:195-277, without key / value networks: A = softmax(dense(key)) over
+    vlad_num_centers + vlad_num_ghosts clusters, residuals of the value against the centres summed with A over the frames, ghosts
+    dropped, each residual l2-normalised, the concatenation once more with vlad_final_l2_norm -> [batch, vlad_num_centers * dim].
+    `features` is not used (as in the reference).  Side effects as in the reference: endpoints gains "vlad_weights" [b, l, K + G],
+    "vlad_value", "vlad_key" (the logits) and "vlad_centers"."""
+    d = params.dict
+    k, g = check_vlad_params(d)
+    value = to_device(endpoints[params.vlad_value_input])
+    assert value.dim() == 3, "the value must be [batch, length, dim]"
+    b, t, dim = shape_list(value)
+    if dim % 4 != 0:
+        raise ValueError("ghost_vlad: the channel count must be a multiple of 4 (got %d)" % dim)
+    kg = k + g
+    kgp = (kg + 3) // 4 * 4      # the dense GEMM writes whole column quads; the softmax reads the first K + G
+    kernel = _get("vlad/vlad_weight_affine/kernel", (dim, kg), "glorot")
+    bias = _get("vlad/vlad_weight_affine/bias", (kg,), 0.0)
+    centers = _get("vlad/vlad_centers", (kg, dim), "glorot")
+    wp, bp = ops.vlad_repitch(kernel, kgp), ops.vlad_repitch(bias.view(1, kg), kgp).view(-1)
+    v = value.contiguous()
+    logits = ops.affine_forward(v.view(b * t, 1, dim), 1, ops.prep_weight_fwd(wp.view(1, dim, kgp), dim), bp, kgp)
+    a = ops.vlad_softmax(logits, kg)
+    r, _ = ops.vlad_pool_forward(v, a, centers, k)
+    out = ops.vlad_normalize_forward(r, bool(d.get("vlad_final_l2_norm", False)))
+    endpoints["vlad_weights"] = a.view(b, t, kg)
+    endpoints["vlad_value"] = value
+    endpoints["vlad_key"] = logits[:, :kg].reshape(b, t, kg)
+    endpoints["vlad_centers"] = centers
+    return out

@@ -13,9 +13,11 @@ import torch
 try:
     from .. import engine as E
     from .common import to_device
+    from .pooling import check_vlad_params
 except (ImportError, ValueError):
     import engine as E
     from model.common import to_device
+    from model.pooling import check_vlad_params
 
 _GRAPH = {"engine": None, "key": None}
 
@@ -41,7 +43,8 @@ def endpoint_order(table=None):
     for i, (k, _) in enumerate(table):
         names += ["tdnn%d_%s" % (i + 1, "conv" if k > 1 else "dense"), "tdnn%d_bn" % (i + 1), "tdnn%d_relu" % (i + 1)]
     # self_attention only (pooling.py:78-149); absent names are skipped for statistics pooling
-    names += ["att_key0_dense", "att_key0_bn", "att_key0_relu", "att_key1_dense", "att_key1_bn", "att_key1_relu", "attention_weights", "pooling"]
+    names += ["att_key0_dense", "att_key0_bn", "att_key0_relu", "att_key1_dense", "att_key1_bn", "att_key1_relu", "attention_weights"]
+    names += ["vlad_weights", "vlad_key", "vlad_centers", "pooling"]      # ghost_vlad only (pooling.py:250,273-275; vlad_value is tdnn<F>_relu)
     n = len(table)
     names += ["tdnn%d_dense" % (n + 1), "tdnn%d_bn" % (n + 1), "tdnn%d_relu" % (n + 1), "tdnn%d_dense" % (n + 2), "tdnn%d_bn" % (n + 2),
               "tdnn%d_relu" % (n + 2)]
@@ -90,9 +93,11 @@ def check_params(params):
         if unsupported:
             raise NotImplementedError("self_attention on the MI355X engine supports the shipped single-head form only; not: "
                                       + ", ".join(unsupported))
+    elif params.pooling_type == "ghost_vlad":
+        # model/pooling.py:195-277 on the last frame layer's ReLU output; key / value networks and other inputs are refused by name
+        nf = len(frame_layer_table(params) or ()) or 5
+        check_vlad_params(params.dict, "tdnn%d_relu" % nf)
     elif params.pooling_type != "statistics_pooling":
-        if params.pooling_type == "ghost_vlad":
-            raise NotImplementedError("Not implement %s pooling on the MI355X engine yet" % params.pooling_type)
         raise NotImplementedError("Not implement %s pooling" % params.pooling_type)
     if "num_nodes_last_layer" not in params.dict:
         params.dict["num_nodes_last_layer"] = 512
@@ -126,6 +131,9 @@ def engine_config(params, dim, num_speakers=0, loss_type="softmax", max_batch=12
     if d["pooling_type"] == "self_attention":
         kw.update(att_key_num_nodes=tuple(d["att_key_num_nodes"]), att_key_network_type=int(d["att_key_network_type"]),
                   att_use_scale=bool(d.get("att_use_scale", False)))
+    if d["pooling_type"] == "ghost_vlad":
+        kw.update(vlad_num_centers=int(d["vlad_num_centers"]), vlad_num_ghosts=int(d.get("vlad_num_ghosts", 0)),
+                  vlad_final_l2_norm=bool(d.get("vlad_final_l2_norm", False)))
     if d.get("feature_norm", False):
         assert "feature_scaling_factor" in d, "If feature normalization is applied, scaling factor is necessary."
     prefix = {"asoftmax": "asoftmax", "additive_margin_softmax": "amsoftmax", "additive_angular_margin_softmax": "arcsoftmax"}.get(loss_type)
@@ -162,7 +170,7 @@ def tdnn(features, params, is_training=None, reuse_variables=None, aux_features=
     key = (dim, params.dict["num_nodes_pooling_layer"], params.dict["num_nodes_last_layer"],
            bool(params.last_layer_no_bn), bool(params.last_layer_linear), frame_layer_table(params),
            params.dict.get("network_relu_type", "relu"), params.dict.get("pooling_type", "statistics_pooling"),
-           tuple(sorted((k, repr(v)) for k, v in params.dict.items() if k.startswith("att_"))))
+           tuple(sorted((k, repr(v)) for k, v in params.dict.items() if k.startswith(("att_", "vlad_")))))
     eng = _GRAPH["engine"]
     if eng is None:
         if reuse_variables is True:

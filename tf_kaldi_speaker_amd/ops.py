@@ -11,11 +11,11 @@ import ctypes as C
 import torch
 
 try:
-    from ._host import _f32, _lib, _p, _s, _ws, pitch4, pitched, workspace
+    from ._host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
     from .pipeline_ops import *       # noqa: F401,F403 (its public names are the pipeline ops)
     from .wave_ops import *           # noqa: F401,F403 (and those of the ops that take PCM)
 except ImportError:
-    from _host import _f32, _lib, _p, _s, _ws, pitch4, pitched, workspace
+    from _host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
     from pipeline_ops import *        # noqa: F401,F403
     from wave_ops import *            # noqa: F401,F403
 
@@ -253,6 +253,111 @@ def att_key_backward(zk, act, query, scale, dscore):
     wp, wb = _ws(zk)
     _lib.call("xv_att_key_backward", _s(), _p(zk), rows, n, int(act), _p(query), float(scale), _p(dscore), _p(dzk), _p(dq), _p(db), wp, wb)
     return dzk, dq, db
+
+
+# ---- GhostVLAD / NetVLAD pooling (csrc/xv_vlad.hip; model/pooling.py:195-277) ----
+def _vlad_shapes(name, x, a, centers, k):
+    """(b, t, c, kg) of x [b, t, c], a [b*t, kg] and centers [kg, c], all contiguous float32; 1 <= k <= kg <= 64, c a multiple of 4."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("%s: x must be a contiguous float32 [batch, length, dim] tensor" % name)
+    b, t, c = x.shape
+    kg = int(centers.shape[0])
+    f32_values(centers, kg * c, "%s: centers [%d, %d]" % (name, kg, c))
+    f32_values(a, b * t * kg, "%s: the assignment weights [%d, %d]" % (name, b * t, kg))
+    if c % 4 != 0 or not 1 <= int(k) <= kg <= 64:
+        raise ValueError("%s: dim %d must be a multiple of 4 and 1 <= centers %d <= clusters %d <= 64" % (name, c, int(k), kg))
+    return b, t, c, kg
+
+
+def vlad_repitch(src, ldd):
+    """src [rows, cols] (contiguous rows) as a new [rows, ldd] buffer: the first min(cols, ldd) columns, zeros behind them."""
+    rows, lds = pitched(src, "vlad_repitch: src")
+    if int(ldd) < 1:
+        raise ValueError("vlad_repitch: the new row pitch must be positive")
+    dst = _f32((rows, int(ldd)), src)
+    _lib.call("xv_vlad_repitch", _s(), _p(src), rows, min(src.shape[1], int(ldd)), lds, _p(dst), int(ldd))
+    return dst
+
+
+def vlad_softmax(logits, kg):
+    """softmax over the first kg <= 64 columns of every row of logits [rows, >= kg] (GEMM padding columns are not read) -> [rows, kg]."""
+    rows, ld = pitched(logits, "vlad_softmax: logits")
+    if not 1 <= int(kg) <= min(64, logits.shape[1]):
+        raise ValueError("vlad_softmax: 1 <= clusters %d <= min(64, %d columns)" % (int(kg), logits.shape[1]))
+    a = _f32((rows, int(kg)), logits)
+    _lib.call("xv_vlad_softmax", _s(), _p(logits), rows, int(kg), ld, _p(a))
+    return a
+
+
+def vlad_pool_forward(x, a, centers, k, frames=None, shrink=0):
+    """x [b, t, c], a [b*t, kg], centers [kg, c] -> (r [b, k, c] = sum_t a (x - c_k), n [b, k] = sum_t a) over the first k clusters;
+    frames (int32 device [b]) / shrink: chunk i pools its first frames[i] - shrink rows only."""
+    b, t, c, kg = _vlad_shapes("vlad_pool_forward", x, a, centers, k)
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() != b or not frames.is_cuda or not frames.is_contiguous()):
+        raise ValueError("vlad_pool_forward: frames must be a contiguous int32 device tensor of %d entries" % b)
+    r, n = _f32((b, int(k), c), x), _f32((b, int(k)), x)
+    _lib.call("xv_vlad_pool_forward", _s(), _p(x), _p(a), _p(centers), b, t, c, int(k), kg, _p(frames), int(shrink), _p(r), _p(n))
+    return r, n
+
+
+def vlad_normalize_forward(r, final_l2_norm):
+    """r [b, k, c] -> [b, k*c]: every residual l2-normalised (epsilon 1e-12 on the squared norm), then - final_l2_norm - the whole row."""
+    if r.dim() != 3 or r.dtype != torch.float32 or not r.is_contiguous() or r.shape[2] % 4 != 0 or not 1 <= r.shape[1] <= 64:
+        raise ValueError("vlad_normalize_forward: r must be a contiguous float32 [batch, 1..64 centers, dim % 4 == 0] tensor")
+    b, k, c = r.shape
+    out = _f32((b, k * c), r)
+    _lib.call("xv_vlad_normalize_forward", _s(), _p(r), b, k, c, int(bool(final_l2_norm)), _p(out))
+    return out
+
+
+def vlad_normalize_backward(r, dout, final_l2_norm):
+    if r.dim() != 3 or r.dtype != torch.float32 or not r.is_contiguous() or r.shape[2] % 4 != 0 or not 1 <= r.shape[1] <= 64:
+        raise ValueError("vlad_normalize_backward: r must be a contiguous float32 [batch, 1..64 centers, dim % 4 == 0] tensor")
+    b, k, c = r.shape
+    f32_values(dout, b * k * c, "vlad_normalize_backward: dout [%d, %d]" % (b, k * c))
+    dr = torch.empty_like(r)
+    _lib.call("xv_vlad_normalize_backward", _s(), _p(r), _p(dout), b, k, c, int(bool(final_l2_norm)), _p(dr))
+    return dr
+
+
+def vlad_pool_backward(x, a, centers, dr):
+    """-> (da [b*t, kg] = (x - c_k) . dr_k for the k centres of dr [b, k, c], 0 for the ghosts; dx [b, t, c] = sum_k a dr_k)."""
+    k = int(dr.shape[1]) if dr.dim() == 3 else 0
+    b, t, c, kg = _vlad_shapes("vlad_pool_backward", x, a, centers, k)
+    f32_values(dr, b * k * c, "vlad_pool_backward: dr [%d, %d, %d]" % (b, k, c))
+    da, dx = _f32((b * t, kg), x), torch.empty_like(x)
+    _lib.call("xv_vlad_pool_backward", _s(), _p(x), _p(a), _p(centers), _p(dr), b, t, c, k, kg, _p(da), _p(dx))
+    return da, dx
+
+
+def vlad_softmax_backward(a, da, ld=None):
+    """dl = a (da - sum_j a da) as [rows, ld] (ld: kg rounded up to 4, the pitch of a GEMM operand; the padding columns are zero)."""
+    if a.dim() != 2 or not 1 <= a.shape[1] <= 64:
+        raise ValueError("vlad_softmax_backward: a must be [rows, 1..64 clusters]")
+    rows, kg = a.shape
+    f32_values(a, rows * kg, "vlad_softmax_backward: a")
+    f32_values(da, rows * kg, "vlad_softmax_backward: da")
+    ld = pitch4(kg) if ld is None else int(ld)
+    if not kg <= ld <= 64:
+        raise ValueError("vlad_softmax_backward: the row pitch %d must lie in %d .. 64" % (ld, kg))
+    dl = _f32((rows, ld), a)
+    _lib.call("xv_vlad_softmax_backward", _s(), _p(a), _p(da), rows, kg, ld, _p(dl))
+    return dl
+
+
+def vlad_centers_backward(n, dr, centers, l2_scale=0.0):
+    """dc [kg, c] = -sum_b n[b, k] dr[b, k] for the k centres of dr [b, k, c], 0 for the ghosts, + l2_scale * centers."""
+    if dr.dim() != 3 or dr.dtype != torch.float32 or not dr.is_contiguous() or centers.dim() != 2:
+        raise ValueError("vlad_centers_backward: dr must be a contiguous float32 [batch, centers, dim] tensor and centers [clusters, dim]")
+    b, k, c = dr.shape
+    kg = int(centers.shape[0])
+    f32_values(centers, kg * c, "vlad_centers_backward: centers [%d, %d]" % (kg, c))
+    f32_values(n, b * k, "vlad_centers_backward: n [%d, %d]" % (b, k))
+    if c % 4 != 0 or not 1 <= k <= kg <= 64:
+        raise ValueError("vlad_centers_backward: dim %d must be a multiple of 4 and 1 <= centers %d <= clusters %d <= 64" % (c, k, kg))
+    dc = torch.empty_like(centers)
+    _lib.call("xv_vlad_centers_backward", _s(), _p(n), _p(dr), _p(centers), b, k, kg, c, float(l2_scale), _p(dc))
+    return dc
 
 
 def bn_relu_backward_pooled(pool_out, dpool, b, t, z, gamma, mean, invstd, scale, shift, relu=True, weights=None):

@@ -9,6 +9,8 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py width                            the row-structured HBM-bound kernels against the channel count (512 ... 3 000)
   python tools/bench_kernel.py pitch                            ... against the row pitch of a 1 500-channel tensor
   python tools/bench_kernel.py pool [frames=186] [channels=1500] statistics pooling (+ BatchNorm) and its backward, warm (Infinity Cache) and cold
+  python tools/bench_kernel.py vlad [frames=186] [centers=8] [ghosts=2] GhostVLAD pooling (xv_vlad.hip) at 128 chunks x frames x 1500: the pooling forward and backward
+                                                                passes alternated with stat_pool_forward on the same tensor - medians, bytes, ratios
   python tools/bench_kernel.py segment                          the segment-level GEMMs: one-launch form (xv_skinny.hip) against GEMM + slab-sum launches
   python tools/bench_kernel.py staged                           plain step vs the staged (multi-GPU) backward, without / with a one-rank RCCL all-reduce
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
@@ -231,6 +233,93 @@ def cmd_pool(argv):
         for cold in (False, True):
             us = timed(fn, cold)
             print("%-62s %s  %7.1f us  %6.1f MB  %.2f TB/s" % (name, "cold" if cold else "warm", us, bytes_mb, bytes_mb / us))
+
+
+def cmd_vlad(argv):
+    """The two HBM-bound passes of GhostVLAD pooling against the statistics-pooling pass over the same [B, T, C] tensor: seven rounds, in each
+    every kernel once warm (the 143 MB tensor partly in the Infinity Cache) and once cold (a 300 MB fill in front); medians over the rounds."""
+    from tf_kaldi_speaker_amd import ops
+    B, C = 128, 1500
+    T = int(argv[0]) if argv else 186
+    K = int(argv[1]) if len(argv) > 1 else 8
+    G = int(argv[2]) if len(argv) > 2 else 2
+    KG = K + G
+    x = torch.relu(rnd(B, T, C)).contiguous()
+    lim = float(np.sqrt(6.0 / (C + KG)))
+    cen = torch.from_numpy(rs.uniform(-lim, lim, size=(KG, C)).astype(np.float32)).cuda()
+    logits = rnd(B * T, (KG + 3) // 4 * 4)
+    a = ops.vlad_softmax(logits, KG)
+    r, n = ops.vlad_pool_forward(x, a, cen, K)
+    dout = rnd(B, K * C)
+    dr = ops.vlad_normalize_backward(r, dout, True)
+    da, _ = ops.vlad_pool_backward(x, a, cen, dr)
+    flush = torch.empty(300 << 18, dtype=torch.float32, device="cuda")
+    mb = B * T * C * 4 / 1e6
+    small = (a.numel() + r.numel() + cen.numel()) * 4 / 1e6
+    kernels = [("stat_pool_forward (statistics pooling, same tensor)", lambda: ops.stat_pool_forward(x), mb),
+               ("vlad_pool_forward (%d + %d clusters)" % (K, G), lambda: ops.vlad_pool_forward(x, a, cen, K), mb + small),
+               ("vlad_pool_backward (d A and the value path of d x)", lambda: ops.vlad_pool_backward(x, a, cen, dr), 2 * mb + small + da.numel() * 4 / 1e6),
+               ("vlad_softmax", lambda: ops.vlad_softmax(logits, KG), (logits.numel() + a.numel()) * 4 / 1e6),
+               ("vlad_softmax_backward", lambda: ops.vlad_softmax_backward(a, da), (2 * a.numel() + logits.numel()) * 4 / 1e6),
+               ("vlad_normalize_forward", lambda: ops.vlad_normalize_forward(r, True), 3 * r.numel() * 4 / 1e6),
+               ("vlad_normalize_backward", lambda: ops.vlad_normalize_backward(r, dout, True), 5 * r.numel() * 4 / 1e6),
+               ("vlad_centers_backward", lambda: ops.vlad_centers_backward(n, dr, cen, 0.01), (dr.numel() + 2 * cen.numel()) * 4 / 1e6)]
+
+    def once(fn, cold):
+        if cold:
+            flush.fill_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+    for _, fn, _ in kernels:
+        for _ in range(3):
+            fn()
+    rounds = 7
+    t = {(name, cold): [] for name, _, _ in kernels for cold in (False, True)}
+    for _ in range(rounds):
+        for name, fn, _ in kernels:
+            for cold in (False, True):
+                t[(name, cold)].append(once(fn, cold))
+    print("# GhostVLAD pooling kernels, %d chunks x %d frames x %d, K = %d, G = %d; %d rounds, every kernel once warm and once cold per round;" % (B, T, C, K, G, rounds))
+    print("# us = median over the rounds (min .. max), one launch between two events; MB = bytes the kernel must move")
+    med = {}
+    for name, _, bytes_mb in kernels:
+        for cold in (False, True):
+            v = sorted(t[(name, cold)])
+            med[(name, cold)] = v[len(v) // 2]
+            print("%-56s %s %8.1f us (%7.1f .. %7.1f) %7.1f MB %5.2f TB/s" % (name, "cold" if cold else "warm", v[len(v) // 2], v[0], v[-1], bytes_mb, bytes_mb / v[len(v) // 2]))
+    base = kernels[0][0]
+    for name in (kernels[1][0], kernels[2][0]):
+        print("%-56s / stat_pool_forward: warm %.2f, cold %.2f" % (name, med[(name, False)] / med[(base, False)], med[(name, True)] / med[(base, True)]))
+    del x, a, r, dr, da, flush, logits, dout
+    torch.cuda.empty_cache()
+    # the full S1 training step (128 x 200 x 30, 7 351 speakers, additive margin softmax, fp32) with either pooling, alternated on this box
+    from tf_kaldi_speaker_amd import engine as E
+    N = 7351
+    xs = [rnd(B, T + 14, 30) for _ in range(2)]
+    ys = [torch.from_numpy(rs.randint(0, N, B).astype(np.int32)).cuda() for _ in range(2)]
+    configs = (("statistics_pooling", {}), ("ghost_vlad %d + %d, final l2" % (K, G), dict(pooling_type="ghost_vlad", vlad_num_centers=K, vlad_num_ghosts=G, vlad_final_l2_norm=True)))
+    ms, arena = {label: [] for label, _ in configs}, {}
+    for rnd_i in range(3):
+        for label, kw in configs:      # one engine alive at a time (with both alive the second one's step took 7.8 ms instead of 5.7)
+            eng = E.Engine(E.make_config(30, N, loss_func="additive_margin_softmax", margin_m=0.2, last_layer_linear=True, max_batch=B, max_frames=T + 14,
+                                         precision="f32", **kw), device="cuda:0")
+            eng.init_variables(seed=0)
+            for i in range(5):
+                eng.train_step(xs[i % 2], ys[i % 2], 0.01, i)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(30):
+                eng.train_step(xs[i % 2], ys[i % 2], 0.01, i)
+            torch.cuda.synchronize()
+            ms[label].append((time.perf_counter() - t0) / 30 * 1e3)
+            arena[label] = eng.arena_bytes
+            eng.close()
+    print("# full S1 training step, %d x %d x 30, %d speakers, fp32; 3 rounds of 30 steps per pooling, alternated (a fresh engine each time); ms / step median (min .. max)" % (B, T + 14, N))
+    for label, _ in configs:
+        v = sorted(ms[label])
+        print("%-40s %.3f ms (%.3f .. %.3f)   arena %.0f MB" % (label, v[1], v[0], v[-1], arena[label] / 1e6))
 
 
 def cmd_segment(argv):
@@ -594,7 +683,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool,
+COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
             "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
