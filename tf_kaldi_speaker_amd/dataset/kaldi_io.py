@@ -429,7 +429,7 @@ class PackedMatrix(object):
 
 
 class VoicedRows(object):
-    """Rows of an utterance AFTER voiced-frame selection, for the GPU front end (xv_frontend, Trainer.predict_batch): `item` is the RAW
+    """Rows of an utterance AFTER voiced-frame selection, for the GPU front end (xv_frontend; Trainer.predict_batch, model/predict.py voiced_source): `item` is the RAW
     utterance (a PackedMatrix or a float32 matrix), `voiced` one uint8 per raw frame (non-zero = kept; None = every frame) and
     [first, first + count) a range of the kept frames - the whole utterance, or one of the chunks extract.py cuts a long one into.  shape and
     row_range() count kept frames, so the chunking and batching code sees the utterance the network will see."""
@@ -469,7 +469,7 @@ class DeviceBatch(object):
 
 class DeviceRows(object):
     """VoicedRows for an utterance of a DeviceBatch: utterance `index` of `batch`, of whose kept frames this piece covers
-    [first, first + count).  shape and row_range() count kept frames.  Trainer.predict_batch gathers the raw rows on the device and runs
+    [first, first + count).  shape and row_range() count kept frames.  Trainer.predict_batch (model/predict.py device_source) gathers the raw rows on the device and runs
     the front end (CMN, selection) there: the features never come to the host."""
     __slots__ = ("batch", "index", "total", "first", "count")
 

@@ -12,10 +12,11 @@ import numpy as np
 import torch
 
 try:
-    from . import _lib
+    from . import _lib, pipeline_ops as _pipeline_ops
     from ._lib import XvConfig, XvError, LOSS_KINDS, OPTIMIZERS, PRECISIONS, POOLINGS, RELU_TYPES, XV_BWD_STAGES
 except ImportError:      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT makes these top-level modules
     import _lib
+    import pipeline_ops as _pipeline_ops
     from _lib import XvConfig, XvError, LOSS_KINDS, OPTIMIZERS, PRECISIONS, POOLINGS, RELU_TYPES, XV_BWD_STAGES
 
 
@@ -269,7 +270,7 @@ class Engine(object):
         if n.numel() != b:
             raise ValueError("%d frame counts for %d chunks" % (n.numel(), b))
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-            # host-side lengths are checked here (device-resident ones are the caller's: Trainer.predict_batch validates before the upload);
+            # host-side lengths are checked here (device-resident ones are the caller's: model/predict.py validates before the upload);
             # the kernels clamp, so a bad length would give an embedding pooled over padding instead of an error
             fh = np.asarray(frames.cpu() if isinstance(frames, torch.Tensor) else frames).reshape(-1)
             if fh.size and (int(fh.min()) < self.min_frames or int(fh.max()) > t):
@@ -312,16 +313,8 @@ class Engine(object):
                 raise ValueError("frontend: %s must be a contiguous %s device tensor" % (name, dtype))
             if a is not None and name != "masks" and a.numel() != b:
                 raise ValueError("frontend: %d entries in %s for %d pieces" % (a.numel(), name, b))
-        t_out = int(t_in if t_out is None else t_out)
-        out = torch.empty((b, t_out, d), dtype=torch.float32, device=x.device)
-        rows_out = torch.empty(b, dtype=torch.int32, device=x.device)
-        ws = torch.empty((b, t_out), dtype=torch.int32, device=x.device) if masks is not None else None
-        _lib.check(self.lib.xv_frontend(_stream(), _ptr(x), _ptr(rows_in), int(b), int(t_in), int(d), int(cmn_window), _ptr(masks),
-                                        C.c_size_t(masks.numel() if masks is not None else 0), _ptr(mask_offsets), _ptr(first), _ptr(count),
-                                        t_out, _ptr(out), _ptr(rows_out), _ptr(ws), C.c_size_t(ws.numel() * 4 if ws is not None else 0)),
-                   "xv_frontend")
-        self._keep_frontend = [x, rows_in, masks, mask_offsets, first, count, ws]
-        return out, rows_out
+        self._keep_frontend = [x, rows_in, masks, mask_offsets, first, count]
+        return _pipeline_ops.frontend(x, rows_in, cmn_window, masks, mask_offsets, first, count, t_out)
 
     def loss(self, labels, global_step, with_margin=True):
         y = self._dev(labels, torch.int32)

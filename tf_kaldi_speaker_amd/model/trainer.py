@@ -28,47 +28,23 @@ try:
     from .. import _lib
     from ..parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from ..dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
-    from ..misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state, plan_length_batches
-    from ..dataset.kaldi_io import DeviceRows, PackedMatrix, VoicedRows
+    from ..misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state
     from ..misc import tf_checkpoint
     from .tdnn import tdnn, extended_tdnn, engine_config, collect_endpoints, check_params
     from . import loss as _loss
+    from . import predict as _predict
 except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT
     import engine as E
     import _lib
     from parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
-    from misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state, plan_length_batches
-    from dataset.kaldi_io import DeviceRows, PackedMatrix, VoicedRows
+    from misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state
     from misc import tf_checkpoint
     from model.tdnn import tdnn, extended_tdnn, engine_config, collect_endpoints, check_params
     from model import loss as _loss
+    from model import predict as _predict
 
 log = logging.getLogger("tf_kaldi_speaker_amd")
-
-
-class _PendingEmbeddings(object):
-    """Embeddings of Trainer.predict_batch(..., return_device=True): still on the GPU, in batch order; cpu().numpy() reads them back and
-    puts them into the caller's order."""
-
-    def __init__(self, dev, inv):
-        # the read-back is enqueued NOW, behind this window's forward passes, into pinned memory, and an event marks its end: numpy()
-        # then waits for that event only.  (A dev.cpu() at read time queues behind whatever the caller has enqueued since - the next
-        # window's decode and forward passes in extract.py - so host post-processing and GPU work took turns; ADVICE round 4.)
-        self.inv = inv
-        self.host = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
-        self.host.copy_(dev, non_blocking=True)
-        self.done = torch.cuda.Event()
-        self.done.record(torch.cuda.current_stream(dev.device))
-        self.dev = dev          # (kept alive until the copy has run)
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        self.done.synchronize()
-        self.dev = None
-        return self.host.numpy()[self.inv]
 
 SOFTMAX_FAMILY = ("softmax", "asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax")
 OTHER_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss", "generalized_angular_triplet_loss")
@@ -443,13 +419,16 @@ class Trainer(object):
         log.info("[Validation %d batches] valid loss: %f" % (num_batches, loss))
         return loss, embeddings_val, labels_val
 
-    def predict(self, features):
-        """Embedding(s) of `embedding_node` with BN in inference mode (trainer.py:708-726)."""
+    def _ensure_loaded(self):
         if not self.is_loaded:
             if os.path.isfile(os.path.join(self.model, "checkpoint")):
                 self.load()
             else:
                 sys.exit("Cannot find model in %s" % self.model)
+
+    def predict(self, features):
+        """Embedding(s) of `embedding_node` with BN in inference mode (trainer.py:708-726)."""
+        self._ensure_loaded()
         features = np.asarray(features, np.float32)
         rank = len(features.shape)
         assert (rank == 2 or rank == 3)
@@ -484,219 +463,9 @@ class Trainer(object):
         non-zero.  An item may also be a kaldi_io.VoicedRows (raw utterance + mask + a range of its kept frames: extract.py's chunks).
         Lengths - the batch plan, the receptive-field check - then count the frames left after selection.
         Items of the third kind, kaldi_io.DeviceRows (all of them, then), are raw features and masks that are on the device already -
-        extract.py's wav mode: _predict_device."""
-        if not self.is_loaded:
-            if os.path.isfile(os.path.join(self.model, "checkpoint")):
-                self.load()
-            else:
-                sys.exit("Cannot find model in %s" % self.model)
-        n = len(items)
-        if n == 0:
-            return np.zeros((0, 0), np.float32)
-        cmn_window = int(cmn_window)
-        if any(isinstance(it, DeviceRows) for it in items):
-            if voiced is not None or not all(isinstance(it, DeviceRows) for it in items):
-                raise ValueError("predict_batch: DeviceRows items carry their own masks (voiced must be None) and do not mix with host items")
-            return self._predict_device(items, return_device, cmn_window)
-        if voiced is not None and len(voiced) != n:
-            raise ValueError("predict_batch: %d voicing masks for %d items" % (len(voiced), n))
-        pieces = None      # the front end is on: every item as a VoicedRows (raw utterance, mask, range of kept frames)
-        if cmn_window > 0 or voiced is not None or any(isinstance(it, VoicedRows) for it in items):
-            if voiced is not None and any(isinstance(it, VoicedRows) for it in items):
-                raise ValueError("predict_batch: a VoicedRows item carries its own mask (voiced must be None)")
-            pieces = [it if isinstance(it, VoicedRows) else VoicedRows(it, None if voiced is None else voiced[i]) for i, it in enumerate(items)]
-            items = [p.item for p in pieces]
-        lengths = [int(it.shape[0]) for it in items] if pieces is None else [p.count for p in pieces]
-        dim = self.dim
-        # every matrix must have the model's feature dimension: the GPU decoder takes the column stride from `dim`, not from the archive
-        # header, so a mismatch would decode garbage (and read past the record) instead of failing; predict() rejects it through
-        # Engine.forward, this is the same check for the batched path
-        for i, it in enumerate(items):
-            if len(it.shape) != 2 or int(it.shape[1]) != dim:
-                raise ValueError("predict_batch: item %d has shape %s, the model expects [frames, %d]" % (i, tuple(it.shape), dim))
-        # an utterance shorter than the network's receptive field has no valid output frame (predict() refuses it in Engine.forward; here the
-        # pooling would clamp to one frame that already sees zero padding); longer than max_frames cannot happen: the plan pads to the longest
-        min_frames = self.engine.min_frames
-        for i, t in enumerate(lengths):
-            if t < min_frames:
-                raise ValueError("predict_batch: item %d has %d frames, fewer than the network's receptive field (%d)" % (i, t, min_frames))
-        # the on-GPU 'CM ' decoder handles at most 128 feature dimensions (one lane per column header); wider archives go through the host codec
-        if dim > 128:
-            items = [it.decode() if isinstance(it, PackedMatrix) else it for it in items]
-        node = self.params.embedding_node
-        plan = plan_length_batches(lengths, self.PREDICT_ROWS, self.PREDICT_CHUNKS)
-        self._ensure_capacity(max(len(idx) for idx, _ in plan), max(t for _, t in plan), rows=max(self.PREDICT_ROWS, max(len(idx) * t for idx, t in plan)))
-        eng = self.engine
-        outs = []
-        # 'CM ' matrices stay where the reader cut them out: the archive blocks they are views of go to the GPU whole, once per call (a
-        # quarter of the fp32 bytes, no per-batch gather on the host); a batch is then a list of byte offsets for the on-GPU decode
-        base, staged, total = {}, [], 0
-        for it in items:
-            if isinstance(it, PackedMatrix) and id(it.block) not in base:
-                base[id(it.block)] = total
-                staged.append(it.block)
-                total += (len(it.block) + 15) // 16 * 16
-        packed_dev = None
-        if total:
-            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-            hv = host.numpy()
-            for blk in staged:
-                o = base[id(blk)]
-                hv[o:o + len(blk)] = np.frombuffer(blk, np.uint8)
-            packed_dev = host.to(eng.device, non_blocking=True)
-        # byte offsets and frame counts of every batch in ONE pinned upload as well: a pageable host -> device copy per batch makes the
-        # host wait for the stream (the previous batch's forward), i.e. host and GPU work would take turns instead of overlapping
-        flat = [i for idx, _ in plan for i in idx]
-        offsets = [base[id(items[i].block)] + items[i].start if isinstance(items[i], PackedMatrix) else 0 for i in flat]
-        if pieces is None:
-            meta = torch.empty((2, len(flat)), dtype=torch.int64, pin_memory=True)
-            mv = meta.numpy()
-            mv[0] = offsets
-            mv[1] = [lengths[i] for i in flat]
-            meta_dev = meta.to(eng.device, non_blocking=True)
-            rows_dev = meta_dev[1].to(torch.int32)
-        else:
-            # the front end's arguments ride in the same upload: per piece the byte offset of its mask, its raw frame count and the range
-            # of kept frames it covers, then the masks themselves back to back (one copy per utterance: the chunks of a long one share
-            # theirs; a piece without a mask beside pieces with one points at a run of ones)
-            raw = [int(items[i].shape[0]) for i in flat]
-            mask_at, mask_list, mask_total = {}, [], 0
-            if any(pieces[i].voiced is not None for i in flat):
-                ones = np.ones(max([r for r, i in zip(raw, flat) if pieces[i].voiced is None] or [0]), np.uint8)
-                for i in flat:
-                    v = pieces[i].voiced if pieces[i].voiced is not None else ones
-                    if id(v) not in mask_at:
-                        mask_at[id(v)] = mask_total
-                        mask_list.append(v)
-                        mask_total += len(v)
-            head = 5 * 8 * len(flat)
-            meta = torch.empty(head + mask_total, dtype=torch.uint8, pin_memory=True)
-            mv = meta.numpy()[:head].view(np.int64).reshape(5, len(flat))
-            mv[0] = offsets
-            mv[1] = [mask_at[id(pieces[i].voiced if pieces[i].voiced is not None else ones)] for i in flat] if mask_total else 0
-            mv[2] = raw
-            mv[3] = [pieces[i].first for i in flat]
-            mv[4] = [pieces[i].count for i in flat]
-            for v in mask_list:
-                meta.numpy()[head + mask_at[id(v)]:head + mask_at[id(v)] + len(v)] = v
-            meta_all = meta.to(eng.device, non_blocking=True)
-            meta_dev = meta_all[:head].view(torch.int64).view(5, len(flat))
-            masks_dev = meta_all[head:] if mask_total else None
-            fe_dev = meta_dev[2:5].to(torch.int32)      # raw rows, first, count
-        cursor = 0
-        for idx, t in plan:
-            b = len(idx)
-            sl = slice(cursor, cursor + b)
-            cursor += b
-            packed = all(isinstance(items[i], PackedMatrix) for i in idx)
-            if pieces is not None:
-                # the raw batch is as long as its longest RAW utterance (the plan's t counts kept frames); host matrices take the same kernel
-                t_raw = max(int(items[i].shape[0]) for i in idx)
-                if packed:
-                    xr, _ = eng.decode_packed(packed_dev, meta_dev[0, sl], fe_dev[0, sl], t_raw)
-                else:
-                    host = np.zeros((b, t_raw, dim), np.float32)
-                    for j, i in enumerate(idx):
-                        m = items[i].decode() if isinstance(items[i], PackedMatrix) else np.asarray(items[i], np.float32)
-                        host[j, :m.shape[0]] = m
-                    xr = torch.from_numpy(host).to(eng.device)
-                x, rows = eng.frontend(xr, fe_dev[0, sl], cmn_window, masks_dev, meta_dev[1, sl] if masks_dev is not None else None,
-                                       fe_dev[1, sl], fe_dev[2, sl], t)
-            elif packed:
-                x, rows = eng.decode_packed(packed_dev, meta_dev[0, sl], rows_dev[sl], t)
-            else:
-                host = np.zeros((b, t, dim), np.float32)
-                for j, i in enumerate(idx):
-                    m = items[i].decode() if isinstance(items[i], PackedMatrix) else np.asarray(items[i], np.float32)
-                    host[j, :lengths[i]] = m
-                x, rows = host, rows_dev[sl]
-            eng.forward_lengths(x, rows)
-            emb = eng.endpoint(node)
-            if emb.shape[0] != b:
-                raise ValueError("predict_batch: embedding node %s is a frame-level endpoint (%d rows for %d utterances)" % (node, emb.shape[0], b))
-            outs.append((idx, emb))
-        dev = torch.cat([e for _, e in outs], dim=0)
-        order = np.concatenate([np.asarray(idx) for idx, _ in outs])
-        inv = np.empty(n, np.int64)
-        inv[order] = np.arange(n)
-        if return_device:
-            # nothing here waits for the GPU (the permutation back to the caller's order is applied on the host after the read-back: an
-            # index tensor uploaded from pageable memory would have made this call wait for the whole window's forward passes)
-            return _PendingEmbeddings(dev, inv)
-        emb = dev.cpu().numpy()[inv]
-        self.endpoints = OrderedDict([(node, emb)])
-        return emb
-
-    def _predict_device(self, items, return_device, cmn_window):
-        """predict_batch for kaldi_io.DeviceRows: the pieces are planned by their kept length exactly as host items are - whichever
-        DeviceBatch they sit in - and a batch of the plan gathers its utterances' raw rows on the device (index_select, cut at the batch's
-        longest raw utterance: the padded block a host batch would upload) and runs Engine.frontend on them with the DeviceBatches' masks,
-        so the front end and the network see what they see when the same features come from an archive.  Nothing but the embeddings
-        leaves the device."""
-        n, dim, node, min_frames = len(items), self.dim, self.params.embedding_node, self.engine.min_frames
-        for i, it in enumerate(items):
-            if it.shape[1] != dim:
-                raise ValueError("predict_batch: item %d has shape %s, the model expects [frames, %d]" % (i, tuple(it.shape), dim))
-            if it.count < min_frames:
-                raise ValueError("predict_batch: item %d has %d frames, fewer than the network's receptive field (%d)" % (i, it.count, min_frames))
-        sources, where = [], {}      # the DeviceBatches of this call, in order of appearance
-        for it in items:
-            if id(it.batch) not in where:
-                where[id(it.batch)] = len(sources)
-                sources.append(it.batch)
-        if len({src.masks is None for src in sources}) != 1:
-            raise ValueError("predict_batch: DeviceRows items with and without masks do not mix")
-        src_of = [where[id(it.batch)] for it in items]
-        plan = plan_length_batches([it.count for it in items], self.PREDICT_ROWS, self.PREDICT_CHUNKS)
-        self._ensure_capacity(max(len(idx) for idx, _ in plan), max(t for _, t in plan), rows=max(self.PREDICT_ROWS, max(len(idx) * t for idx, t in plan)))
-        eng = self.engine      # (the engine that has the capacity)
-        # the sources' frame counts and masks back to back (a copy only when a call spans several sources: the end of a feature window)
-        row_base = np.concatenate([[0], np.cumsum([len(src.frames) for src in sources])])
-        mask_base = np.concatenate([[0], np.cumsum([len(src.frames) * int(src.x.shape[1]) for src in sources])])
-        rows_all = sources[0].rows if len(sources) == 1 else torch.cat([src.rows for src in sources])
-        masks_all = None
-        if sources[0].masks is not None:
-            masks_all = sources[0].masks.reshape(-1) if len(sources) == 1 else torch.cat([src.masks.reshape(-1) for src in sources])
-        # per piece, in plan order: its utterance's index in its source and among all sources, the byte offset of its mask, first, count
-        flat = [i for idx, _ in plan for i in idx]
-        meta = torch.empty((5, len(flat)), dtype=torch.int64, pin_memory=True)
-        mv = meta.numpy()
-        mv[0] = [items[i].index for i in flat]
-        mv[1] = [row_base[src_of[i]] + items[i].index for i in flat]
-        mv[2] = [mask_base[src_of[i]] + items[i].index * int(items[i].batch.x.shape[1]) for i in flat]
-        mv[3] = [items[i].first for i in flat]
-        mv[4] = [items[i].count for i in flat]
-        meta_dev = meta.to(eng.device, non_blocking=True)
-        range_dev = meta_dev[3:5].to(torch.int32)
-        outs, cursor = [], 0
-        for idx, t in plan:
-            sl = slice(cursor, cursor + len(idx))
-            cursor += len(idx)
-            t_raw = max(items[i].batch.frames[items[i].index] for i in idx)
-            here = sorted({src_of[i] for i in idx})
-            if len(here) == 1:
-                xr = sources[here[0]].x[:, :t_raw].index_select(0, meta_dev[0, sl])
-            else:
-                xr = torch.zeros((len(idx), t_raw, dim), dtype=torch.float32, device=eng.device)
-                for g in here:
-                    pos = torch.as_tensor([k for k, i in enumerate(idx) if src_of[i] == g], dtype=torch.int64, device=eng.device)
-                    tg = min(t_raw, int(sources[g].x.shape[1]))
-                    xr[pos, :tg] = sources[g].x[:, :tg].index_select(0, meta_dev[0, sl].index_select(0, pos))
-            x, rows = eng.frontend(xr, rows_all.index_select(0, meta_dev[1, sl]), cmn_window, masks_all, meta_dev[2, sl] if masks_all is not None else None,
-                                   range_dev[0, sl], range_dev[1, sl], t)
-            eng.forward_lengths(x, rows)
-            emb = eng.endpoint(node)
-            if emb.shape[0] != len(idx):
-                raise ValueError("predict_batch: embedding node %s is a frame-level endpoint (%d rows for %d utterances)" % (node, emb.shape[0], len(idx)))
-            outs.append(emb)
-        dev = torch.cat(outs, dim=0)
-        inv = np.empty(n, np.int64)
-        inv[np.asarray(flat)] = np.arange(n)
-        if return_device:
-            return _PendingEmbeddings(dev, inv)
-        emb = dev.cpu().numpy()[inv]
-        self.endpoints = OrderedDict([(node, emb)])
-        return emb
+        extract.py's wav mode.  The path itself - plan, staging, batch loop - is model/predict.py."""
+        self._ensure_loaded()
+        return _predict.predict_batch(self, items, return_device, cmn_window, voiced)
 
     # ------------------------------------------------------------------ fine-tuning / diagnostics (trainer.py:522-590, 728-920)
     def set_trainable_variables(self, variable_list=None):

@@ -10,7 +10,7 @@ half-overlapping chunks whose embeddings are length-weighted averaged (reference
 -g selects the HIP device (the reference's CPU mode `-g -1` maps to device 0: there is no CPU path).
 --cmn-window / --vad (not in the reference's CLI) take over the two Kaldi programs the recipe pipes in front of this script
 (run_extract_embeddings.sh:47: apply-cmvn-sliding --cmn-window=300 | select-voiced-frames): the rspecifier then names the RAW features,
-both steps run on the GPU behind the 'CM ' decode (Trainer.predict_batch), and every length - --min-chunk-size, --chunk-size, the log
+both steps run on the GPU behind the 'CM ' decode (Trainer.predict_batch: model/predict.py), and every length - --min-chunk-size, --chunk-size, the log
 lines - counts the frames left after selection, as it does behind the pipe.
 --mfcc-config / --fbank-config (exactly one): the rspecifier names a wav.scp, read as make_mfcc.py reads it (paths and `cmd |` entries, its
 rate rules, its error texts), and the whole chain runs on the device: PCM upload -> (resample) -> xv_mfcc / xv_fbank -> xv_energy_vad
@@ -31,7 +31,7 @@ from model.trainer import Trainer
 from misc.utils import Params, EmbeddingWindow, prefetch_iter, select_voiced
 from dataset.kaldi_io import open_or_fd, read_mat_ark_packed, write_vec_flt, DeviceRows, VecFltTable, VoicedRows
 
-# utterances gathered before they go to the GPU together (sorted by length into padded batches, Trainer.predict_batch); results are
+# utterances gathered before they go to the GPU together (sorted by length into padded batches: Trainer.predict_batch, model/predict.py); results are
 # written in archive order.  One utterance per forward, as the reference runs (extract.py:64-93), left the chip at 9-20 % of its
 # training-pass rate at real utterance lengths (profiles/r03_extract_bench.txt).
 WINDOW_UTTERANCES = 512
