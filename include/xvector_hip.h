@@ -770,7 +770,9 @@ int xv_l2_scaling_forward(void* stream, const float* x, int rows, int n, float f
 int xv_l2_scaling_backward(void* stream, const float* x, const float* dy, int rows, int n, float factor, float* dx);
 
 /* Loss family, loss.py:9-355. */
-enum { XV_LOSS_SOFTMAX = 0, XV_LOSS_ASOFTMAX = 1, XV_LOSS_AMSOFTMAX = 2, XV_LOSS_ARCSOFTMAX = 3 };
+enum { XV_LOSS_SOFTMAX = 0, XV_LOSS_ASOFTMAX = 1, XV_LOSS_AMSOFTMAX = 2, XV_LOSS_ARCSOFTMAX = 3,
+       /* pairwise heads (below, "Pairwise loss heads"): no softmax/output variables whatever num_speakers says; options through xv_engine_set_pair_loss */
+       XV_LOSS_SEMIHARD_TRIPLET = 4, XV_LOSS_ANGULAR_TRIPLET = 5 };
 /* ---- segment-level layers in one launch (rows <= XV_SEGMENT_MAX_ROWS chunks of a batch) ------------------------------
  * tf.layers.dense at tdnn.py:147,166 and the logits / gradient products of loss.py with M = chunks rows: the GEMM, its split-K sum
  * and the consumer's per-column work run in one launch.  ws: slabs (xv_op_workspace_bytes); tickets: one ZEROED uint32 per 32
@@ -815,6 +817,41 @@ int xv_add_norm_grad(void* stream, const float* x, const float* dnorm, int rows,
 int xv_loss_weight_backward(void* stream, const float* dwn, int lddwn, const float* wn, int ldn,
                             const float* inv_norm, const float* w, int c, int n, int normalize,
                             float l2_scale, float* dw, void* ws, size_t ws_bytes);
+
+/* ---- Pairwise loss heads (loss.py:358-705), fp32: semi-hard triplet, angular triplet, end-to-end validation ----
+ * x [b][d] is the embedding at row pitch ldx; b <= 1024 rows, d a multiple of 4, rows 16-byte aligned.  With G = x x^T:
+ *   cosine     S_ij = clip(G_ij r_i r_j, -1, 1), r_i = rsqrt(max(G_ii, 1e-12))                                    common.py:97-110
+ *   Euclidean  D2_ij = max((G_ii - 2 G_ij) + G_jj, 0) (exactly 0 on the diagonal); squared: d = D2, else d = sqrt(D2), 0 where D2 == 0  common.py:61-94
+ *   semi-hard  sum over ordered pairs (x, i), equal labels, x != i, of max(margin + (d_xi - neg(x, i)), 0) / max(#pairs, 1e-16);
+ *              neg = min{d_xy: other label, d_xy > d_xi}, else max{d_xy: other label}, else (one speaker) the row minimum
+ *   angular    f = the positive side's transform by margin_kind / margin (loss.py:537-560); the negative side is S itself
+ *              all:  sum over valid (a, p, n) of max(S_an - f(S_ap), 0) / (#{terms > 1e-12} + 1e-16)
+ *              hard: mean over a of max(hn_a - hp_a, 0) with the fillers of loss.py:617-625
+ * stats [4]: {pairs | valid triplets | anchors, 0 | positive triplets | anchors with a positive hinge, the fraction positive / valid (0 for
+ * semi-hard), 0}.  Backward: maximum(x, 0) passes at x >= 0, the clip passes at its bounds, the masked sqrt entries get 0; a tie in a
+ * min / max gives the whole gradient to the lowest index; the arc margin's 1 - S^2 is clamped at 1e-12 in the derivative (finite at |S| = 1).
+ * No atomics: two calls give the same bits.  xv_pair_loss_forward leaves G, the gradient with respect to the pair matrix and
+ * 1 / normaliser in ws; xv_pair_loss_backward (same cfg, x, b, d, ws) reads them and writes dx [b][d] at row pitch lddx (a multiple of 4). */
+enum { XV_PAIR_SEMIHARD = 0, XV_PAIR_ANGULAR = 1 };
+enum { XV_TRIPLET_ALL = 0, XV_TRIPLET_HARD = 1 };
+typedef struct xv_pair_loss_config {
+    int32_t struct_bytes;             /* = sizeof(xv_pair_loss_config) of the header the host was built against; anything else is refused */
+    int32_t kind;                     /* XV_PAIR_* */
+    int32_t squared;                  /* semi-hard: triplet_loss_squared */
+    int32_t triplet_type;             /* angular: XV_TRIPLET_* */
+    int32_t margin_kind;              /* angular: XV_LOSS_ASOFTMAX (margin 1, 2, 4) / _AMSOFTMAX / _ARCSOFTMAX */
+    float margin;
+    int32_t valid_speakers;           /* num_valid_speakers_per_batch / num_valid_segments_per_speaker: the N x M layout of a validation batch - read by */
+    int32_t valid_segments;           /* the engine (xv_engine_loss_forward with with_margin = 0 on the angular kind), not by the op entry points below */
+} xv_pair_loss_config;
+size_t xv_pair_loss_workspace_bytes(int b, int d);      /* 0 (and xv_last_error) for a b or d outside the limits */
+int xv_pair_loss_forward(void* stream, const xv_pair_loss_config* cfg, const float* x, int b, int d, int ldx, const int32_t* labels,
+                         float* loss, float* stats, void* ws, size_t ws_bytes);
+int xv_pair_loss_backward(void* stream, const xv_pair_loss_config* cfg, const float* x, int b, int d, int ldx, const int32_t* labels,
+                          void* ws, size_t ws_bytes, float* dx, int lddx);
+/* e2e_valid_loss (loss.py:637-705): x holds speakers x segments rows, speaker-major.  Rows l2-normalised, per-speaker centres (normalised
+ * means), for a row's own speaker the normalised sum of the OTHER rows of that speaker, similarities x 20, mean sparse softmax cross-entropy. */
+int xv_e2e_valid_loss(void* stream, const float* x, int speakers, int segments, int d, int ldx, float* loss, void* ws, size_t ws_bytes);
 
 /* sum over a flat range of 0.5*scale*w^2 accumulated into *out (regularization_loss). */
 int xv_l2_reg_loss(void* stream, const float* w, size_t count, float scale, float* out_accum);
@@ -938,6 +975,11 @@ int xv_engine_forward_lengths(xv_engine* e, void* stream, const float* features,
  * host overlap the gradient all-reduce of finished slices with the rest of the backward). */
 #define XV_BWD_STAGES 4
 int xv_engine_loss_forward(xv_engine* e, void* stream, const int32_t* labels, int global_step, int with_margin);
+/* loss_kind XV_LOSS_SEMIHARD_TRIPLET / _ANGULAR_TRIPLET: the head's options (cfg->kind must match the engine's loss_kind), handed over after
+ * create; xv_engine_loss_forward without them is refused by name.  With with_margin = 0 the angular kind evaluates xv_e2e_valid_loss on
+ * valid_speakers x valid_segments rows (trainer.py:272-275; no backward follows it), the semi-hard kind the same loss as in training.
+ * Stage 0 of the backward then has no head weight gradient: xv_pair_loss_backward writes d out, and tdnn7 / tdnn6 run unfused from there. */
+int xv_engine_set_pair_loss(xv_engine* e, const xv_pair_loss_config* cfg);
 int xv_engine_backward(xv_engine* e, void* stream, int stage);
 /* Staged backward without the join at the end of stages 0..2: `stream` does not wait for the engine's weight-gradient stream,
  * so the next stage's data-gradient chain keeps overlapping it.  The slice of stage k is complete on any stream that called

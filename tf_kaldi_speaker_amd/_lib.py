@@ -163,11 +163,32 @@ class XvResampleConfig(_SizedConfig):
     DEFAULTS = dict(fin=0, fout=0, num_zeros=0, cutoff=0.0)
 
 
+class XvPairLossConfig(_SizedConfig):
+    """Mirror of `struct xv_pair_loss_config` (include/xvector_hip.h): the options of the pairwise loss heads; the defaults are the semi-hard
+    loss, unsquared, margin 0."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("kind", C.c_int32),
+        ("squared", C.c_int32),
+        ("triplet_type", C.c_int32),
+        ("margin_kind", C.c_int32),
+        ("margin", C.c_float),
+        ("valid_speakers", C.c_int32),
+        ("valid_segments", C.c_int32),
+    ]
+    DEFAULTS = dict(kind=0, squared=0, triplet_type=0, margin_kind=2, margin=0.0, valid_speakers=0, valid_segments=0)
+
+
+PAIR_KINDS = {"semihard_triplet_loss": 0, "angular_triplet_loss": 1}      # XV_PAIR_SEMIHARD / XV_PAIR_ANGULAR
+TRIPLET_TYPES = {"all": 0, "hard": 1}                                     # XV_TRIPLET_ALL / XV_TRIPLET_HARD
 LOSS_KINDS = {
     "softmax": 0,
     "asoftmax": 1,
     "additive_margin_softmax": 2,
     "additive_angular_margin_softmax": 3,
+    "semihard_triplet_loss": 4,          # XV_LOSS_SEMIHARD_TRIPLET / XV_LOSS_ANGULAR_TRIPLET: the pairwise heads (XvPairLossConfig carries their options)
+    "angular_triplet_loss": 5,
 }
 OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
 PRECISIONS = {"f32": 0, "f16x3": 1}
@@ -297,6 +318,10 @@ SIGNATURES = {
                                           _VP, _VP, _I, _VP, _VP, _SZ, _VP]),
     "xv_segment_dgrad_bn_backward": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, C.c_long, _VP, _VP, _VP, _VP, _VP,
                                           _VP, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "xv_pair_loss_workspace_bytes": (_SZ, [_I, _I]),
+    "xv_pair_loss_forward": (_I, [_VP, C.POINTER(XvPairLossConfig), _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _SZ]),
+    "xv_pair_loss_backward": (_I, [_VP, C.POINTER(XvPairLossConfig), _VP, _I, _I, _I, _VP, _VP, _SZ, _VP, _I]),
+    "xv_e2e_valid_loss": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _SZ]),
     "xv_loss_weight_backward": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _SZ]),
     "xv_l2_reg_loss": (_I, [_VP, _VP, _SZ, _F, _VP]),
     "xv_sgd_update": (_I, [_VP, _VP, _VP, _SZ, _F, _F]),
@@ -314,6 +339,7 @@ SIGNATURES = {
     "xv_engine_forward": (_I, [_VP, _VP, _VP, _I, _I, _I]),
     "xv_engine_forward_lengths": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "xv_engine_loss_forward": (_I, [_VP, _VP, _VP, _I, _I]),
+    "xv_engine_set_pair_loss": (_I, [_VP, C.POINTER(XvPairLossConfig)]),
     "xv_engine_backward": (_I, [_VP, _VP, _I]),
     "xv_engine_backward_async": (_I, [_VP, _VP, _I]),
     "xv_engine_stage_wait": (_I, [_VP, _VP, _I]),

@@ -171,6 +171,12 @@ struct xv_engine {
     int Tl[XV_MAX_FRAME_LAYERS + 1] = {};   // frames after each frame layer (index 0 = input)
     float lambda = 0.f;
     int with_margin = 1;
+    // pairwise loss heads (loss_kind 4 / 5, xv_triplet.hip): N = 0 (no softmax/output variables), options from xv_engine_set_pair_loss
+    bool pair = false, pair_set = false, pair_e2e = false;      // pair_e2e: the last loss was the e2e validation loss (no backward)
+    xv_pair_loss_config pair_cfg = {};
+    float *pair_ws = nullptr, *pair_stats = nullptr;
+    size_t pair_ws_bytes = 0;
+    bool has_loss() const { return N > 0 || pair; }
     hipStream_t last_stream = nullptr;
     size_t stage_begin[XV_BWD_STAGES], stage_end[XV_BWD_STAGES];
     // scratch of the endpoints that are rebuilt on demand (xv_engine_endpoint: "<layer>_bn", "att_key1_relu"): a buffer of its own, allocated at

@@ -29,7 +29,8 @@ void build_variables(xv_engine* e) {
     const int D = c.feat_dim;
     e->P = c.num_nodes_pooling_layer;
     e->Lout = c.num_nodes_last_layer;
-    e->N = c.num_speakers;
+    e->pair = c.loss_kind == XV_LOSS_SEMIHARD_TRIPLET || c.loss_kind == XV_LOSS_ANGULAR_TRIPLET;
+    e->N = e->pair ? 0 : c.num_speakers;
     e->att = c.pooling == XV_POOL_SELF_ATTENTION;
     e->vlad = c.pooling == XV_POOL_GHOST_VLAD;
     e->VK = e->vlad ? c.vlad_num_centers : 0; e->VG = e->vlad ? c.vlad_num_ghosts : 0;
@@ -196,7 +197,7 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         take(e->vl_logits, rows_pool * kgp); take(e->vl_dl, rows_pool * kgp);
         take(e->vl_A, rows_pool * kg); take(e->vl_dA, rows_pool * kg);
         take(e->vl_R, B * e->pool_dim); take(e->vl_dR, B * e->pool_dim); take(e->vl_n, B * (size_t)e->VK);
-        if (e->N > 0) take(e->vl_dxv, rows_pool * e->P);      // (backward only: a predict-only engine does not pay for it)
+        if (e->has_loss()) take(e->vl_dxv, rows_pool * e->P);      // (backward only: a predict-only engine does not pay for it)
     }
     take(e->pool, B * (size_t)e->pool_dim);
     take(e->h7_buf, B * e->Lout);
@@ -212,6 +213,11 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         take(e->wn, (size_t)e->Lout * e->ldl);
         take(e->wnt, (size_t)e->N * e->Lout);
         take(e->dwn, (size_t)e->Lout * e->ldl);
+    }
+    if (e->pair) {      // G, the pair-matrix gradient and its symmetrised form for as many rows as the heads take (xv_pair_loss_workspace_bytes)
+        e->pair_ws_bytes = xv_pair_loss_workspace_bytes((int)std::min<size_t>(B, 1024), e->Lout);
+        take(e->pair_ws, e->pair_ws_bytes / sizeof(float));
+        take(e->pair_stats, 4);
     }
     take(e->bufD, p.bufd);
     for (int i = 0; i < e->nz; ++i) take(e->bufZ[i], p.bufz);
@@ -312,7 +318,7 @@ int alloc_buffers(xv_engine* e) {
         if (!env) return 2;
         // ... and only an engine with a loss head can run one: a predict-only engine (num_speakers == 0; Trainer.predict_batch builds them with
         // 49 152 rows) keeps the two slots - nine would be 2 GB of arena nothing ever reads
-        if (env->dz_slots != 2 && !e->f16 && e->N > 0 && e->NL + 2 <= XV_Z_SLOTS && (size_t)(e->NL + 2) * p.bufz * sizeof(float) <= ((size_t)6 << 30))
+        if (env->dz_slots != 2 && !e->f16 && e->has_loss() && e->NL + 2 <= XV_Z_SLOTS && (size_t)(e->NL + 2) * p.bufz * sizeof(float) <= ((size_t)6 << 30))
             e->nz = e->NL + 2;
     }
     e->z_private = e->nz > 2;
@@ -391,7 +397,7 @@ extern "C" int xv_engine_create(const xv_config* cfg, xv_engine** out) {
                "engine_create: num_nodes_pooling_layer must be a positive multiple of 4 (got %d)", cfg->num_nodes_pooling_layer);
     XV_REQUIRE(cfg->num_nodes_last_layer > 0 && cfg->num_nodes_last_layer % 4 == 0,
                "engine_create: num_nodes_last_layer must be a positive multiple of 4 (got %d)", cfg->num_nodes_last_layer);
-    XV_REQUIRE(cfg->loss_kind >= XV_LOSS_SOFTMAX && cfg->loss_kind <= XV_LOSS_ARCSOFTMAX, "Not implement loss kind %d", cfg->loss_kind);
+    XV_REQUIRE(cfg->loss_kind >= XV_LOSS_SOFTMAX && cfg->loss_kind <= XV_LOSS_ANGULAR_TRIPLET, "Not implement loss kind %d", cfg->loss_kind);
     XV_REQUIRE(cfg->optimizer >= 0 && cfg->optimizer <= 2, "Optimizer %d is not supported.", cfg->optimizer);
     if (cfg->loss_kind == XV_LOSS_ASOFTMAX && cfg->num_speakers > 0)
         XV_REQUIRE(cfg->margin_m == 1.f || cfg->margin_m == 2.f || cfg->margin_m == 4.f, "[ERROR] m=%d is not unsupported.", (int)cfg->margin_m);
@@ -435,11 +441,29 @@ extern "C" int xv_engine_create(const xv_config* cfg, xv_engine** out) {
         e->cfg.aux_ring = 0;
         e->cfg.aux_mhe = 0;
     }
+    if (cfg->loss_kind >= XV_LOSS_SEMIHARD_TRIPLET) {
+        // the reference's triplet functions never call aux_loss_func (loss.py:358-634): no ring / MHE term, no softmax_ringloss/r
+        e->cfg.aux_ring = 0;
+        e->cfg.aux_mhe = 0;
+    }
     e->f16 = cfg->precision == XV_PRECISION_F16X3;
     build_variables(e);
     int rc = alloc_buffers(e);
     if (rc) { xv_engine_destroy(e); return rc; }
     *out = e;
+    return 0;
+}
+
+extern "C" int xv_engine_set_pair_loss(xv_engine* e, const xv_pair_loss_config* cfg) {
+    XV_REQUIRE(e && cfg, "engine_set_pair_loss: null argument");
+    XV_REQUIRE(e->pair, "engine_set_pair_loss: the engine's loss_kind %d is not a pairwise head (semihard_triplet_loss 4, angular_triplet_loss 5)", e->cfg.loss_kind);
+    XV_REQUIRE(cfg->struct_bytes == (int32_t)sizeof(xv_pair_loss_config), "engine_set_pair_loss: xv_pair_loss_config.struct_bytes is %d, this library's struct has %zu bytes",
+               cfg->struct_bytes, sizeof(xv_pair_loss_config));
+    XV_REQUIRE(cfg->kind == (e->cfg.loss_kind == XV_LOSS_SEMIHARD_TRIPLET ? XV_PAIR_SEMIHARD : XV_PAIR_ANGULAR),
+               "engine_set_pair_loss: pair loss kind %d does not belong to the engine's loss_kind %d", cfg->kind, e->cfg.loss_kind);
+    XV_REQUIRE(cfg->valid_speakers >= 0 && cfg->valid_segments >= 0, "engine_set_pair_loss: negative validation layout %d x %d", cfg->valid_speakers, cfg->valid_segments);
+    e->pair_cfg = *cfg;
+    e->pair_set = true;
     return 0;
 }
 

@@ -322,15 +322,19 @@ int backward_segment(xv_engine* e, hipStream_t s) {
     const int b = e->B;
     if (e->f16 && !e->amax_dz_clean) XV_CHECK_HIP(hipMemsetAsync(e->amax + AMAX_DZ, 0, xv_align(e->F + 2, 4) * sizeof(uint32_t), s));   // every layer's dz scale slot
     e->amax_dz_clean = false;
-    int rc = loss_head_wgrad(e, s);
+    int rc = e->pair ? 0 : loss_head_wgrad(e, s);
     if (rc) return rc;
     // d out = dlogits . wn^T   (pad column of both is zero, so K = ldl is exact), + the gradient through ||out|| (loss.py:122,147).
     // Fused form (xv_skinny.hip): one launch, and with a BatchNorm in tdnn7 and no l2_scaling in between, tdnn7's BN backward too
     XvAffine &l6 = e->L[e->S0()], &l7 = e->L[e->S1()];
     const bool sk = e->sk && b <= XV_SEGMENT_MAX_ROWS;
-    const bool fuse7 = sk && l7.has_bn && !c.feature_norm;
+    const bool fuse7 = !e->pair && sk && l7.has_bn && !c.feature_norm;
     float* dz7_fused = nullptr;
-    if (sk) {
+    if (e->pair) {      // pairwise heads: no head weight gradient; d out straight from the mined pair matrix (tdnn7 below runs unfused)
+        XV_REQUIRE(!e->pair_e2e, "engine_backward: the last loss was the end-to-end validation loss, which has no backward");
+        rc = xv_pair_loss_backward(s, &e->pair_cfg, e->out, b, e->Lout, e->Lout, e->labels_dev, e->pair_ws, e->pair_ws_bytes, e->d_small0, e->Lout);
+        if (rc) return rc;
+    } else if (sk) {
         XvSkinny g = xve_skinny(e, e->dlogits, e->ldl, e->wn, e->ldl, b, e->Lout, e->ldl);
         g.row_coef = e->dnorm; g.row_norm = e->xnorm; g.X = e->out; g.ldx = e->Lout;
         g.C = e->d_small0; g.ldc = e->Lout;

@@ -285,7 +285,7 @@ int engine_forward(xv_engine* e, void* stream, const float* features, int b, int
     const bool want_pad = !e->f16 && e->weights_dirty;
     e->pad_src = want_pad ? features : nullptr;
     e->pad_rows = b * t;
-    int rc = ensure_weights(e, s, training != 0 && e->N > 0);
+    int rc = ensure_weights(e, s, training != 0 && e->has_loss());
     e->amax_wt_clean = false;
     const bool padded = want_pad && e->pad_src == nullptr;      // prep_layers took the job
     e->pad_src = nullptr;
@@ -347,7 +347,7 @@ extern "C" int xv_engine_forward_lengths(xv_engine* e, void* stream, const float
 }
 
 extern "C" int xv_engine_loss_forward(xv_engine* e, void* stream, const int32_t* labels, int global_step, int with_margin) {
-    XV_REQUIRE(e && e->V && e->N > 0, "engine_loss_forward: engine has no loss head");
+    XV_REQUIRE(e && e->V && e->has_loss(), "engine_loss_forward: engine has no loss head");
     XV_REQUIRE(e->B > 0, "engine_loss_forward: run forward first");
     hipStream_t s = (hipStream_t)stream;
     const xv_config& c = e->cfg;
@@ -360,6 +360,19 @@ extern "C" int xv_engine_loss_forward(xv_engine* e, void* stream, const int32_t*
     if (rc) return rc;
     rc = xve_wait_lossprep(e, s);
     if (rc) return rc;
+    if (e->pair) {      // pairwise heads: no logits, no head weights; the embedding is the whole input
+        XV_REQUIRE(e->pair_set, "engine_loss_forward: loss_kind %d (%s) needs its options: call xv_engine_set_pair_loss first", c.loss_kind,
+                   c.loss_kind == XV_LOSS_SEMIHARD_TRIPLET ? "semihard_triplet_loss" : "angular_triplet_loss");
+        e->pair_e2e = !with_margin && c.loss_kind == XV_LOSS_ANGULAR_TRIPLET;      // trainer.py:272-275; the semi-hard loss validates as it trains
+        e->reg_valid = false;
+        if (e->pair_e2e) {
+            XV_REQUIRE((long)e->pair_cfg.valid_speakers * e->pair_cfg.valid_segments == b,
+                       "engine_loss_forward: the end-to-end validation loss takes num_valid_speakers_per_batch x num_valid_segments_per_speaker = %d x %d rows, the batch has %d",
+                       e->pair_cfg.valid_speakers, e->pair_cfg.valid_segments, b);
+            return xv_e2e_valid_loss(s, e->out, e->pair_cfg.valid_speakers, e->pair_cfg.valid_segments, e->Lout, e->Lout, e->scalars + 0, e->pair_ws, e->pair_ws_bytes);
+        }
+        return xv_pair_loss_forward(s, &e->pair_cfg, e->out, b, e->Lout, e->Lout, labels, e->scalars + 0, e->pair_stats, e->pair_ws, e->pair_ws_bytes);
+    }
     const float* bias = e->v_loss_bias >= 0 ? vptr(e, e->v_loss_bias) : nullptr;
     if (e->sk && b <= XV_SEGMENT_MAX_ROWS) {
         XvSkinny g = xve_skinny(e, e->out, e->Lout, e->wnt, e->Lout, b, e->N, e->Lout);

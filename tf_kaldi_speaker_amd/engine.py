@@ -11,11 +11,14 @@ import os
 import numpy as np
 import torch
 
+import logging
+
 try:
-    from . import _lib, pipeline_ops as _pipeline_ops
+    from . import _lib, ops as _ops, pipeline_ops as _pipeline_ops
     from ._lib import XvConfig, XvError, LOSS_KINDS, OPTIMIZERS, PRECISIONS, POOLINGS, RELU_TYPES, XV_BWD_STAGES
 except ImportError:      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT makes these top-level modules
     import _lib
+    import ops as _ops
     import pipeline_ops as _pipeline_ops
     from _lib import XvConfig, XvError, LOSS_KINDS, OPTIMIZERS, PRECISIONS, POOLINGS, RELU_TYPES, XV_BWD_STAGES
 
@@ -30,6 +33,7 @@ except ImportError:      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT makes these
 #            speed; passes the same parity tests at the same tolerances, but its operands are narrower than fp32, so it is
 #            never selected silently and bench.py reports it separately.
 DEFAULT_PRECISION = "f32"
+log = logging.getLogger("tf_kaldi_speaker_amd")
 
 
 def _ptr(t):
@@ -48,7 +52,12 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
                 clip_gradient_norm=0.0, max_batch=128, max_frames=400, precision=None, pooling_type="statistics_pooling",
                 att_key_num_nodes=(1500, 1500), att_key_network_type=3, att_use_scale=True, aux_loss_func=(), ring_loss_init=20.0,
                 ring_loss_lambda=0.01, mhe_lambda=0.01, frame_layers=None, network_relu_type="relu", max_rows=0,
-                vlad_num_centers=0, vlad_num_ghosts=0, vlad_final_l2_norm=False):
+                vlad_num_centers=0, vlad_num_ghosts=0, vlad_final_l2_norm=False, margin=0.0, triplet_loss_squared=False, triplet_type="all",
+                loss_type="additive_margin_softmax", num_valid_speakers_per_batch=0, num_valid_segments_per_speaker=0):
+    """loss_func "semihard_triplet_loss" / "angular_triplet_loss" (loss kinds 4 / 5): the options margin, triplet_loss_squared, triplet_type,
+    loss_type (the margin on the angular loss's positive side) and the N x M layout of an end-to-end validation batch travel on the returned
+    config as `.pair_loss` (an XvPairLossConfig); Engine hands them to xv_engine_set_pair_loss.  No softmax/output variables are created for
+    these kinds, whatever num_speakers says, and aux_loss_func is not evaluated (the reference's triplet functions never call it)."""
     if pooling_type not in POOLINGS:
         raise NotImplementedError("Not implement %s pooling" % pooling_type)
     if loss_func not in LOSS_KINDS:
@@ -56,6 +65,13 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
     if optimizer not in OPTIMIZERS:
         raise SystemExit("Optimizer %s is not supported." % optimizer)
     c = XvConfig()
+    c.pair_loss = None
+    if loss_func in _lib.PAIR_KINDS:
+        if aux_loss_func:
+            log.info("%s: aux_loss_func %s is not evaluated with this loss (the reference's triplet functions never call it)" % (loss_func, list(aux_loss_func)))
+            aux_loss_func = ()
+        c.pair_loss = _ops.pair_loss_config(loss_func, margin=margin, squared=triplet_loss_squared, triplet_type=triplet_type, loss_type=loss_type,
+                                            valid_speakers=num_valid_speakers_per_batch, valid_segments=num_valid_segments_per_speaker)
     c.feat_dim = int(feat_dim)
     c.num_speakers = int(num_speakers or 0)
     c.num_nodes_pooling_layer = int(num_nodes_pooling_layer)
@@ -140,6 +156,8 @@ class Engine(object):
         h = C.c_void_p()
         _lib.check(self.lib.xv_engine_create(C.byref(config), C.byref(h)), "xv_engine_create")
         self.h = h
+        if getattr(config, "pair_loss", None) is not None:
+            _lib.check(self.lib.xv_engine_set_pair_loss(h, C.byref(config.pair_loss)), "xv_engine_set_pair_loss")
         self.n_all = self.lib.xv_engine_variables_count(h)
         self.n_train = self.lib.xv_engine_trainable_count(h)
         self.n_opt = self.lib.xv_engine_optimizer_state_count(h)

@@ -1,4 +1,4 @@
-"""Softmax loss family with the reference's signatures (model/loss.py:9,51,172,260):
+"""Loss functions with the reference's signatures.  The softmax family (model/loss.py:9,51,172,260):
 
     f(features[B,E], labels[B], num_outputs, params, is_training=None, reuse_variables=None, name="softmax")
         -> (loss, endpoints{"logits", "labels"})        side effect: params.dict["softmax_w"] = w
@@ -7,6 +7,9 @@ These are the *forward* (evaluation) forms on GPU buffers; gradients of the same
 produced inside the engine (csrc/xv_engine_fwd.hip: xv_engine_loss_forward; its gradient: csrc/xv_engine_bwd.hip)
 that Trainer drives.  Variables live in a module-level store keyed by "<name>/output/kernel" exactly like the TF variable scope, so a second call with
 reuse_variables=True sees the same weight (loss.py:96-102).
+
+The pairwise heads (loss.py:358-705) have no variables: semihard_triplet_loss, angular_triplet_loss and e2e_valid_loss return
+(loss, endpoints{"loss", "labels"}) from csrc/xv_triplet.hip; their gradient is ops.pair_loss_backward, and the engine's stage 0.
 """
 from collections import OrderedDict
 
@@ -123,8 +126,50 @@ def additive_angular_margin_softmax(features, labels, num_outputs, params, is_tr
                 _lambda(params, "arcsoftmax"), False)
 
 
-def _not_hot_path(*a, **k):
-    raise NotImplementedError("triplet / end-to-end losses are outside the hot path (no shipped config selects them, SURVEY.md section 2)")
+def _embeddings(features, labels):
+    x = to_device(features)
+    y = to_device(labels, torch.int32)
+    assert len(shape_list(x)) == len(shape_list(y)) + 1
+    return x, y
 
 
-semihard_triplet_loss = angular_triplet_loss = e2e_valid_loss = generalized_angular_triplet_loss = _not_hot_path
+def _pair_endpoints(loss, y, stats=None):
+    endpoints = OrderedDict()
+    endpoints["loss"] = loss[0]
+    endpoints["labels"] = y
+    if stats is not None:
+        endpoints["stats"] = stats
+    return loss[0], endpoints
+
+
+def semihard_triplet_loss(features, labels, num_outputs, params, is_training=None, reuse_variables=None, name="triplet_loss"):
+    """loss.py:358-498; params.margin, params.triplet_loss_squared.  -> (loss, endpoints{"loss", "labels", "stats"})"""
+    x, y = _embeddings(features, labels)
+    cfg = ops.pair_loss_config("semihard_triplet_loss", margin=float(params.margin), squared=params.triplet_loss_squared)
+    loss, stats, _ = ops.pair_loss(cfg, x, y)
+    return _pair_endpoints(loss, y, stats)
+
+
+def angular_triplet_loss(features, labels, num_outputs, params, is_training=None, reuse_variables=None, name="angular_triplet_loss"):
+    """loss.py:501-634; params.margin, params.triplet_type ("all", "hard"), params.loss_type (the margin on the positive side)."""
+    x, y = _embeddings(features, labels)
+    assert params.triplet_type == "all" or params.triplet_type == "hard"
+    assert params.loss_type in ["asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax"]
+    params.margin = float(params.margin)
+    cfg = ops.pair_loss_config("angular_triplet_loss", margin=params.margin, triplet_type=params.triplet_type, loss_type=params.loss_type)
+    loss, stats, _ = ops.pair_loss(cfg, x, y)
+    return _pair_endpoints(loss, y, stats)
+
+
+def e2e_valid_loss(features, labels, num_outputs, params, is_training=None, reuse_variables=None, name="valid_e2e_loss"):
+    """loss.py:637-705: the features are arranged by speaker, params.num_valid_speakers_per_batch x params.num_valid_segments_per_speaker."""
+    x, y = _embeddings(features, labels)
+    assert "num_valid_speakers_per_batch" in params.dict and "num_valid_segments_per_speaker" in params.dict, \
+        "Valid parameters should be set if E2E loss is selected"
+    loss = ops.e2e_valid_loss(x, int(params.num_valid_speakers_per_batch), int(params.num_valid_segments_per_speaker))
+    return _pair_endpoints(loss, y)
+
+
+def generalized_angular_triplet_loss(*a, **k):
+    raise NotImplementedError("generalized_angular_triplet_loss (the centre-based triplet loss with a [batch, num_speakers] distance matrix and a "
+                              "moving-average centre update, loss.py:708) is not implemented; semihard_triplet_loss and angular_triplet_loss are")

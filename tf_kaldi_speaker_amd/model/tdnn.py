@@ -107,6 +107,9 @@ def check_params(params):
         params.last_layer_linear = False
 
 
+PAIR_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss")
+
+
 def engine_config(params, dim, num_speakers=0, loss_type="softmax", max_batch=128, max_frames=400, max_rows=0):
     check_params(params)
     d = params.dict
@@ -141,6 +144,17 @@ def engine_config(params, dim, num_speakers=0, loss_type="softmax", max_batch=12
         kw.update(margin_m=float(d[prefix + "_m"]), lambda_min=float(d[prefix + "_lambda_min"]),
                   lambda_base=float(d[prefix + "_lambda_base"]), lambda_gamma=float(d[prefix + "_lambda_gamma"]),
                   lambda_power=float(d[prefix + "_lambda_power"]))
+    if loss_type in PAIR_LOSSES:      # trainer.py:234-250 with the asserts of loss.py:518-519; the validation layout: loss.py:657-658
+        if loss_type == "angular_triplet_loss":
+            assert d["triplet_type"] == "all" or d["triplet_type"] == "hard"
+            assert d["loss_type"] in ["asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax"]
+            assert "num_valid_speakers_per_batch" in d and "num_valid_segments_per_speaker" in d, "Valid parameters should be set if E2E loss is selected"
+            kw.update(triplet_type=d["triplet_type"], loss_type=d["loss_type"], num_valid_speakers_per_batch=int(d["num_valid_speakers_per_batch"]),
+                      num_valid_segments_per_speaker=int(d["num_valid_segments_per_speaker"]))
+        else:
+            kw.update(triplet_loss_squared=bool(d["triplet_loss_squared"]))
+        kw.update(margin=float(d["margin"]), aux_loss_func=tuple(d.get("aux_loss_func") or ()))
+        return E.make_config(dim, num_speakers, loss_func=loss_type, **kw)
     return E.make_config(dim, num_speakers, loss_func=loss_type if num_speakers else "softmax", **kw)
 
 

@@ -47,7 +47,8 @@ except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_RO
 log = logging.getLogger("tf_kaldi_speaker_amd")
 
 SOFTMAX_FAMILY = ("softmax", "asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax")
-OTHER_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss", "generalized_angular_triplet_loss")
+PAIR_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss")      # the engine's pairwise heads (csrc/xv_triplet.hip)
+OTHER_LOSSES = ("generalized_angular_triplet_loss",)
 
 
 class _Session(object):
@@ -180,7 +181,7 @@ class Trainer(object):
 
         self.params.dict["global_step"] = 0
         self.loss_type = loss_type
-        if loss_type in SOFTMAX_FAMILY:
+        if loss_type in SOFTMAX_FAMILY or loss_type in PAIR_LOSSES:
             self.loss_network = getattr(_loss, loss_type)
         elif loss_type in OTHER_LOSSES:
             raise NotImplementedError("Not implement %s loss on the MI355X engine (outside the hot path)" % loss_type)
@@ -368,9 +369,13 @@ class Trainer(object):
         mode; optionally all "output" embeddings + labels in file order (trainer.py:592-706)."""
         assert "valid" in self.modes, "call build('valid', ...) first"
         assert batch_type == "softmax" or batch_type == "end2end", "The batch_type can only be softmax or end2end"
-        if batch_type == "end2end":
-            raise NotImplementedError("end2end validation batches belong to the triplet/GE2E losses (outside the hot path)")
         p = self.params
+        if batch_type == "end2end":
+            # N speakers x M segments per batch, speaker-major, as the end-to-end validation loss needs them (trainer.py:667-680)
+            assert "num_valid_speakers_per_batch" in p.dict and "num_valid_segments_per_speaker" in p.dict, \
+                "Valid parameters should be set if E2E loss is selected"
+            if self.loss_type not in PAIR_LOSSES:
+                raise NotImplementedError("end2end validation batches belong to semihard_triplet_loss / angular_triplet_loss, not to %s" % self.loss_type)
         curr_step = 0
         if os.path.isfile(os.path.join(self.model, "checkpoint")):
             curr_step = self.load()
@@ -397,8 +402,13 @@ class Trainer(object):
                 loader.stop()
             if embs:
                 embeddings_val, labels_val = np.concatenate(embs, 0), np.concatenate(labs, 0)
-        loader = KaldiDataSeqQueue(data, spklist, num_parallel=2, max_qsize=10, batch_size=bsz,
-                                   min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=True)
+        if batch_type == "end2end":
+            loader = KaldiDataRandomQueue(data, spklist, num_parallel=2, max_qsize=10, num_speakers=p.num_valid_speakers_per_batch,
+                                          num_segments=p.num_valid_segments_per_speaker, min_len=p.min_segment_len, max_len=p.max_segment_len,
+                                          shuffle=True)
+        else:
+            loader = KaldiDataSeqQueue(data, spklist, num_parallel=2, max_qsize=10, batch_size=bsz,
+                                       min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=True)
         loader.start()
         total, num_batches = 0.0, 0
         try:
@@ -411,6 +421,7 @@ class Trainer(object):
                 self.engine.forward(features, False)
                 self.engine.loss(labels, curr_step, with_margin=False)
                 self._last_valid_labels = np.asarray(labels)
+                self._last_valid_features = features          # (the batch a test restates; a reference to what the loader returned)
                 total += self.engine.raw_loss()
                 num_batches += 1
         finally:

@@ -421,6 +421,68 @@ def margin_softmax_rows(kind, logits, n, x, labels, m, lam):
     return loss, dlogits, dnorm, row_loss
 
 
+def pair_loss_config(loss_func, margin=0.0, squared=False, triplet_type="all", loss_type="additive_margin_softmax", valid_speakers=0,
+                     valid_segments=0):
+    """The xv_pair_loss_config of "semihard_triplet_loss" / "angular_triplet_loss" with the reference's option names (loss.py:376-377, 509-511)."""
+    if loss_func not in _lib.PAIR_KINDS:
+        raise NotImplementedError("Not implement %s loss" % loss_func)
+    if loss_func == "angular_triplet_loss":
+        assert triplet_type == "all" or triplet_type == "hard"
+        assert loss_type in ["asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax"]
+        if loss_type == "asoftmax" and int(margin) not in (1, 2, 4):
+            raise NotImplementedError("[ERROR] m=%d is not unsupported if asoftmax is selected." % margin)
+    return _lib.XvPairLossConfig(kind=_lib.PAIR_KINDS[loss_func], squared=int(bool(squared)), triplet_type=_lib.TRIPLET_TYPES.get(triplet_type, 0),
+                                 margin_kind=_lib.LOSS_KINDS.get(loss_type, 2), margin=float(margin), valid_speakers=int(valid_speakers),
+                                 valid_segments=int(valid_segments))
+
+
+def _pair_ws(x, d, ws):
+    b, ldx = pitched(x, "pair loss: x")
+    need = int(_lib.load().xv_pair_loss_workspace_bytes(b, d))
+    if need == 0:
+        _lib.check(2, "xv_pair_loss_workspace_bytes")
+    if ws is None:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    return b, ldx, ws
+
+
+def pair_loss(cfg, x, labels, d=None, ws=None):
+    """x: [b, >= d] float32 view with contiguous rows (d: x.shape[1]), labels int32 [b].  -> (loss [1], stats [4], ws); ws holds what
+    pair_loss_backward reads."""
+    d = x.shape[1] if d is None else int(d)
+    b, ldx, ws = _pair_ws(x, d, ws)
+    if labels.dtype != torch.int32 or labels.numel() != b or not labels.is_contiguous():
+        raise ValueError("pair loss: labels must be %d contiguous int32 values" % b)
+    loss, stats = _f32((1,), x), _f32((4,), x)
+    _lib.call("xv_pair_loss_forward", _s(), C.byref(cfg), _p(x), b, d, ldx, _p(labels), _p(loss), _p(stats), _p(ws), C.c_size_t(ws.numel() * 4))
+    return loss, stats, ws
+
+
+def pair_loss_backward(cfg, x, labels, ws, d=None, out=None):
+    """d loss / d x [b, d] (or into `out`, a [b, >= d] view with contiguous rows) from the workspace pair_loss left."""
+    d = x.shape[1] if d is None else int(d)
+    if ws is None:
+        raise ValueError("pair loss: the backward needs the workspace pair_loss returned for the same cfg, x and labels")
+    b, ldx, ws = _pair_ws(x, d, ws)
+    if labels.dtype != torch.int32 or labels.numel() != b or not labels.is_contiguous():
+        raise ValueError("pair loss: labels must be %d contiguous int32 values" % b)
+    dx = _f32((b, d), x) if out is None else out
+    _, lddx = pitched(dx, "pair loss: dx")
+    _lib.call("xv_pair_loss_backward", _s(), C.byref(cfg), _p(x), b, d, ldx, _p(labels), _p(ws), C.c_size_t(ws.numel() * 4), _p(dx), lddx)
+    return dx
+
+
+def e2e_valid_loss(x, speakers, segments, d=None, ws=None):
+    """loss [1] of speakers x segments speaker-major rows (loss.py:637-705)"""
+    d = x.shape[1] if d is None else int(d)
+    if x.shape[0] != int(speakers) * int(segments):
+        raise ValueError("e2e_valid_loss: %d rows are not %d speakers x %d segments" % (x.shape[0], speakers, segments))
+    b, ldx, ws = _pair_ws(x, d, ws)
+    loss = _f32((1,), x)
+    _lib.call("xv_e2e_valid_loss", _s(), _p(x), int(speakers), int(segments), d, ldx, _p(loss), _p(ws), C.c_size_t(ws.numel() * 4))
+    return loss
+
+
 def add_norm_grad(x, dnorm, dx):
     _lib.call("xv_add_norm_grad", _s(), _p(x), _p(dnorm), x.shape[0], x.shape[1], _p(dx))
     return dx

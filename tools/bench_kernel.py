@@ -11,6 +11,10 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py pool [frames=186] [channels=1500] statistics pooling (+ BatchNorm) and its backward, warm (Infinity Cache) and cold
   python tools/bench_kernel.py vlad [frames=186] [centers=8] [ghosts=2] GhostVLAD pooling (xv_vlad.hip) at 128 chunks x frames x 1500: the pooling forward and backward
                                                                 passes alternated with stat_pool_forward on the same tensor - medians, bytes, ratios
+  python tools/bench_kernel.py triplet                          the pairwise loss heads (xv_triplet.hip): forward and backward of every kind at 64 speakers x
+                                                                10 segments x 512 and at 128 x 512, the e2e validation loss; warm and cold, alternated rounds
+  python tools/bench_kernel.py triplet steps <parent tree> [rounds] the S1-shaped training step with a pairwise head against the AM-Softmax step of a checkout
+                                                                of the parent commit and of this tree, fresh processes, alternated
   python tools/bench_kernel.py segment                          the segment-level GEMMs: one-launch form (xv_skinny.hip) against GEMM + slab-sum launches
   python tools/bench_kernel.py staged                           plain step vs the staged (multi-GPU) backward, without / with a one-rank RCCL all-reduce
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
@@ -31,7 +35,7 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.environ.get("XV_BENCH_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # XV_BENCH_ROOT: import the package of another checkout (triplet steps)
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
@@ -320,6 +324,108 @@ def cmd_vlad(argv):
     for label, _ in configs:
         v = sorted(ms[label])
         print("%-40s %.3f ms (%.3f .. %.3f)   arena %.0f MB" % (label, v[1], v[0], v[-1], arena[label] / 1e6))
+
+
+def triplet_steps(argv):
+    """triplet step <head>: ms / step of 30 S1-shaped training steps (128 x 200 x 30, fp32, SGD) in this process, with the library $XV_LIB names -
+    head = softmax (AM-Softmax m = 0.2 over 7 351 speakers, the benchmark's step) | angular (angular_triplet_loss, "all" mining, additive margin
+    0.1, 64 speakers x 2 segments) | semihard.   triplet steps <checkout of the parent commit, library built> [rounds=5]: those runs as fresh
+    processes, alternated: the parent's softmax step (its package and library, through $XV_BENCH_ROOT), this tree's softmax step, this tree's
+    pairwise steps; medians and spreads."""
+    import subprocess
+    if argv[0] == "step":
+        from tf_kaldi_speaker_amd import engine as E
+        B, T, head = 128, 200, argv[1]
+        kw = dict(loss_func="additive_margin_softmax", margin_m=0.2) if head == "softmax" else (
+            dict(loss_func="angular_triplet_loss", margin=0.1, triplet_type="all", loss_type="additive_margin_softmax") if head == "angular" else
+            dict(loss_func="semihard_triplet_loss", margin=0.2, feature_norm=True, feature_scaling_factor=1.0))
+        eng = E.Engine(E.make_config(30, 7351, last_layer_linear=True, max_batch=B, max_frames=T, precision="f32", **kw), device="cuda:0")
+        eng.init_variables(seed=0)
+        xs = [rnd(B, T, 30) for _ in range(2)]
+        ys = [torch.from_numpy((rs.randint(0, 7351, B) if head == "softmax" else np.repeat(rs.permutation(7351)[:B // 2], 2)).astype(np.int32)).cuda() for _ in range(2)]
+        for i in range(5):
+            eng.train_step(xs[i % 2], ys[i % 2], 0.01, i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(30):
+            eng.train_step(xs[i % 2], ys[i % 2], 0.01, i)
+        torch.cuda.synchronize()
+        print("STEP_MS %s %.4f" % (head, (time.perf_counter() - t0) / 30 * 1e3))
+        eng.close()
+        return
+    parent, rounds = os.path.abspath(argv[1]), int(argv[2]) if len(argv) > 2 else 5
+    runs = [("parent commit, AM-Softmax", "softmax", parent), ("this tree, AM-Softmax", "softmax", None), ("this tree, angular_triplet_loss", "angular", None),
+            ("this tree, semihard_triplet_loss", "semihard", None)]
+    ms = {label: [] for label, _, _ in runs}
+    for _ in range(rounds):
+        for label, head, lib in runs:
+            env = dict(os.environ)
+            env.pop("XV_BENCH_ROOT", None)
+            if lib:
+                env["XV_BENCH_ROOT"] = lib
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "triplet", "step", head], env=env, capture_output=True, text=True, timeout=240)
+            line = [l for l in out.stdout.split("\n") if l.startswith("STEP_MS")]
+            if out.returncode != 0 or not line:
+                sys.exit("step run failed (%s): %s" % (label, out.stderr[-2000:]))
+            ms[label].append(float(line[0].split()[2]))
+    print("# S1-shaped training step, 128 x 200 x 30, fp32, SGD: 30 steps after 5 in a fresh process per figure, %d alternated rounds; ms / step" % rounds)
+    for label, _, _ in runs:
+        v = sorted(ms[label])
+        print("%-36s median %.3f  (%.3f .. %.3f)  spread %.3f   %s" % (label, v[len(v) // 2], v[0], v[-1], v[-1] - v[0], " ".join("%.3f" % x for x in ms[label])), flush=True)
+
+
+def cmd_triplet(argv):
+    """Forward (G = X X^T, the row scan, the final sum: 3 launches) and backward (symmetrise, d X = A X: 2 launches) of each pairwise head, and
+    the e2e validation loss (4 launches), as the ops launch them: seven rounds, in each every call once warm and once cold (a 300 MB fill in
+    front); medians over the rounds."""
+    if argv and argv[0] in ("step", "steps"):
+        return triplet_steps(argv)
+    from tf_kaldi_speaker_amd import ops
+    flush = torch.empty(300 << 18, dtype=torch.float32, device="cuda")
+    heads = [("semihard", ops.pair_loss_config("semihard_triplet_loss", margin=0.2)),
+             ("semihard squared", ops.pair_loss_config("semihard_triplet_loss", margin=0.2, squared=True)),
+             ("angular all am 0.1", ops.pair_loss_config("angular_triplet_loss", margin=0.1, triplet_type="all")),
+             ("angular all arc 0.3", ops.pair_loss_config("angular_triplet_loss", margin=0.3, triplet_type="all", loss_type="additive_angular_margin_softmax")),
+             ("angular all asoftmax 4", ops.pair_loss_config("angular_triplet_loss", margin=4, triplet_type="all", loss_type="asoftmax")),
+             ("angular hard am 0.1", ops.pair_loss_config("angular_triplet_loss", margin=0.1, triplet_type="hard"))]
+
+    def once(fn, cold):
+        if cold:
+            flush.fill_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+    rounds = 7
+    print("# pairwise loss heads, D = 512; %d rounds, every call once warm and once cold per round; us = median over the rounds (min .. max)," % rounds)
+    print("# between two events around the op (forward: 3 launches, backward: 2, e2e: 4; the ops' own allocations of loss / stats / dx included)")
+    for n_spk, n_seg in ((64, 10), (128, 1), (32, 4)):
+        b = n_spk * n_seg
+        x = rnd(b, 512) + 0.5 * rnd(n_spk, 512).repeat_interleave(n_seg, dim=0)
+        xu = (x / x.norm(dim=1, keepdim=True)).contiguous()
+        y = torch.arange(n_spk, dtype=torch.int32, device="cuda").repeat_interleave(n_seg).contiguous()
+        calls = []
+        for name, cfg in heads:
+            xin = xu if name.startswith("semihard") else x
+            _, _, ws = ops.pair_loss(cfg, xin, y)
+            dx = torch.empty_like(xin)
+            calls.append((name + " forward", lambda cfg=cfg, xin=xin, ws=ws: ops.pair_loss(cfg, xin, y, ws=ws)))
+            calls.append((name + " backward", lambda cfg=cfg, xin=xin, ws=ws, dx=dx: ops.pair_loss_backward(cfg, xin, y, ws, out=dx)))
+        ws2 = torch.empty_like(ws)
+        calls.append(("e2e_valid_loss", lambda: ops.e2e_valid_loss(x, n_spk, n_seg, ws=ws2)))
+        for _, fn in calls:
+            for _ in range(3):
+                fn()
+        t = {(name, cold): [] for name, _ in calls for cold in (False, True)}
+        for _ in range(rounds):
+            for name, fn in calls:
+                for cold in (False, True):
+                    t[(name, cold)].append(once(fn, cold))
+        print("%d speakers x %d segments x 512 (B = %d)" % (n_spk, n_seg, b))
+        for name, _ in calls:
+            for cold in (False, True):
+                v = sorted(t[(name, cold)])
+                print("  %-36s %s %8.1f us (%7.1f .. %7.1f)" % (name, "cold" if cold else "warm", v[len(v) // 2], v[0], v[-1]), flush=True)
 
 
 def cmd_segment(argv):
@@ -684,7 +790,7 @@ def cmd_resample(argv):
 
 
 COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
-            "segment": cmd_segment, "staged": cmd_staged}
+            "triplet": cmd_triplet, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:
