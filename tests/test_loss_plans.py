@@ -66,7 +66,7 @@ def test_misaligned_rows_take_three_passes(ldl, off_logits, off_dlogits):
 @pytest.mark.parametrize("n,want", [(7351, RQ8), (8189, RQ8), (8193, RQ16), (12289, RQ16), (16381, RQ16), (16385, THREE_PASS),
                                     (20011, THREE_PASS)])
 def test_engine_pitch_of_speaker_counts(n, want):
-    """The engine's logits pitch is align(N, 4) (xv_engine.hip, alloc_buffers): VoxCeleb1+2 (7 351 speakers) keeps RQ = 8, 8 193 ... 16 384 speakers
+    """The engine's logits pitch is align(N, 4) (xv_engine_head.hip, xvh_configure): VoxCeleb1+2 (7 351 speakers) keeps RQ = 8, 8 193 ... 16 384 speakers
     run RQ = 16, more than 16 384 the three-pass form."""
     ldl = align4(n)
     assert rows_form(ldl, BASE, BASE) == want

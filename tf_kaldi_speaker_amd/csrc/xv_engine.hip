@@ -3,14 +3,13 @@
 // runtime does under sess.run(train_op) - the Python Trainer only feeds pointers.  This unit: what exists before the first step - argument
 // checks of xv_engine_create, the variable table in TF order (build_variables), the device arena (one layout walk, measured then
 // assigned), streams and events - and destroy / bind / introspection.  What a step launches is in xv_engine_fwd.hip, xv_engine_bwd.hip
-// and xv_engine_step.hip; the shared state in xv_engine.h.
+// and xv_engine_step.hip; what the pooling layer and the loss head add to each phase in xv_engine_pool.hip and xv_engine_head.hip; the
+// shared state in xv_engine.h.
 #include <algorithm>
 
 #include "xv_engine.h"
 
-namespace {
-
-int add_var(xv_engine* e, const std::string& name, std::initializer_list<int> shape, bool trainable) {
+int xve_add_var(xv_engine* e, const std::string& name, std::initializer_list<int> shape, bool trainable) {
     XvVar v;
     v.name = name;
     v.rank = (int32_t)shape.size();
@@ -24,57 +23,44 @@ int add_var(xv_engine* e, const std::string& name, std::initializer_list<int> sh
     return (int)e->vars.size() - 1;
 }
 
+namespace {
+
 void build_variables(xv_engine* e) {
     const xv_config& c = e->cfg;
     const int D = c.feat_dim;
-    e->P = c.num_nodes_pooling_layer;
     e->Lout = c.num_nodes_last_layer;
-    e->pair = c.loss_kind == XV_LOSS_SEMIHARD_TRIPLET || c.loss_kind == XV_LOSS_ANGULAR_TRIPLET;
-    e->N = e->pair ? 0 : c.num_speakers;
-    e->att = c.pooling == XV_POOL_SELF_ATTENTION;
-    e->vlad = c.pooling == XV_POOL_GHOST_VLAD;
-    e->VK = e->vlad ? c.vlad_num_centers : 0; e->VG = e->vlad ? c.vlad_num_ghosts : 0;
-    e->VKG = e->VK + e->VG; e->VKGp = (int)xv_align(e->VKG, 4);
-    e->pool_dim = e->vlad ? e->VK * e->P : 2 * e->P;
-    const int F = e->F;
-    e->NL = e->att ? F + 4 : F + 2;
-    e->L.assign(F + 4, XvAffine());
+    xvp_configure(e);
+    xvh_configure(e);
+    const int F = e->F, P = e->pool_.P;
     // slot groups start on 16-byte boundaries and are zeroed in multiples of 16 bytes: an unaligned / odd-sized hipMemsetAsync is split
     // into two fill kernels (~5 us each on the stream)
     e->amax_a = 4; e->amax_wt = 4 + (int)xv_align(F, 4); e->amax_dz = e->amax_wt + (int)xv_align(F + 2, 4);
-    struct Spec { std::string prefix; const char* kind; const char* scope; int k, cin, cout; bool bn, relu, fused; int in_layer, act; };
-    std::vector<Spec> specs;
+    std::vector<XvLayerSpec> specs;
     {
         int cin = D;
         for (int i = 0; i < F; ++i) {
             const int k = c.num_frame_layers > 0 ? c.frame_context[i] : (i == 0 || i == 1 ? 5 : (i == 2 ? 7 : 1));
-            const int w = c.num_frame_layers > 0 ? c.frame_width[i] : (i == F - 1 ? e->P : 512);
+            const int w = c.num_frame_layers > 0 ? c.frame_width[i] : (i == F - 1 ? P : 512);
             // [TF] rank-4 inputs (the conv layers, tdnn.py:39-93) take the fused BN kernel: SURVEY N4
             specs.push_back({"tdnn" + std::to_string(i + 1), k > 1 ? "conv" : "dense", "", k, cin, w, true, true, k > 1, i - 1, 0});
             cin = w;
         }
     }
     const int Ckey = specs[F - 2].cout;      // the attention key network reads the last-but-one frame layer (tdnn4_relu in the shipped configs)
-    specs.push_back({"tdnn" + std::to_string(F + 1), "dense", "", 1, e->pool_dim, 512, true, true, false, -1, 0});
+    specs.push_back({"tdnn" + std::to_string(F + 1), "dense", "", 1, e->pool_.pool_dim, 512, true, true, false, -1, 0});
     specs.push_back({"tdnn" + std::to_string(F + 2), "dense", "", 1, 512, e->Lout, !c.last_layer_no_bn, !c.last_layer_linear, false, F, 0});
-    // self-attention key network (pooling.py:78-96): dense+bn+relu on the key input, then dense (+tanh)
-    specs.push_back({"att_key0", "dense", "attention/att_key0/", 1, Ckey, c.att_key0_nodes, true, true, false, F - 2, 0});
-    // last key layer (att_key_network_type): 0 affine, 1 + relu, 3 + tanh as an activation inside the score kernels; 2 = + bn + relu
-    specs.push_back({"att_key1", "dense", "attention/att_key1/", 1, c.att_key0_nodes, c.att_key1_nodes, c.att_key_type == 2, c.att_key_type == 2, false,
-                     F + 2, c.att_key_type == 2 ? 0 : c.att_key_type});
-    // graph-construction order of the reference: the frame layers, the pooling layer's variables, the segment layers
+    xvp_key_layers(e, Ckey, specs);
+    e->NL = (int)specs.size();
+    e->L.assign(e->NL, XvAffine());
+    // graph-construction order of the reference: the frame layers, the pooling layer's key layers and variables, the segment layers
     std::vector<int> order;
     for (int i = 0; i < F; ++i) order.push_back(i);
-    order.push_back(F + 2); order.push_back(F + 3); order.push_back(F); order.push_back(F + 1);
+    for (int i = F + 2; i < e->NL; ++i) order.push_back(i);
+    order.push_back(F); order.push_back(F + 1);
     for (int i : order) {
-        if (i >= e->NL) continue;
-        if (i == F && e->vlad) {      // pooling.py:242-256: the variables of the "vlad" scope sit where the attention variables sit
-            e->v_vlad_w = add_var(e, "tdnn/vlad/vlad_weight_affine/kernel", {e->P, e->VKG}, true);
-            e->v_vlad_b = add_var(e, "tdnn/vlad/vlad_weight_affine/bias", {e->VKG}, true);
-            e->v_vlad_c = add_var(e, "tdnn/vlad/vlad_centers", {e->VKG, e->P}, true);
-        }
+        if (i == F) xvp_declare_variables(e);
         XvAffine& a = e->L[i];
-        const Spec& s = specs[i];
+        const XvLayerSpec& s = specs[i];
         a.prefix = s.prefix; a.kind = s.kind; a.scope = s.scope; a.in_layer = s.in_layer; a.act = s.act;
         a.k = s.k; a.c_in = s.cin; a.c_out = s.cout;
         // operand pitch: 16-byte chunks of fp16 planes need multiples of 8 (feature layer 30 -> 32, att_key1 1500 -> 1504)
@@ -83,32 +69,27 @@ void build_variables(xv_engine* e) {
         // The pooled layer's pre-BN tensor and its gradient are the largest tensors of the step and are streamed by HBM-bound kernels (pooling, the
         // pooled BatchNorm backward) and by the GEMMs' LDS-DMA: 1 500 channels = 6 000-byte rows start off the 128-byte grid (nine cache lines
         // per KiB instead of eight).  Plain fp32 path with statistics pooling and a plain ReLU only (the kernels of the other paths take dense rows).
-        a.ldz = (i == F - 1 && !e->f16 && !e->att && !e->vlad && c.relu_type == XV_RELU_RELU && s.k == 1) ? (int)xv_align(s.cout, 32) : s.cout;
+        a.ldz = (i == F - 1 && !e->f16 && e->pool_.z_on_row_grid() && c.relu_type == XV_RELU_RELU && s.k == 1) ? (int)xv_align(s.cout, 32) : s.cout;
         a.has_bn = s.bn; a.has_relu = s.relu; a.fused_bn = s.fused;
         a.wslot = i < F ? i : i - 2;          // amax slots of the weights: tdnn1..F -> 0..F-1, att_key0/1 -> F, F+1
         a.aslot = i < F ? i : F - 1;          // BN+ReLU output planes: tdnn1..F-1 -> 0..F-2, att_key0 -> F-1
         std::string base = std::string("tdnn/") + s.scope + s.prefix + "_" + s.kind;
-        if (s.k > 1) a.v_kernel = add_var(e, base + "/kernel", {1, s.k, s.cin, s.cout}, true);
-        else a.v_kernel = add_var(e, base + "/kernel", {s.cin, s.cout}, true);
-        a.v_bias = add_var(e, base + "/bias", {s.cout}, true);
+        if (s.k > 1) a.v_kernel = xve_add_var(e, base + "/kernel", {1, s.k, s.cin, s.cout}, true);
+        else a.v_kernel = xve_add_var(e, base + "/kernel", {s.cin, s.cout}, true);
+        a.v_bias = xve_add_var(e, base + "/bias", {s.cout}, true);
         a.v_gamma = a.v_beta = a.v_mmean = a.v_mvar = -1;
         if (s.bn) {
             std::string bn = std::string("tdnn/") + s.scope + s.prefix + "_bn";
-            a.v_gamma = add_var(e, bn + "/gamma", {s.cout}, true);
-            a.v_beta = add_var(e, bn + "/beta", {s.cout}, true);
-            a.v_mmean = add_var(e, bn + "/moving_mean", {s.cout}, false);
-            a.v_mvar = add_var(e, bn + "/moving_variance", {s.cout}, false);
+            a.v_gamma = xve_add_var(e, bn + "/gamma", {s.cout}, true);
+            a.v_beta = xve_add_var(e, bn + "/beta", {s.cout}, true);
+            a.v_mmean = xve_add_var(e, bn + "/moving_mean", {s.cout}, false);
+            a.v_mvar = xve_add_var(e, bn + "/moving_variance", {s.cout}, false);
         }
         if (c.relu_type == XV_RELU_PRELU && s.relu)      // prelu(x, name): variable_scope("<prefix>_relu") / "alpha" [C], common.py:35-39
-            a.v_alpha = add_var(e, std::string("tdnn/") + s.scope + s.prefix + "_relu/alpha", {s.cout}, true);
-        if (i == F + 3) e->v_query = add_var(e, "tdnn/attention/query", {1, s.cout}, true);   // [heads, key dim], pooling.py:131
+            a.v_alpha = xve_add_var(e, std::string("tdnn/") + s.scope + s.prefix + "_relu/alpha", {s.cout}, true);
     }
     e->c_pad0 = e->L[0].c_pad;
-    if (e->N > 0) {
-        e->v_loss_kernel = add_var(e, "softmax/output/kernel", {e->Lout, e->N}, true);
-        if (c.loss_kind == XV_LOSS_SOFTMAX) e->v_loss_bias = add_var(e, "softmax/output/bias", {e->N}, true);
-        if (c.aux_ring) e->v_ring = add_var(e, "softmax_ringloss/r", {}, true);      // scalar, loss.py:1008-1011
-    }
+    xvh_declare_variables(e);
     // offsets: trainable section first (graph order), then non-trainable; 16-byte aligned starts
     size_t off = 0;
     for (auto& v : e->vars) if (v.trainable) { v.offset = off; off += xv_align(v.count, 4); }
@@ -128,35 +109,11 @@ void build_variables(xv_engine* e) {
     e->stage_begin[3] = 0;                e->stage_end[3] = first_off(lo);
 }
 
-// What the arena layout depends on besides the layer table: row capacities, the backward ping-pong sizes, the GEMM workspace.
-struct ArenaPlan {
-    std::vector<size_t> rows;      // rows[i] = chunks x frames entering frame layer i; rows[F] = frames that are pooled
-    size_t B = 0, maxc = 512, bufd = 0, bufz = 0, dzh_halfs = 0, ntick = 0, ws = 0;
-    size_t lrows(const xv_engine* e, int i) const { return i < e->F ? rows[i + 1] : (i >= e->F + 2 ? rows[e->F] : B); }
-};
-
-// The cursor of a layout walk: 256-byte aligned buffers one behind the other.  Measuring (base == nullptr) only adds the sizes up;
-// assigning also sets the pointers, and a buffer that would end behind the arena gets none (`ok` says so).
-struct ArenaCursor {
-    char* base = nullptr;
-    size_t capacity = 0, used = 0;
-    bool ok = true;
-    template <class T> void operator()(T*& p, size_t floats) {
-        const size_t bytes = xv_align(floats * sizeof(float), 256);
-        if (base) {
-            if (used + bytes > capacity) { p = nullptr; ok = false; return; }
-            p = (T*)(base + used);
-        }
-        used += bytes;
-    }
-};
-
 // THE arena layout: every buffer, its size (in floats - the half-typed ones too: two planes of halfs are one float per element) and
 // the condition under which it exists, in address order.  alloc_buffers runs it twice, to measure and to assign.
 void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
-    const xv_config& c = e->cfg;
     const int F = e->F;
-    const size_t B = p.B, rows_pool = p.rows[F];
+    const size_t B = p.B;
     take(e->xpad, p.rows[0] * e->c_pad0);
     for (int i = 0; i < e->NL; ++i) {
         XvAffine& a = e->L[i];
@@ -187,38 +144,10 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         }
         take(e->amax, AMAX_SLOTS);
     }
-    if (e->att) {
-        take(e->att_score, rows_pool); take(e->att_w, rows_pool); take(e->att_dw, rows_pool); take(e->att_ds, rows_pool);
-        take(e->bufA, rows_pool * e->L[F - 2].c_out);
-    }
-    if (e->vlad) {
-        const size_t kgp = e->VKGp, kg = e->VKG;
-        take(e->vl_wp, (size_t)e->P * kgp); take(e->vl_wt, kgp * e->P); take(e->vl_bp, kgp); take(e->vl_dwp, (size_t)e->P * kgp);
-        take(e->vl_logits, rows_pool * kgp); take(e->vl_dl, rows_pool * kgp);
-        take(e->vl_A, rows_pool * kg); take(e->vl_dA, rows_pool * kg);
-        take(e->vl_R, B * e->pool_dim); take(e->vl_dR, B * e->pool_dim); take(e->vl_n, B * (size_t)e->VK);
-        if (e->has_loss()) take(e->vl_dxv, rows_pool * e->P);      // (backward only: a predict-only engine does not pay for it)
-    }
-    take(e->pool, B * (size_t)e->pool_dim);
+    xvp_arena(e, p, take);      // the pooling layer's buffers, the pooled vector
     take(e->h7_buf, B * e->Lout);
     take(e->out_buf, B * e->Lout);
-    if (e->N > 0 && c.aux_mhe) {
-        take(e->mhe_coef, 1 + 2 * (size_t)e->Lout);
-        take(e->mhe_counts, e->N);
-    }
-    if (e->N > 0) {
-        take(e->logits, B * e->ldl); take(e->dlogits, B * e->ldl);
-        take(e->dnorm, B); take(e->row_loss, B);
-        take(e->inv_norm, e->N);
-        take(e->wn, (size_t)e->Lout * e->ldl);
-        take(e->wnt, (size_t)e->N * e->Lout);
-        take(e->dwn, (size_t)e->Lout * e->ldl);
-    }
-    if (e->pair) {      // G, the pair-matrix gradient and its symmetrised form for as many rows as the heads take (xv_pair_loss_workspace_bytes)
-        e->pair_ws_bytes = xv_pair_loss_workspace_bytes((int)std::min<size_t>(B, 1024), e->Lout);
-        take(e->pair_ws, e->pair_ws_bytes / sizeof(float));
-        take(e->pair_stats, 4);
-    }
+    xvh_arena(e, p, take);      // the loss head's buffers
     take(e->bufD, p.bufd);
     for (int i = 0; i < e->nz; ++i) take(e->bufZ[i], p.bufz);
     if (e->f16) {
@@ -226,15 +155,14 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         take(e->dzh[0], p.dzh_halfs);
         take(e->dzh[1], p.dzh_halfs);
     }
-    const size_t small = B * (size_t)(e->pool_dim > 512 ? e->pool_dim : 512);
+    const size_t small = B * (size_t)(e->pool_.pool_dim > 512 ? e->pool_.pool_dim : 512);
     take(e->d_small0, small);
     take(e->d_small1, small);
     take(e->scalars, 16);
     take(e->lrelu_slope, xv_align(p.maxc, 4) + 4);
     take(e->sk_tickets, p.ntick);       // zero (arena memset); every launch leaves them zero
-    take(e->xnorm, B);
-    take(e->pool_wpos, B * (size_t)e->P);
-    take(e->pool_amax, B * (size_t)e->P);
+    xvh_arena_tail(e, p, take);
+    xvp_arena_tail(e, p, take);
     take(e->ws, p.ws / sizeof(float));
     take(e->ws_side, p.ws / sizeof(float));
     take(e->ws_side2, p.ws / sizeof(float));
@@ -242,8 +170,6 @@ void arena_layout(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
 
 // GEMM split slabs: weight-gradient partials dominate
 size_t workspace_bytes(const xv_engine* e, const ArenaPlan& p) {
-    const xv_config& c = e->cfg;
-    const size_t rows_pool = p.rows[e->F];
     size_t ws = 0;
     for (int i = 0; i < e->NL; ++i) {
         const XvAffine& a = e->L[i];
@@ -256,22 +182,7 @@ size_t workspace_bytes(const xv_engine* e, const ArenaPlan& p) {
             if (s > ws) ws = s;
         }
     }
-    if (e->N > 0) {
-        size_t s = (size_t)xv_tn_splits_direct(e->Lout, e->ldl, (int)p.B) * e->Lout * e->ldl * sizeof(float);
-        if (s > ws) ws = s;
-        s = (size_t)16 * p.B * e->ldl * sizeof(float);
-        if (s > ws) ws = s;
-    }
-    size_t opws = xv_op_workspace_bytes((int)p.rows[1], 2 * e->P, 2 * e->P);
-    if (opws > ws) ws = opws;
-    if (e->vlad) {      // the assignment layer's weight gradient [P][KGp] over the pooled rows
-        size_t s = (size_t)xv_tn_splits(e->P, e->VKGp, (int)rows_pool) * e->P * e->VKGp * sizeof(float);
-        if (s > ws) ws = s;
-    }
-    if (e->att) {       // xv_att_key_backward: per-chunk partials + the column-sum workspace
-        size_t s = 2 * ((size_t)xv_cdiv(rows_pool, 64) * 2 * c.att_key1_nodes * sizeof(float) + xv_op_workspace_bytes((int)rows_pool, c.att_key1_nodes, c.att_key1_nodes)) + 4096;
-        if (s > ws) ws = s;
-    }
+    ws = std::max(ws, std::max(xvh_workspace_bytes(e, p), xvp_workspace_bytes(e, p)));
     return xv_align(ws, 256);
 }
 
@@ -295,7 +206,6 @@ int alloc_buffers(xv_engine* e) {
             for (int i = 0; i <= F; ++i) p.rows[i] = std::min<size_t>(p.rows[i], (size_t)c.max_rows);
         }
     }
-    e->ldl = e->N > 0 ? (int)xv_align(e->N, 4) : 0;
     // widest frame-level tensor (channels) and the ping-pong buffers of the backward pass: bufD holds d(layer output) /
     // d(layer input) ([rows][c]), bufZ a dz with k-1 zero frames around every chunk
     size_t max_pad_rows = 0;
@@ -325,7 +235,7 @@ int alloc_buffers(xv_engine* e) {
     e->zr[0].n = e->f16 ? 2 : e->nz;
     e->zr[1].n = 2;
     p.dzh_halfs = xv_align(max_pad_rows * (size_t)xv_align(p.maxc, 8), 8);
-    p.ntick = xv_skinny_tickets((int)std::max<size_t>(std::max<size_t>(e->N, (size_t)e->pool_dim), std::max<size_t>(p.maxc, (size_t)e->Lout))) + 8;
+    p.ntick = xv_skinny_tickets((int)std::max<size_t>(std::max<size_t>(e->head_.N, (size_t)e->pool_.pool_dim), std::max<size_t>(p.maxc, (size_t)e->Lout))) + 8;
     p.ws = workspace_bytes(e, p);
     ArenaCursor measured;
     arena_layout(e, p, measured);
@@ -397,27 +307,11 @@ extern "C" int xv_engine_create(const xv_config* cfg, xv_engine** out) {
                "engine_create: num_nodes_pooling_layer must be a positive multiple of 4 (got %d)", cfg->num_nodes_pooling_layer);
     XV_REQUIRE(cfg->num_nodes_last_layer > 0 && cfg->num_nodes_last_layer % 4 == 0,
                "engine_create: num_nodes_last_layer must be a positive multiple of 4 (got %d)", cfg->num_nodes_last_layer);
-    XV_REQUIRE(cfg->loss_kind >= XV_LOSS_SOFTMAX && cfg->loss_kind <= XV_LOSS_ANGULAR_TRIPLET, "Not implement loss kind %d", cfg->loss_kind);
+    if (int rc = xvh_check_config(cfg)) return rc;
     XV_REQUIRE(cfg->optimizer >= 0 && cfg->optimizer <= 2, "Optimizer %d is not supported.", cfg->optimizer);
-    if (cfg->loss_kind == XV_LOSS_ASOFTMAX && cfg->num_speakers > 0)
-        XV_REQUIRE(cfg->margin_m == 1.f || cfg->margin_m == 2.f || cfg->margin_m == 4.f, "[ERROR] m=%d is not unsupported.", (int)cfg->margin_m);
     XV_REQUIRE(!cfg->feature_norm || cfg->feature_scaling_factor > 0.f, "If feature normalization is applied, scaling factor is necessary.");
     XV_REQUIRE(cfg->precision == XV_PRECISION_F32 || cfg->precision == XV_PRECISION_F16X3, "engine_create: unknown precision %d", cfg->precision);
-    XV_REQUIRE(cfg->pooling == XV_POOL_STATISTICS || cfg->pooling == XV_POOL_SELF_ATTENTION || cfg->pooling == XV_POOL_GHOST_VLAD,
-               "Not implement pooling kind %d", cfg->pooling);
-    if (cfg->pooling == XV_POOL_GHOST_VLAD) {
-        XV_REQUIRE(cfg->precision == XV_PRECISION_F32, "engine_create: ghost_vlad pooling runs in precision f32 only (not f16x3)");
-        XV_REQUIRE(cfg->vlad_num_centers >= 1 && cfg->vlad_num_ghosts >= 0 && cfg->vlad_num_centers + cfg->vlad_num_ghosts <= 64,
-                   "engine_create: ghost_vlad needs vlad_num_centers >= 1, vlad_num_ghosts >= 0 and at most 64 clusters in all (got %d + %d)",
-                   cfg->vlad_num_centers, cfg->vlad_num_ghosts);
-    }
-    if (cfg->pooling == XV_POOL_SELF_ATTENTION) {
-        XV_REQUIRE(cfg->att_key0_nodes > 0 && cfg->att_key0_nodes % 4 == 0 && cfg->att_key1_nodes > 0 && cfg->att_key1_nodes % 4 == 0,
-                   "engine_create: att_key_num_nodes must be two positive multiples of 4 (got %d, %d)", cfg->att_key0_nodes, cfg->att_key1_nodes);
-        XV_REQUIRE(cfg->att_key_type >= 0 && cfg->att_key_type <= 3, "engine_create: att_key_network_type %d is not one of 0..3", cfg->att_key_type);
-    }
-    XV_REQUIRE(!cfg->aux_mhe || cfg->num_speakers == 0 || cfg->loss_kind != XV_LOSS_SOFTMAX,
-               "engine_create: mhe_loss needs a loss with normalised speaker weights (asoftmax / additive margin losses)");
+    if (int rc = xvp_check_config(cfg)) return rc;
     if (cfg->num_frame_layers != 0) {       // extended frame-layer table (no reference counterpart: tdnn.py hard-codes 5 layers)
         XV_REQUIRE(cfg->num_frame_layers >= 3 && cfg->num_frame_layers <= XV_MAX_FRAME_LAYERS,
                    "engine_create: num_frame_layers must be 0 (the reference's 5) or 3..%d (got %d)", XV_MAX_FRAME_LAYERS, cfg->num_frame_layers);
@@ -430,40 +324,14 @@ extern "C" int xv_engine_create(const xv_config* cfg, xv_engine** out) {
                    "engine_create: the last frame layer is the pooling layer: frame_width[%d] must equal num_nodes_pooling_layer", cfg->num_frame_layers - 1);
     }
     XV_REQUIRE(cfg->relu_type >= XV_RELU_RELU && cfg->relu_type <= XV_RELU_LRELU, "engine_create: unknown network_relu_type code %d", cfg->relu_type);
-    XV_REQUIRE(!(cfg->relu_type != XV_RELU_RELU && cfg->pooling == XV_POOL_SELF_ATTENTION && cfg->att_key_type == 1),
-               "engine_create: att_key_network_type 1 (affine + relu inside the score kernel) is built for a plain ReLU; use type 0, 2 or 3 with prelu / lrelu");
     xv_engine* e = new xv_engine();
     e->cfg = *cfg;
     e->F = cfg->num_frame_layers > 0 ? cfg->num_frame_layers : 5;
-    if (cfg->loss_kind == XV_LOSS_ASOFTMAX && cfg->margin_m == 1.f) {
-        // asoftmax with m = 1 returns its plain cross entropy before aux_loss_func is reached (loss.py:110-115): no ring / MHE
-        // term, and the variable softmax_ringloss/r is never created
-        e->cfg.aux_ring = 0;
-        e->cfg.aux_mhe = 0;
-    }
-    if (cfg->loss_kind >= XV_LOSS_SEMIHARD_TRIPLET) {
-        // the reference's triplet functions never call aux_loss_func (loss.py:358-634): no ring / MHE term, no softmax_ringloss/r
-        e->cfg.aux_ring = 0;
-        e->cfg.aux_mhe = 0;
-    }
     e->f16 = cfg->precision == XV_PRECISION_F16X3;
     build_variables(e);
     int rc = alloc_buffers(e);
     if (rc) { xv_engine_destroy(e); return rc; }
     *out = e;
-    return 0;
-}
-
-extern "C" int xv_engine_set_pair_loss(xv_engine* e, const xv_pair_loss_config* cfg) {
-    XV_REQUIRE(e && cfg, "engine_set_pair_loss: null argument");
-    XV_REQUIRE(e->pair, "engine_set_pair_loss: the engine's loss_kind %d is not a pairwise head (semihard_triplet_loss 4, angular_triplet_loss 5)", e->cfg.loss_kind);
-    XV_REQUIRE(cfg->struct_bytes == (int32_t)sizeof(xv_pair_loss_config), "engine_set_pair_loss: xv_pair_loss_config.struct_bytes is %d, this library's struct has %zu bytes",
-               cfg->struct_bytes, sizeof(xv_pair_loss_config));
-    XV_REQUIRE(cfg->kind == (e->cfg.loss_kind == XV_LOSS_SEMIHARD_TRIPLET ? XV_PAIR_SEMIHARD : XV_PAIR_ANGULAR),
-               "engine_set_pair_loss: pair loss kind %d does not belong to the engine's loss_kind %d", cfg->kind, e->cfg.loss_kind);
-    XV_REQUIRE(cfg->valid_speakers >= 0 && cfg->valid_segments >= 0, "engine_set_pair_loss: negative validation layout %d x %d", cfg->valid_speakers, cfg->valid_segments);
-    e->pair_cfg = *cfg;
-    e->pair_set = true;
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // Engine, forward: the kernel-layout weight copies of a step (prep_layers, ensure_weights and the two waits for their side-stream
-// halves), the forward pass - frame layers, attention key network, pooling, segment layers, output - in both precisions, the loss head's
-// forward, and the regularisation loss.  Everything here is enqueued on the caller's stream except the overlapped weight copies.
+// halves), the forward pass - frame layers, pooling (xv_engine_pool.hip), segment layers, output - in both precisions, the preamble of
+// the loss head's forward (xv_engine_head.hip), and the regularisation loss.  Everything here is enqueued on the caller's stream except the overlapped weight copies.
 #include <algorithm>
 
 #include "xv_engine.h"
@@ -71,12 +71,6 @@ int prep_layers(xv_engine* e, hipStream_t s, int first, int last) {
     return xv_launch_weight_prep(s, J);
 }
 
-int prep_loss_head(xv_engine* e, hipStream_t s) {
-    if (e->N <= 0) return 0;
-    return xv_loss_prep_weight(s, vptr(e, e->v_loss_kernel), e->Lout, e->N, e->cfg.loss_kind != XV_LOSS_SOFTMAX, e->inv_norm, e->wn, e->ldl,
-                               e->wnt);
-}
-
 int ensure_weights(xv_engine* e, hipStream_t s, bool overlap = false) {
     if (!e->weights_dirty) return 0;
     int rc;
@@ -89,14 +83,14 @@ int ensure_weights(xv_engine* e, hipStream_t s, bool overlap = false) {
         if (rc) return rc;
         XV_CHECK_HIP(hipEventRecord(e->ev_prep, e->side));
         e->prep_pending = true;
-        rc = prep_loss_head(e, e->side);
+        rc = xvh_prep_weights(e, e->side);
         if (rc) return rc;
         XV_CHECK_HIP(hipEventRecord(e->ev_lossprep, e->side));
         e->lossprep_pending = true;
     } else {
         rc = prep_layers(e, s, 0, e->NL);
         if (rc) return rc;
-        rc = prep_loss_head(e, s);
+        rc = xvh_prep_weights(e, s);
         if (rc) return rc;
     }
     e->weights_dirty = false;
@@ -164,14 +158,16 @@ int bn_forward_split(xv_engine* e, hipStream_t s, XvAffine& a, int rows, uint32_
     return dst_a ? xv_bn_apply(s, a.z, rows, a.c_out, a.c_out, a.scale, a.shift, 1, dst_a, a.c_out) : 0;
 }
 
+}  // namespace
+
 // Forward of frame-level layer i (a frame layer or an attention key layer) over `segs` chunks of t_in frames: the affine GEMM on the
 // output of a.in_layer (the features for tdnn1), then BN (+ activation).  The pooled layer writes no activation (it is applied inside
 // the pooling reduction); in split precision a layer a GEMM reads leaves fp16 planes instead of the fp32 tensor.
-int layer_forward(xv_engine* e, hipStream_t s, int i, int segs, int t_in) {
+int xve_layer_forward(xv_engine* e, hipStream_t s, int i, int segs, int t_in) {
     XvAffine& a = e->L[i];
     const int rows = segs * (t_in - a.k + 1);
     const XvAffine* in = a.in_layer < 0 ? nullptr : &e->L[a.in_layer];
-    float* dst_a = (i == e->F - 1 && !e->vlad) ? nullptr : a.a;      // (ghost_vlad reads the activation twice: it is written)
+    float* dst_a = (i == e->F - 1 && !e->pool_.writes_activation()) ? nullptr : a.a;
     int rc;
     if (e->f16) {
         const unsigned short* xh = in ? in->ah : e->xh;
@@ -190,6 +186,8 @@ int layer_forward(xv_engine* e, hipStream_t s, int i, int segs, int t_in) {
     a.rows = rows;
     return rc;
 }
+
+namespace {
 
 // The features as the first GEMM's operand: two fp16 planes + a device-side max |x| (split precision: every frame-level operand
 // travels that way), or the channel-padded copy - unless that rode on the first layer's weight-copy launch (`padded`)
@@ -241,27 +239,6 @@ int output_forward(xv_engine* e, hipStream_t s) {
     return rc;
 }
 
-// ghost_vlad (pooling.py:225-277) on the last frame layer's ReLU output: the assignment logits on the dense GEMM (W and the bias as
-// copies padded to whole column quads), softmax over the K + G clusters, the residual sums of the K centres, the normalisations
-int vlad_forward(xv_engine* e, hipStream_t s, int b, int Tp, const int32_t* frames, int shrink) {
-    const xv_config& c = e->cfg;
-    XvAffine& a = e->L[e->F - 1];
-    const int rows = b * Tp, P = e->P, K = e->VK, KG = e->VKG, KGp = e->VKGp;
-    int rc = xv_vlad_repitch(s, vptr(e, e->v_vlad_w), P, KG, KG, e->vl_wp, KGp);
-    if (rc) return rc;
-    rc = xv_vlad_repitch(s, vptr(e, e->v_vlad_b), 1, KG, KG, e->vl_bp, KGp);
-    if (rc) return rc;
-    rc = xv_prep_weight_fwd(s, e->vl_wp, 1, P, KGp, e->vl_wt, P);
-    if (rc) return rc;
-    rc = xv_affine_forward(s, a.a, rows, 1, P, 1, e->vl_wt, e->vl_bp, e->vl_logits, KGp, KGp, nullptr, e->ws, e->ws_bytes);
-    if (rc) return rc;
-    rc = xv_vlad_softmax(s, e->vl_logits, rows, KG, KGp, e->vl_A);
-    if (rc) return rc;
-    rc = xv_vlad_pool_forward_ex(s, a.a, e->vl_A, vptr(e, e->v_vlad_c), b, Tp, P, K, KG, frames, shrink, e->vl_R, e->vl_n);
-    if (rc) return rc;
-    return xv_vlad_normalize_forward(s, e->vl_R, b, K, P, c.vlad_final_l2_norm, e->pool);
-}
-
 int engine_forward(xv_engine* e, void* stream, const float* features, int b, int t, int training, const int32_t* frames) {
     XV_REQUIRE(e && e->V, "engine_forward: engine not bound");
     XV_REQUIRE(b >= 1 && b <= e->cfg.max_batch, "engine_forward: batch %d exceeds capacity %d", b, e->cfg.max_batch);
@@ -296,40 +273,14 @@ int engine_forward(xv_engine* e, void* stream, const float* features, int b, int
     e->Tl[0] = t;
     for (int i = 0; i < F; ++i) {
         if (i == 1) { rc = xve_wait_prep(e, s); if (rc) return rc; }
-        rc = layer_forward(e, s, i, b, e->Tl[i]);
+        rc = xve_layer_forward(e, s, i, b, e->Tl[i]);
         if (rc) return rc;
         e->Tl[i + 1] = e->Tl[i] - e->L[i].k + 1;
     }
-    const int Tp = e->Tl[F];      // pooled frames
-    const float* frame_w = nullptr;
-    if (e->att) {
-        // key network on the last-but-one frame layer's output (tdnn4_relu; in split precision its planes are still there):
-        // att_key0 = dense+bn+relu, att_key1 = dense (+ bn + relu: att_key_network_type 2, kept in fp32 for the score)
-        rc = layer_forward(e, s, e->K0(), b * Tp, 1);
-        if (rc) return rc;
-        rc = layer_forward(e, s, e->K1(), b * Tp, 1);
-        if (rc) return rc;
-        // scores = key.query (/ sqrt(dk)), weights = softmax over the frames of each chunk (pooling.py:134-148)
-        XvAffine& k1 = e->L[e->K1()];
-        const float scale = e->cfg.att_use_scale ? 1.0f / sqrtf((float)k1.c_out) : 1.0f;
-        rc = xv_att_score(s, k1.has_bn ? k1.a : k1.z, b * Tp, k1.c_out, k1.c_out, k1.act, vptr(e, e->v_query), scale, e->att_score);
-        if (rc) return rc;
-        rc = xv_softmax_segments_ex(s, e->att_score, b, Tp, e->att_w, frames, t - Tp);
-        if (rc) return rc;
-        frame_w = e->att_w;
-    }
-    if (e->vlad) {
-        rc = vlad_forward(e, s, b, Tp, frames, t - Tp);
-    } else {
-        // the last frame layer's BN + ReLU is applied inside the pooling reduction: its [b*t][1500] activation is never written
-        XvAffine& a = e->L[F - 1];
-        ActScope act(e, a);
-        rc = xv_stat_pool_forward_bn_ex(s, a.z, b, Tp, e->P, a.scale, a.shift, 1, frame_w, e->pool, training ? e->pool_wpos : nullptr,
-                                        e->f16 ? e->pool_amax : nullptr /* bounds |d a| for the dz planes' scale */, frames, t - Tp, a.ldz);
-    }
+    rc = xvp_forward(e, s, b, t, frames);
     if (rc) return rc;
     XvAffine &l6 = e->L[e->S0()], &l7 = e->L[e->S1()];
-    rc = segment_forward(e, s, l6, e->pool, l6.a);
+    rc = segment_forward(e, s, l6, e->pool_.pool, l6.a);
     if (rc) return rc;
     rc = segment_forward(e, s, l7, l6.a, e->h7_buf);
     if (rc) return rc;
@@ -350,67 +301,15 @@ extern "C" int xv_engine_loss_forward(xv_engine* e, void* stream, const int32_t*
     XV_REQUIRE(e && e->V && e->has_loss(), "engine_loss_forward: engine has no loss head");
     XV_REQUIRE(e->B > 0, "engine_loss_forward: run forward first");
     hipStream_t s = (hipStream_t)stream;
-    const xv_config& c = e->cfg;
-    const int b = e->B;
-    e->labels_dev = (int32_t*)labels;
-    e->with_margin = with_margin;
+    e->head_.labels_dev = (int32_t*)labels;
+    e->head_.with_margin = with_margin;
     int rc = ensure_weights(e, s);
     if (rc) return rc;
     rc = xve_wait_prep(e, s);
     if (rc) return rc;
     rc = xve_wait_lossprep(e, s);
     if (rc) return rc;
-    if (e->pair) {      // pairwise heads: no logits, no head weights; the embedding is the whole input
-        XV_REQUIRE(e->pair_set, "engine_loss_forward: loss_kind %d (%s) needs its options: call xv_engine_set_pair_loss first", c.loss_kind,
-                   c.loss_kind == XV_LOSS_SEMIHARD_TRIPLET ? "semihard_triplet_loss" : "angular_triplet_loss");
-        e->pair_e2e = !with_margin && c.loss_kind == XV_LOSS_ANGULAR_TRIPLET;      // trainer.py:272-275; the semi-hard loss validates as it trains
-        e->reg_valid = false;
-        if (e->pair_e2e) {
-            XV_REQUIRE((long)e->pair_cfg.valid_speakers * e->pair_cfg.valid_segments == b,
-                       "engine_loss_forward: the end-to-end validation loss takes num_valid_speakers_per_batch x num_valid_segments_per_speaker = %d x %d rows, the batch has %d",
-                       e->pair_cfg.valid_speakers, e->pair_cfg.valid_segments, b);
-            return xv_e2e_valid_loss(s, e->out, e->pair_cfg.valid_speakers, e->pair_cfg.valid_segments, e->Lout, e->Lout, e->scalars + 0, e->pair_ws, e->pair_ws_bytes);
-        }
-        return xv_pair_loss_forward(s, &e->pair_cfg, e->out, b, e->Lout, e->Lout, labels, e->scalars + 0, e->pair_stats, e->pair_ws, e->pair_ws_bytes);
-    }
-    const float* bias = e->v_loss_bias >= 0 ? vptr(e, e->v_loss_bias) : nullptr;
-    if (e->sk && b <= XV_SEGMENT_MAX_ROWS) {
-        XvSkinny g = xve_skinny(e, e->out, e->Lout, e->wnt, e->Lout, b, e->N, e->Lout);
-        g.bias = bias; g.C = e->logits; g.ldc = e->ldl;
-        rc = xv_launch_skinny(s, g);
-    } else {
-        XvGemmNT g = {};
-        g.A = e->out; g.lda = e->Lout; g.a_rps = 1; g.a_pitch = 1;
-        g.Bt = e->wnt; g.ldb = e->Lout;
-        g.C = e->logits; g.ldc = e->ldl;
-        g.M = b; g.N = e->N; g.K = e->Lout;
-        g.bias = bias;
-        g.ws = e->ws; g.ws_bytes = e->ws_bytes;
-        rc = xv_launch_gemm_nt(s, g);
-    }
-    if (rc) return rc;
-    // lambda schedule, loss.py:144-145 (host side: global_step is a fed placeholder, trainer.py:507)
-    double lam = (double)c.lambda_base * pow(1.0 + (double)c.lambda_gamma * (double)global_step, -(double)c.lambda_power);
-    if (lam < (double)c.lambda_min) lam = (double)c.lambda_min;
-    e->lambda = (float)lam;
-    int kind = c.loss_kind;
-    float m = c.margin_m;
-    if (!with_margin && kind != XV_LOSS_SOFTMAX) { kind = XV_LOSS_ASOFTMAX; m = 1.0f; }   // trainer.py:261-271
-    // one launch: the rows, ||out[r]|| (divides the ||x|| gradient in backward) and the mean (last ticket of sk_tickets)
-    rc = xv_margin_softmax_rows_ex(s, kind, e->logits, b, e->N, e->ldl, e->out, e->Lout, labels, m, e->lambda, e->dlogits, e->dnorm,
-                                   e->row_loss, e->scalars + 0, e->xnorm, e->sk_tickets + (e->sk_ntickets - 1));
-    if (rc) return rc;
-    // auxiliary losses are part of the training loss only (trainer.py:279-289 clears aux_loss_func for validation)
-    if (with_margin && c.aux_ring) {
-        rc = xv_ring_loss(s, e->out, b, e->Lout, e->Lout, vptr(e, e->v_ring), c.ring_loss_lambda, e->scalars + 0, e->dnorm, e->scalars + 3);
-        if (rc) return rc;
-    }
-    if (with_margin && c.aux_mhe) {
-        rc = xv_mhe_loss(s, e->wn, e->Lout, e->N, e->ldl, labels, b, c.mhe_lambda, e->scalars + 0, e->mhe_coef, e->mhe_counts);
-        if (rc) return rc;
-    }
-    e->reg_valid = false;
-    return 0;
+    return xvh_loss_forward(e, s, labels, global_step);
 }
 
 // regularization_loss, trainer.py:357-358.  It does not feed any gradient (the L2 term is added
@@ -423,16 +322,10 @@ int xve_reg_loss(xv_engine* e, hipStream_t s) {
         int rc = xv_sumsq_ordered(s, vptr(e, e->L[i].v_kernel), e->vars[e->L[i].v_kernel].count, 0.5f * c.weight_l2_regularizer, e->scalars + 1, (float*)e->ws);
         if (rc) return rc;
     }
-    if (e->vlad) {      // pooling.py:245,256: the assignment kernel and every centre (ghosts included), not the bias
-        for (int v : {e->v_vlad_w, e->v_vlad_c}) {
-            int rc = xv_sumsq_ordered(s, vptr(e, v), e->vars[v].count, 0.5f * c.weight_l2_regularizer, e->scalars + 1, (float*)e->ws);
-            if (rc) return rc;
-        }
-    }
-    if (e->N > 0) {
-        int rc = xv_sumsq_ordered(s, vptr(e, e->v_loss_kernel), e->vars[e->v_loss_kernel].count, 0.5f * xve_output_l2(c), e->scalars + 1, (float*)e->ws);
-        if (rc) return rc;
-    }
+    int rc = xvp_reg_loss(e, s);
+    if (rc) return rc;
+    rc = xvh_reg_loss(e, s);
+    if (rc) return rc;
     e->reg_valid = true;
     return 0;
 }

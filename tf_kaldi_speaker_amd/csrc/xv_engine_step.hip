@@ -114,7 +114,7 @@ extern "C" int xv_debug_engine_clip_sumsq(xv_engine* e, float** sumsq) {
 }
 
 // (grows only; the stream is drained before a smaller buffer is freed: a copy of the previous endpoint may still be reading it)
-static float* endpoint_scratch(xv_engine* e, size_t floats) {
+float* xve_endpoint_scratch(xv_engine* e, size_t floats) {
     if (floats <= e->ep_scratch_floats) return e->ep_scratch;
     if (e->ep_scratch) {
         if (hipStreamSynchronize(e->last_stream) != hipSuccess) { xv_set_error("engine_endpoint: stream synchronisation failed"); return nullptr; }
@@ -133,57 +133,33 @@ extern "C" int xv_engine_endpoint(xv_engine* e, const char* name, float** ptr, i
     XV_REQUIRE(e && name && ptr && rows && cols && ld, "engine_endpoint: null argument");
     XV_REQUIRE(e->B > 0, "engine_endpoint: run forward first");
     std::string n(name);
-    auto set = [&](float* p, int r, int c, int l) { *ptr = p; *rows = r; *cols = c; *ld = l; return 0; };
+    const XvView view = {ptr, rows, cols, ld};
     for (int i = 0; i < e->NL; ++i) {
         XvAffine& a = e->L[i];
-        if (n == a.prefix + "_" + a.kind) return set(a.z, a.rows, a.c_out, a.ldz);
+        if (n == a.prefix + "_" + a.kind) return view.set(a.z, a.rows, a.c_out, a.ldz);
         if (n == a.prefix + "_relu" && a.has_relu) {
             if ((e->f16 && (i < e->F - 1 || i == e->K0())) || i == e->F - 1) {     // not materialised on the hot path (fp16 planes / fused into pooling): rebuild on demand
                 ActScope act(e, a);
                 int rc = xv_bn_apply(e->last_stream, a.z, a.rows, a.c_out, a.ldz, a.scale, a.shift, 1, a.a, a.c_out);
                 if (rc) return rc;
             }
-            return set(i == e->S1() ? e->h7 : a.a, a.rows, a.c_out, a.c_out);
+            return view.set(i == e->S1() ? e->h7 : a.a, a.rows, a.c_out, a.c_out);
         }
         if (n == a.prefix + "_bn" && a.has_bn) {
-            if (!a.has_relu) return set(i == e->S1() ? e->h7 : a.a, a.rows, a.c_out, a.c_out);
+            if (!a.has_relu) return view.set(i == e->S1() ? e->h7 : a.a, a.rows, a.c_out, a.c_out);
             // BN output is never materialised on the hot path (fused with ReLU): rebuild on demand
-            float* sc = endpoint_scratch(e, (size_t)a.rows * a.c_out);
+            float* sc = xve_endpoint_scratch(e, (size_t)a.rows * a.c_out);
             if (!sc) return 1;
             int rc = xv_bn_apply(e->last_stream, a.z, a.rows, a.c_out, a.ldz, a.scale, a.shift, 0, sc, a.c_out);
             if (rc) return rc;
-            return set(sc, a.rows, a.c_out, a.c_out);
+            return view.set(sc, a.rows, a.c_out, a.c_out);
         }
     }
-    // debug views of the backward scratch (valid right after backward stage 0)
-    if (n == "debug:da5" && !e->vlad) {     // evaluated on demand with the standalone pooling backward (valid after backward stage 0, before stage 1)
-        XvAffine& a5 = e->L[e->F - 1];
-        ActScope act(e, a5);
-        int rc = xv_bn_apply(e->last_stream, a5.z, a5.rows, a5.c_out, a5.ldz, a5.scale, a5.shift, 1, a5.a, a5.c_out);
-        if (rc) return rc;
-        rc = xv_stat_pool_backward(e->last_stream, a5.a, e->pool, e->d_small0, e->B, e->Tl[e->F], e->P, e->bufD);
-        if (rc) return rc;
-        return set(e->bufD, e->B * e->Tl[e->F], e->P, e->P);
-    }
-    if (n == "debug:dpool") return set(e->d_small0, e->B, e->pool_dim, e->pool_dim);
-    if (e->vlad) {      // pooling.py:250,273-275
-        const int rows = e->B * e->Tl[e->F];
-        if (n == "vlad_key") return set(e->vl_logits, rows, e->VKG, e->VKGp);
-        if (n == "vlad_weights") return set(e->vl_A, rows, e->VKG, e->VKG);
-        if (n == "vlad_centers") return set(vptr(e, e->v_vlad_c), e->VKG, e->P, e->P);
-    }
-    if (n == "attention_weights" && e->att) return set(e->att_w, e->B, e->Tl[e->F], e->Tl[e->F]);     // [b, heads = 1, frames]
-    if (n == "att_key1_relu" && e->att && e->L[e->K1()].act == 1) {      // relu key (type 1) lives inside the score kernels: rebuild on demand
-        XvAffine& k1 = e->L[e->K1()];
-        float* sc = endpoint_scratch(e, (size_t)k1.rows * k1.c_out);
-        if (!sc) return 1;
-        int rc = xv_relu_backward(e->last_stream, k1.z, k1.z, (size_t)k1.rows * k1.c_out, sc);      // z > 0 ? z : 0
-        if (rc) return rc;
-        return set(sc, k1.rows, k1.c_out, k1.c_out);
-    }
-    if (n == "pooling") return set(e->pool, e->B, e->pool_dim, e->pool_dim);
-    if (n == "output") return set(e->out, e->B, e->Lout, e->Lout);
-    if (n == "logits" && e->N > 0) return set(e->logits, e->B, e->N, e->ldl);
+    int rc = xvp_endpoint(e, n, view);      // the pooling layer's views, then the loss head's
+    if (rc != XV_EP_UNKNOWN) return rc;
+    rc = xvh_endpoint(e, n, view);
+    if (rc != XV_EP_UNKNOWN) return rc;
+    if (n == "output") return view.set(e->out, e->B, e->Lout, e->Lout);
     xv_set_error("engine_endpoint: unknown endpoint '%s'", name);
-    return 3;
+    return XV_EP_UNKNOWN;
 }
