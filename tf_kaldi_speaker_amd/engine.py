@@ -14,13 +14,14 @@ import torch
 import logging
 
 try:
-    from . import _lib, ops as _ops, pipeline_ops as _pipeline_ops
-    from ._lib import XvConfig, XvError, LOSS_KINDS, OPTIMIZERS, PRECISIONS, POOLINGS, RELU_TYPES, XV_BWD_STAGES
+    from . import _lib, kinds, ops as _ops, pipeline_ops as _pipeline_ops
+    from ._lib import XvConfig, XvError, OPTIMIZERS, PRECISIONS, RELU_TYPES, XV_BWD_STAGES
 except ImportError:      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT makes these top-level modules
     import _lib
+    import kinds
     import ops as _ops
     import pipeline_ops as _pipeline_ops
-    from _lib import XvConfig, XvError, LOSS_KINDS, OPTIMIZERS, PRECISIONS, POOLINGS, RELU_TYPES, XV_BWD_STAGES
+    from _lib import XvConfig, XvError, OPTIMIZERS, PRECISIONS, RELU_TYPES, XV_BWD_STAGES
 
 
 # How tdnn1-5's contractions are evaluated unless make_config(precision=...) / the config key "precision" / $XV_PRECISION
@@ -44,6 +45,22 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _flag(v):
+    return int(bool(v))
+
+
+def _count(v):
+    return int(v or 0)
+
+
+# the make_config keywords that are copied into the XvConfig field of the same name: (coercion, names)
+_COPIED = ((int, ("feat_dim", "num_nodes_pooling_layer", "num_nodes_last_layer", "max_batch", "max_frames")),
+           (_count, ("num_speakers", "max_rows")),
+           (_flag, ("last_layer_no_bn", "last_layer_linear", "feature_norm", "fused_bn_unbiased_moving_var", "use_nesterov")),
+           (float, ("feature_scaling_factor", "margin_m", "lambda_min", "lambda_base", "lambda_gamma", "lambda_power", "weight_l2_regularizer",
+                    "batchnorm_momentum", "bn_epsilon", "momentum", "clip_gradient_norm", "ring_loss_init", "ring_loss_lambda", "mhe_lambda")))
+
+
 def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lambda_min=0.0, lambda_base=1000.0,
                 lambda_gamma=1e-4, lambda_power=5.0, num_nodes_pooling_layer=1500, num_nodes_last_layer=512,
                 last_layer_no_bn=False, last_layer_linear=False, feature_norm=False, feature_scaling_factor=1.0,
@@ -57,57 +74,32 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
     """loss_func "semihard_triplet_loss" / "angular_triplet_loss" (loss kinds 4 / 5): the options margin, triplet_loss_squared, triplet_type,
     loss_type (the margin on the angular loss's positive side) and the N x M layout of an end-to-end validation batch travel on the returned
     config as `.pair_loss` (an XvPairLossConfig); Engine hands them to xv_engine_set_pair_loss.  No softmax/output variables are created for
-    these kinds, whatever num_speakers says, and aux_loss_func is not evaluated (the reference's triplet functions never call it)."""
-    if pooling_type not in POOLINGS:
-        raise NotImplementedError("Not implement %s pooling" % pooling_type)
-    if loss_func not in LOSS_KINDS:
-        raise NotImplementedError("Not implement %s loss" % loss_func)
+    these kinds, whatever num_speakers says, and aux_loss_func is not evaluated (the reference's triplet functions never call it).
+    What a pooling kind or a loss kind reads of these keywords, and what it refuses, is its record's in kinds.py."""
+    kw = dict(locals())
+    pooling, head = kinds.pooling(pooling_type), kinds.loss(loss_func)
     if optimizer not in OPTIMIZERS:
         raise SystemExit("Optimizer %s is not supported." % optimizer)
     c = XvConfig()
     c.pair_loss = None
-    if loss_func in _lib.PAIR_KINDS:
+    if head.family == kinds.PAIR:
         if aux_loss_func:
             log.info("%s: aux_loss_func %s is not evaluated with this loss (the reference's triplet functions never call it)" % (loss_func, list(aux_loss_func)))
             aux_loss_func = ()
         c.pair_loss = _ops.pair_loss_config(loss_func, margin=margin, squared=triplet_loss_squared, triplet_type=triplet_type, loss_type=loss_type,
                                             valid_speakers=num_valid_speakers_per_batch, valid_segments=num_valid_segments_per_speaker)
-    c.feat_dim = int(feat_dim)
-    c.num_speakers = int(num_speakers or 0)
-    c.num_nodes_pooling_layer = int(num_nodes_pooling_layer)
-    c.num_nodes_last_layer = int(num_nodes_last_layer)
-    c.last_layer_no_bn = int(bool(last_layer_no_bn))
-    c.last_layer_linear = int(bool(last_layer_linear))
-    c.feature_norm = int(bool(feature_norm))
-    c.feature_scaling_factor = float(feature_scaling_factor)
-    c.loss_kind = LOSS_KINDS[loss_func]
-    c.margin_m = float(margin_m)
-    c.lambda_min, c.lambda_base = float(lambda_min), float(lambda_base)
-    c.lambda_gamma, c.lambda_power = float(lambda_gamma), float(lambda_power)
-    c.weight_l2_regularizer = float(weight_l2_regularizer)
+    for coerce, names in _COPIED:
+        for name in names:
+            setattr(c, name, coerce(kw[name]))
+    c.loss_kind = head.code
     c.output_weight_l2_regularizer = -1.0 if output_weight_l2_regularizer is None else float(output_weight_l2_regularizer)
-    c.batchnorm_momentum = float(batchnorm_momentum)
-    c.bn_epsilon = float(bn_epsilon)
-    c.fused_bn_unbiased_moving_var = int(bool(fused_bn_unbiased_moving_var))
     c.optimizer = OPTIMIZERS[optimizer]
-    c.momentum = float(momentum)
-    c.use_nesterov = int(bool(use_nesterov))
-    c.clip_gradient_norm = float(clip_gradient_norm)
-    c.max_batch = int(max_batch)
-    c.max_frames = int(max_frames)
-    c.max_rows = int(max_rows or 0)
     if precision is None:
         precision = os.environ.get("XV_PRECISION", DEFAULT_PRECISION)
     if precision not in PRECISIONS:
         raise ValueError("precision must be one of %s" % sorted(PRECISIONS))
     c.precision = PRECISIONS[precision]
-    for aux in aux_loss_func or ():
-        if aux not in ("ring_loss", "mhe_loss"):
-            raise NotImplementedError("Unsupported loss function %s" % aux)
-    c.aux_ring = int("ring_loss" in (aux_loss_func or ()))
-    c.ring_loss_init, c.ring_loss_lambda = float(ring_loss_init), float(ring_loss_lambda)
-    c.aux_mhe = int("mhe_loss" in (aux_loss_func or ()))
-    c.mhe_lambda = float(mhe_lambda)
+    kinds.write_aux(c, aux_loss_func or ())
     if network_relu_type not in RELU_TYPES:
         raise NotImplementedError("network_relu_type %r (relu, prelu or lrelu: tdnn.py:24-30)" % network_relu_type)
     c.relu_type = RELU_TYPES[network_relu_type]
@@ -122,24 +114,8 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
         c.num_frame_layers = len(table)
         for i, (k, w) in enumerate(table):
             c.frame_context[i], c.frame_width[i] = k, w
-    c.pooling = POOLINGS[pooling_type]
-    if pooling_type == "self_attention":
-        # the shipped single-head form (nnet_conf/*_tdnn4_att.json): two key layers on tdnn4_relu, value = tdnn5_relu
-        if len(att_key_num_nodes) != 2:
-            raise NotImplementedError("self_attention: att_key_num_nodes must have two entries (dense+bn+relu, then the key layer)")
-        if int(att_key_network_type) not in (0, 1, 2, 3):
-            raise NotImplementedError("self_attention: att_key_network_type %r is not one of 0..3 (pooling.py:84-96)" % att_key_network_type)
-        c.att_key0_nodes, c.att_key1_nodes = int(att_key_num_nodes[0]), int(att_key_num_nodes[1])
-        c.att_key_type = int(att_key_network_type)
-        c.att_use_scale = int(bool(att_use_scale))
-    if pooling_type == "ghost_vlad":
-        # pooling.py:195-277 with key = value = the last frame layer's ReLU output (model/tdnn.check_params refuses the other inputs by name)
-        k, g = int(vlad_num_centers), int(vlad_num_ghosts)
-        if k < 1 or g < 0 or k + g > 64:
-            raise NotImplementedError("ghost_vlad: vlad_num_centers >= 1, vlad_num_ghosts >= 0 and at most 64 clusters in all (got %d + %d)" % (k, g))
-        if precision != "f32":
-            raise NotImplementedError("ghost_vlad: precision %s is not supported (f32 only)" % precision)
-        c.vlad_num_centers, c.vlad_num_ghosts, c.vlad_final_l2_norm = k, g, int(bool(vlad_final_l2_norm))
+    c.pooling = pooling.code
+    pooling.write(c, dict(kw, precision=precision))
     return c
 
 
@@ -204,51 +180,23 @@ class Engine(object):
         self.variables.copy_(torch.from_numpy(host))
         _lib.check(self.lib.xv_engine_invalidate_weights(self.h))
 
+    def _by_name(self, flat, trainable_only=False):
+        host = flat.cpu().numpy()
+        return OrderedDict((name, host[off:off + int(np.prod(shape))].reshape(shape).copy())
+                           for name, (shape, off, trainable) in self.table.items() if trainable or not trainable_only)
+
     def get_variables(self):
-        host = self.variables.cpu().numpy()
-        out = OrderedDict()
-        for name, (shape, off, _) in self.table.items():
-            n = int(np.prod(shape))
-            out[name] = host[off:off + n].reshape(shape).copy()
-        return out
+        return self._by_name(self.variables)
 
     def get_gradients(self):
-        host = self.grads.cpu().numpy()
-        out = OrderedDict()
-        for name, (shape, off, trainable) in self.table.items():
-            if trainable:
-                n = int(np.prod(shape))
-                out[name] = host[off:off + n].reshape(shape).copy()
-        return out
+        return self._by_name(self.grads, trainable_only=True)
 
     def init_variables(self, seed=0):
-        """Glorot-uniform kernels, zero biases, gamma=1, beta=0, moving_mean=0, moving_variance=1
-        ([TF] defaults of tf.layers.conv2d/dense/batch_normalization and xavier_initializer, loss.py:100-102)."""
+        """kinds.initial_value of every variable, drawn from one RandomState(seed) in table order: Glorot-uniform kernels, zero biases,
+        gamma=1, beta=0, moving_mean=0, moving_variance=1, the ring loss's radius = config.ring_loss_init."""
         rs = np.random.RandomState(seed)
-        vals = {}
-        for name, (shape, _, _) in self.table.items():
-            leaf = name.rsplit("/", 1)[1]
-            if leaf == "kernel":
-                if len(shape) == 4:
-                    fan_in, fan_out = shape[1] * shape[2], shape[1] * shape[3]
-                else:
-                    fan_in, fan_out = shape
-                lim = np.sqrt(6.0 / (fan_in + fan_out))
-                vals[name] = rs.uniform(-lim, lim, size=shape).astype(np.float32)
-            elif name == "softmax_ringloss/r":
-                vals[name] = np.full(shape, self.config.ring_loss_init, np.float32)
-            elif leaf == "vlad_centers":      # tf.contrib.layers.xavier_initializer() on [K + G, dim], pooling.py:253-255
-                lim = np.sqrt(6.0 / (shape[0] + shape[1]))
-                vals[name] = rs.uniform(-lim, lim, size=shape).astype(np.float32)
-            elif leaf == "query":      # truncated_normal(stddev=0.1), pooling.py:131-132
-                vals[name] = np.clip(rs.randn(*shape) * 0.1, -0.2, 0.2).astype(np.float32)
-            elif leaf in ("gamma", "moving_variance"):
-                vals[name] = np.ones(shape, np.float32)
-            elif leaf == "alpha":      # tf.constant_initializer(0.01), common.py:37
-                vals[name] = np.full(shape, 0.01, np.float32)
-            else:
-                vals[name] = np.zeros(shape, np.float32)
-        self.set_variables(vals)
+        self.set_variables({name: kinds.initial_value(name.rsplit("/", 1)[1], shape, rs, self.config.ring_loss_init if name == "softmax_ringloss/r" else None)
+                            for name, (shape, _, _) in self.table.items()})
 
     # ---- graph execution ------------------------------------------------------------
     def _dev(self, a, dtype):
@@ -365,31 +313,31 @@ class Engine(object):
     def arena_bytes(self):
         return int(self.lib.xv_engine_arena_bytes(self.h))
 
+    def _read_back(self, p, rows, cols, ld, what="xv_copy_2d"):
+        """Device copy [rows, cols] of the engine-owned floats at p (row pitch ld), enqueued on the current stream."""
+        out = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), cols, p, ld, rows, cols), what)
+        return out
+
     def losses(self):
         """(raw_loss, regularization_loss) of the last loss() call - synchronises."""
         raw, reg = C.c_void_p(), C.c_void_p()
         _lib.check(self.lib.xv_engine_loss_ptrs(self.h, C.byref(raw), C.byref(reg)))
-        out = torch.empty(2, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), 2, raw, 2, 1, 2), "xv_copy_2d")
-        v = out.cpu().numpy()
+        v = self._read_back(raw, 1, 2, 2).cpu().numpy()[0]
         return float(v[0]), float(v[1])
 
     def raw_loss(self):
         """Mean loss of the last loss() call (synchronises); does not evaluate the regulariser."""
         raw = C.c_void_p()
         _lib.check(self.lib.xv_engine_loss_ptrs(self.h, C.byref(raw), None))
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), 1, raw, 1, 1, 1), "xv_copy_2d")
-        return float(out.cpu().numpy()[0])
+        return float(self._read_back(raw, 1, 1, 1).cpu().numpy()[0, 0])
 
     def clip_sumsq(self):
         """Sum of squares of the flat gradient buffer as the last clipped apply() took it, before grad_scale (diagnostics: the
         global norm of that update is sqrt(clip_sumsq()) * grad_scale) - synchronises."""
         p = C.c_void_p()
         _lib.check(self.lib.xv_debug_engine_clip_sumsq(self.h, C.byref(p)), "xv_debug_engine_clip_sumsq")
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), 1, p, 1, 1, 1), "xv_copy_2d")
-        return float(out.cpu().numpy()[0])
+        return float(self._read_back(p, 1, 1, 1).cpu().numpy()[0, 0])
 
     def endpoint(self, name):
         """Copy of an endpoint of the most recent forward as a torch tensor [rows, cols]."""
@@ -397,9 +345,7 @@ class Engine(object):
         rows, cols, ld = C.c_int32(), C.c_int32(), C.c_int32()
         _lib.check(self.lib.xv_engine_endpoint(self.h, name.encode(), C.byref(p), C.byref(rows), C.byref(cols), C.byref(ld)),
                    "xv_engine_endpoint(%s)" % name)
-        out = torch.empty((rows.value, cols.value), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.xv_copy_2d(_stream(), _ptr(out), cols.value, p, ld.value, rows.value, cols.value), "xv_copy_2d")
-        return out
+        return self._read_back(p, rows.value, cols.value, ld.value)
 
     # ---- fine-tuning: variables the optimiser must not touch (trainer.py:379-403 noupdate_var_list, :728-773 set_trainable_variables)
     def set_update_filter(self, frozen_names=()):
@@ -465,3 +411,23 @@ class Engine(object):
         if frozen:
             _lib.check(self.lib.xv_engine_invalidate_weights(self.h), "xv_engine_invalidate_weights")
         return out
+
+
+def rebuild(old, config, seed=None, training_state=False):
+    """A new engine for `config` in the place of `old`, which is closed before the new one takes its memory.  Carried over: the variables
+    whose name and shape still exist (the others start from init_variables(seed); seed None: there are none, nothing is drawn) and, with
+    training_state, what a training run holds besides - the optimiser state where its size is unchanged, the update count and the update
+    filter."""
+    values = old.get_variables()
+    opt, count, frozen = old.opt_state.clone() if training_state else None, old.update_count, getattr(old, "frozen_names", ())
+    old.close()
+    new = Engine(config, device=old.device)
+    if seed is not None:
+        new.init_variables(seed=seed)
+    new.set_variables({k: v for k, v in values.items() if k in new.table and new.table[k][0] == v.shape})
+    if training_state:
+        if new.opt_state.numel() == opt.numel():
+            new.opt_state.copy_(opt)
+        new.update_count = count
+        new.set_update_filter(frozen)
+    return new

@@ -7,34 +7,37 @@ csrc/xv_attention.hip, csrc/xv_vlad.hip); inside the training engine the same ke
 callables are the evaluation forms a caller of the reference API reaches.  `self_attention` covers the single-head form
 every shipped attention config uses (key network on `endpoints[att_key_input]`, value = `endpoints[att_value_input]`, key
 not split, no value network, no penalty term, no post non-linearity); the other options of the reference function are
-refused by name.  `ghost_vlad` takes its key and its value straight from endpoints (no key / value networks).
+refused by name.  `ghost_vlad` takes its key and its value straight from endpoints (no key / value networks).  What each kind refuses is its
+record's `refuse` in kinds.py, which the engine form (model/tdnn.check_params) shares.
 
 The attention and VLAD variables live in a module-level store under the reference's scope names ("attention/att_key0/att_key0_dense/kernel",
 ..., "attention/query", "vlad/vlad_weight_affine/kernel", "vlad/vlad_centers"), like the loss functions' `softmax/output/kernel` (model/loss.py): the first call creates them,
-a second creating call raises as tf.get_variable would, `reuse_variables()` re-enters them.
+a second creating call raises as tf.get_variable would, `reuse_variables()` re-enters them (model/common.VariableStore; initial values: kinds.initial_value).
 """
-from collections import OrderedDict
-
 import numpy as np
 import torch
 
 try:
-    from .. import ops
-    from .common import to_device, shape_list
+    from .. import ops, kinds
+    from .common import to_device, shape_list, VariableStore
 except (ImportError, ValueError):
     import ops
-    from model.common import to_device, shape_list
+    import kinds
+    from model.common import to_device, shape_list, VariableStore
 
 VAR2STD_EPSILON = 1e-12
 BN_EPSILON = 1e-3            # tf.layers.batch_normalization default
 
-_VARIABLES = OrderedDict()   # "attention/..." -> device tensor
-_STATE = {"seed": 0, "reuse": False}
+_STORE = VariableStore(lambda v: to_device(v))
+_VARIABLES = _STORE.variables   # "attention/..." -> device tensor
+_STATE = {"reuse": False}
+set_variable = _STORE.preset
+check_vlad_params = kinds.POOLINGS["ghost_vlad"].refuse      # (d, last_relu=None) -> (centres, ghosts); shared with model/tdnn.check_params
 
 
 def reset_variables(seed=0):
-    _VARIABLES.clear()
-    _STATE["seed"], _STATE["reuse"] = seed, False
+    _STORE.reset(seed)
+    _STATE["reuse"] = False
 
 
 def reuse_variables(flag=True):
@@ -42,31 +45,14 @@ def reuse_variables(flag=True):
     _STATE["reuse"] = bool(flag)
 
 
-def set_variable(name, value):
-    _VARIABLES[name] = to_device(np.asarray(value, np.float32))
-
-
 def get_variables():
     return _VARIABLES
 
 
 def _get(name, shape, init):
-    if name in _VARIABLES:
-        v = _VARIABLES[name]      # created by an earlier call or preset with set_variable(): re-entered like a reused scope
-        assert tuple(v.shape) == tuple(shape), "variable %s has shape %s, requested %s" % (name, tuple(v.shape), tuple(shape))
-        return v
-    if _STATE["reuse"]:
-        raise ValueError("Variable %s does not exist, or was not created with tf.get_variable()." % name)
-    rs = np.random.RandomState(_STATE["seed"] + len(_VARIABLES))
-    if init == "glorot":
-        lim = np.sqrt(6.0 / (shape[0] + shape[1]))
-        val = rs.uniform(-lim, lim, size=shape)
-    elif init == "query":        # tf.initializers.truncated_normal(stddev=0.1), pooling.py:131-132
-        val = np.clip(rs.randn(*shape) * 0.1, -0.2, 0.2)
-    else:
-        val = np.full(shape, float(init))
-    _VARIABLES[name] = to_device(val.astype(np.float32))
-    return _VARIABLES[name]
+    """init: "glorot" / "query" (what kinds.initial_value gives this name) or the constant.  A variable created by an earlier call or preset
+    with set_variable() is re-entered like a reused scope."""
+    return _STORE.get(name, shape, create=not _STATE["reuse"], constant=init if isinstance(init, float) else None)
 
 
 def statistics_pooling(features, aux_features, endpoints, params, is_training):
@@ -118,22 +104,8 @@ def self_attention(features, aux_features, endpoints, params, is_training=None):
     "att_output_before_nonlinear".
     """
     d = params.dict
-    if d.get("network_relu_type", "relu") != "relu":
-        raise NotImplementedError("self_attention: network_relu_type %r (relu only)" % d.get("network_relu_type"))
-    if len(d.get("att_value_num_nodes", [])) != 0:
-        raise NotImplementedError("self_attention on the MI355X kernels: no value network (att_value_num_nodes must be empty)")
-    if int(d.get("att_num_heads", 1)) != 1 or d.get("att_split_key", False):
-        raise NotImplementedError("self_attention on the MI355X kernels: one head, key not split")
-    if d.get("att_apply_nonlinear", False):
-        raise NotImplementedError("self_attention on the MI355X kernels: att_apply_nonlinear is not supported")
-    if float(d.get("att_penalty_term", 0) or 0) != 0.0:
-        raise NotImplementedError("self_attention on the MI355X kernels: att_penalty_term must be 0 (one head has no penalty)")
-    key_nodes = list(d["att_key_num_nodes"])
-    if len(key_nodes) < 1:
-        raise NotImplementedError("self_attention: att_key_num_nodes needs at least the key layer")
-    key_type = int(d["att_key_network_type"])
-    if key_type not in (0, 1, 2, 3):
-        raise NotImplementedError("self_attention: att_key_network_type %r is not one of 0..3" % key_type)
+    kinds.POOLINGS["self_attention"].refuse(d)
+    key_nodes, key_type = list(d["att_key_num_nodes"]), int(d["att_key_network_type"])
 
     value = to_device(endpoints[params.att_value_input])
     key_in = to_device(endpoints[params.att_key_input])
@@ -183,29 +155,6 @@ def self_attention(features, aux_features, endpoints, params, is_training=None):
     att = torch.cat([pooled[:, :vdim], pooled[:, vpad:vpad + vdim]], dim=1) if vpad != vdim else pooled
     endpoints["att_output_before_nonlinear"] = att
     return att
-
-
-def check_vlad_params(d, last_relu=None):
-    """The ghost_vlad options the kernels cover, the rest refused by name (shared with model/tdnn.check_params).  last_relu: the only
-    endpoint the engine can pool ("tdnn5_relu"); None (the op-level function) takes any endpoint."""
-    unsupported = []
-    if len(d.get("vlad_key_num_nodes", [])) != 0:
-        unsupported.append("vlad_key_num_nodes (no key network)")
-    if len(d.get("vlad_value_num_nodes", [])) != 0:
-        unsupported.append("vlad_value_num_nodes (no value network)")
-    for key in ("vlad_key_input", "vlad_value_input"):
-        if last_relu is not None and d.get(key) != last_relu:
-            unsupported.append("%s=%r (%s)" % (key, d.get(key), last_relu))
-    if d.get("vlad_key_input") != d.get("vlad_value_input"):
-        unsupported.append("vlad_key_input != vlad_value_input (one tensor is key and value)")
-    k, g = int(d.get("vlad_num_centers", 0)), int(d.get("vlad_num_ghosts", 0))
-    if k < 1 or g < 0 or k + g > 64:
-        unsupported.append("vlad_num_centers=%d, vlad_num_ghosts=%d (at least one centre, at most 64 clusters)" % (k, g))
-    if d.get("precision", "f32") not in (None, "f32"):
-        unsupported.append("precision %s (f32)" % d["precision"])
-    if unsupported:
-        raise NotImplementedError("ghost_vlad on the MI355X kernels: not " + ", ".join(unsupported))
-    return k, g
 
 
 def ghost_vlad(features, aux_features, endpoints, params, is_training=None):

@@ -11,13 +11,13 @@ from collections import OrderedDict
 import torch
 
 try:
-    from .. import engine as E
+    from .. import engine as E, kinds, _lib
     from .common import to_device
-    from .pooling import check_vlad_params
 except (ImportError, ValueError):
     import engine as E
+    import kinds
+    import _lib
     from model.common import to_device
-    from model.pooling import check_vlad_params
 
 _GRAPH = {"engine": None, "key": None}
 
@@ -42,9 +42,8 @@ def endpoint_order(table=None):
     names = []
     for i, (k, _) in enumerate(table):
         names += ["tdnn%d_%s" % (i + 1, "conv" if k > 1 else "dense"), "tdnn%d_bn" % (i + 1), "tdnn%d_relu" % (i + 1)]
-    # self_attention only (pooling.py:78-149); absent names are skipped for statistics pooling
-    names += ["att_key0_dense", "att_key0_bn", "att_key0_relu", "att_key1_dense", "att_key1_bn", "att_key1_relu", "attention_weights"]
-    names += ["vlad_weights", "vlad_key", "vlad_centers", "pooling"]      # ghost_vlad only (pooling.py:250,273-275; vlad_value is tdnn<F>_relu)
+    for pooling in kinds.POOLINGS.values():      # each kind's own names; collect_endpoints skips the ones the engine's kind does not have
+        names += pooling.endpoints
     n = len(table)
     names += ["tdnn%d_dense" % (n + 1), "tdnn%d_bn" % (n + 1), "tdnn%d_relu" % (n + 1), "tdnn%d_dense" % (n + 2), "tdnn%d_bn" % (n + 2),
               "tdnn%d_relu" % (n + 2)]
@@ -52,6 +51,7 @@ def endpoint_order(table=None):
 
 
 ENDPOINT_ORDER = endpoint_order()
+POOLING_KEY_PREFIXES = tuple(p for pooling in kinds.POOLINGS.values() for p in pooling.key_prefixes)      # the options of every pooling kind
 
 
 def reset_default_graph():
@@ -60,54 +60,24 @@ def reset_default_graph():
     _GRAPH["engine"], _GRAPH["key"] = None, None
 
 
+def _last_relu(params):
+    return "tdnn%d_relu" % (len(frame_layer_table(params) or ()) or 5)
+
+
 def check_params(params):
-    """The static checks of model/tdnn.py:24-30,111-113,133-142,162-184 (defaults are inserted into params)."""
-    if params.dict.get("network_relu_type", "relu") not in ("relu", "prelu", "lrelu"):
+    """The static checks of model/tdnn.py:24-30,111-113,133-142,162-184 (defaults are inserted into params); what the pooling kind refuses
+    is its record's (kinds.py)."""
+    if params.dict.get("network_relu_type", "relu") not in _lib.RELU_TYPES:
         raise NotImplementedError("network_relu_type %s (relu, prelu or lrelu: tdnn.py:24-30)" % params.network_relu_type)
     if "num_nodes_pooling_layer" not in params.dict:
         params.dict["num_nodes_pooling_layer"] = 1500
-    if params.pooling_type == "self_attention":
-        # model/pooling.py:37-192 in the form the shipped attention config uses; everything else the function offers
-        # (value network, several heads, split keys, penalty term, post non-linearity) is refused by name
-        d = params.dict
-        unsupported = []
-        nf = len(frame_layer_table(params) or ()) or 5       # key = the last-but-one frame layer, value = the last (tdnn4_relu / tdnn5_relu)
-        if d.get("att_key_input") != "tdnn%d_relu" % (nf - 1):
-            unsupported.append("att_key_input=%r (tdnn%d_relu)" % (d.get("att_key_input"), nf - 1))
-        if d.get("att_value_input") != "tdnn%d_relu" % nf:
-            unsupported.append("att_value_input=%r (tdnn%d_relu)" % (d.get("att_value_input"), nf))
-        if len(d.get("att_value_num_nodes", [])) != 0:
-            unsupported.append("att_value_num_nodes (no value network)")
-        if len(d.get("att_key_num_nodes", [])) != 2:
-            unsupported.append("att_key_num_nodes (two key layers)")
-        if int(d.get("att_key_network_type", -1)) not in (0, 1, 2, 3):
-            unsupported.append("att_key_network_type=%r (0..3)" % d.get("att_key_network_type"))
-        if int(d.get("att_key_network_type", -1)) == 1 and d.get("network_relu_type", "relu") != "relu":
-            unsupported.append("att_key_network_type 1 with network_relu_type %s (the score kernel's fused ReLU is a plain one)" % d["network_relu_type"])
-        if int(d.get("att_num_heads", 1)) != 1 or d.get("att_split_key", False):
-            unsupported.append("att_num_heads / att_split_key (one head)")
-        if float(d.get("att_penalty_term", 0) or 0) != 0.0:
-            unsupported.append("att_penalty_term (0)")
-        if d.get("att_apply_nonlinear", False):
-            unsupported.append("att_apply_nonlinear (false)")
-        if unsupported:
-            raise NotImplementedError("self_attention on the MI355X engine supports the shipped single-head form only; not: "
-                                      + ", ".join(unsupported))
-    elif params.pooling_type == "ghost_vlad":
-        # model/pooling.py:195-277 on the last frame layer's ReLU output; key / value networks and other inputs are refused by name
-        nf = len(frame_layer_table(params) or ()) or 5
-        check_vlad_params(params.dict, "tdnn%d_relu" % nf)
-    elif params.pooling_type != "statistics_pooling":
-        raise NotImplementedError("Not implement %s pooling" % params.pooling_type)
+    kinds.pooling(params.pooling_type).refuse(params.dict, _last_relu(params))
     if "num_nodes_last_layer" not in params.dict:
         params.dict["num_nodes_last_layer"] = 512
     if "last_layer_no_bn" not in params.dict:
         params.last_layer_no_bn = False
     if "last_layer_linear" not in params.dict:
         params.last_layer_linear = False
-
-
-PAIR_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss")
 
 
 def engine_config(params, dim, num_speakers=0, loss_type="softmax", max_batch=128, max_frames=400, max_rows=0):
@@ -125,37 +95,17 @@ def engine_config(params, dim, num_speakers=0, loss_type="softmax", max_batch=12
               frame_layers=frame_layer_table(params), network_relu_type=d.get("network_relu_type", "relu"),
               precision=d.get("precision", None),      # engine extension: "f32" (default) | "f16x3" (opt-in fast mode); absent from reference configs
               pooling_type=d["pooling_type"])
-    if num_speakers and d.get("aux_loss_func"):      # loss.py:985-1036; every loss function adds them (loss.py:40,161,249,347)
-        kw.update(aux_loss_func=tuple(d["aux_loss_func"]))
-        if "ring_loss" in d["aux_loss_func"]:
-            kw.update(ring_loss_init=float(d["ring_loss_init"]), ring_loss_lambda=float(d["ring_loss_lambda"]))
-        if "mhe_loss" in d["aux_loss_func"]:
-            kw.update(mhe_lambda=float(d["mhe_lambda"]))
-    if d["pooling_type"] == "self_attention":
-        kw.update(att_key_num_nodes=tuple(d["att_key_num_nodes"]), att_key_network_type=int(d["att_key_network_type"]),
-                  att_use_scale=bool(d.get("att_use_scale", False)))
-    if d["pooling_type"] == "ghost_vlad":
-        kw.update(vlad_num_centers=int(d["vlad_num_centers"]), vlad_num_ghosts=int(d.get("vlad_num_ghosts", 0)),
-                  vlad_final_l2_norm=bool(d.get("vlad_final_l2_norm", False)))
+    if num_speakers and d.get("aux_loss_func"):
+        kw.update(kinds.aux_keywords(d))
+    kw.update(kinds.pooling(d["pooling_type"]).keywords(d))
     if d.get("feature_norm", False):
         assert "feature_scaling_factor" in d, "If feature normalization is applied, scaling factor is necessary."
-    prefix = {"asoftmax": "asoftmax", "additive_margin_softmax": "amsoftmax", "additive_angular_margin_softmax": "arcsoftmax"}.get(loss_type)
-    if prefix is not None and num_speakers:
-        kw.update(margin_m=float(d[prefix + "_m"]), lambda_min=float(d[prefix + "_lambda_min"]),
-                  lambda_base=float(d[prefix + "_lambda_base"]), lambda_gamma=float(d[prefix + "_lambda_gamma"]),
-                  lambda_power=float(d[prefix + "_lambda_power"]))
-    if loss_type in PAIR_LOSSES:      # trainer.py:234-250 with the asserts of loss.py:518-519; the validation layout: loss.py:657-658
-        if loss_type == "angular_triplet_loss":
-            assert d["triplet_type"] == "all" or d["triplet_type"] == "hard"
-            assert d["loss_type"] in ["asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax"]
-            assert "num_valid_speakers_per_batch" in d and "num_valid_segments_per_speaker" in d, "Valid parameters should be set if E2E loss is selected"
-            kw.update(triplet_type=d["triplet_type"], loss_type=d["loss_type"], num_valid_speakers_per_batch=int(d["num_valid_speakers_per_batch"]),
-                      num_valid_segments_per_speaker=int(d["num_valid_segments_per_speaker"]))
-        else:
-            kw.update(triplet_loss_squared=bool(d["triplet_loss_squared"]))
-        kw.update(margin=float(d["margin"]), aux_loss_func=tuple(d.get("aux_loss_func") or ()))
-        return E.make_config(dim, num_speakers, loss_func=loss_type, **kw)
-    return E.make_config(dim, num_speakers, loss_func=loss_type if num_speakers else "softmax", **kw)
+    # a pairwise head has no speakers to count: it is configured whatever num_speakers says; the softmax family only with an output layer
+    # (an unknown loss_type goes to make_config, which names it)
+    head = num_speakers or kinds.family(loss_type) == kinds.PAIR
+    if head and loss_type in kinds.LOSSES:
+        kw.update(kinds.LOSSES[loss_type].keywords(d))
+    return E.make_config(dim, num_speakers, loss_func=loss_type if head else "softmax", **kw)
 
 
 def collect_endpoints(eng, b, names=None):
@@ -184,7 +134,7 @@ def tdnn(features, params, is_training=None, reuse_variables=None, aux_features=
     key = (dim, params.dict["num_nodes_pooling_layer"], params.dict["num_nodes_last_layer"],
            bool(params.last_layer_no_bn), bool(params.last_layer_linear), frame_layer_table(params),
            params.dict.get("network_relu_type", "relu"), params.dict.get("pooling_type", "statistics_pooling"),
-           tuple(sorted((k, repr(v)) for k, v in params.dict.items() if k.startswith(("att_", "vlad_")))))
+           tuple(sorted((k, repr(v)) for k, v in params.dict.items() if k.startswith(POOLING_KEY_PREFIXES))))
     eng = _GRAPH["engine"]
     if eng is None:
         if reuse_variables is True:
@@ -197,11 +147,8 @@ def tdnn(features, params, is_training=None, reuse_variables=None, aux_features=
             raise ValueError("Variable tdnn/tdnn1_conv/kernel already exists, disallowed. Did you mean to set reuse=True?")
         assert key == _GRAPH["key"], "tdnn() re-entered with a different architecture"
         if b > eng.config.max_batch or t > eng.config.max_frames:     # grow: new capacity, same variables
-            values = eng.get_variables()
-            eng.close()
-            eng = E.Engine(engine_config(params, dim, 0, "softmax", max_batch=max(b, eng.config.max_batch),
-                                         max_frames=max(t, eng.config.max_frames)))
-            eng.set_variables(values)
+            eng = E.rebuild(eng, engine_config(params, dim, 0, "softmax", max_batch=max(b, eng.config.max_batch),
+                                               max_frames=max(t, eng.config.max_frames)))
             _GRAPH["engine"] = eng
     eng.forward(x, bool(is_training))
     endpoints = collect_endpoints(eng, b)

@@ -25,7 +25,7 @@ import torch
 
 try:
     from .. import engine as E
-    from .. import _lib
+    from .. import _lib, kinds
     from ..parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from ..dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
     from ..misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state
@@ -36,6 +36,7 @@ try:
 except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_ROOT
     import engine as E
     import _lib
+    import kinds
     from parallel import GradAllReduce, average_bn_statistics, broadcast_variables
     from dataset.data_loader import KaldiDataRandomQueue, KaldiDataSeqQueue, PlannedRandomQueue, DataOutOfRange
     from misc.utils import substring_in_list, read_checkpoint_state, write_checkpoint_state
@@ -45,10 +46,6 @@ except (ImportError, ValueError):      # drop-in layout: PYTHONPATH=$TF_KALDI_RO
     from model import predict as _predict
 
 log = logging.getLogger("tf_kaldi_speaker_amd")
-
-SOFTMAX_FAMILY = ("softmax", "asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax")
-PAIR_LOSSES = ("semihard_triplet_loss", "angular_triplet_loss")      # the engine's pairwise heads (csrc/xv_triplet.hip)
-OTHER_LOSSES = ("generalized_angular_triplet_loss",)
 
 
 class _Session(object):
@@ -127,13 +124,16 @@ class Trainer(object):
         t = int(p.get("max_segment_len", 400))
         return max(b, 1), max(t, 15)
 
-    def _make_engine(self, num_speakers, loss_type, max_batch, max_frames, keep=None, max_rows=0):
+    def _make_engine(self, num_speakers, loss_type, max_batch, max_frames, max_rows=0, training_state=False):
+        """The engine of this configuration and capacity; in the place of the present one (engine.rebuild: its variables carried over, with
+        training_state also the optimiser state, the update count and the update filter), else new with initial values."""
         cfg = engine_config(self.params, self.dim, num_speakers or 0, loss_type or "softmax", max_batch, max_frames, max_rows)
-        eng = E.Engine(cfg, device=self.device)
         seed = int(self.params.dict.get("seed", 0))
+        if self.engine is not None:
+            old, self.engine = self.engine, None
+            return E.rebuild(old, cfg, seed=seed, training_state=training_state)
+        eng = E.Engine(cfg, device=self.device)
         eng.init_variables(seed=seed)
-        if keep:
-            eng.set_variables({k: v for k, v in keep.items() if k in eng.table})
         return eng
 
     def _ensure_capacity(self, b, t, rows=0):
@@ -145,8 +145,6 @@ class Trainer(object):
         need_rows = rows if rows > 0 else b * t      # (rows given: b and t are the largest batch and the longest utterance of DIFFERENT batches)
         if b <= cfg.max_batch and t <= cfg.max_frames and need_rows <= have_rows:
             return
-        values = eng.get_variables()
-        opt, cnt = eng.opt_state.clone(), eng.update_count
         nb, nt = max(b, cfg.max_batch), max(t, cfg.max_frames)
         if t > cfg.max_frames:
             nt = max(t, min(2 * cfg.max_frames, 20000))
@@ -156,12 +154,7 @@ class Trainer(object):
             # rebuilding the engine whenever a later window holds a slightly longer utterance or a slightly larger batch
             nrows = max(need_rows, cfg.max_rows)
             nb, nt = max(nb, self.PREDICT_CHUNKS), max(nt, 20000)
-        self._close_engine()
-        self.engine = self._make_engine(self.num_speakers, self.loss_type, nb, nt, keep=values, max_rows=nrows)
-        if self.engine.opt_state.numel() == opt.numel():
-            self.engine.opt_state.copy_(opt)
-        self._apply_update_filter()
-        self.engine.update_count = cnt
+        self.engine = self._make_engine(self.num_speakers, self.loss_type, nb, nt, max_rows=nrows, training_state=True)
 
     # ------------------------------------------------------------------ build
     def build(self, mode, dim, loss_type=None, num_speakers=None, noupdate_var_list=None):
@@ -181,12 +174,9 @@ class Trainer(object):
 
         self.params.dict["global_step"] = 0
         self.loss_type = loss_type
-        if loss_type in SOFTMAX_FAMILY or loss_type in PAIR_LOSSES:
-            self.loss_network = getattr(_loss, loss_type)
-        elif loss_type in OTHER_LOSSES:
+        if kinds.family(loss_type) == kinds.REFUSED:
             raise NotImplementedError("Not implement %s loss on the MI355X engine (outside the hot path)" % loss_type)
-        else:
-            raise NotImplementedError("Not implement %s loss" % self.loss_type)
+        self.loss_network = getattr(_loss, kinds.loss(loss_type).name)
         if mode == "train":
             if "optimizer" not in self.params.dict:
                 self.params.dict["optimizer"] = "sgd"
@@ -198,12 +188,8 @@ class Trainer(object):
             self.optimizer = self.params.optimizer
         self.num_speakers = int(num_speakers)
         b, t = self._capacity()
-        if self.engine is None:
+        if self.engine is None or self.engine.config.num_speakers != self.num_speakers:
             self.engine = self._make_engine(self.num_speakers, loss_type, b, t)
-        elif self.engine.config.num_speakers != self.num_speakers:
-            keep = self.engine.get_variables()
-            self._close_engine()
-            self.engine = self._make_engine(self.num_speakers, loss_type, b, t, keep=keep)
         self.embeddings = "output"          # valid embeddings = endpoints["output"], trainer.py:308
         self.modes.add(mode)
         self.is_built = True
@@ -253,6 +239,13 @@ class Trainer(object):
                     os.remove(old + ext)
         write_checkpoint_state(self.model, name, names)
 
+    def _set_variables_or_exit(self, stored, path):
+        """The engine's table filled from a checkpoint's variables (either format); a checkpoint that lacks one ends the run."""
+        missing = [k for k in self.engine.table if k not in stored]
+        if missing:
+            sys.exit("Checkpoint %s lacks variables: %s" % (path, ", ".join(missing[:5])))
+        self.engine.set_variables({k: stored[k] for k in self.engine.table})
+
     def load(self):
         log.info("Reading checkpoints...")
         current, _ = read_checkpoint_state(self.model)
@@ -266,22 +259,13 @@ class Trainer(object):
             if os.path.isfile(prefix + ".index"):
                 # a checkpoint written by the reference's tf.train.Saver (trainer.py:318,444; the pretrained models of README.md:86-104):
                 # same variable names and shapes, read without TensorFlow (misc/tf_checkpoint.py).  Optimiser slots are not taken over.
-                tf_vars = tf_checkpoint.read_checkpoint(prefix)
-                values = {k: v for k, v in tf_vars.items() if k in self.engine.table}
-                missing = [k for k in self.engine.table if k not in values]
-                if missing:
-                    sys.exit("Checkpoint %s.index lacks variables: %s" % (prefix, ", ".join(missing[:5])))
-                self.engine.set_variables(values)
+                self._set_variables_or_exit(tf_checkpoint.read_checkpoint(prefix), prefix + ".index")
                 log.info("Succeed to load TensorFlow checkpoint {}".format(ckpt_name))
                 self.is_loaded = True
                 return step
             sys.exit("Failed to find a checkpoint in {}".format(self.model))
         data = np.load(path)
-        values = {k: data[k] for k in data.files if not k.startswith("__") and k in self.engine.table}
-        missing = [k for k in self.engine.table if k not in values]
-        if missing:
-            sys.exit("Checkpoint %s lacks variables: %s" % (path, ", ".join(missing[:5])))
-        self.engine.set_variables(values)
+        self._set_variables_or_exit({k: data[k] for k in data.files if not k.startswith("__")}, path)
         if "__opt_state__" in data.files and data["__opt_state__"].size == self.engine.opt_state.numel():
             self.engine.opt_state.copy_(torch.from_numpy(data["__opt_state__"]))
         if "__update_count__" in data.files:
@@ -291,6 +275,17 @@ class Trainer(object):
         return step
 
     # ------------------------------------------------------------------ training
+    def _training_queue(self, data, spklist, gpu_decode=False):
+        """The random queue of training batches.  KaldiDataRandomQueue = the C++ loader (libxvector_io.so: planning + decoding in native
+        threads); XV_LOADER=python plans the batches in Python and only decodes natively (dataset/data_loader.py) - same rules, same batch
+        contract.  gpu_decode (train() under XV_LOADER=gpu_decode): the native threads only gather the rows' 'CM ' bytes, the batch is
+        decoded on the GPU (xv_cm_decode) - a quarter of the host memory traffic and PCIe bytes, bit-identical features ('CM ' archives only)."""
+        p = self.params
+        queue_cls = PlannedRandomQueue if os.environ.get("XV_LOADER", "native") == "python" else KaldiDataRandomQueue
+        return queue_cls(data, spklist, num_parallel=p.num_parallel_datasets, max_qsize=p.max_queue_size,
+                         num_speakers=p.num_speakers_per_batch, num_segments=p.num_segments_per_speaker,
+                         min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=True, **({"packed": True} if gpu_decode else {}))
+
     def train(self, data, spklist, learning_rate, aux_data=None):
         """One epoch over `num_steps_per_epoch` random batches (reference trainer.py:451-520)."""
         assert "train" in self.modes, "call build('train', ...) first"
@@ -302,16 +297,7 @@ class Trainer(object):
         if dist is not None:
             broadcast_variables(dist, self.engine.variables, 0)
             self.engine.lib.xv_engine_invalidate_weights(self.engine.h)
-        # KaldiDataRandomQueue = the C++ loader (libxvector_io.so: planning + decoding in native threads); XV_LOADER=python
-        # plans the batches in Python and only decodes natively (dataset/data_loader.py) - same rules, same batch contract
-        # XV_LOADER=gpu_decode: the native threads only gather the rows' 'CM ' bytes, the batch is decoded on the GPU (xv_cm_decode) -
-        # a quarter of the host memory traffic and PCIe bytes, bit-identical features ('CM ' archives only)
-        which = os.environ.get("XV_LOADER", "native")
-        queue_cls = PlannedRandomQueue if which == "python" else KaldiDataRandomQueue
-        extra = {"packed": True} if which == "gpu_decode" else {}
-        loader = queue_cls(data, spklist, num_parallel=p.num_parallel_datasets, max_qsize=p.max_queue_size,
-                           num_speakers=p.num_speakers_per_batch, num_segments=p.num_segments_per_speaker,
-                           min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=True, **extra)
+        loader = self._training_queue(data, spklist, gpu_decode=os.environ.get("XV_LOADER") == "gpu_decode")
         loader.start()
         try:
             if hasattr(loader, "device_batches"):        # pinned staging + asynchronous H2D on a copy stream
@@ -374,8 +360,9 @@ class Trainer(object):
             # N speakers x M segments per batch, speaker-major, as the end-to-end validation loss needs them (trainer.py:667-680)
             assert "num_valid_speakers_per_batch" in p.dict and "num_valid_segments_per_speaker" in p.dict, \
                 "Valid parameters should be set if E2E loss is selected"
-            if self.loss_type not in PAIR_LOSSES:
-                raise NotImplementedError("end2end validation batches belong to semihard_triplet_loss / angular_triplet_loss, not to %s" % self.loss_type)
+            if kinds.family(self.loss_type) != kinds.PAIR:
+                raise NotImplementedError("end2end validation batches belong to %s, not to %s"
+                                          % (" / ".join(n for n in kinds.LOSSES if kinds.family(n) == kinds.PAIR), self.loss_type))
         curr_step = 0
         if os.path.isfile(os.path.join(self.model, "checkpoint")):
             curr_step = self.load()
@@ -383,52 +370,51 @@ class Trainer(object):
             log.info("[Warning] Cannot find model in %s. Random initialization is used in validation." % self.model)
         bsz = p.num_speakers_per_batch * p.num_segments_per_speaker
         embeddings_val, labels_val = None, None
+        common = dict(num_parallel=2, max_qsize=10, min_len=p.min_segment_len, max_len=p.max_segment_len)
         if output_embeddings:
-            loader = KaldiDataSeqQueue(data, spklist, num_parallel=2, max_qsize=10, batch_size=bsz,
-                                       min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=False)
-            loader.start()
             embs, labs = [], []
-            try:
-                while True:
-                    try:
-                        features, labels = loader.fetch()
-                    except DataOutOfRange:
-                        break
-                    self._ensure_capacity(features.shape[0], features.shape[1])
-                    self.engine.forward(features, False)
-                    embs.append(self.engine.endpoint("output").cpu().numpy())
-                    labs.append(np.asarray(labels))
-            finally:
-                loader.stop()
+
+            def keep_embeddings(features, labels):
+                embs.append(self.engine.endpoint("output").cpu().numpy())
+                labs.append(np.asarray(labels))
+            self._inference_pass(KaldiDataSeqQueue(data, spklist, batch_size=bsz, shuffle=False, **common), keep_embeddings)
             if embs:
                 embeddings_val, labels_val = np.concatenate(embs, 0), np.concatenate(labs, 0)
         if batch_type == "end2end":
-            loader = KaldiDataRandomQueue(data, spklist, num_parallel=2, max_qsize=10, num_speakers=p.num_valid_speakers_per_batch,
-                                          num_segments=p.num_valid_segments_per_speaker, min_len=p.min_segment_len, max_len=p.max_segment_len,
-                                          shuffle=True)
+            loader = KaldiDataRandomQueue(data, spklist, num_speakers=p.num_valid_speakers_per_batch,
+                                          num_segments=p.num_valid_segments_per_speaker, shuffle=True, **common)
         else:
-            loader = KaldiDataSeqQueue(data, spklist, num_parallel=2, max_qsize=10, batch_size=bsz,
-                                       min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=True)
+            loader = KaldiDataSeqQueue(data, spklist, batch_size=bsz, shuffle=True, **common)
+        losses = []
+
+        def keep_loss(features, labels):
+            self.engine.loss(labels, curr_step, with_margin=False)
+            self._last_valid_labels = np.asarray(labels)
+            self._last_valid_features = features          # (the batch a test restates; a reference to what the loader returned)
+            losses.append(self.engine.raw_loss())
+        self._inference_pass(loader, keep_loss, int(p.valid_max_iterations))
+        total, num_batches = sum(losses, 0.0), len(losses)
+        loss = total / max(num_batches, 1)
+        log.info("[Validation %d batches] valid loss: %f" % (num_batches, loss))
+        return loss, embeddings_val, labels_val
+
+    def _inference_pass(self, loader, each, limit=None):
+        """each(features, labels) after an inference forward of every batch the loader gives - at most `limit`, else until it runs out;
+        the loader is started here and stopped here, whatever happens."""
         loader.start()
-        total, num_batches = 0.0, 0
         try:
-            for _ in range(int(p.valid_max_iterations)):
+            n = 0
+            while limit is None or n < limit:
                 try:
                     features, labels = loader.fetch()
                 except DataOutOfRange:
                     break
                 self._ensure_capacity(features.shape[0], features.shape[1])
                 self.engine.forward(features, False)
-                self.engine.loss(labels, curr_step, with_margin=False)
-                self._last_valid_labels = np.asarray(labels)
-                self._last_valid_features = features          # (the batch a test restates; a reference to what the loader returned)
-                total += self.engine.raw_loss()
-                num_batches += 1
+                each(features, labels)
+                n += 1
         finally:
             loader.stop()
-        loss = total / max(num_batches, 1)
-        log.info("[Validation %d batches] valid loss: %f" % (num_batches, loss))
-        return loss, embeddings_val, labels_val
 
     def _ensure_loaded(self):
         if not self.is_loaded:
@@ -539,10 +525,7 @@ class Trainer(object):
         self.engine.init_variables(seed=int(p.dict.get("seed", 0)))
         if os.path.isfile(os.path.join(self.model, "checkpoint")):
             self.load()
-        queue_cls = PlannedRandomQueue if os.environ.get("XV_LOADER", "native") == "python" else KaldiDataRandomQueue
-        loader = queue_cls(data, spklist, num_parallel=p.num_parallel_datasets, max_qsize=p.max_queue_size,
-                           num_speakers=p.num_speakers_per_batch, num_segments=p.num_segments_per_speaker,
-                           min_len=p.min_segment_len, max_len=p.max_segment_len, shuffle=True)
+        loader = self._training_queue(data, spklist)      # never the packed form: this loop fetches host batches
         loader.start()
         init_learning_rate, factor = 1e-5, 1.15
         os.makedirs(self.model, exist_ok=True)

@@ -11,10 +11,12 @@ import ctypes as C
 import torch
 
 try:
+    from . import kinds
     from ._host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
     from .pipeline_ops import *       # noqa: F401,F403 (its public names are the pipeline ops)
     from .wave_ops import *           # noqa: F401,F403 (and those of the ops that take PCM)
 except ImportError:
+    import kinds
     from _host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
     from pipeline_ops import *        # noqa: F401,F403
     from wave_ops import *            # noqa: F401,F403
@@ -424,14 +426,9 @@ def margin_softmax_rows(kind, logits, n, x, labels, m, lam):
 def pair_loss_config(loss_func, margin=0.0, squared=False, triplet_type="all", loss_type="additive_margin_softmax", valid_speakers=0,
                      valid_segments=0):
     """The xv_pair_loss_config of "semihard_triplet_loss" / "angular_triplet_loss" with the reference's option names (loss.py:376-377, 509-511)."""
-    if loss_func not in _lib.PAIR_KINDS:
-        raise NotImplementedError("Not implement %s loss" % loss_func)
-    if loss_func == "angular_triplet_loss":
-        assert triplet_type == "all" or triplet_type == "hard"
-        assert loss_type in ["asoftmax", "additive_margin_softmax", "additive_angular_margin_softmax"]
-        if loss_type == "asoftmax" and int(margin) not in (1, 2, 4):
-            raise NotImplementedError("[ERROR] m=%d is not unsupported if asoftmax is selected." % margin)
-    return _lib.XvPairLossConfig(kind=_lib.PAIR_KINDS[loss_func], squared=int(bool(squared)), triplet_type=_lib.TRIPLET_TYPES.get(triplet_type, 0),
+    head = kinds.loss(loss_func, kinds.PAIR)
+    head.check(margin, triplet_type, loss_type)      # what the kind refuses of these options (kinds.py)
+    return _lib.XvPairLossConfig(kind=head.pair_code, squared=int(bool(squared)), triplet_type=_lib.TRIPLET_TYPES.get(triplet_type, 0),
                                  margin_kind=_lib.LOSS_KINDS.get(loss_type, 2), margin=float(margin), valid_speakers=int(valid_speakers),
                                  valid_segments=int(valid_segments))
 
