@@ -464,6 +464,13 @@ int xv_score_cohort_stats(void* stream, const float* x, int ldx, int rows, const
  * (ops.score_normalize checks the host arrays before the upload). */
 int xv_score_normalize(void* stream, const float* scores, const int32_t* ei, const int32_t* ti, int64_t m, const float* e_stats,
                        const float* t_stats, float* out);
+/* score_dense (the all-pairs matrix of one recording's prepared rows, for the clusterer below): out[i][j] = sum_c x[i][c] * x[j][c],
+ * i, j < n, on rows x [n][ldx] prepared by xv_score_prepare or by the back end's unit chain.  One launch of the fp32 GEMM of
+ * score_cohort_stats (the rows on both sides, K = d rounded up to 4: columns d .. K are read and must be zero, pitch a multiple of 4,
+ * 16-byte aligned base, below 4 GB - the GEMM refuses by name), written straight into out [n][ldo]: ldo >= n, any alignment, so out may be
+ * a view into a packed buffer of many recordings; columns n .. ldo are not written.  out[i][j] and out[j][i] come from different lanes of
+ * the GEMM's tile and are not promised to be the same bits: xv_ahc_cluster reads the upper triangle only. */
+int xv_score_dense(void* stream, const float* x, int ldx, int n, int d, float* out, int ldo);
 
 /* The LDA / PLDA back end behind extraction, device side: what ivector-mean (with and without spk2utt), ivector-compute-lda,
  * ivector-compute-plda, ivector-subtract-global-mean and ivector-plda-scoring --normalize-length=true do on the embedding tables
@@ -530,6 +537,42 @@ size_t xv_backend_plda_cohort_workspace_bytes(int rows, int n_cohort, int d, int
 int xv_backend_plda_cohort_stats(void* stream, const float* x, int ldx, int rows, const int32_t* nidx, const float* cohort, int ldc,
                                  int n_cohort, int d, const float* coef, int ldcoef, int n_distinct, const float* g, const float* k0,
                                  int top_k, float* stats, void* ws, size_t ws_bytes);
+/* plda_dense (ivector-plda-scoring-dense without its per-recording PCA: the all-pairs matrix of one recording, for the clusterer below):
+ * out[r][j] = the one-utterance log-likelihood ratio of rows r and j of x [n][ldx] (PLDA-normalised with one utterance), in the factored
+ * form of plda_cohort_stats with the single table entry of n_utts = 1 (coef [2][ldk], g, k0 [1]): out[r][j] = (slab[r][j] + C[j]) + R[r].
+ * The column-term and fold kernels and the GEMM are plda_cohort_stats' (the rows are their own cohort); the GEMM writes the slab into out
+ * and one small kernel adds the two terms in place, so the error budget of an element is plda_cohort_stats'.  out [n][ldo]: ldo >= n, any
+ * alignment (a view into a packed buffer); columns n .. ldo are not written.  The result is not bit-symmetric (the GEMM's operands differ
+ * by the fold; the two adds are taken in the order above): xv_ahc_cluster reads the upper triangle only.  ws, in floats: [P] column terms,
+ * [n][K] folded rows, [n] row terms, P = n and K = d rounded up to 4; xv_backend_plda_dense_workspace_bytes(n, d) bytes, 16-byte aligned -
+ * fewer is refused, as are n <= 0, d <= 0, ldx below K, ldk below d, ldo below n and what the GEMM refuses. */
+size_t xv_backend_plda_dense_workspace_bytes(int n, int d);
+int xv_backend_plda_dense(void* stream, const float* x, int ldx, int n, int d, const float* coef, int ldk, const float* g, const float* k0,
+                          float* out, int ldo, void* ws, size_t ws_bytes);
+
+/* Agglomerative clustering of score matrices, average linkage on scores (speaker diarization: agglomerative-cluster of Kaldi's
+ * callhome_diarization recipes, restated - agreement with a Kaldi run is not pinned).  b recordings per call, one workgroup each, no
+ * hand-over between workgroups: a recording's result depends on its own matrix only and is the same bits every time.
+ * Inputs, all on the device: scores, a packed fp32 buffer of scores_floats floats; recording r's matrix [n[r]][ld[r]] starts at float
+ * mat_offsets[r] (int64) and only its upper triangle s[i][j], i < j, is read; it is not modified.  targets[r] = 0: stop by threshold;
+ * t >= 1: stop at t clusters and ignore the threshold.
+ * The arithmetic is part of the operation - a float32 restatement gives the same bits (tests/ahc_ref.py):
+ *   clusters start as the singletons 0 .. n - 1, T[i][j] = T[j][i] = s[min(i,j)][max(i,j)], A(a, b) = T[a][b] / (float)(size_a * size_b)
+ *   (one correctly rounded fp32 divide).  Step: among the active pairs a < b the largest A, on a tie the lowest a, then the lowest b.
+ *   Stop if the cluster count equals max(target, 1); with target = 0 stop unless A >= threshold.  Merge: b goes into a - for every other
+ *   active k, T[a][k] = T[k][a] = T[a][k] + T[b][k] (one fp32 add), then size_a += size_b and b is inactive; (a, b, A) is logged.
+ * A cluster's id is its smallest member; labels number the final clusters 0, 1, ... in ascending id.  A NaN score is undefined.
+ * Outputs: labels int32 [total_n], recording r's at the exclusive prefix of n; merges int32 [total_n - b][2] and merge_values fp32
+ * [total_n - b], recording r's log at the exclusive prefix of n - 1, of which the first n_merges[r] entries are written; n_merges int32 [b].
+ * total_n = sum n, sum_n2 = sum n^2, max_n = the largest n: host values the caller states.  ws: xv_ahc_workspace_bytes(sum_n2) bytes (T
+ * of every recording, full symmetric storage).  Refused by name: b <= 0, max_n < 1, max_n > 2048 (longer recordings want Kaldi's two-pass
+ * clustering: not here), totals that do not fit, a workspace too small.  The device arrays are NOT checked on the host side of this call
+ * (ops.ahc_cluster checks the host arrays before the upload: n in 1 .. 2048, ld >= n, 0 <= target <= n, every matrix inside the buffer); a
+ * recording whose entries would take the kernel outside the buffers of the call is skipped and gets n_merges = -1. */
+size_t xv_ahc_workspace_bytes(int64_t sum_n2);
+int xv_ahc_cluster(void* stream, const float* scores, int64_t scores_floats, const int64_t* mat_offsets, const int32_t* n, const int32_t* ld,
+                   const int32_t* targets, int b, int max_n, int64_t total_n, int64_t sum_n2, float threshold, int32_t* labels,
+                   int32_t* merges, float* merge_values, int32_t* n_merges, void* ws, size_t ws_bytes);
 
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);

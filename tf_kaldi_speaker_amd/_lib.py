@@ -304,6 +304,7 @@ SIGNATURES = {
     "xv_score_cohort_workspace_bytes": (_SZ, [_I, _I, _I]),
     "xv_score_cohort_stats": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _SZ]),
     "xv_score_normalize": (_I, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
+    "xv_score_dense": (_I, [_VP, _VP, _I, _I, _I, _VP, _I]),
     "xv_backend_group_means": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I, C.c_int64, _VP, _VP, _I]),
     "xv_backend_center": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _I]),
     "xv_backend_scatter_workspace_bytes": (_SZ, [_I, _I]),
@@ -312,6 +313,10 @@ SIGNATURES = {
     "xv_backend_plda_trials": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _VP, _VP, C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "xv_backend_plda_cohort_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "xv_backend_plda_cohort_stats": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _SZ]),
+    "xv_backend_plda_dense_workspace_bytes": (_SZ, [_I, _I]),
+    "xv_backend_plda_dense": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _I, _VP, _SZ]),
+    "xv_ahc_workspace_bytes": (_SZ, [C.c_int64]),
+    "xv_ahc_cluster": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, C.c_int64, C.c_int64, _F, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "xv_add_norm_grad": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "xv_segment_gemm": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, _VP, C.c_long, _VP, C.c_long, _VP, _SZ, _VP]),
     "xv_segment_affine_bn_forward": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, _F, _F, _I, _VP, _VP, _VP, _VP, _VP,

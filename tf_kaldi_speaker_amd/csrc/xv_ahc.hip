@@ -1,0 +1,269 @@
+// Agglomerative clustering of score matrices (speaker diarization: Kaldi's agglomerative-cluster behind ivector-plda-scoring-dense, as
+// callhome_diarization/v2 runs it): average linkage on scores, one workgroup per recording, the recordings of a call side by side.
+// Synchronisation is __syncthreads only - no grid-wide barrier, no wait on another workgroup, no atomics - so one recording cannot
+// stall another, and a result depends on the recording's matrix alone: the same bits every time.  gfx950 only.
+//
+// The arithmetic is fixed to the operation (include/xvector_hip.h states it; tests/ahc_ref.py restates it in NumPy and the GPU's merge
+// log is bit-equal to that at float32):
+//     T[i][j] = T[j][i] = s[min(i,j)][max(i,j)];   A(a, b) = T[a][b] / (float)(size_a * size_b)        one IEEE fp32 divide
+//     step:  the largest A over active pairs a < b, ties to the lowest a, then the lowest b
+//     merge: T[a][k] = T[k][a] = T[a][k] + T[b][k] for every other active k (one fp32 add), size_a += size_b, b leaves
+// (size_a * size_b <= 1024^2 < 2^24 is exact in fp32.)
+//
+// State.  T lies in the workspace in full symmetric storage, pitch n, so that every read of the loop is a coalesced read along a row;
+// the price is the n strided 4-byte stores of a merge (T[k][a]).  In LDS, for the cap of 2048 rows: size[] (0 = inactive), per row k
+// the best pair of the row, bv[k] = max over active c > k of A(k, c) and bc[k] = its lowest column (-1: none), parent[] (the merge
+// forest, read once at the end for the labels) and the repair lists - 40 KB of the 64 KB a workgroup gets by default.
+//
+// A step: (1) argmax over the n row bests (each thread its rows k = tid, tid + 256, ..., a butterfly per wave, four partials in LDS);
+// (2) the row update: thread of column k adds T[b][k] into T[a][k] and T[k][a]; a row k < a whose best names neither a nor b compares
+// the new A(k, a) with its best - nothing else in that row moved; a row k < b whose best named a or b goes on its wave's repair list
+// (ballot + popcount: the list slot needs no atomic); (3) one wave per listed row, and one for row a, rescans that row of T.  Rows
+// above b hold no pair with a or b and are not touched.
+// Worst case of a step: n row bests, 2 n coalesced loads and n + n stores for the update, and (1 + r) row scans of at most n elements
+// (one divide each), r = the rows below b whose best named a or b.  r < n, so an adversarial matrix (every row's best in one column) makes
+// a step read n^2 / 2 elements; on scores of clustered embeddings r stays a handful, and a step is O(n) work behind four barriers.
+// A recording takes at most n - 1 steps.  No rate is claimed here: profiles/ahc_bench.txt holds what was measured.
+//
+// A NaN score is undefined behaviour of the operation (every comparison with it is false); it is not checked.
+#include "xv_common.h"
+#include "xv_ew.h"
+
+#define AHC_MAX_N 2048
+#define AHC_THREADS 256
+#define AHC_WAVES (AHC_THREADS / XV_WAVE)
+#define AHC_COLS (AHC_MAX_N / AHC_THREADS)      // columns a thread owns at the cap
+#define AHC_SCAN_UNROLL 4
+
+// (v, i) beats (w, j): the larger value, on a tie the lower index; an index below 0 is "nothing yet"
+__device__ __forceinline__ bool ahc_better(float v, int i, float w, int j) { return i >= 0 && (j < 0 || v > w || (v == w && i < j)); }
+
+// the best (value, index) of the wave, in every lane: indices differ between lanes (or are < 0), so the order of the exchanges is immaterial
+__device__ __forceinline__ void ahc_wave_best(float& v, int& i) {
+#pragma unroll
+    for (int off = XV_WAVE / 2; off; off >>= 1) {
+        const float w = __shfl_xor(v, off);
+        const int j = __shfl_xor(i, off);
+        if (ahc_better(w, j, v, i)) { v = w; i = j; }
+    }
+}
+
+// row k's best pair over the active columns c > k, by one wave; a lane walks its columns upwards, so `>` keeps the lowest on a tie
+__device__ __forceinline__ void ahc_scan_row(const float* row, int k, int n, const int* size, float* bv, int* bc, int lane) {
+    const int sk = size[k];
+    float v = 0.f;
+    int best = -1;
+    // four loads in flight per lane, issued whatever the columns' activity (a load behind the test would wait out its latency alone)
+    for (int c0 = k + 1 + lane; c0 < n; c0 += AHC_SCAN_UNROLL * XV_WAVE) {
+        float t[AHC_SCAN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AHC_SCAN_UNROLL; ++u) {
+            const int c = c0 + u * XV_WAVE;
+            t[u] = c < n ? row[c] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < AHC_SCAN_UNROLL; ++u) {
+            const int c = c0 + u * XV_WAVE;
+            const int sc = c < n ? size[c] : 0;
+            if (sc > 0) {
+                const float a = t[u] / (float)(sk * sc);
+                if (best < 0 || a > v) { v = a; best = c; }
+            }
+        }
+    }
+    ahc_wave_best(v, best);
+    if (lane == 0) { bv[k] = v; bc[k] = best; }
+}
+
+struct AhcArgs {
+    const float* scores; long scores_floats;
+    const int64_t* mat_offsets; const int32_t* n; const int32_t* ld; const int32_t* targets;
+    long total_n; long sum_n2; float threshold;
+    int32_t* labels; int32_t* merges; float* merge_values; int32_t* n_merges;
+    float* ws;
+};
+
+__global__ __launch_bounds__(AHC_THREADS) void ahc_cluster_kernel(AhcArgs g) {
+    XV_EW_PRIORITY();
+    __shared__ int size[AHC_MAX_N];
+    __shared__ float bv[AHC_MAX_N];
+    __shared__ int bc[AHC_MAX_N];
+    __shared__ int parent[AHC_MAX_N];
+    __shared__ int list[AHC_WAVES][AHC_MAX_N / AHC_WAVES];
+    __shared__ int lcount[AHC_WAVES];
+    __shared__ float red_v[AHC_WAVES];
+    __shared__ int red_i[AHC_WAVES];
+    __shared__ long red_n[AHC_WAVES], red_t[AHC_WAVES];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & (XV_WAVE - 1), w = tid / XV_WAVE;
+
+    // where this recording's outputs and its T start: the exclusive prefixes of n and n^2 over the recordings before it.  (A count is
+    // clamped into 1 .. the cap here and this recording's spans are checked against the totals below, so that even arrays the caller
+    // got wrong - it guarantees them, ops.ahc_cluster checks them - cannot take a store outside the buffers of the call.)
+    long pn = 0, pt = 0;
+    for (int i = tid; i < r; i += AHC_THREADS) {
+        const long ni = min(max(g.n[i], 1), AHC_MAX_N);
+        pn += ni;
+        pt += ni * ni;
+    }
+#pragma unroll
+    for (int off = XV_WAVE / 2; off; off >>= 1) {
+        pn += __shfl_xor(pn, off);
+        pt += __shfl_xor(pt, off);
+    }
+    if (lane == 0) { red_n[w] = pn; red_t[w] = pt; }
+    __syncthreads();
+    pn = pt = 0;
+#pragma unroll
+    for (int i = 0; i < AHC_WAVES; ++i) { pn += red_n[i]; pt += red_t[i]; }
+    const long pm = pn - r;      // the merges before this recording: sum of (n - 1)
+    const int n = g.n[r], ld = g.ld[r], target = g.targets[r];
+    const long s0 = g.mat_offsets[r];
+    if (n < 1 || n > AHC_MAX_N || ld < n || target < 0 || target > n || pn + n > g.total_n || pt + (long)n * n > g.sum_n2 || s0 < 0 ||
+        s0 + (long)(n - 1) * ld + n > g.scores_floats) {
+        if (tid == 0) g.n_merges[r] = -1;
+        return;
+    }
+    const float* __restrict__ S = g.scores + s0;
+    float* T = g.ws + pt;
+
+    // T from the upper triangle: row i of s is read along the row, T[i][j] stored along the row and T[j][i] down the column
+    // (a thread's loads of a row are issued together, ahead of their stores: AHC_COLS in flight)
+    for (int i = 0; i < n; ++i) {
+        float t[AHC_COLS];
+#pragma unroll
+        for (int u = 0; u < AHC_COLS; ++u) {
+            const int j = i + tid + u * AHC_THREADS;
+            t[u] = j < n && j != i ? S[(long)i * ld + j] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < AHC_COLS; ++u) {
+            const int j = i + tid + u * AHC_THREADS;
+            if (j < n) {
+                T[(long)i * n + j] = t[u];
+                T[(long)j * n + i] = t[u];
+            }
+        }
+    }
+    for (int k = tid; k < n; k += AHC_THREADS) { size[k] = 1; parent[k] = k; }
+    __syncthreads();
+    for (int k = w; k < n; k += AHC_WAVES) ahc_scan_row(T + (long)k * n, k, n, size, bv, bc, lane);
+    __syncthreads();
+
+    const int stop_at = target > 1 ? target : 1;
+    int count = n, nm = 0;
+    while (count > stop_at) {
+        // (1) the best pair: rows walked upwards by a thread, so its own ties go to the lowest row already
+        float v = 0.f;
+        int a = -1;
+        for (int k = tid; k < n; k += AHC_THREADS)
+            if (size[k] > 0 && bc[k] >= 0 && ahc_better(bv[k], k, v, a)) { v = bv[k]; a = k; }
+        ahc_wave_best(v, a);
+        if (lane == 0) { red_v[w] = v; red_i[w] = a; }
+        __syncthreads();
+        v = red_v[0]; a = red_i[0];
+#pragma unroll
+        for (int i = 1; i < AHC_WAVES; ++i)
+            if (ahc_better(red_v[i], red_i[i], v, a)) { v = red_v[i]; a = red_i[i]; }
+        if (a < 0) break;                                   // (cannot happen with count >= 2; uniform)
+        if (target == 0 && !(v >= g.threshold)) break;      // uniform: every thread holds the same (v, a)
+        const int b = bc[a], sa = size[a], sb = size[b], sab = sa + sb;
+        if (tid == 0) {
+            g.merges[2 * (pm + nm)] = a;
+            g.merges[2 * (pm + nm) + 1] = b;
+            g.merge_values[pm + nm] = v;
+        }
+        ++nm;
+        // (2) b into a
+        float* Ta = T + (long)a * n;
+        const float* Tb = T + (long)b * n;
+        int cnt = 0;
+        // both rows first, every column a thread owns in flight together; the adds and the stores follow
+        float ra[AHC_COLS], rb[AHC_COLS];
+#pragma unroll
+        for (int u = 0; u < AHC_COLS; ++u) {
+            const int k = u * AHC_THREADS + tid;
+            ra[u] = k < n ? Ta[k] : 0.f;
+            rb[u] = k < n ? Tb[k] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < AHC_COLS; ++u) {
+            if (u * AHC_THREADS >= n) break;      // (uniform: the ballot below is taken by whole waves)
+            const int k = u * AHC_THREADS + tid;
+            bool need = false;
+            if (k < n && k != a && k != b) {
+                const int sk = size[k];
+                if (sk > 0) {
+                    const float t = ra[u] + rb[u];
+                    Ta[k] = t;
+                    T[(long)k * n + a] = t;
+                    if (k < b) {
+                        const int c = bc[k];
+                        if (c == a || c == b) {
+                            need = true;
+                        } else if (k < a) {
+                            const float cand = t / (float)(sab * sk);
+                            if (cand > bv[k] || (cand == bv[k] && a < c)) { bv[k] = cand; bc[k] = a; }
+                        }
+                    }
+                }
+            }
+            const unsigned long long m = __ballot(need);
+            if (need) list[w][cnt + __popcll(m & ((1ull << lane) - 1ull))] = k;
+            cnt += __popcll(m);
+        }
+        if (lane == 0) lcount[w] = cnt;
+        __syncthreads();      // every thread has read size[a], size[b]; T's row a and the lists are complete
+        if (tid == 0) { size[a] = sab; size[b] = 0; bc[b] = -1; parent[b] = a; }
+        __syncthreads();
+        // (3) the rows whose best is gone, and row a
+        int total = 0;
+#pragma unroll
+        for (int i = 0; i < AHC_WAVES; ++i) total += lcount[i];
+        for (int i = w; i <= total; i += AHC_WAVES) {
+            int k = a;
+            if (i < total) {
+                int q = i, l = 0;
+                while (q >= lcount[l]) { q -= lcount[l]; ++l; }
+                k = list[l][q];
+            }
+            ahc_scan_row(T + (long)k * n, k, n, size, bv, bc, lane);
+        }
+        __syncthreads();
+        --count;
+    }
+    if (tid == 0) g.n_merges[r] = nm;
+    // labels: a cluster's id is its smallest member - the root of the merge forest, since b > a always joins a; the final clusters are
+    // numbered in ascending id
+    for (int m = tid; m < n; m += AHC_THREADS) {
+        int root = m;
+        while (size[root] == 0) root = parent[root];
+        int label = 0;
+        for (int c = 0; c < root; ++c) label += size[c] > 0 ? 1 : 0;
+        g.labels[pn + m] = label;
+    }
+}
+
+extern "C" size_t xv_ahc_workspace_bytes(int64_t sum_n2) { return (size_t)(sum_n2 > 0 ? sum_n2 : 0) * sizeof(float); }
+
+extern "C" int xv_ahc_cluster(void* stream, const float* scores, int64_t scores_floats, const int64_t* mat_offsets, const int32_t* n,
+                              const int32_t* ld, const int32_t* targets, int b, int max_n, int64_t total_n, int64_t sum_n2, float threshold,
+                              int32_t* labels, int32_t* merges, float* merge_values, int32_t* n_merges, void* ws, size_t ws_bytes) {
+    XV_REQUIRE(b > 0, "ahc_cluster: no recording in the call (b=%d)", b);
+    XV_REQUIRE(max_n >= 1, "ahc_cluster: a recording needs at least one row (largest n=%d)", max_n);
+    XV_REQUIRE(max_n <= AHC_MAX_N, "ahc_cluster: a recording of %d rows exceeds the cap of %d", max_n, AHC_MAX_N);
+    XV_REQUIRE(scores && mat_offsets && n && ld && targets && labels && n_merges && scores_floats > 0, "ahc_cluster: bad arguments");
+    XV_REQUIRE(total_n >= b && total_n <= (int64_t)b * max_n && sum_n2 >= total_n && sum_n2 <= total_n * max_n,
+               "ahc_cluster: total_n / sum_n2 do not fit b recordings of at most %d rows", max_n);
+    XV_REQUIRE(total_n == b || (merges && merge_values), "ahc_cluster: merges and merge_values are needed (some recording has two rows or more)");
+    XV_REQUIRE(ws && ws_bytes / sizeof(float) >= (size_t)sum_n2, "ahc_cluster: workspace of %zu bytes, %zu needed", ws_bytes,
+               (size_t)sum_n2 * sizeof(float));
+    AhcArgs g;
+    g.scores = scores; g.scores_floats = (long)scores_floats;
+    g.mat_offsets = mat_offsets; g.n = n; g.ld = ld; g.targets = targets;
+    g.total_n = (long)total_n; g.sum_n2 = (long)sum_n2; g.threshold = threshold;
+    g.labels = labels; g.merges = merges; g.merge_values = merge_values; g.n_merges = n_merges;
+    g.ws = (float*)ws;
+    hipLaunchKernelGGL(ahc_cluster_kernel, dim3(b), dim3(AHC_THREADS), 0, (hipStream_t)stream, g);
+    XV_LAUNCH_CHECK();
+    return 0;
+}

@@ -191,3 +191,63 @@ extern "C" int xv_backend_plda_cohort_stats(void* stream, const float* x, int ld
     }
     return 0;
 }
+
+// ---- the dense matrix of one recording (xv_backend_plda_dense): the same factored ratio, every pair written instead of selected ----
+
+// out[r][j] = (out[r][j] + ct[j]) + rt[r] in place over the GEMM's sums: PcRow::load1's expression with the single table entry.  One
+// thread per element, a row of workgroups per matrix row; out's pitch and base are the caller's (a view into a packed buffer), so the
+// accesses are single floats.
+__global__ __launch_bounds__(256) void plda_dense_finish_kernel(float* out, long ldo, int n, const float* __restrict__ ct, const float* __restrict__ rterm) {
+    XV_EW_PRIORITY();
+    const int j = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (j >= n) return;
+    float* o = out + (long)r * ldo + j;
+    *o = (*o + ct[j]) + rterm[r];
+}
+
+// Workspace, in floats: [ct: pitch][xs: n x kd][rterm: n], pitch = n rounded up to 4 - every part starts on a 16-byte boundary.
+extern "C" size_t xv_backend_plda_dense_workspace_bytes(int n, int d) {
+    const size_t rows = n > 0 ? n : 1;
+    return (sc_slab_pitch((int)rows) + rows * xv_align(d > 0 ? d : 1, 4) + xv_align(rows, 4)) * sizeof(float);
+}
+
+extern "C" int xv_backend_plda_dense(void* stream, const float* x, int ldx, int n, int d, const float* coef, int ldk, const float* g, const float* k0,
+                                     float* out, int ldo, void* ws, size_t ws_bytes) {
+    XV_REQUIRE(n > 0, "backend_plda_dense: n must be positive (got %d)", n);
+    XV_REQUIRE(d > 0, "backend_plda_dense: d must be positive (got %d)", d);
+    XV_REQUIRE(x && coef && g && k0 && out, "backend_plda_dense: bad arguments");
+    const int kd = (int)xv_align(d, 4);      // the GEMM's K: columns d .. kd of the rows are read (plda_normalize wrote them as zero)
+    XV_REQUIRE(ldx >= kd, "backend_plda_dense: the pitch must reach d rounded up to 4 (d=%d ldx=%d)", d, ldx);
+    XV_REQUIRE(ldk >= d, "backend_plda_dense: the pitch of coef is below d (d=%d ldk=%d)", d, ldk);
+    XV_REQUIRE(ldo >= n, "backend_plda_dense: the pitch of out is below n (n=%d ldo=%d)", n, ldo);
+    XV_REQUIRE(ldx % 4 == 0 && sc_aligned16(x), "backend_plda_dense: the rows must be a GEMM operand (pitch a multiple of 4, 16-byte aligned; ldx=%d)", ldx);
+    XV_REQUIRE(n <= 65535, "backend_plda_dense: too many rows in one call (%d)", n);
+    XV_REQUIRE(ws && sc_aligned16(ws) && ws_bytes >= xv_backend_plda_dense_workspace_bytes(n, d),
+               "backend_plda_dense: workspace of %zu bytes, %zu needed (16-byte aligned)", ws_bytes, xv_backend_plda_dense_workspace_bytes(n, d));
+    XV_REQUIRE(!sc_overlap(x, (size_t)(n - 1) * ldx + kd, out, (size_t)(n - 1) * ldo + n), "backend_plda_dense: x and out overlap");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t pitch = sc_slab_pitch(n);
+    float* ct = (float*)ws;
+    float* xs = ct + pitch;
+    float* rterm = xs + (size_t)n * kd;
+    const dim3 block(256), rgrid(xv_cdiv(n, SC_ROWS_PER_WG));
+    // the column terms and the fold of plda_cohort_stats with n_distinct = 1 and the rows as their own cohort
+    const bool vec = d % 4 == 0 && ldk % 4 == 0 && sc_aligned16(coef) && sc_aligned16(g);
+    if (vec) hipLaunchKernelGGL(plda_cohort_colterm_kernel<true>, rgrid, block, 0, s, x, (long)ldx, n, d, coef, (long)ldk, 1, g, ct, (long)pitch);
+    else hipLaunchKernelGGL(plda_cohort_colterm_kernel<false>, rgrid, block, 0, s, x, (long)ldx, n, d, coef, (long)ldk, 1, g, ct, (long)pitch);
+    XV_LAUNCH_CHECK();
+    const bool vec_x = d % 4 == 0 && ldk % 4 == 0 && sc_aligned16(coef);
+    if (vec_x) hipLaunchKernelGGL(plda_cohort_fold_kernel<true>, rgrid, block, 0, s, x, (long)ldx, n, d, (const int*)nullptr, coef, (long)ldk, k0, xs, kd, rterm);
+    else hipLaunchKernelGGL(plda_cohort_fold_kernel<false>, rgrid, block, 0, s, x, (long)ldx, n, d, (const int*)nullptr, coef, (long)ldk, k0, xs, kd, rterm);
+    XV_LAUNCH_CHECK();
+    XvGemmNT gm = {};
+    gm.A = xs; gm.lda = kd; gm.a_rps = 1; gm.a_pitch = 1;
+    gm.Bt = x; gm.ldb = ldx;
+    gm.C = out; gm.ldc = ldo;
+    gm.M = n; gm.N = n; gm.K = kd;
+    const int rc = xv_launch_gemm_nt(s, gm);
+    if (rc) return rc;
+    hipLaunchKernelGGL(plda_dense_finish_kernel, dim3(xv_cdiv(n, 256), n), block, 0, s, out, (long)ldo, n, (const float*)ct, (const float*)rterm);
+    XV_LAUNCH_CHECK();
+    return 0;
+}

@@ -156,6 +156,21 @@ extern "C" int xv_score_cohort_stats(void* stream, const float* x, int ldx, int 
     return 0;
 }
 
+extern "C" int xv_score_dense(void* stream, const float* x, int ldx, int n, int d, float* out, int ldo) {
+    XV_REQUIRE(x && out && n > 0 && d > 0, "score_dense: bad arguments");
+    const int kd = (int)xv_align(d, 4);      // the GEMM's K: columns d .. kd of the rows are read (score_prepare wrote them as zero)
+    XV_REQUIRE(ldx >= kd, "score_dense: the pitch must reach d rounded up to 4 (d=%d ldx=%d)", d, ldx);
+    XV_REQUIRE(ldo >= n, "score_dense: the pitch of out is below n (n=%d ldo=%d)", n, ldo);
+    XV_REQUIRE(!sc_overlap(x, (size_t)(n - 1) * ldx + kd, out, (size_t)(n - 1) * ldo + n), "score_dense: x and out overlap");
+    // xv_score_cohort_stats's GEMM with the rows as their own cohort; no scratch: one workgroup per tile
+    XvGemmNT g = {};
+    g.A = x; g.lda = ldx; g.a_rps = 1; g.a_pitch = 1;
+    g.Bt = x; g.ldb = ldx;
+    g.C = out; g.ldc = ldo;
+    g.M = n; g.N = n; g.K = kd;
+    return xv_launch_gemm_nt((hipStream_t)stream, g);
+}
+
 extern "C" int xv_score_normalize(void* stream, const float* scores, const int32_t* ei, const int32_t* ti, int64_t m, const float* e_stats,
                                   const float* t_stats, float* out) {
     XV_REQUIRE(scores && ei && ti && e_stats && t_stats && out && m > 0, "score_normalize: bad arguments");

@@ -397,6 +397,7 @@ class BackendScorer(object):
 
     MODES = ("lda_cos", "plda")
     _cohort, top_k = None, 0      # no cohort until cohort() sets one
+    _dense_tables = None          # the one-utterance coefficient tables on the device, built by the first dense()
 
     def __init__(self, backend, mode="plda", device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
         if mode not in self.MODES:
@@ -447,6 +448,16 @@ class BackendScorer(object):
         if n_utts is not None and len(n_utts) != x.shape[0]:
             raise ValueError("BackendScorer.prepare: n_utts must hold one count per row (%d, got %d)" % (x.shape[0], len(n_utts)))
         return self.chain.run(x, self.mode == "plda", None if n_utts is None else np.asarray(n_utts))
+
+    def dense(self, prepared, out=None):
+        """The score of every pair of the prepared rows (one utterance each), a device float32 [n, n] matrix: the cosine in the lda_cos mode
+        (ops.score_dense), the log-likelihood ratio in the plda mode (ops.backend_plda_dense); no cohort enters.  out: a [n, n] view of any
+        pitch to write - misc/diarization.py hands views into one packed buffer; default a new matrix."""
+        if self.mode == "lda_cos":
+            return self.ops.score_dense(prepared, self.dim, out=out)
+        if self._dense_tables is None:
+            self._dense_tables = tuple(upload(a, np.float32, self.device) for a in plda_coefficients(self.backend.plda["psi"], [1]))
+        return self.ops.backend_plda_dense(prepared, self.dim, *self._dense_tables, out=out)
 
     def score(self, enrol, test, ei, ti, enrol_n=None):
         ei, ti = np.asarray(ei), np.asarray(ti)

@@ -1,0 +1,198 @@
+"""Speaker diarization behind the x-vector network and the scoring back ends (nnet/lib/diarize.py): what Kaldi's callhome_diarization/v2
+recipe does around its x-vectors - sliding sub-segments, all-pairs scores per recording, agglomerative clustering, RTTM - restated;
+nothing is compared with a Kaldi run.
+
+Host side, NumPy only: speech segments from VAD decisions or a `segments` file, the window planner, the turns of an RTTM from clustered
+windows, RTTM files and a plain diarization error rate.  Device side: Diarizer, which takes the windows' embeddings of many recordings
+through a scorer's prepare -> dense into one packed buffer and clusters them in one ops.ahc_cluster call per batch.
+Not here: the per-recording PCA of ivector-plda-scoring-dense, threshold calibration, overlap detection,
+resegmentation, collars / md-eval, recordings of more than 2048 windows.
+"""
+import logging
+
+import numpy as np
+
+_LOG = logging.getLogger("tf_kaldi_speaker_amd")
+DER_FRAME = 0.01      # seconds per frame of der()
+
+
+def speech_segments(vad, min_frames=1):
+    """The maximal runs of voiced frames (vad[i] != 0) of at least min_frames frames -> list of (start, end), end exclusive."""
+    v = np.concatenate([[False], np.asarray(vad) != 0, [False]])
+    edges = np.flatnonzero(v[1:] != v[:-1])
+    return [(int(s), int(e)) for s, e in zip(edges[0::2], edges[1::2]) if e - s >= min_frames]
+
+
+def read_segments(path):
+    """Kaldi `segments` lines `utterance recording start end` (seconds) -> list of (utterance, recording, start, end) in file order.  Blank
+    lines are skipped; a line of another width, or an end that is not behind its start, is refused with its line number."""
+    out = []
+    with open(path, "r") as f:
+        for no, line in enumerate(f, 1):
+            cols = line.split()
+            if not cols:
+                continue
+            if len(cols) not in (4, 5):      # (a fifth column is the channel: ignored)
+                raise ValueError("%s:%d: a segment is `utterance recording start end`, got %d columns" % (path, no, len(cols)))
+            start, end = float(cols[2]), float(cols[3])
+            if not 0.0 <= start < end:
+                raise ValueError("%s:%d: segment %s runs from %g to %g" % (path, no, cols[0], start, end))
+            out.append((cols[0], cols[1], start, end))
+    return out
+
+
+def subsegments(start, end, window, period, min_segment, log=None):
+    """The sliding windows of the segment [start, end), all in frames: window k starts at t_k = start + k * period and is
+    [t_k, min(t_k + window, end)); the first window with t_k + window >= end is the last.  A window shorter than min_segment is kept only
+    if it is the first; a segment shorter than min_segment gives none (a log line says so).  -> list of (start, end)."""
+    start, end, window, period, min_segment = int(start), int(end), int(window), int(period), int(min_segment)
+    if window <= 0 or period <= 0:
+        raise ValueError("subsegments: window and period must be positive (got %d, %d)" % (window, period))
+    if end - start < min_segment or end <= start:
+        (log or _LOG).info("[INFO] Segment %d .. %d: %d frames, fewer than %d, dropped." % (start, end, end - start, min_segment))
+        return []
+    out, t, k = [], start, 0
+    while True:
+        stop = min(t + window, end)
+        if stop - t >= min_segment or k == 0:
+            out.append((t, stop))
+        if t + window >= end:
+            return out
+        t, k = t + period, k + 1
+
+
+def rttm_turns(subsegs, labels):
+    """Speaker turns from clustered windows: subsegs [(start, end)] (any unit), labels one per window.  The windows are sorted by start;
+    where two consecutive windows overlap, the first ends and the second starts at the midpoint of the overlap; then abutting windows of
+    one label are merged.  -> list of (start, end, label)."""
+    if len(subsegs) != len(labels):
+        raise ValueError("rttm_turns: %d windows, %d labels" % (len(subsegs), len(labels)))
+    order = sorted(range(len(subsegs)), key=lambda i: (subsegs[i][0], subsegs[i][1]))
+    cut = [[float(subsegs[i][0]), float(subsegs[i][1]), int(labels[i])] for i in order]
+    for a, b in zip(cut[:-1], cut[1:]):
+        if a[1] > b[0]:
+            a[1] = b[0] = 0.5 * (a[1] + b[0])
+    turns = []
+    for s, e, l in cut:
+        if turns and turns[-1][2] == l and turns[-1][1] == s:
+            turns[-1][1] = e
+        else:
+            turns.append([s, e, l])
+    return [(s, e, l) for s, e, l in turns]
+
+
+def write_rttm(path, turns_by_recording):
+    """`SPEAKER <recording> 0 <start> <duration> <NA> <NA> <label + 1> <NA> <NA>` per turn; turns_by_recording: {recording: [(start, end,
+    label)]} in seconds, written in the mapping's order."""
+    with open(path, "w") as f:
+        for reco, turns in turns_by_recording.items():
+            for s, e, l in turns:
+                f.write("SPEAKER %s 0 %.3f %.3f <NA> <NA> %d <NA> <NA>\n" % (reco, s, e - s, int(l) + 1))
+
+
+def read_rttm(path):
+    """{recording: [(start, end, speaker name)]} of the SPEAKER lines of an RTTM file, in file order; other line types are skipped, a
+    SPEAKER line of fewer than 8 columns is refused with its line number."""
+    out = {}
+    with open(path, "r") as f:
+        for no, line in enumerate(f, 1):
+            cols = line.split()
+            if not cols or cols[0] != "SPEAKER":
+                continue
+            if len(cols) < 8:
+                raise ValueError("%s:%d: a SPEAKER line has at least 8 columns, got %d" % (path, no, len(cols)))
+            start, dur = float(cols[3]), float(cols[4])
+            out.setdefault(cols[1], []).append((start, start + dur, cols[7]))
+    return out
+
+
+def _frame_labels(turns, frames, names):
+    lab = np.full(frames, -1, np.int64)
+    for s, e, l in sorted(turns, key=lambda t: (t[0], t[1])):
+        a, b = int(round(s / DER_FRAME)), int(round(e / DER_FRAME))
+        span = lab[a:b]
+        span[span < 0] = names.setdefault(l, len(names))      # overlapped speech: the first speaker only
+    return lab
+
+
+def der(ref, hyp):
+    """Diarization error of the turns hyp against ref ([(start, end, speaker)] in seconds, one recording) on 10 ms frames, no collar;
+    where turns of one side overlap, the frame goes to the turn that starts first.  The speakers are mapped one to one such that the
+    matched time is largest (scipy.optimize.linear_sum_assignment).  -> (miss, false alarm, confusion, DER), fractions of the reference's
+    speech time."""
+    from scipy.optimize import linear_sum_assignment
+    frames = int(round(max([e for _, e, _ in list(ref) + list(hyp)] or [0.0]) / DER_FRAME))
+    r_names, h_names = {}, {}
+    r, h = _frame_labels(ref, frames, r_names), _frame_labels(hyp, frames, h_names)
+    speech = int((r >= 0).sum())
+    if speech == 0:
+        raise ValueError("der: the reference holds no speech")
+    both = (r >= 0) & (h >= 0)
+    overlap = np.zeros((max(len(r_names), 1), max(len(h_names), 1)), np.int64)
+    np.add.at(overlap, (r[both], h[both]), 1)
+    rows, cols = linear_sum_assignment(-overlap)
+    miss = int(((r >= 0) & (h < 0)).sum())
+    fa = int(((r < 0) & (h >= 0)).sum())
+    conf = int(both.sum()) - int(overlap[rows, cols].sum())
+    return miss / speech, fa / speech, conf / speech, (miss + fa + conf) / speech
+
+
+class Diarizer(object):
+    """Clusters the window embeddings of recordings behind a scorer (CosineScorer, or BackendScorer in either mode).
+
+        diar = Diarizer(scorer, threshold=0.2)                      # merge while the best average score is >= the threshold
+        diar = Diarizer(scorer, reco2num_spk={"rec1": 2, ...})      # or: merge down to the given number of speakers
+        labels = diar.cluster({"rec1": matrix1, ...})               # {recording: int32 labels, one per row}
+
+    cluster() runs prepare -> dense per recording into one packed buffer of score matrices and one ops.ahc_cluster call over them, in
+    batches such that the buffer and the clusterer's scratch of a call stay under the scorer's workspace_bytes."""
+
+    def __init__(self, scorer, threshold=None, reco2num_spk=None):
+        if (threshold is None) == (reco2num_spk is None):
+            raise ValueError("Diarizer: exactly one of threshold and reco2num_spk says when the merging stops")
+        self.scorer, self.threshold, self.reco2num_spk = scorer, threshold, reco2num_spk
+        self.torch, self.ops = scorer.torch, scorer.ops
+
+    def cluster(self, embeddings):
+        """embeddings: {recording: float32 [n, d] matrix} (host or device).  -> {recording: NumPy int32 [n]} in the mapping's order."""
+        keys = list(embeddings)
+        if not keys:
+            return {}
+        try:      # (here, not at load time: the host side of this module needs NumPy only)
+            from .._host import greedy_batches, pitch4
+        except (ImportError, ValueError):
+            from _host import greedy_batches, pitch4
+        n = np.asarray([int(embeddings[k].shape[0]) for k in keys], np.int64)
+        for k, rows in zip(keys, n):
+            if rows < 1 or rows > self.ops.AHC_MAX_N:
+                raise ValueError("Diarizer: recording %s has %d windows, 1 .. %d are taken" % (k, rows, self.ops.AHC_MAX_N))
+        if self.reco2num_spk is not None:
+            missing = [k for k in keys if k not in self.reco2num_spk]
+            if missing:
+                raise ValueError("Diarizer: no number of speakers for recording %s" % missing[0])
+            targets = np.asarray([int(self.reco2num_spk[k]) for k in keys], np.int64)
+            if targets.min() < 1:
+                raise ValueError("Diarizer: recording %s: the number of speakers must be positive" % keys[int(np.argmin(targets))])
+            targets = np.minimum(targets, n)      # (fewer windows than speakers: every window its own cluster)
+        else:
+            targets = np.zeros(len(keys), np.int64)
+        ld = np.asarray([pitch4(int(r)) for r in n], np.int64)
+        cost = 4 * (n * ld + n * n)      # bytes of a recording: its matrix in the packed buffer and the clusterer's copy
+        out = {}
+        batches = greedy_batches(len(keys), lambda i, total=0: (total + int(cost[i]),), lambda total: total, self.scorer.workspace_bytes,
+                                 too_big=lambda i, c: "Diarizer: recording %s needs %d bytes of scores, the workspace holds %d"
+                                 % (keys[i], c, self.scorer.workspace_bytes))
+        for batch in batches:
+            offsets = np.concatenate([[0], np.cumsum(n[batch] * ld[batch])]).astype(np.int64)
+            packed = self.torch.empty(int(offsets[-1]), dtype=self.torch.float32, device=self.scorer.device)
+            for j, i in enumerate(batch):
+                prepared = self.scorer.prepare(embeddings[keys[i]])
+                view = packed[int(offsets[j]):int(offsets[j + 1])].view(int(n[i]), int(ld[i]))[:, :int(n[i])]
+                self.scorer.dense(prepared, out=view)
+            labels = self.ops.ahc_cluster(packed, offsets[:-1], n[batch].astype(np.int32), ld[batch].astype(np.int32),
+                                          threshold=0.0 if self.threshold is None else float(self.threshold),
+                                          targets=targets[batch].astype(np.int32))[0].cpu().numpy()
+            at = np.concatenate([[0], np.cumsum(n[batch])])
+            for j, i in enumerate(batch):
+                out[keys[i]] = labels[at[j]:at[j + 1]]
+        return out

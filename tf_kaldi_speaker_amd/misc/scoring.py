@@ -147,6 +147,11 @@ class CosineScorer(object):
                                                       ws_bytes=self.ops.score_cohort_workspace_bytes(r1 - r0, n_cohort, self.d))
                           for r0, r1 in steps(x.shape[0], step)])
 
+    def dense(self, prepared, out=None):
+        """The cosine of every pair of the prepared rows, a device float32 [n, n] matrix (ops.score_dense; no cohort enters).  out: a
+        [n, n] view of any pitch to write - misc/diarization.py hands views into one packed buffer; default a new matrix."""
+        return self.ops.score_dense(prepared, self.d, out=out)
+
     def score(self, enrol, test, ei, ti):
         ei, ti = np.asarray(ei), np.asarray(ti)
         e_stats = t_stats = None

@@ -100,7 +100,23 @@ ARGUMENTS = {
     "resample_out_dir": (("out_dir",), dict(type=str, help="Receives wav/<key>.wav and wav.scp.")),
     "seed": (("--seed",), dict(type=int, default=0, help="The seed of --make-plan (numpy.random.RandomState).")),
     "fg_interval": (("--fg-interval",), dict(type=float, default=1.0, help="--make-plan noise: seconds between two foreground noises.")),
+    "window": (("--window",), dict(type=float, default=1.5, help="Length in seconds of the sliding windows an embedding is taken from.")),
+    "period": (("--period",), dict(type=float, default=0.75, help="Seconds between the starts of two windows.")),
+    "min_segment": (("--min-segment",), dict(type=float, default=0.5, help="Speech segments shorter than this many seconds are dropped, and so "
+                                                                           "is a window that is not the first of its segment.")),
+    "segments": (("--segments",), dict(type=str, default="", help="Kaldi segments file (`utterance recording start end`): the speech of every "
+                                                                  "recording.  Not together with --vad; without either a recording is one segment.")),
+    "diar_vad": (("--vad",), dict(type=str, default="", help="ark: or scp: rspecifier of the VAD decisions: the speech segments are their voiced "
+                                                             "runs.  No frame is removed.")),
+    "diar_scoring": (("--scoring",), dict(type=str, default="cosine", choices=("cosine", "lda_cos", "plda"),
+                                          help="The score of two windows: cosine (no back end), the cosine behind --backend's LDA, or its PLDA "
+                                               "log-likelihood ratio.")),
+    "threshold": (("--threshold",), dict(type=float, default=None, help="Merge clusters while their average score is at least this.")),
+    "reco2num_spk": (("--reco2num-spk",), dict(type=str, default="", help="`recording speakers` per line: merge down to that many clusters.")),
+    "write_embeddings": (("--write-embeddings",), dict(type=str, default="", help="Kaldi wspecifier (or ark file) for the windows' embeddings, keyed "
+                                                                                  "`recording-startframe-endframe` (7 digits each).")),
     # positionals
+    "rttm_out": (("rttm_out",), dict(type=str, help="The RTTM file to write.")),
     "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),
     "augment_out_dir": (("out_dir",), dict(type=str, nargs="?", default="", help="Receives wav/<key>.wav and wav.scp (not needed with --make-plan).")),
     "wav_scp": (("wav_scp",), dict(type=str, help="Kaldi wav.scp: `key rxfilename` per line, the rxfilename a RIFF PCM-16 file or `command |`.")),

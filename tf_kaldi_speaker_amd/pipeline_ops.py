@@ -287,3 +287,91 @@ def score_normalize(scores, ei, ti, e_stats, t_stats, out=None):
     ei_d, ti_d = upload(ei, np.int32, scores.device), upload(ti, np.int32, scores.device)
     _lib.call("xv_score_normalize", _s(), _p(scores), _p(ei_d), _p(ti_d), C.c_int64(m), _p(e_stats), _p(t_stats), _p(out))
     return out
+
+
+def _dense_out(name, out, n, device):      # the [n, n] matrix a dense op writes: a new one on the pitch n rounded up to 4, or the caller's view
+    if out is None:
+        return torch.empty((n, pitch4(n)), dtype=torch.float32, device=device)[:, :n]
+    rows, ldo = pitched(out, "%s: out" % name)
+    if tuple(out.shape) != (n, n) or out.device != device:
+        raise ValueError("%s: out must be a float32 [%d, %d] view on the rows' device (its pitch is free)" % (name, n, n))
+    return out
+
+
+def score_dense(x, d, out=None):
+    """out[i][j] = x[i][:d] . x[j][:d] for every pair of the prepared rows x (xv_score_dense: score_cohort_stats' GEMM, the rows as their
+    own cohort).  out: a float32 [n, n] view of any pitch - into a packed buffer of many recordings, say; default a new matrix.  The two
+    triangles are not promised to hold the same bits."""
+    n, ldx = pitched(x, "score_dense: x")
+    out = _dense_out("score_dense", out, n, x.device)
+    _lib.call("xv_score_dense", _s(), _p(x), ldx, n, int(d), _p(out), pitched(out, "score_dense: out")[1])
+    return out
+
+
+def backend_plda_dense_workspace_bytes(n, d):
+    return int(_lib.load().xv_backend_plda_dense_workspace_bytes(int(n), int(d)))
+
+
+def backend_plda_dense(x, d, coef, g, k0, out=None):
+    """out[r][j] = the one-utterance PLDA log-likelihood ratio of rows r and j of x, PLDA-normalised with one utterance each
+    (xv_backend_plda_dense).  coef, g, k0: plda_coefficients' tables of the single count 1 on the device.  out as in score_dense."""
+    n, ldx = pitched(x, "backend_plda_dense: x")
+    d = int(d)
+    nq, ldk = _plda_tables("backend_plda_dense", coef, g, k0, d)
+    if nq != 1:
+        raise ValueError("backend_plda_dense: the tables must hold the single entry of one utterance (got %d entries)" % nq)
+    out = _dense_out("backend_plda_dense", out, n, x.device)
+    ws_bytes = backend_plda_dense_workspace_bytes(n, d)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    _lib.call("xv_backend_plda_dense", _s(), _p(x), ldx, n, d, _p(coef), ldk, _p(g), _p(k0), _p(out), pitched(out, "backend_plda_dense: out")[1],
+              _p(ws), C.c_size_t(ws_bytes))
+    return out
+
+
+AHC_MAX_N = 2048      # the rows of one recording xv_ahc_cluster takes
+
+
+def ahc_workspace_bytes(n):
+    """Bytes of scratch xv_ahc_cluster needs for recordings of n[i] rows (a host integer array): every recording's n x n matrix."""
+    n = np.asarray(n, dtype=np.int64)
+    return int(_lib.load().xv_ahc_workspace_bytes(C.c_int64(int((n * n).sum()))))
+
+
+def ahc_cluster(scores, mat_offsets, n, ld=None, threshold=0.0, targets=None):
+    """Average-linkage agglomerative clustering of b score matrices in one call (xv_ahc_cluster; include/xvector_hip.h states the arithmetic,
+    tests/ahc_ref.py restates it).  scores: a contiguous 1-D float32 device buffer; recording i's matrix [n[i], ld[i]] starts at float
+    mat_offsets[i] and only its upper triangle is read.  targets[i] = 0 (None: all 0): merge while the best average score is >= threshold;
+    t >= 1: merge down to t clusters, whatever the scores.  mat_offsets, n, ld (None: n), targets: HOST integer arrays, checked here before
+    the upload - the kernel trusts them.  -> (labels int32 [sum n], merges int32 [sum (n - 1), 2], merge_values float32 [sum (n - 1)],
+    n_merges int32 [b]), device tensors; recording i's labels start at the exclusive prefix of n, its merge log at that of n - 1 and holds
+    n_merges[i] entries.  A NaN score is undefined."""
+    if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous() or scores.numel() == 0:
+        raise ValueError("ahc_cluster: scores must be a non-empty contiguous 1-D float32 tensor")
+    n = host_ints(n, "ahc_cluster: n", min_size=1)
+    b = n.size
+    if n.min() < 1:
+        raise ValueError("ahc_cluster: recording %d has no row (n = %d)" % (int(np.argmax(n < 1)), int(n.min())))
+    if n.max() > AHC_MAX_N:
+        raise ValueError("ahc_cluster: recording %d has %d rows, the cap is %d" % (int(np.argmax(n > AHC_MAX_N)), int(n.max()), AHC_MAX_N))
+    ld = n if ld is None else host_ints(ld, "ahc_cluster: ld", n=b)
+    if (ld < n).any():
+        raise ValueError("ahc_cluster: recording %d: the pitch %d is below its %d rows" % (int(np.argmax(ld < n)), int(ld[np.argmax(ld < n)]), int(n[np.argmax(ld < n)])))
+    targets = np.zeros(b, np.int32) if targets is None else host_ints(targets, "ahc_cluster: targets", n=b)
+    if (targets < 0).any() or (targets > n).any():
+        i = int(np.argmax((targets < 0) | (targets > n)))
+        raise ValueError("ahc_cluster: recording %d: target %d outside 0 .. %d" % (i, int(targets[i]), int(n[i])))
+    mat_offsets = host_ints(mat_offsets, "ahc_cluster: mat_offsets", n=b, dtype=np.int64)
+    n64, ld64 = n.astype(np.int64), ld.astype(np.int64)
+    spans_inside(mat_offsets, (n64 - 1) * ld64 + n64, scores.numel(), "ahc_cluster: a matrix lies outside the %d floats of scores" % scores.numel())
+    dev = scores.device
+    total, sum_n2 = int(n64.sum()), int((n64 * n64).sum())
+    labels = torch.empty(total, dtype=torch.int32, device=dev)
+    merges = torch.empty((max(total - b, 1), 2), dtype=torch.int32, device=dev)
+    values = torch.empty(max(total - b, 1), dtype=torch.float32, device=dev)
+    n_merges = torch.empty(b, dtype=torch.int32, device=dev)
+    ws_bytes = ahc_workspace_bytes(n)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    off_d, n_d, ld_d, t_d = upload(mat_offsets, np.int64, dev), upload(n, np.int32, dev), upload(ld, np.int32, dev), upload(targets, np.int32, dev)
+    _lib.call("xv_ahc_cluster", _s(), _p(scores), C.c_int64(scores.numel()), _p(off_d), _p(n_d), _p(ld_d), _p(t_d), b, int(n.max()), C.c_int64(total),
+              C.c_int64(sum_n2), C.c_float(float(threshold)), _p(labels), _p(merges), _p(values), _p(n_merges), _p(ws), C.c_size_t(ws_bytes))
+    return labels, merges[:total - b], values[:total - b], n_merges

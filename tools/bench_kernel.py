@@ -20,6 +20,10 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py score [small|large]              the scoring stage (xv_score.hip) on synthetic unit vectors, d = 512: VoxCeleb1-O-sized and E-sized
   python tools/bench_kernel.py backend [small|large]            the LDA / PLDA back end's device ops (xv_backend.hip) on synthetic vectors, d = 512, LDA to 200
   python tools/bench_kernel.py plda_cohort [small|large]        the cohort statistics of PLDA scores (xv_backend_cohort.hip): d = 200, 4 k rows, cohorts of 4 k / 40 k
+  python tools/bench_kernel.py dense [n ...]                     the all-pairs score matrix of one recording (xv_score_dense, xv_backend_plda_dense) at d = 200,
+                                                                n = 200 / 800 / 2000 windows, into a view of a packed buffer
+  python tools/bench_kernel.py ahc [recordings=64] [n ...]      agglomerative clustering (xv_ahc.hip): one call over 64 recordings of n = 200 / 800 / 2000
+                                                                windows, medians over alternated rounds, beside scipy's average linkage on 16 CPUs
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
   python tools/bench_kernel.py fbank [utterances=256]            xv_fbank (30 bins) against xv_mfcc on the same batch, alternated five times: medians and spread
   python tools/bench_kernel.py cm_encode [utterances=256]        'CM ' compression (xv_cm_encode.hip) of 400 - 2000 frames x 30 per utterance, both header forms,
@@ -582,6 +586,79 @@ def cmd_plda_cohort(argv):
               % (us_all, us_gemm, fl / us_gemm / 1e6, us_gemm / us_all, us_all - us_gemm, 1.0 - us_gemm / us_all), flush=True)
 
 
+def cmd_dense(argv):
+    """Time of the dense score matrix of one recording at d = 200: xv_score_dense (one GEMM launch) and xv_backend_plda_dense (column terms,
+    fold, the GEMM, the finishing kernel), written into a view of a packed buffer as misc/diarization.py does; five alternated rounds."""
+    from tf_kaldi_speaker_amd import ops
+    from tf_kaldi_speaker_amd.misc import backend as B
+    d = 200
+    psi = np.sort(rs.uniform(0.05, 5.0, d))[::-1].copy()
+    tabs = tuple(torch.from_numpy(a).cuda() for a in B.plda_coefficients(psi, [1]))
+    sizes = [int(a) for a in argv] or [200, 800, 2000]
+    xs = {n: ops.score_prepare(rnd(n, d)) for n in sizes}
+    views = {n: torch.empty(8 + n * ((n + 3) // 4 * 4), device="cuda")[8:].view(n, (n + 3) // 4 * 4)[:, :n] for n in sizes}
+    times = {(n, k): [] for n in sizes for k in ("cos", "plda")}
+    for _ in range(5):
+        for n in sizes:
+            times[(n, "cos")].append(timeit(lambda: ops.score_dense(xs[n], d, out=views[n]), 20, 3))
+            times[(n, "plda")].append(timeit(lambda: ops.backend_plda_dense(xs[n], d, *tabs, out=views[n]), 20, 3))
+    for n in sizes:
+        cos, plda = np.median(times[(n, "cos")]), np.median(times[(n, "plda")])
+        print("dense: n = %4d, d = %d: score_dense %8.1f us (%.2f TF; rounds %s), backend_plda_dense %8.1f us (rounds %s)"
+              % (n, d, cos, 2.0 * n * n * d / cos / 1e6, " ".join("%.1f" % t for t in times[(n, "cos")]), plda,
+                 " ".join("%.1f" % t for t in times[(n, "plda")])), flush=True)
+
+
+def _scipy_average_linkage(s):      # (module level: the pool's workers import it)
+    from scipy.cluster.hierarchy import linkage
+    n = s.shape[0]
+    return linkage(-s.astype(np.float64)[np.triu_indices(n, 1)], "average")[:, 2].sum()
+
+
+def cmd_ahc(argv):
+    """One xv_ahc_cluster call over `recordings` score matrices of n windows each (cosines of clustered unit vectors, 4 speakers), merged down
+    to one cluster: milliseconds per call, medians over five rounds that alternate the sizes.  Beside it scipy.cluster.hierarchy.linkage
+    (-S, "average") over the same matrices on 16 worker processes - started and joined BEFORE this process opens the GPU, so that no child
+    holds it."""
+    import multiprocessing as mp
+    from tf_kaldi_speaker_amd import ops
+    recordings = int(argv[0]) if argv else 64
+    sizes = [int(a) for a in argv[1:]] or [200, 800, 2000]
+    host = {}
+    for n in sizes:
+        mats = []
+        for _ in range(recordings):
+            x = rs.randn(4, 64)[rs.randint(0, 4, n)] + 0.6 * rs.randn(n, 64)
+            x /= np.linalg.norm(x, axis=1, keepdims=True)
+            mats.append((x @ x.T).astype(np.float32))
+        host[n] = mats
+    cpu = {}
+    with mp.get_context("spawn").Pool(16) as pool:
+        pool.map(_scipy_average_linkage, host[sizes[0]][:16])      # the workers have imported scipy
+        for n in sizes:
+            t0 = time.time()
+            pool.map(_scipy_average_linkage, host[n], chunksize=1)
+            cpu[n] = (time.time() - t0) * 1e3
+    dev = {}
+    for n in sizes:
+        ld = (n + 3) // 4 * 4
+        buf = torch.zeros(recordings * n * ld, device="cuda")
+        for i, m in enumerate(host[n]):
+            buf[i * n * ld:(i + 1) * n * ld].view(n, ld)[:, :n] = torch.from_numpy(m).cuda()
+        dev[n] = (buf, np.arange(recordings, dtype=np.int64) * n * ld, np.full(recordings, n, np.int32), np.full(recordings, ld, np.int32),
+                  np.ones(recordings, np.int32))
+    times = {n: [] for n in sizes}
+    for _ in range(5):
+        for n in sizes:
+            buf, off, nn, ld, tg = dev[n]
+            times[n].append(timeit(lambda: ops.ahc_cluster(buf, off, nn, ld, targets=tg), 2, 1) / 1e3)
+    for n in sizes:
+        med = float(np.median(times[n]))
+        print("ahc: %d recordings x n = %4d, %d merges each: %9.2f ms per call (rounds %s) = %.2f us per merge step of a recording's workgroup; "
+              "scipy average linkage, 16 processes, the same matrices: %9.1f ms"
+              % (recordings, n, n - 1, med, " ".join("%.2f" % t for t in times[n]), med * 1e3 / (n - 1), cpu[n]), flush=True)
+
+
 def cmd_mfcc(argv):
     """Frames per second of xv_mfcc alone and of xv_mfcc + xv_energy_vad on one padded batch (VoxCeleb conf: 16 kHz, 25 / 10 ms, 30 bins, 30
     coefficients); the bytes the kernel has to move (2 S bytes of new samples in, 4 num_ceps bytes out per frame, plus the zeroed padding
@@ -789,7 +866,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
+COMMANDS = {"ahc": cmd_ahc, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
             "triplet": cmd_triplet, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
