@@ -574,6 +574,47 @@ int xv_ahc_cluster(void* stream, const float* scores, int64_t scores_floats, con
                    const int32_t* targets, int b, int max_n, int64_t total_n, int64_t sum_n2, float threshold, int32_t* labels,
                    int32_t* merges, float* merge_values, int32_t* n_merges, void* ws, size_t ws_bytes);
 
+/* VB-HMM clustering of x-vectors (VBx, Landini et al.: a Bayesian HMM whose states are speakers and whose state distributions come from
+ * the PLDA model, started from the clusterer's labels), as recalled from BUT's VB_diarization.py and restated - agreement with a run of
+ * that code is not pinned.  b recordings per call, one workgroup each, every iteration in the one launch, no hand-over between
+ * workgroups: a recording's result depends on its own inputs only and is the same bits every time.
+ * Inputs, all on the device: x, a packed fp32 buffer of x_floats floats; recording r's rows [t[r]][ld[r]], ld[r] >= d, start at float
+ * x_offsets[r] (int64): vectors in the PLDA space in which the within-class covariance is I and the between-class covariance diag(phi)
+ * (the affine step of the back end WITHOUT backend_plda_normalize); phi [d]; gamma_in, the initial responsibilities, recording r's
+ * [t[r]][s[r]] (rows summing to 1) at the exclusive prefix of t * s; pi_in, the initial speaker priors, recording r's [s[r]] at the exclusive
+ * prefix of s.  None of them is modified.
+ * The arithmetic is part of the operation (tests/vbx_ref.py restates it: the definition in the log domain and the form computed).  Per
+ * recording, rho = x * sqrt(phi), G_t = -(sum_d x_td^2 + d ln 2 pi) / 2, and an iteration is
+ *   N_s = sum_t gamma_ts,  invL_sd = 1 / (1 + (fa / fb) N_s phi_d),  alpha_sd = (fa / fb) invL_sd sum_t gamma_ts rho_td
+ *   logp_ts = fa (sum_d rho_td alpha_sd - sum_d (invL_sd + alpha_sd^2) phi_d / 2 + G_t)
+ *   forward-backward over the HMM with initial distribution pi, transitions tr_ij = loop_prob [i = j] + (1 - loop_prob) pi_j and state
+ *   likelihoods exp(logp): the new gamma and tll = log p(x)
+ *   ELBO = tll + fb / 2 sum_sd (ln invL_sd - invL_sd - alpha_sd^2 + 1)
+ *   pi_j <- gamma_0j + (1 - loop_prob) pi_j sum_{t >= 1} [sum_i A_{t-1,i}] p_tj B_tj / p(x) (A, B the forward and backward variables), then
+ *   pi <- pi / sum pi
+ *   stop after this iteration if it is not the first and ELBO - ELBO of the one before < epsilon (epsilon = -inf: never).
+ * The speaker models and the scores are computed in double from the fp32 inputs, the recursions in fp32 in a per-frame scaled form: fa G_t, common to the speakers of a frame, leaves the scores and enters tll only;
+ * b_tj = exp(logp'_tj - m_t), m_t the largest logp' of the frame among the speakers with pi > 0 (a speaker with pi = 0 has b = 0: it has
+ * gamma 0 everywhere, stays at pi = 0 and makes no NaN); a_tj = b_tj (loop_prob a^_{t-1,j} + (1 - loop_prob) pi_j) (t = 0: b_0j pi_j),
+ * n_t = sum_j a_tj, a^_t = a_t / n_t; w = b_{t+1} * B^_{t+1}, B^_t = (loop_prob w + (1 - loop_prob) sum_j pi_j w_j) / n_{t+1}, B^_{T-1} = 1;
+ * gamma = a^ * B^; pi_j <- gamma_0j + (1 - loop_prob) pi_j sum_{t >= 1} b_tj B^_tj / n_t.  tll = sum_t (ln n_t + m_t) + fa sum_t G_t and the
+ * ELBO's second term are accumulated in double; every sum runs in a fixed order.  The state between two iterations is (gamma, pi) in fp32
+ * and nothing else: k iterations in one call are the same bits as k calls of one iteration.  With t = 1 there is no transition.
+ * Outputs: gamma and pi (laid out as gamma_in and pi_in); elbo, double [b][max_iters], of which recording r's first n_iters[r] entries are
+ * written; n_iters int32 [b], the iterations run; labels int32 [total_t], recording r's at the exclusive prefix of t: labels[t] = the
+ * speaker with the largest gamma, the lowest on a tie.
+ * total_t = sum t, total_ts = sum t * s, total_s = sum s, max_t, max_s: host values the caller states.  ws: xv_vbx_workspace_bytes bytes,
+ * 16-byte aligned (per recording the scores in double, the partial sums of the models, b, a^, n and m).  Refused by name:
+ * b <= 0, max_t outside 1 .. 2048 (the clusterer's cap), max_s outside 1 .. 32, d outside 1 .. 256, max_iters outside 1 .. 64, loop_prob
+ * outside (0, 1), fa or fb not positive, an epsilon that is NaN, totals that do not fit, a workspace too small.  The device arrays are NOT
+ * checked on the host side of this call (ops.vbx checks the host arrays before the upload); a recording whose entries would take the
+ * kernel outside the buffers of the call is skipped and gets n_iters = -1.  NaN inputs and a pi without a positive entry are undefined. */
+size_t xv_vbx_workspace_bytes(int64_t total_t, int64_t total_ts, int64_t total_s, int d);
+int xv_vbx(void* stream, const float* x, int64_t x_floats, const int64_t* x_offsets, const int32_t* t, const int32_t* ld, const int32_t* s,
+           int b, int d, int max_t, int max_s, int64_t total_t, int64_t total_ts, int64_t total_s, const float* phi, const float* gamma_in,
+           const float* pi_in, float loop_prob, float fa, float fb, int max_iters, double epsilon, float* gamma, float* pi, double* elbo,
+           int32_t* n_iters, int32_t* labels, void* ws, size_t ws_bytes);
+
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);
  * columns c in [C, c_pad) are zero. */

@@ -317,6 +317,9 @@ SIGNATURES = {
     "xv_backend_plda_dense": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _I, _VP, _SZ]),
     "xv_ahc_workspace_bytes": (_SZ, [C.c_int64]),
     "xv_ahc_cluster": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, C.c_int64, C.c_int64, _F, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "xv_vbx_workspace_bytes": (_SZ, [C.c_int64, C.c_int64, C.c_int64, _I]),
+    "xv_vbx": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, _F, _F, _F, _I, C.c_double,
+                    _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "xv_add_norm_grad": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "xv_segment_gemm": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, _VP, C.c_long, _VP, C.c_long, _VP, _SZ, _VP]),
     "xv_segment_affine_bn_forward": (_I, [_VP, _VP, C.c_long, _VP, C.c_long, _I, _I, _I, _VP, _VP, _VP, _F, _F, _I, _VP, _VP, _VP, _VP, _VP,

@@ -449,6 +449,19 @@ class BackendScorer(object):
             raise ValueError("BackendScorer.prepare: n_utts must hold one count per row (%d, got %d)" % (x.shape[0], len(n_utts)))
         return self.chain.run(x, self.mode == "plda", None if n_utts is None else np.asarray(n_utts))
 
+    def plda_space(self, matrix):
+        """The rows of `matrix` (host [n, d] or device tensor, raw vectors as prepare takes them) in the space of the PLDA model, where the
+        within-class covariance is I and the between-class covariance diag(psi): centred, LDA-transformed, length-normalised and taken
+        through the PLDA transform, WITHOUT backend_plda_normalize - what ops.vbx models.  -> (device float32 [n, dim rounded up to 4],
+        psi device float32 [dim])."""
+        if self.backend.plda is None or self.mode != "plda":
+            raise ValueError("BackendScorer.plda_space: needs a PLDA model and the plda mode (this scorer: mode %s, %s)"
+                             % (self.mode, "no PLDA model" if self.backend.plda is None else "with a PLDA model"))
+        x = _device_rows(self.torch, matrix, self.device, self.d, "BackendScorer.plda_space")
+        chain = self.chain
+        rows = cat([self.ops.backend_affine(chain.unit(x[r0:r1]), chain.plda_w, chain.plda_b) for r0, r1 in steps(x.shape[0], PREPARE_ROWS)])
+        return rows, chain.psi
+
     def dense(self, prepared, out=None):
         """The score of every pair of the prepared rows (one utterance each), a device float32 [n, n] matrix: the cosine in the lda_cos mode
         (ops.score_dense), the log-likelihood ratio in the plda mode (ops.backend_plda_dense); no cohort enters.  out: a [n, n] view of any

@@ -4,9 +4,10 @@ nothing is compared with a Kaldi run.
 
 Host side, NumPy only: speech segments from VAD decisions or a `segments` file, the window planner, the turns of an RTTM from clustered
 windows, RTTM files and a plain diarization error rate.  Device side: Diarizer, which takes the windows' embeddings of many recordings
-through a scorer's prepare -> dense into one packed buffer and clusters them in one ops.ahc_cluster call per batch.
+through a scorer's prepare -> dense into one packed buffer and clusters them in one ops.ahc_cluster call per batch; with VbxOptions the
+clusterer's labels start the VB-HMM clustering of the windows (VBx, ops.vbx: DESIGN.md section 6j) over the same batch.
 Not here: the per-recording PCA of ivector-plda-scoring-dense, threshold calibration, overlap detection,
-resegmentation, collars / md-eval, recordings of more than 2048 windows.
+collars / md-eval, recordings of more than 2048 windows.
 """
 import logging
 
@@ -137,6 +138,37 @@ def der(ref, hyp):
     return miss / speech, fa / speech, conf / speech, (miss + fa + conf) / speech
 
 
+def vbx_init(labels, num_speakers, smoothing=5.0):
+    """The responsibilities VBx starts from: one-hot rows of the clusterer's labels times `smoothing`, a softmax per row (smoothing 5: 0.99
+    on the labelled speaker of two, less with more speakers).  -> float32 [len(labels), num_speakers]; host arithmetic in double."""
+    labels = np.asarray(labels, dtype=np.int64)
+    num_speakers = int(num_speakers)
+    if labels.ndim != 1 or labels.size == 0 or num_speakers < 1 or labels.min() < 0 or labels.max() >= num_speakers:
+        raise ValueError("vbx_init: labels must be a non-empty 1-D array of values in 0 .. %d" % (num_speakers - 1))
+    if not smoothing >= 0:
+        raise ValueError("vbx_init: smoothing must not be negative (got %r)" % (smoothing,))
+    z = np.zeros((labels.size, num_speakers), np.float64)
+    z[np.arange(labels.size), labels] = float(smoothing)
+    z = np.exp(z - z.max(axis=1, keepdims=True))
+    return (z / z.sum(axis=1, keepdims=True)).astype(np.float32)
+
+
+class VbxOptions(object):
+    """What ops.vbx is run with behind the clusterer: the scaling factors fa and fb of the statistics, the probability loop_prob of staying
+    with a speaker from one window to the next, at most max_iters iterations that stop once the ELBO gains less than epsilon, and the
+    smoothing of vbx_init."""
+
+    def __init__(self, fa=0.3, fb=17.0, loop_prob=0.99, max_iters=20, epsilon=1e-4, init_smoothing=5.0):
+        self.fa, self.fb, self.loop_prob = float(fa), float(fb), float(loop_prob)
+        self.max_iters, self.epsilon, self.init_smoothing = int(max_iters), float(epsilon), float(init_smoothing)
+
+
+def _first_appearance(labels):
+    """Labels renumbered 0, 1, ... by the first row of each: the clusterer's convention."""
+    _, first, inverse = np.unique(labels, return_index=True, return_inverse=True)
+    return np.argsort(np.argsort(first))[inverse].astype(np.int32)
+
+
 class Diarizer(object):
     """Clusters the window embeddings of recordings behind a scorer (CosineScorer, or BackendScorer in either mode).
 
@@ -144,14 +176,51 @@ class Diarizer(object):
         diar = Diarizer(scorer, reco2num_spk={"rec1": 2, ...})      # or: merge down to the given number of speakers
         labels = diar.cluster({"rec1": matrix1, ...})               # {recording: int32 labels, one per row}
 
-    cluster() runs prepare -> dense per recording into one packed buffer of score matrices and one ops.ahc_cluster call over them, in
-    batches such that the buffer and the clusterer's scratch of a call stay under the scorer's workspace_bytes."""
+        diar = Diarizer(scorer, threshold=0.0, vbx=VbxOptions())    # ... and VBx behind the clusterer (a BackendScorer in the plda mode)
 
-    def __init__(self, scorer, threshold=None, reco2num_spk=None):
+    cluster() runs prepare -> dense per recording into one packed buffer of score matrices and one ops.ahc_cluster call over them, in
+    batches such that the buffer and the clusterer's scratch of a call stay under the scorer's workspace_bytes.  With vbx the clusterer
+    should stop early (too many speakers rather than too few): its labels give vbx_init's responsibilities, the windows go through the
+    scorer's plda_space, and one ops.vbx call per batch re-assigns them and drops redundant speakers; the surviving speakers are numbered
+    0, 1, ... by their first window.  A recording the clusterer leaves with more than 32 clusters is clustered once more down to 32.
+    After cluster(), vbx_report holds per recording (speakers before, speakers after, iterations, last ELBO)."""
+
+    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None):
         if (threshold is None) == (reco2num_spk is None):
             raise ValueError("Diarizer: exactly one of threshold and reco2num_spk says when the merging stops")
-        self.scorer, self.threshold, self.reco2num_spk = scorer, threshold, reco2num_spk
+        if vbx is not None and not hasattr(scorer, "plda_space"):
+            raise ValueError("Diarizer: VBx needs a BackendScorer in the plda mode (its PLDA space), not %s" % type(scorer).__name__)
+        self.scorer, self.threshold, self.reco2num_spk, self.vbx = scorer, threshold, reco2num_spk, vbx
         self.torch, self.ops = scorer.torch, scorer.ops
+        self.vbx_report = {}
+
+    def _ahc(self, packed, offsets, n, ld, targets):
+        return self.ops.ahc_cluster(packed, offsets, n.astype(np.int32), ld.astype(np.int32),
+                                    threshold=0.0 if self.threshold is None else float(self.threshold),
+                                    targets=targets.astype(np.int32))[0].cpu().numpy()
+
+    def _vbx(self, names, matrices, labels, n):
+        """ops.vbx over one batch: labels = the clusterer's, back to back.  -> the new labels, back to back."""
+        opt, ops, torch = self.vbx, self.ops, self.torch
+        at = np.concatenate([[0], np.cumsum(n)])
+        rows, psi = zip(*(self.scorer.plda_space(m) for m in matrices))
+        dim, ld = int(psi[0].numel()), int(rows[0].shape[1])
+        speakers = np.asarray([int(labels[at[j]:at[j + 1]].max()) + 1 for j in range(len(names))], np.int64)
+        gamma = np.concatenate([vbx_init(labels[at[j]:at[j + 1]], speakers[j], opt.init_smoothing).ravel() for j in range(len(names))])
+        pi = np.concatenate([np.full(k, 1.0 / k, np.float32) for k in speakers])
+        x = torch.cat([r.reshape(-1) for r in rows]) if len(rows) > 1 else rows[0].reshape(-1)
+        dev = x.device
+        gamma_d, _, elbo, n_iters, new = ops.vbx(x, at[:-1] * ld, n, dim, psi[0], torch.from_numpy(gamma).to(dev), torch.from_numpy(pi).to(dev), speakers,
+                                                 ld=np.full(len(names), ld, np.int64), loop_prob=opt.loop_prob, fa=opt.fa, fb=opt.fb,
+                                                 max_iters=opt.max_iters, epsilon=opt.epsilon)
+        new, elbo, n_iters = new.cpu().numpy(), elbo.cpu().numpy(), n_iters.cpu().numpy()
+        out = np.empty_like(new)
+        for j, name in enumerate(names):
+            if n_iters[j] < 1:
+                raise RuntimeError("Diarizer: xv_vbx skipped recording %s (n_iters = %d)" % (name, int(n_iters[j])))
+            out[at[j]:at[j + 1]] = _first_appearance(new[at[j]:at[j + 1]])
+            self.vbx_report[name] = (int(speakers[j]), int(out[at[j]:at[j + 1]].max()) + 1, int(n_iters[j]), float(elbo[j, n_iters[j] - 1]))
+        return out
 
     def cluster(self, embeddings):
         """embeddings: {recording: float32 [n, d] matrix} (host or device).  -> {recording: NumPy int32 [n]} in the mapping's order."""
@@ -178,6 +247,10 @@ class Diarizer(object):
             targets = np.zeros(len(keys), np.int64)
         ld = np.asarray([pitch4(int(r)) for r in n], np.int64)
         cost = 4 * (n * ld + n * n)      # bytes of a recording: its matrix in the packed buffer and the clusterer's copy
+        if self.vbx is not None:         # (VBx runs once the clusterer's buffers are gone: a batch must hold the larger of the two)
+            cap_s, dim4 = self.ops.VBX_MAX_SPEAKERS, pitch4(self.scorer.dim)
+            cost = np.maximum(cost, np.asarray([4 * r * dim4 + 8 * r * cap_s + self.ops.vbx_workspace_bytes([r], [cap_s], self.scorer.dim) for r in n], np.int64))
+            self.vbx_report = {}
         out = {}
         batches = greedy_batches(len(keys), lambda i, total=0: (total + int(cost[i]),), lambda total: total, self.scorer.workspace_bytes,
                                  too_big=lambda i, c: "Diarizer: recording %s needs %d bytes of scores, the workspace holds %d"
@@ -189,10 +262,21 @@ class Diarizer(object):
                 prepared = self.scorer.prepare(embeddings[keys[i]])
                 view = packed[int(offsets[j]):int(offsets[j + 1])].view(int(n[i]), int(ld[i]))[:, :int(n[i])]
                 self.scorer.dense(prepared, out=view)
-            labels = self.ops.ahc_cluster(packed, offsets[:-1], n[batch].astype(np.int32), ld[batch].astype(np.int32),
-                                          threshold=0.0 if self.threshold is None else float(self.threshold),
-                                          targets=targets[batch].astype(np.int32))[0].cpu().numpy()
+            labels = self._ahc(packed, offsets[:-1], n[batch], ld[batch], targets[batch])
             at = np.concatenate([[0], np.cumsum(n[batch])])
+            if self.vbx is not None:
+                cap = self.ops.VBX_MAX_SPEAKERS
+                many = [j for j in range(len(batch)) if labels[at[j]:at[j + 1]].max() >= cap]
+                if many:      # the clusterer once more, down to the most speakers VBx takes, for the batch as it stands
+                    _LOG.info("[INFO] Recording %s: more than %d clusters, clustered once more down to %d for VBx."
+                              % (", ".join(keys[batch[j]] for j in many), cap, cap))
+                    again = targets[batch].copy()
+                    again[many] = cap
+                    relabel = self._ahc(packed, offsets[:-1], n[batch], ld[batch], again)
+                    for j in many:
+                        labels[at[j]:at[j + 1]] = relabel[at[j]:at[j + 1]]
+                del packed
+                labels = self._vbx([keys[i] for i in batch], [embeddings[keys[i]] for i in batch], labels, n[batch])
             for j, i in enumerate(batch):
                 out[keys[i]] = labels[at[j]:at[j + 1]]
         return out

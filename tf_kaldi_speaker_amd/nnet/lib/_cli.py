@@ -115,6 +115,16 @@ ARGUMENTS = {
     "reco2num_spk": (("--reco2num-spk",), dict(type=str, default="", help="`recording speakers` per line: merge down to that many clusters.")),
     "write_embeddings": (("--write-embeddings",), dict(type=str, default="", help="Kaldi wspecifier (or ark file) for the windows' embeddings, keyed "
                                                                                   "`recording-startframe-endframe` (7 digits each).")),
+    "vbx": (("--vbx",), dict(action="store_true", help="VB-HMM clustering of the windows (VBx) behind the clusterer, which should then stop early "
+                                                       "(a threshold that leaves too many speakers).  Needs --scoring plda.")),
+    "vbx_fa": (("--vbx-fa",), dict(type=float, default=0.3, help="VBx: the scaling factor of the sufficient statistics.")),
+    "vbx_fb": (("--vbx-fb",), dict(type=float, default=17.0, help="VBx: the scaling factor of the speaker models' regularisation.")),
+    "vbx_loop_prob": (("--vbx-loop-prob",), dict(type=float, default=0.99, help="VBx: the probability of staying with a speaker from one window "
+                                                                                "to the next.")),
+    "vbx_max_iters": (("--vbx-max-iters",), dict(type=int, default=20, help="VBx: the most iterations (1 .. 64).")),
+    "vbx_epsilon": (("--vbx-epsilon",), dict(type=float, default=1e-4, help="VBx: stop once an iteration gains less than this on the ELBO.")),
+    "vbx_init_smoothing": (("--vbx-init-smoothing",), dict(type=float, default=5.0, help="VBx: the clusterer's labels times this, a softmax per "
+                                                                                         "window, are the first responsibilities.")),
     # positionals
     "rttm_out": (("rttm_out",), dict(type=str, help="The RTTM file to write.")),
     "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),

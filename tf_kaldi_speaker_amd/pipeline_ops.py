@@ -375,3 +375,72 @@ def ahc_cluster(scores, mat_offsets, n, ld=None, threshold=0.0, targets=None):
     _lib.call("xv_ahc_cluster", _s(), _p(scores), C.c_int64(scores.numel()), _p(off_d), _p(n_d), _p(ld_d), _p(t_d), b, int(n.max()), C.c_int64(total),
               C.c_int64(sum_n2), C.c_float(float(threshold)), _p(labels), _p(merges), _p(values), _p(n_merges), _p(ws), C.c_size_t(ws_bytes))
     return labels, merges[:total - b], values[:total - b], n_merges
+
+
+VBX_MAX_SPEAKERS = 32      # the speakers (HMM states) of one recording xv_vbx takes
+VBX_MAX_DIM = 256          # ... the dimensions of its rows
+VBX_MAX_ITERS = 64         # ... and the iterations of one call
+
+
+def vbx_workspace_bytes(t, s, d):
+    """Bytes of scratch xv_vbx needs for recordings of t[i] rows and s[i] speakers (host integer arrays of one length) in d dimensions."""
+    t, s = np.asarray(t, dtype=np.int64), np.asarray(s, dtype=np.int64)
+    return int(_lib.load().xv_vbx_workspace_bytes(C.c_int64(int(t.sum())), C.c_int64(int((t * s).sum())), C.c_int64(int(s.sum())), int(d)))
+
+
+def vbx(x, x_offsets, t, d, phi, gamma, pi, s, ld=None, loop_prob=0.99, fa=0.3, fb=17.0, max_iters=20, epsilon=1e-4):
+    """VB-HMM clustering (VBx) of b recordings in one call (xv_vbx; include/xvector_hip.h states the arithmetic, tests/vbx_ref.py restates
+    it).  x: a contiguous 1-D float32 device buffer; recording i's rows [t[i], ld[i]] (ld None: d) start at float x_offsets[i]: vectors in
+    the PLDA space with within-class covariance I and between-class covariance diag(phi) (BackendScorer.plda_space).  phi: float32 [d]
+    on the device.  gamma: the initial responsibilities, recording i's [t[i], s[i]] back to back in one 1-D float32 device tensor; pi: the
+    initial priors, recording i's [s[i]] back to back.  x_offsets, t, ld, s: HOST integer arrays, checked here before the upload - the
+    kernel trusts them.  epsilon: the smallest gain of the ELBO that keeps iterating (-inf: always max_iters).
+    -> (gamma, pi, elbo float64 [b, max_iters] - NaN behind the iterations run -, n_iters int32 [b], labels int32 [sum t]), device tensors
+    laid out as the inputs; x, phi and the initial gamma and pi are not modified."""
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("vbx: x must be a non-empty contiguous 1-D float32 tensor")
+    d, max_iters = int(d), int(max_iters)
+    if not 1 <= d <= VBX_MAX_DIM:
+        raise ValueError("vbx: d must lie in 1 .. %d (got %d)" % (VBX_MAX_DIM, d))
+    if not 1 <= max_iters <= VBX_MAX_ITERS:
+        raise ValueError("vbx: max_iters must lie in 1 .. %d (got %d)" % (VBX_MAX_ITERS, max_iters))
+    loop32 = float(np.float32(loop_prob))
+    if not 0.0 < loop32 < 1.0:
+        raise ValueError("vbx: loop_prob must lie strictly between 0 and 1 as a float32 (got %r)" % (loop_prob,))
+    if not (float(np.float32(fa)) > 0.0 and float(np.float32(fb)) > 0.0 and np.isfinite(np.float32(fa)) and np.isfinite(np.float32(fb))):
+        raise ValueError("vbx: fa and fb must be positive (got %r, %r)" % (fa, fb))
+    if np.isnan(epsilon):
+        raise ValueError("vbx: epsilon is not a number")
+    t = host_ints(t, "vbx: t", min_size=1)
+    b = t.size
+    if t.min() < 1:
+        raise ValueError("vbx: recording %d has no row (t = %d)" % (int(np.argmax(t < 1)), int(t.min())))
+    if t.max() > AHC_MAX_N:
+        raise ValueError("vbx: recording %d has %d rows, the cap is %d" % (int(np.argmax(t > AHC_MAX_N)), int(t.max()), AHC_MAX_N))
+    s = host_ints(s, "vbx: s", n=b)
+    if s.min() < 1:
+        raise ValueError("vbx: recording %d has no speaker (s = %d)" % (int(np.argmax(s < 1)), int(s.min())))
+    if s.max() > VBX_MAX_SPEAKERS:
+        raise ValueError("vbx: recording %d has %d speakers, the cap is %d" % (int(np.argmax(s > VBX_MAX_SPEAKERS)), int(s.max()), VBX_MAX_SPEAKERS))
+    ld = np.full(b, d, np.int64) if ld is None else host_ints(ld, "vbx: ld", n=b)
+    if (ld < d).any():
+        raise ValueError("vbx: recording %d: the pitch %d is below the %d dimensions" % (int(np.argmax(ld < d)), int(ld[np.argmax(ld < d)]), d))
+    x_offsets = host_ints(x_offsets, "vbx: x_offsets", n=b, dtype=np.int64)
+    t64, s64, ld64 = t.astype(np.int64), s.astype(np.int64), ld.astype(np.int64)
+    spans_inside(x_offsets, (t64 - 1) * ld64 + d, x.numel(), "vbx: a recording's rows lie outside the %d floats of x" % x.numel())
+    total_t, total_ts, total_s = int(t64.sum()), int((t64 * s64).sum()), int(s64.sum())
+    f32_values(phi, d, "vbx: phi")
+    f32_values(gamma, total_ts, "vbx: gamma (sum of t * s)")
+    f32_values(pi, total_s, "vbx: pi (sum of s)")
+    dev = x.device
+    gamma_out, pi_out = torch.empty_like(gamma), torch.empty_like(pi)
+    elbo = torch.full((b, max_iters), float("nan"), dtype=torch.float64, device=dev)
+    n_iters = torch.empty(b, dtype=torch.int32, device=dev)
+    labels = torch.empty(total_t, dtype=torch.int32, device=dev)
+    ws_bytes = vbx_workspace_bytes(t, s, d)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    off_d, t_d, ld_d, s_d = upload(x_offsets, np.int64, dev), upload(t, np.int32, dev), upload(ld, np.int32, dev), upload(s, np.int32, dev)
+    _lib.call("xv_vbx", _s(), _p(x), C.c_int64(x.numel()), _p(off_d), _p(t_d), _p(ld_d), _p(s_d), b, d, int(t.max()), int(s.max()), C.c_int64(total_t),
+              C.c_int64(total_ts), C.c_int64(total_s), _p(phi), _p(gamma), _p(pi), C.c_float(loop32), C.c_float(float(fa)), C.c_float(float(fb)),
+              max_iters, C.c_double(float(epsilon)), _p(gamma_out), _p(pi_out), _p(elbo), _p(n_iters), _p(labels), _p(ws), C.c_size_t(ws_bytes))
+    return gamma_out, pi_out, elbo, n_iters, labels

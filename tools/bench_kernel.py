@@ -24,6 +24,9 @@ sub-command per question (they used to be eight scripts):
                                                                 n = 200 / 800 / 2000 windows, into a view of a packed buffer
   python tools/bench_kernel.py ahc [recordings=64] [n ...]      agglomerative clustering (xv_ahc.hip): one call over 64 recordings of n = 200 / 800 / 2000
                                                                 windows, medians over alternated rounds, beside scipy's average linkage on 16 CPUs
+  python tools/bench_kernel.py vbx [recordings=64] [T,S ...]     VB-HMM clustering (xv_vbx.hip): one call over 64 recordings at (T, D, S) = (200, 128, 6), (800, 128, 10)
+                                                                and (2000, 128, 16), 20 iterations, medians over alternated rounds, beside the float64 NumPy
+                                                                restatement of one recording on the CPU
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
   python tools/bench_kernel.py fbank [utterances=256]            xv_fbank (30 bins) against xv_mfcc on the same batch, alternated five times: medians and spread
   python tools/bench_kernel.py cm_encode [utterances=256]        'CM ' compression (xv_cm_encode.hip) of 400 - 2000 frames x 30 per utterance, both header forms,
@@ -659,6 +662,39 @@ def cmd_ahc(argv):
               % (recordings, n, n - 1, med, " ".join("%.2f" % t for t in times[n]), med * 1e3 / (n - 1), cpu[n]), flush=True)
 
 
+def cmd_vbx(argv):
+    """One xv_vbx call over `recordings` recordings of T windows in 128 dimensions started from S speakers (the generator of tests/vbx_ref.py:
+    S // 2 true speakers, each split in two), 20 iterations, never stopped: milliseconds per call, medians over five rounds that alternate
+    the sizes, and microseconds per iteration of a recording's workgroup.  Beside it, for scale only, the float64 NumPy restatement of the
+    same 20 iterations of ONE recording on the CPU."""
+    from tf_kaldi_speaker_amd import ops
+    from tests import vbx_ref as R
+    recordings = int(argv[0]) if argv else 64
+    sizes = [tuple(int(v) for v in a.split(",")) for a in argv[1:]] or [(200, 6), (800, 10), (2000, 16)]
+    d, iters, (fa, fb, lp) = 128, 20, R.PARAMS[0]
+    dev, cpu = {}, {}
+    for t, s in sizes:
+        cases = [R.make_case(t, d, s, seed) for seed in range(recordings)]
+        t0 = time.time()
+        R.vbx(cases[0]["x"], cases[0]["phi"], cases[0]["gamma"], cases[0]["pi"], lp, fa, fb, iters, -np.inf, "scaled", np.float64)
+        cpu[(t, s)] = (time.time() - t0) * 1e3
+        x = torch.from_numpy(np.concatenate([c["x"].ravel() for c in cases])).cuda()
+        gamma = torch.from_numpy(np.concatenate([c["gamma"].ravel() for c in cases])).cuda()
+        pi = torch.from_numpy(np.concatenate([c["pi"] for c in cases])).cuda()
+        dev[(t, s)] = (x, np.arange(recordings, dtype=np.int64) * t * d, np.full(recordings, t, np.int32), torch.from_numpy(cases[0]["phi"].copy()).cuda(),
+                       gamma, pi, np.full(recordings, s, np.int32))
+    times = {k: [] for k in sizes}
+    for _ in range(5):
+        for k in sizes:
+            x, off, tt, phi, gamma, pi, ss = dev[k]
+            times[k].append(timeit(lambda: ops.vbx(x, off, tt, d, phi, gamma, pi, ss, loop_prob=lp, fa=fa, fb=fb, max_iters=iters, epsilon=-np.inf), 2, 1) / 1e3)
+    for t, s in sizes:
+        med = float(np.median(times[(t, s)]))
+        print("vbx: %d recordings x (T, D, S) = (%4d, %d, %2d), %d iterations each: %9.2f ms per call (rounds %s) = %.1f us per iteration of a recording's "
+              "workgroup; float64 NumPy restatement, one recording, one CPU: %9.1f ms"
+              % (recordings, t, d, s, iters, med, " ".join("%.2f" % v for v in times[(t, s)]), med * 1e3 / iters, cpu[(t, s)]), flush=True)
+
+
 def cmd_mfcc(argv):
     """Frames per second of xv_mfcc alone and of xv_mfcc + xv_energy_vad on one padded batch (VoxCeleb conf: 16 kHz, 25 / 10 ms, 30 bins, 30
     coefficients); the bytes the kernel has to move (2 S bytes of new samples in, 4 num_ceps bytes out per frame, plus the zeroed padding
@@ -866,7 +902,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"ahc": cmd_ahc, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
+COMMANDS = {"ahc": cmd_ahc, "vbx": cmd_vbx, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
             "triplet": cmd_triplet, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
