@@ -9,8 +9,9 @@
 // Error budget of plda_trials (tests/test_gpu_backend.py): per column a lane runs
 //     diff = fma(-a, e, t); acc = fma(-0.5 * (iv * diff), diff, acc); acc = fma(0.5 * (g * t), t, acc)
 // - three roundings inside the first term (diff counts twice in diff^2, iv * diff once), one inside the second, and two adds on the chain,
-// which is 2 * (chain(d) - 6) + 6 = 2 chain(d) - 6 adds long (chain(d) of xv_rowsum.h; both forms interleaved in ONE sum, so a partial sum
-// is bounded by the sum of the |terms|, not by either quadratic form alone).  With the final k0 + s that is at most
+// which is 2 * (chain(d) - 6) + 6 = 2 chain(d) - 6 adds long (sc_row_sum of xv_rowsum.h calls a lane's term at most chain(d) - 6 times, this
+// term puts two fmas on acc, and the butterfly adds six; both forms interleaved in ONE sum, so a partial sum is bounded by the sum of the
+// |terms|, not by either quadratic form alone).  With the final k0 + s that is at most
 //     (2 chain(d) - 2) EPS * sum_c (|0.5 iv (t - a e)^2| + |0.5 g t^2|) + EPS |k0|
 // to first order, inside the 2 * (2 chain(d) + 6) EPS * sum + EPS |k0| the test asserts.
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include "xv_ew.h"
 #include "xv_gemm.h"
 #include "xv_rowsum.h"
+#include "xv_score_launch.h"
 
 #define BE_BLOCK_ROWS 8192        // rows per scatter block: the longest fp32 add chain of a scatter element, whatever n is
 
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void backend_slab_add_kernel(const float* __re
 }
 
 // out[r][c] = u[r][c] * sqrt(d / sum_c u[r][c]^2 / (psi[c] + 1 / n_r)) for c < d, 0 for d <= c < ldo.  One wave per row; the sum is
-// sc_row_dot's (chain(d)).  A row whose sum is 0 stays 0.  In place a lane reads back exactly the elements it then overwrites.
+// sc_row_sum's (chain(d)).  A row whose sum is 0 stays 0.  In place a lane reads back exactly the elements it then overwrites (sc_row_store).
 template <bool VEC>
 __global__ __launch_bounds__(256) void backend_plda_normalize_kernel(const float* u, int rows, int d, long ldu, const float* __restrict__ psi,
                                                                      const int* __restrict__ n_utts, float* out, long ldo) {
@@ -85,21 +87,13 @@ __global__ __launch_bounds__(256) void backend_plda_normalize_kernel(const float
     const float* ur = u + (long)r * ldu;
     float* yr = out + (long)r * ldo;
     const float inv_n = n_utts ? 1.0f / (float)n_utts[r] : 1.0f;
-    const float ss = sc_row_dot<VEC, false, true>(ur, psi, nullptr, d, lane, inv_n);
+    const float ss = sc_row_sum<VEC>(d, lane, [inv_n](float acc, float v, float p) { return fmaf(v, v / (p + inv_n), acc); }, ur, psi);
     const float scale = ss > 0.f ? sqrtf((float)d / ss) : 0.f;
-    if (VEC) {
-        for (int q = lane; q < (int)(ldo / 4); q += XV_WAVE) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (q < d / 4) v = *(const f32x4*)(ur + 4 * q) * scale;
-            *(f32x4*)(yr + 4 * q) = v;
-        }
-    } else {
-        for (int c = lane; c < (int)ldo; c += XV_WAVE) yr[c] = c < d ? ur[c] * scale : 0.f;
-    }
+    sc_row_store<VEC>(yr, ldo, d, lane, [scale](auto v) { return v * scale; }, ur);
 }
 
 // out[j] = k0[q] + sum_c (-0.5 iv[q][c] (t_c - a[q][c] e_c)^2 + 0.5 g[c] t_c^2), e = enrol row ei[j], t = test row ti[j], q = nidx[ei[j]];
-// coef[q] = (a[ldc], iv[ldc]).  One wave per trial, the lanes and the butterfly of sc_row_dot, the two forms interleaved in one sum (the
+// coef[q] = (a[ldc], iv[ldc]).  One wave per trial, the lanes and the butterfly of sc_row_sum, the two forms interleaved in one sum (the
 // budget is in the header of this file).  No division, no logarithm: the host built the tables in double.
 template <bool VEC>
 __global__ __launch_bounds__(256) void backend_plda_trials_kernel(const float* __restrict__ e, long lde, const float* __restrict__ t, long ldt, int d,
@@ -116,27 +110,11 @@ __global__ __launch_bounds__(256) void backend_plda_trials_kernel(const float* _
     const float* tr = t + (long)b_row * ldt;
     const float* ca = coef + (long)q * 2 * ldc;
     const float* ci = ca + ldc;
-    float acc = 0.f;
-    if (VEC) {
-        for (int p = lane; p < d / 4; p += XV_WAVE) {
-            const f32x4 ev = *(const f32x4*)(er + 4 * p), tv = *(const f32x4*)(tr + 4 * p);
-            const f32x4 av = *(const f32x4*)(ca + 4 * p), iv = *(const f32x4*)(ci + 4 * p), gv = *(const f32x4*)(g + 4 * p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float diff = fmaf(-av[k], ev[k], tv[k]);
-                acc = fmaf(-0.5f * (iv[k] * diff), diff, acc);
-                acc = fmaf(0.5f * (gv[k] * tv[k]), tv[k], acc);
-            }
-        }
-    } else {
-        for (int c = lane; c < d; c += XV_WAVE) {
-            const float tc = tr[c];
-            const float diff = fmaf(-ca[c], er[c], tc);
-            acc = fmaf(-0.5f * (ci[c] * diff), diff, acc);
-            acc = fmaf(0.5f * (g[c] * tc), tc, acc);
-        }
-    }
-    const float s = wave_sum(acc);
+    const float s = sc_row_sum<VEC>(d, lane, [](float acc, float ec, float tc, float ac, float ic, float gc) {
+        const float diff = fmaf(-ac, ec, tc);
+        acc = fmaf(-0.5f * (ic * diff), diff, acc);
+        return fmaf(0.5f * (gc * tc), tc, acc);
+    }, er, tr, ca, ci, g);
     if (lane == 0) out[j] = k0[q] + s;
 }
 
@@ -160,10 +138,7 @@ extern "C" int xv_backend_center(void* stream, const float* x, int rows, int d, 
     XV_REQUIRE(d > 0, "backend_center: d must be positive (got %d)", d);
     XV_REQUIRE(x && y && rows > 0, "backend_center: bad arguments");
     XV_REQUIRE(ldx >= d && ldy >= d, "backend_center: a pitch is below d (d=%d ldx=%d ldy=%d)", d, ldx, ldy);
-    const bool in_place = x == y && ldx == ldy;
-    XV_REQUIRE(in_place || !sc_overlap(x, (size_t)(rows - 1) * ldx + d, y, (size_t)rows * ldy),
-               "backend_center: x and y overlap (in place needs y == x and the same pitch)");
-    XV_REQUIRE(!mean || !sc_overlap(mean, d, y, (size_t)rows * ldy), "backend_center: mean and y overlap");
+    if (const int rc = sc_check_row_out("backend_center", "x", x, ldx, "y", y, ldy, rows, d, "mean", mean)) return rc;
     hipLaunchKernelGGL(backend_center_kernel, dim3(grid_for((long)rows * ldy, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, rows, d, mean,
                        y, (long)ldy);
     XV_LAUNCH_CHECK();
@@ -231,16 +206,9 @@ extern "C" int xv_backend_plda_normalize(void* stream, const float* u, int rows,
     XV_REQUIRE(d > 0, "backend_plda_normalize: d must be positive (got %d)", d);
     XV_REQUIRE(u && psi && out && rows > 0, "backend_plda_normalize: bad arguments");
     XV_REQUIRE(ldu >= d && ldo >= d, "backend_plda_normalize: a pitch is below d (d=%d ldu=%d ldo=%d)", d, ldu, ldo);
-    const bool in_place = u == out && ldu == ldo;
-    XV_REQUIRE(in_place || !sc_overlap(u, (size_t)(rows - 1) * ldu + d, out, (size_t)rows * ldo),
-               "backend_plda_normalize: u and out overlap (in place needs out == u and the same pitch)");
-    XV_REQUIRE(!sc_overlap(psi, d, out, (size_t)rows * ldo), "backend_plda_normalize: psi and out overlap");
-    const bool vec = d % 4 == 0 && ldu % 4 == 0 && ldo % 4 == 0 && sc_aligned16(u) && sc_aligned16(out) && sc_aligned16(psi);
-    const dim3 grid(xv_cdiv(rows, SC_ROWS_PER_WG)), block(256);
-    if (vec) hipLaunchKernelGGL(backend_plda_normalize_kernel<true>, grid, block, 0, (hipStream_t)stream, u, rows, d, (long)ldu, psi, (const int*)n_utts, out, (long)ldo);
-    else hipLaunchKernelGGL(backend_plda_normalize_kernel<false>, grid, block, 0, (hipStream_t)stream, u, rows, d, (long)ldu, psi, (const int*)n_utts, out, (long)ldo);
-    XV_LAUNCH_CHECK();
-    return 0;
+    if (const int rc = sc_check_row_out("backend_plda_normalize", "u", u, ldu, "out", out, ldo, rows, d, "psi", psi)) return rc;
+    return sc_launch_rows(backend_plda_normalize_kernel<true>, backend_plda_normalize_kernel<false>, sc_vec_ok(d, {ldu, ldo}, {u, out, psi}), rows, nullptr,
+                          (hipStream_t)stream, u, rows, d, ldu, psi, n_utts, out, ldo);
 }
 
 extern "C" int xv_backend_plda_trials(void* stream, const float* e, int lde, int ne, const float* t, int ldt, int nt, int d, const int32_t* ei,
@@ -249,11 +217,7 @@ extern "C" int xv_backend_plda_trials(void* stream, const float* e, int lde, int
     XV_REQUIRE(d > 0, "backend_plda_trials: d must be positive (got %d)", d);
     XV_REQUIRE(e && t && ei && ti && nidx && coef && g && k0 && out && ne > 0 && nt > 0 && m > 0 && n_distinct > 0, "backend_plda_trials: bad arguments");
     XV_REQUIRE(lde >= d && ldt >= d && ldc >= d, "backend_plda_trials: a pitch is below d (d=%d lde=%d ldt=%d ldc=%d)", d, lde, ldt, ldc);
-    XV_REQUIRE(m <= (int64_t)SC_ROWS_PER_WG * 0x7fffffff, "backend_plda_trials: too many trials in one call (%lld)", (long long)m);
-    const bool vec = d % 4 == 0 && lde % 4 == 0 && ldt % 4 == 0 && ldc % 4 == 0 && sc_aligned16(e) && sc_aligned16(t) && sc_aligned16(coef) && sc_aligned16(g);
-    const dim3 grid((unsigned)((m + SC_ROWS_PER_WG - 1) / SC_ROWS_PER_WG)), block(256);
-    if (vec) hipLaunchKernelGGL(backend_plda_trials_kernel<true>, grid, block, 0, (hipStream_t)stream, e, (long)lde, t, (long)ldt, d, (const int*)ei, (const int*)ti, (long)m, (const int*)nidx, coef, (long)ldc, g, k0, out);
-    else hipLaunchKernelGGL(backend_plda_trials_kernel<false>, grid, block, 0, (hipStream_t)stream, e, (long)lde, t, (long)ldt, d, (const int*)ei, (const int*)ti, (long)m, (const int*)nidx, coef, (long)ldc, g, k0, out);
-    XV_LAUNCH_CHECK();
-    return 0;
+    return sc_launch_rows(backend_plda_trials_kernel<true>, backend_plda_trials_kernel<false>, sc_vec_ok(d, {lde, ldt, ldc}, {e, t, coef, g}), m,
+                          "backend_plda_trials: too many trials in one call (%lld)", (hipStream_t)stream, e, lde, t, ldt, d, ei, ti, m, nidx, coef, ldc, g, k0,
+                          out);
 }

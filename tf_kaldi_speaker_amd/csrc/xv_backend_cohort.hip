@@ -22,24 +22,22 @@
 //   GEMM      xs_c carries two roundings (iv a, then times x); each of the kd steps of a sum of products, in whatever order the GEMM takes
 //             its K, rounds at most twice (the product and the add; once where the unit fuses them), every partial sum bounded by
 //             sum_c |xs_c t_c|: (2 kd + 2) EPS sum_c |xs_c t_c|
-//   C_q(t_j)  a term 0.5 ((g - iv) t) t carries two roundings and the fma's; the chain is sc_row_dot's: (chain(d) + 2) EPS sum_c |term|
-//   R(x_r)    a term (a xs) x carries xs's two roundings and one more, the chain the same, then one fma -0.5 S + k0:
+//   C_q(t_j)  a term 0.5 ((g - iv) t) t carries two roundings and the fma's; the chain is sc_row_sum's: (chain(d) + 2) EPS sum_c |term|
+//   R(x_r)    a term (a xs) x carries xs's two roundings and one more, the chain the same (the fold kernel walks sc_row_sum's lanes,
+//             one fma on acc per column), then one fma -0.5 S + k0:
 //             (chain(d) + 3) EPS sum_c |term| + EPS |R|
 //   v         two adds: 2 EPS (|slab| + |C| + |R|)
 // together at most c1 EPS (sum |xs t| + sum |terms of C| + sum |terms of R| + |k0|) with c1 = max(2 kd + 2, chain(d) + 3) + 4: the three
 // roundings above that every part meets, and one more for the second order (c1 EPS < 1e-4, so (1 + EPS)^c1 - 1 < (c1 + 1) EPS).  The test
 // asserts exactly this c1.
-#include <algorithm>
-
 #include "xv_common.h"
 #include "xv_ew.h"
 #include "xv_gemm.h"
 #include "xv_rowsum.h"
+#include "xv_score_launch.h"
 #include "xv_select.h"
 
-// ct[q][j] = 0.5 sum_c (g[c] - iv_q[c]) t_j[c]^2: one wave per (q, j).  coef[q] = (a[ldk], iv[ldk]).  The lane loop and the butterfly are
-// sc_row_dot's (xv_rowsum.h) written out, because the term has three factors where the helper takes two: keep the two in step - chain(d)
-// in the budget above is that helper's figure.  (The fold kernel below and backend_plda_trials_kernel restate it for the same reason.)
+// ct[q][j] = 0.5 sum_c (g[c] - iv_q[c]) t_j[c]^2: one wave per (q, j).  coef[q] = (a[ldk], iv[ldk]).  The sum is sc_row_sum's.
 template <bool VEC>
 __global__ __launch_bounds__(256) void plda_cohort_colterm_kernel(const float* __restrict__ cohort, long ldc, int n_cohort, int d,
                                                                   const float* __restrict__ coef, long ldk, int n_distinct,
@@ -51,25 +49,13 @@ __global__ __launch_bounds__(256) void plda_cohort_colterm_kernel(const float* _
     const int q = (int)(idx / n_cohort), j = (int)(idx - (long)q * n_cohort);
     const float* tr = cohort + (long)j * ldc;
     const float* ci = coef + ((long)q * 2 + 1) * ldk;
-    float acc = 0.f;
-    if (VEC) {
-        for (int p = lane; p < d / 4; p += XV_WAVE) {
-            const f32x4 tv = *(const f32x4*)(tr + 4 * p), iv = *(const f32x4*)(ci + 4 * p), gv = *(const f32x4*)(g + 4 * p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc = fmaf(0.5f * ((gv[k] - iv[k]) * tv[k]), tv[k], acc);
-        }
-    } else {
-        for (int c = lane; c < d; c += XV_WAVE) {
-            const float tc = tr[c];
-            acc = fmaf(0.5f * ((g[c] - ci[c]) * tc), tc, acc);
-        }
-    }
-    const float s = wave_sum(acc);
+    const float s = sc_row_sum<VEC>(d, lane, [](float acc, float tc, float ic, float gc) { return fmaf(0.5f * ((gc - ic) * tc), tc, acc); }, tr, ci, g);
     if (lane == 0) ct[(long)q * pitch + j] = s;
 }
 
 // xs[r][c] = (iv_q[c] a_q[c]) x[r][c] for c < d, 0 for d <= c < kd (the GEMM operand); rterm[r] = k0[q] - 0.5 sum_c (a_q[c] xs[r][c]) x[r][c];
-// q = nidx[r] (nullptr: 0).  One wave per row.
+// q = nidx[r] (nullptr: 0).  One wave per row.  The lanes and the butterfly are sc_row_sum's (xv_rowsum.h) written out: the pass that sums
+// also stores xs, and its scalar form runs on to kd for the padding, which is neither that walker nor sc_row_store.
 template <bool VEC>
 __global__ __launch_bounds__(256) void plda_cohort_fold_kernel(const float* __restrict__ x, long ldx, int rows, int d, const int* __restrict__ nidx,
                                                                const float* __restrict__ coef, long ldk, const float* __restrict__ k0,
@@ -122,14 +108,31 @@ struct PcRow {
     __device__ __forceinline__ float load1(int i) const { return (slab[i] + ct[i]) + rt; }
 };
 
-// Workspace, in floats: [ct: n_distinct x pitch][slab: tile x pitch][xs: tile x kd][rterm: tile], pitch = n_cohort rounded up to 4, kd = d
-// rounded up to 4, tile = the rows of one round, a multiple of 128 - so every part starts on a 16-byte boundary.
-static size_t pc_row_floats(size_t pitch, int kd) { return pitch + (size_t)kd + 1; }
+// The column terms of every (q, cohort row) and the fold of m rows: the two launches the cohort op and the dense op share.  too_many: the
+// op's refusal of more pairs than one grid takes (sc_launch_rows).
+static int pc_launch_colterm(hipStream_t s, const char* too_many, const float* cohort, int ldc, int n_cohort, int d, const float* coef, int ldk,
+                             int n_distinct, const float* g, float* ct, size_t pitch) {
+    return sc_launch_rows(plda_cohort_colterm_kernel<true>, plda_cohort_colterm_kernel<false>, sc_vec_ok(d, {ldc, ldk}, {cohort, coef, g}),
+                          (long)n_distinct * n_cohort, too_many, s, cohort, ldc, n_cohort, d, coef, ldk, n_distinct, g, ct, pitch);
+}
+static int pc_launch_fold(hipStream_t s, const float* x, int ldx, int m, int d, const int* nidx, const float* coef, int ldk, const float* k0, float* xs,
+                          int kd, float* rterm) {
+    return sc_launch_rows(plda_cohort_fold_kernel<true>, plda_cohort_fold_kernel<false>, sc_vec_ok(d, {ldx, ldk}, {x, coef}), m, nullptr, s, x, ldx, m, d,
+                          nidx, coef, ldk, k0, xs, kd, rterm);
+}
+
+// Workspace of the cohort op, as float offsets: [ct: n_distinct x pitch][slab: tile x pitch][xs: tile x kd][rterm: tile], pitch = n_cohort
+// rounded up to 4, kd = d rounded up to 4, tile = the rows of one round, a multiple of 128 - so every part starts on a 16-byte boundary.
+struct PcLayout {
+    size_t pitch, kd, slab, xs, rterm, total;      // (ct is at 0)
+    PcLayout(size_t tile, int n_cohort, int d, int n_distinct)
+        : pitch(sc_slab_pitch(n_cohort)), kd(xv_align(d > 0 ? d : 1, 4)), slab((size_t)(n_distinct > 0 ? n_distinct : 1) * pitch),
+          xs(slab + tile * pitch), rterm(xs + tile * kd), total(rterm + tile) {}
+    size_t rows_that_fit(size_t floats) const { return (floats - slab) / (pitch + kd + 1); }      // (floats >= slab)
+};
 
 extern "C" size_t xv_backend_plda_cohort_workspace_bytes(int rows, int n_cohort, int d, int n_distinct) {
-    const size_t pitch = sc_slab_pitch(n_cohort);
-    const int kd = (int)xv_align(d > 0 ? d : 1, 4);
-    return ((size_t)(n_distinct > 0 ? n_distinct : 1) * pitch + xv_align((size_t)(rows > 0 ? rows : 1), SC_TILE_ROWS) * pc_row_floats(pitch, kd)) * sizeof(float);
+    return PcLayout(xv_align((size_t)(rows > 0 ? rows : 1), SC_TILE_ROWS), n_cohort, d, n_distinct).total * sizeof(float);
 }
 
 extern "C" int xv_backend_plda_cohort_stats(void* stream, const float* x, int ldx, int rows, const int32_t* nidx, const float* cohort, int ldc,
@@ -144,49 +147,26 @@ extern "C" int xv_backend_plda_cohort_stats(void* stream, const float* x, int ld
     XV_REQUIRE(ldcoef >= d, "backend_plda_cohort_stats: the pitch of coef is below d (d=%d ldcoef=%d)", d, ldcoef);
     // (what the GEMM would refuse, asked here so that a refusal comes before the first launch)
     XV_REQUIRE(ldc % 4 == 0 && sc_aligned16(cohort), "backend_plda_cohort_stats: the cohort must be a GEMM operand (pitch a multiple of 4, 16-byte aligned; ldc=%d)", ldc);
-    const size_t pitch = sc_slab_pitch(n_cohort);
-    const size_t head = (size_t)n_distinct * pitch, per_row = pc_row_floats(pitch, kd), ws_floats = ws_bytes / sizeof(float);
-    XV_REQUIRE(ws && sc_aligned16(ws) && ws_floats >= head && (ws_floats - head) / per_row >= SC_TILE_ROWS,
+    const PcLayout one(SC_TILE_ROWS, n_cohort, d, n_distinct);
+    XV_REQUIRE(ws && sc_aligned16(ws) && ws_bytes / sizeof(float) >= one.total,
                "backend_plda_cohort_stats: workspace of %zu bytes, the column terms and at least one %d-row tile need %zu (16-byte aligned)", ws_bytes,
-               SC_TILE_ROWS, (head + (size_t)SC_TILE_ROWS * per_row) * sizeof(float));
+               SC_TILE_ROWS, one.total * sizeof(float));
     hipStream_t s = (hipStream_t)stream;
-    // rows per round: whole GEMM row tiles, as many as the workspace holds and as the GEMM addresses (an operand spans less than 4 GB)
-    const size_t fit = (ws_floats - head) / per_row / SC_TILE_ROWS * SC_TILE_ROWS;
-    const size_t span = (((size_t)1 << 32) - 1) / ((size_t)kd * sizeof(float));
-    const size_t cap = span > SC_TILE_ROWS + 1 ? (span - 1) / SC_TILE_ROWS * SC_TILE_ROWS : SC_TILE_ROWS;
-    const int tile = (int)std::min(std::min(fit, cap), (size_t)1 << 20);
-    float* ct = (float*)ws;
-    float* slab = ct + head;
-    float* xs = slab + (size_t)tile * pitch;
-    float* rterm = xs + (size_t)tile * kd;
+    const int tile = sc_tile_rows(one.rows_that_fit(ws_bytes / sizeof(float)), kd);
+    const PcLayout at(tile, n_cohort, d, n_distinct);
+    float *ct = (float*)ws, *slab = ct + at.slab, *xs = ct + at.xs, *rterm = ct + at.rterm;
     const int k = top_k < n_cohort ? top_k : n_cohort;
-    const dim3 block(256);
-    const bool vec_c = d % 4 == 0 && ldc % 4 == 0 && ldcoef % 4 == 0 && sc_aligned16(cohort) && sc_aligned16(coef) && sc_aligned16(g);
-    const long pairs = (long)n_distinct * n_cohort;
-    XV_REQUIRE(pairs <= (long)SC_ROWS_PER_WG * 0x7fffffff, "backend_plda_cohort_stats: too many (count, cohort row) pairs in one call (%ld)", pairs);
-    const dim3 cgrid((unsigned)((pairs + SC_ROWS_PER_WG - 1) / SC_ROWS_PER_WG));
-    if (vec_c) hipLaunchKernelGGL(plda_cohort_colterm_kernel<true>, cgrid, block, 0, s, cohort, (long)ldc, n_cohort, d, coef, (long)ldcoef, n_distinct, g, ct, (long)pitch);
-    else hipLaunchKernelGGL(plda_cohort_colterm_kernel<false>, cgrid, block, 0, s, cohort, (long)ldc, n_cohort, d, coef, (long)ldcoef, n_distinct, g, ct, (long)pitch);
-    XV_LAUNCH_CHECK();
-    const bool vec_x = d % 4 == 0 && ldx % 4 == 0 && ldcoef % 4 == 0 && sc_aligned16(x) && sc_aligned16(coef);
+    if (const int rc = pc_launch_colterm(s, "backend_plda_cohort_stats: too many (count, cohort row) pairs in one call (%lld)", cohort, ldc, n_cohort, d, coef,
+                                         ldcoef, n_distinct, g, ct, at.pitch))
+        return rc;
     for (int r0 = 0; r0 < rows; r0 += tile) {
         const int m = rows - r0 < tile ? rows - r0 : tile;
-        const float* xr = x + (size_t)r0 * ldx;
-        const int* nr = nidx ? (const int*)nidx + r0 : nullptr;
-        const dim3 fgrid(xv_cdiv(m, SC_ROWS_PER_WG));
-        if (vec_x) hipLaunchKernelGGL(plda_cohort_fold_kernel<true>, fgrid, block, 0, s, xr, (long)ldx, m, d, nr, coef, (long)ldcoef, k0, xs, kd, rterm);
-        else hipLaunchKernelGGL(plda_cohort_fold_kernel<false>, fgrid, block, 0, s, xr, (long)ldx, m, d, nr, coef, (long)ldcoef, k0, xs, kd, rterm);
-        XV_LAUNCH_CHECK();
+        const int* nr = nidx ? nidx + r0 : nullptr;
+        if (const int rc = pc_launch_fold(s, x + (size_t)r0 * ldx, ldx, m, d, nr, coef, ldcoef, k0, xs, kd, rterm)) return rc;
         // xv_score_cohort_stats's GEMM, on the folded rows
-        XvGemmNT gm = {};
-        gm.A = xs; gm.lda = kd; gm.a_rps = 1; gm.a_pitch = 1;
-        gm.Bt = cohort; gm.ldb = ldc;
-        gm.C = slab; gm.ldc = (long)pitch;
-        gm.M = m; gm.N = n_cohort; gm.K = kd;
-        const int rc = xv_launch_gemm_nt(s, gm);
-        if (rc) return rc;
+        if (const int rc = sc_gemm_nt(s, xs, kd, cohort, ldc, slab, (long)at.pitch, m, n_cohort, kd)) return rc;
         hipLaunchKernelGGL((sc_select_kernel<PcRow, const float*, const int*, const float*>), dim3(m), dim3(SC_SEL_THREADS), 0, s, (const float*)slab,
-                           (long)pitch, n_cohort, k, stats + 2 * (size_t)r0, (const float*)ct, nr, (const float*)rterm);
+                           (long)at.pitch, n_cohort, k, stats + 2 * (size_t)r0, (const float*)ct, nr, (const float*)rterm);
         XV_LAUNCH_CHECK();
     }
     return 0;
@@ -205,11 +185,16 @@ __global__ __launch_bounds__(256) void plda_dense_finish_kernel(float* out, long
     *o = (*o + ct[j]) + rterm[r];
 }
 
-// Workspace, in floats: [ct: pitch][xs: n x kd][rterm: n], pitch = n rounded up to 4 - every part starts on a 16-byte boundary.
-extern "C" size_t xv_backend_plda_dense_workspace_bytes(int n, int d) {
-    const size_t rows = n > 0 ? n : 1;
-    return (sc_slab_pitch((int)rows) + rows * xv_align(d > 0 ? d : 1, 4) + xv_align(rows, 4)) * sizeof(float);
-}
+// Workspace of the dense op, as float offsets: [ct: pitch][xs: n x kd][rterm: n], pitch = n rounded up to 4 - every part starts on a 16-byte
+// boundary.
+struct PdLayout {
+    size_t pitch, kd, xs, rterm, total;      // (ct is at 0)
+    PdLayout(int n, int d)
+        : pitch(sc_slab_pitch(n)), kd(xv_align(d > 0 ? d : 1, 4)), xs(pitch), rterm(xs + (size_t)(n > 0 ? n : 1) * kd),
+          total(rterm + xv_align(n > 0 ? n : 1, 4)) {}
+};
+
+extern "C" size_t xv_backend_plda_dense_workspace_bytes(int n, int d) { return PdLayout(n, d).total * sizeof(float); }
 
 extern "C" int xv_backend_plda_dense(void* stream, const float* x, int ldx, int n, int d, const float* coef, int ldk, const float* g, const float* k0,
                                      float* out, int ldo, void* ws, size_t ws_bytes) {
@@ -222,32 +207,17 @@ extern "C" int xv_backend_plda_dense(void* stream, const float* x, int ldx, int 
     XV_REQUIRE(ldo >= n, "backend_plda_dense: the pitch of out is below n (n=%d ldo=%d)", n, ldo);
     XV_REQUIRE(ldx % 4 == 0 && sc_aligned16(x), "backend_plda_dense: the rows must be a GEMM operand (pitch a multiple of 4, 16-byte aligned; ldx=%d)", ldx);
     XV_REQUIRE(n <= 65535, "backend_plda_dense: too many rows in one call (%d)", n);
-    XV_REQUIRE(ws && sc_aligned16(ws) && ws_bytes >= xv_backend_plda_dense_workspace_bytes(n, d),
-               "backend_plda_dense: workspace of %zu bytes, %zu needed (16-byte aligned)", ws_bytes, xv_backend_plda_dense_workspace_bytes(n, d));
+    const PdLayout at(n, d);
+    XV_REQUIRE(ws && sc_aligned16(ws) && ws_bytes >= at.total * sizeof(float), "backend_plda_dense: workspace of %zu bytes, %zu needed (16-byte aligned)",
+               ws_bytes, at.total * sizeof(float));
     XV_REQUIRE(!sc_overlap(x, (size_t)(n - 1) * ldx + kd, out, (size_t)(n - 1) * ldo + n), "backend_plda_dense: x and out overlap");
     hipStream_t s = (hipStream_t)stream;
-    const size_t pitch = sc_slab_pitch(n);
-    float* ct = (float*)ws;
-    float* xs = ct + pitch;
-    float* rterm = xs + (size_t)n * kd;
-    const dim3 block(256), rgrid(xv_cdiv(n, SC_ROWS_PER_WG));
-    // the column terms and the fold of plda_cohort_stats with n_distinct = 1 and the rows as their own cohort
-    const bool vec = d % 4 == 0 && ldk % 4 == 0 && sc_aligned16(coef) && sc_aligned16(g);
-    if (vec) hipLaunchKernelGGL(plda_cohort_colterm_kernel<true>, rgrid, block, 0, s, x, (long)ldx, n, d, coef, (long)ldk, 1, g, ct, (long)pitch);
-    else hipLaunchKernelGGL(plda_cohort_colterm_kernel<false>, rgrid, block, 0, s, x, (long)ldx, n, d, coef, (long)ldk, 1, g, ct, (long)pitch);
-    XV_LAUNCH_CHECK();
-    const bool vec_x = d % 4 == 0 && ldk % 4 == 0 && sc_aligned16(coef);
-    if (vec_x) hipLaunchKernelGGL(plda_cohort_fold_kernel<true>, rgrid, block, 0, s, x, (long)ldx, n, d, (const int*)nullptr, coef, (long)ldk, k0, xs, kd, rterm);
-    else hipLaunchKernelGGL(plda_cohort_fold_kernel<false>, rgrid, block, 0, s, x, (long)ldx, n, d, (const int*)nullptr, coef, (long)ldk, k0, xs, kd, rterm);
-    XV_LAUNCH_CHECK();
-    XvGemmNT gm = {};
-    gm.A = xs; gm.lda = kd; gm.a_rps = 1; gm.a_pitch = 1;
-    gm.Bt = x; gm.ldb = ldx;
-    gm.C = out; gm.ldc = ldo;
-    gm.M = n; gm.N = n; gm.K = kd;
-    const int rc = xv_launch_gemm_nt(s, gm);
-    if (rc) return rc;
-    hipLaunchKernelGGL(plda_dense_finish_kernel, dim3(xv_cdiv(n, 256), n), block, 0, s, out, (long)ldo, n, (const float*)ct, (const float*)rterm);
+    float *ct = (float*)ws, *xs = ct + at.xs, *rterm = ct + at.rterm;
+    // the column terms and the fold of plda_cohort_stats with n_distinct = 1 and the rows as their own cohort (n <= 65535 pairs: no refusal)
+    if (const int rc = pc_launch_colterm(s, nullptr, x, ldx, n, d, coef, ldk, 1, g, ct, at.pitch)) return rc;
+    if (const int rc = pc_launch_fold(s, x, ldx, n, d, nullptr, coef, ldk, k0, xs, kd, rterm)) return rc;
+    if (const int rc = sc_gemm_nt(s, xs, kd, x, ldx, out, ldo, n, n, kd)) return rc;
+    hipLaunchKernelGGL(plda_dense_finish_kernel, dim3(xv_cdiv(n, 256), n), dim3(256), 0, s, out, (long)ldo, n, (const float*)ct, (const float*)rterm);
     XV_LAUNCH_CHECK();
     return 0;
 }

@@ -31,7 +31,13 @@ static inline int grid_for(long total, int block, int cap = 4096) {
     return (int)g;
 }
 
+// butterfly: a + b and b + a are the same bits, so every lane holds one value
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;

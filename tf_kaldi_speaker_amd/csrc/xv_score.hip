@@ -6,16 +6,14 @@
 // select per row, xv_select.h).  No floating-point atomics and no cross-workgroup hand-over in
 // these kernels (the select's histogram is integer LDS atomics: a count does not depend on the order of its increments): a result
 // depends on the shape of the call only, so it is the same bits every time.  gfx950 only.
-#include <algorithm>
-
 #include "xv_common.h"
 #include "xv_ew.h"
-#include "xv_gemm.h"
-#include "xv_rowsum.h"      // sc_row_dot and chain(d), SC_ROWS_PER_WG, sc_aligned16, sc_overlap
-#include "xv_select.h"      // sc_select_kernel: the exact top-k selection and its statistics; SC_TILE_ROWS, sc_slab_pitch
+#include "xv_rowsum.h"            // sc_row_sum and chain(d), sc_row_store, SC_ROWS_PER_WG
+#include "xv_score_launch.h"      // the operand checks, sc_launch_rows, sc_gemm_nt, sc_tile_rows
+#include "xv_select.h"            // sc_select_kernel: the exact top-k selection and its statistics; SC_TILE_ROWS, sc_slab_pitch
 
 // y[r][c] = v * rsqrt(max(Σ v², 1e-12)), v = x[r][c] - mean[c], for c < d; y[r][d .. ldy) = 0.  One wave per row.  In place (y == x,
-// ldy == ldx) a lane reads back exactly the elements it then overwrites, and the padding belongs to the row.
+// ldy == ldx) a lane reads back exactly the elements it then overwrites, and the padding belongs to the row (sc_row_store).
 template <bool VEC, bool SUB>
 __global__ __launch_bounds__(256) void score_prepare_kernel(const float* x, int rows, int d, long ldx, const float* __restrict__ mean, float* y, long ldy) {
     XV_EW_PRIORITY();
@@ -23,29 +21,11 @@ __global__ __launch_bounds__(256) void score_prepare_kernel(const float* x, int 
     if (r >= rows) return;
     const float* xr = x + (long)r * ldx;
     float* yr = y + (long)r * ldy;
-    const float ss = sc_row_dot<VEC, SUB>(xr, xr, mean, d, lane);
+    const float ss = SUB ? sc_row_sum<VEC>(d, lane, [](float acc, float u, float m) { u -= m; return fmaf(u, u, acc); }, xr, mean)
+                         : sc_row_sum<VEC>(d, lane, [](float acc, float u, float v) { return fmaf(u, v, acc); }, xr, xr);
     const float inv = rsqrtf(fmaxf(ss, 1e-12f));
-    if (VEC) {
-        for (int q = lane; q < (int)(ldy / 4); q += XV_WAVE) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (q < d / 4) {
-                v = *(const f32x4*)(xr + 4 * q);
-                if (SUB) v -= *(const f32x4*)(mean + 4 * q);
-                v *= inv;
-            }
-            *(f32x4*)(yr + 4 * q) = v;
-        }
-    } else {
-        for (int c = lane; c < (int)ldy; c += XV_WAVE) {
-            float v = 0.f;
-            if (c < d) {
-                v = xr[c];
-                if (SUB) v -= mean[c];
-                v *= inv;
-            }
-            yr[c] = v;
-        }
-    }
+    if (SUB) sc_row_store<VEC>(yr, ldy, d, lane, [inv](auto v, auto m) { v -= m; return v * inv; }, xr, mean);
+    else sc_row_store<VEC>(yr, ldy, d, lane, [inv](auto v) { return v * inv; }, xr);
 }
 
 // AS-norm of a score s with the cohort statistics (μ, σ) of its enrolment row a and its test row b: one expression, so score_trials_kernel
@@ -55,7 +35,7 @@ __device__ __forceinline__ float sc_as_norm(float s, const float* __restrict__ e
 }
 
 // out[j] = s = Σ_c e[ei[j]][c] * t[ti[j]][c], or with the row statistics 0.5 * ((s - μe) / σe + (s - μt) / σt).  One wave per trial;
-// the sum is sc_row_dot's (chain(d) above).
+// the sum is sc_row_sum's (chain(d) of xv_rowsum.h).
 template <bool VEC>
 __global__ __launch_bounds__(256) void score_trials_kernel(const float* __restrict__ e, long lde, const float* __restrict__ t, long ldt, int d,
                                                            const int* __restrict__ ei, const int* __restrict__ ti, long m,
@@ -66,7 +46,7 @@ __global__ __launch_bounds__(256) void score_trials_kernel(const float* __restri
     const int lane = threadIdx.x & 63;
     if (j >= m) return;
     const int a = ei[j], b = ti[j];
-    float s = sc_row_dot<VEC, false>(e + (long)a * lde, t + (long)b * ldt, nullptr, d, lane);
+    float s = sc_row_sum<VEC>(d, lane, [](float acc, float u, float v) { return fmaf(u, v, acc); }, e + (long)a * lde, t + (long)b * ldt);
     if (e_stats) s = sc_as_norm(s, e_stats, a, t_stats, b);
     if (lane == 0) out[j] = s;
 }
@@ -86,19 +66,10 @@ __global__ __launch_bounds__(256) void score_normalize_kernel(const float* score
 extern "C" int xv_score_prepare(void* stream, const float* x, int rows, int d, int ldx, const float* mean, float* y, int ldy) {
     XV_REQUIRE(x && y && rows > 0 && d > 0, "score_prepare: bad arguments");
     XV_REQUIRE(ldx >= d && ldy >= d, "score_prepare: a pitch is below d (d=%d ldx=%d ldy=%d)", d, ldx, ldy);
-    const bool in_place = x == y && ldx == ldy;
-    XV_REQUIRE(in_place || !sc_overlap(x, (size_t)(rows - 1) * ldx + d, y, (size_t)rows * ldy),
-               "score_prepare: x and y overlap (in place needs y == x and the same pitch)");
-    XV_REQUIRE(!mean || !sc_overlap(mean, d, y, (size_t)rows * ldy), "score_prepare: mean and y overlap");
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && sc_aligned16(x) && sc_aligned16(y) && (!mean || sc_aligned16(mean));
-    const dim3 grid(xv_cdiv(rows, SC_ROWS_PER_WG)), block(256);
-    if (vec && mean) hipLaunchKernelGGL((score_prepare_kernel<true, true>), grid, block, 0, s, x, rows, d, (long)ldx, mean, y, (long)ldy);
-    else if (vec) hipLaunchKernelGGL((score_prepare_kernel<true, false>), grid, block, 0, s, x, rows, d, (long)ldx, mean, y, (long)ldy);
-    else if (mean) hipLaunchKernelGGL((score_prepare_kernel<false, true>), grid, block, 0, s, x, rows, d, (long)ldx, mean, y, (long)ldy);
-    else hipLaunchKernelGGL((score_prepare_kernel<false, false>), grid, block, 0, s, x, rows, d, (long)ldx, mean, y, (long)ldy);
-    XV_LAUNCH_CHECK();
-    return 0;
+    if (const int rc = sc_check_row_out("score_prepare", "x", x, ldx, "y", y, ldy, rows, d, "mean", mean)) return rc;
+    return sc_launch_rows(mean ? score_prepare_kernel<true, true> : score_prepare_kernel<true, false>,
+                          mean ? score_prepare_kernel<false, true> : score_prepare_kernel<false, false>,
+                          sc_vec_ok(d, {ldx, ldy}, {x, y, mean}), rows, nullptr, (hipStream_t)stream, x, rows, d, ldx, mean, y, ldy);
 }
 
 extern "C" int xv_score_trials(void* stream, const float* e, int lde, int ne, const float* t, int ldt, int nt, int d, const int32_t* ei,
@@ -106,14 +77,8 @@ extern "C" int xv_score_trials(void* stream, const float* e, int lde, int ne, co
     XV_REQUIRE(e && t && ei && ti && out && ne > 0 && nt > 0 && d > 0 && m > 0, "score_trials: bad arguments");
     XV_REQUIRE(lde >= d && ldt >= d, "score_trials: a pitch is below d (d=%d lde=%d ldt=%d)", d, lde, ldt);
     XV_REQUIRE((e_stats != nullptr) == (t_stats != nullptr), "score_trials: e_stats and t_stats must both be given or both be NULL");
-    XV_REQUIRE(m <= (int64_t)SC_ROWS_PER_WG * 0x7fffffff, "score_trials: too many trials in one call (%lld)", (long long)m);
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec = d % 4 == 0 && lde % 4 == 0 && ldt % 4 == 0 && sc_aligned16(e) && sc_aligned16(t);
-    const dim3 grid((unsigned)((m + SC_ROWS_PER_WG - 1) / SC_ROWS_PER_WG)), block(256);
-    if (vec) hipLaunchKernelGGL(score_trials_kernel<true>, grid, block, 0, s, e, (long)lde, t, (long)ldt, d, (const int*)ei, (const int*)ti, (long)m, e_stats, t_stats, out);
-    else hipLaunchKernelGGL(score_trials_kernel<false>, grid, block, 0, s, e, (long)lde, t, (long)ldt, d, (const int*)ei, (const int*)ti, (long)m, e_stats, t_stats, out);
-    XV_LAUNCH_CHECK();
-    return 0;
+    return sc_launch_rows(score_trials_kernel<true>, score_trials_kernel<false>, sc_vec_ok(d, {lde, ldt}, {e, t}), m,
+                          "score_trials: too many trials in one call (%lld)", (hipStream_t)stream, e, lde, t, ldt, d, ei, ti, m, e_stats, t_stats, out);
 }
 
 extern "C" size_t xv_score_cohort_workspace_bytes(int rows, int n_cohort, int d) {
@@ -133,23 +98,11 @@ extern "C" int xv_score_cohort_stats(void* stream, const float* x, int ldx, int 
                "score_cohort_stats: workspace of %zu bytes, at least one %d-row tile of %zu needed (16-byte aligned)", ws_bytes, SC_TILE_ROWS,
                (size_t)SC_TILE_ROWS * pitch * sizeof(float));
     hipStream_t s = (hipStream_t)stream;
-    // rows per slab: whole GEMM row tiles, as many as the workspace holds and as the GEMM addresses (an operand spans less than 4 GB:
-    // xv_launch_gemm_nt; a pitch so long that not even one tile fits under that is refused there)
-    const size_t fit = ws_bytes / (pitch * sizeof(float)) / SC_TILE_ROWS * SC_TILE_ROWS;
-    const size_t span = (((size_t)1 << 32) - 1) / ((size_t)ldx * sizeof(float));
-    const size_t cap = span > SC_TILE_ROWS + 1 ? (span - 1) / SC_TILE_ROWS * SC_TILE_ROWS : SC_TILE_ROWS;
-    const int tile = (int)std::min(std::min(fit, cap), (size_t)1 << 20);
+    const int tile = sc_tile_rows(ws_bytes / (pitch * sizeof(float)), ldx);
     const int k = top_k < n_cohort ? top_k : n_cohort;
     for (int r0 = 0; r0 < rows; r0 += tile) {
         const int m = rows - r0 < tile ? rows - r0 : tile;
-        // xv_affine_forward with k = 1, segs = m, t_in = 1, except that a row pitch may exceed K; no scratch: one workgroup per tile
-        XvGemmNT g = {};
-        g.A = x + (size_t)r0 * ldx; g.lda = ldx; g.a_rps = 1; g.a_pitch = 1;
-        g.Bt = cohort; g.ldb = ldc;
-        g.C = (float*)ws; g.ldc = (long)pitch;
-        g.M = m; g.N = n_cohort; g.K = kd;
-        const int rc = xv_launch_gemm_nt(s, g);
-        if (rc) return rc;
+        if (const int rc = sc_gemm_nt(s, x + (size_t)r0 * ldx, ldx, cohort, ldc, (float*)ws, (long)pitch, m, n_cohort, kd)) return rc;
         hipLaunchKernelGGL(sc_select_kernel<ScSlabRow>, dim3(m), dim3(SC_SEL_THREADS), 0, s, (const float*)ws, (long)pitch, n_cohort, k, stats + 2 * (size_t)r0);
         XV_LAUNCH_CHECK();
     }
@@ -162,13 +115,7 @@ extern "C" int xv_score_dense(void* stream, const float* x, int ldx, int n, int 
     XV_REQUIRE(ldx >= kd, "score_dense: the pitch must reach d rounded up to 4 (d=%d ldx=%d)", d, ldx);
     XV_REQUIRE(ldo >= n, "score_dense: the pitch of out is below n (n=%d ldo=%d)", n, ldo);
     XV_REQUIRE(!sc_overlap(x, (size_t)(n - 1) * ldx + kd, out, (size_t)(n - 1) * ldo + n), "score_dense: x and out overlap");
-    // xv_score_cohort_stats's GEMM with the rows as their own cohort; no scratch: one workgroup per tile
-    XvGemmNT g = {};
-    g.A = x; g.lda = ldx; g.a_rps = 1; g.a_pitch = 1;
-    g.Bt = x; g.ldb = ldx;
-    g.C = out; g.ldc = ldo;
-    g.M = n; g.N = n; g.K = kd;
-    return xv_launch_gemm_nt((hipStream_t)stream, g);
+    return sc_gemm_nt((hipStream_t)stream, x, ldx, x, ldx, out, ldo, n, n, kd);      // xv_score_cohort_stats's GEMM with the rows as their own cohort
 }
 
 extern "C" int xv_score_normalize(void* stream, const float* scores, const int32_t* ei, const int32_t* ti, int64_t m, const float* e_stats,

@@ -16,8 +16,7 @@ static inline size_t sc_slab_pitch(int n_cohort) { return xv_align((size_t)(n_co
 
 // a double summed over the workgroup in a fixed order: butterfly inside each wave, the four wave totals added first to last
 __device__ __forceinline__ double sc_block_sum(double v, double* wtot, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     __syncthreads();      // (wtot may still be read from the call before)
     if ((tid & 63) == 0) wtot[tid >> 6] = v;
     __syncthreads();

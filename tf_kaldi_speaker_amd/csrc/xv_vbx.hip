@@ -63,18 +63,6 @@ __device__ __forceinline__ float vbx_sum32(float v) {
     return lo + hi;
 }
 
-__device__ __forceinline__ float vbx_wave_sum(float v) {      // butterfly: a + b and b + a are the same bits, so every lane holds one value
-#pragma unroll
-    for (int off = XV_WAVE / 2; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ double vbx_wave_sum(double v) {
-#pragma unroll
-    for (int off = XV_WAVE / 2; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 struct VbxArgs {
     const float* x; long x_floats;
     const int64_t* x_offsets; const int32_t* t; const int32_t* ld; const int32_t* s;
@@ -161,7 +149,7 @@ __global__ __launch_bounds__(VBX_THREADS) void vbx_kernel(VbxArgs g) {
         }
         gsum += -0.5 * (q + (double)D * 1.8378770664093454835606594728112);
     }
-    gsum = vbx_wave_sum(gsum);
+    gsum = wave_sum(gsum);
     if (lane == 0) dred[w] = gsum;
     for (long i = tid; i < (long)T * S; i += VBX_THREADS) gam[i] = g.gamma_in[pts + i];
     if (tid < VBX_MAX_S) pi_s[tid] = tid < S ? g.pi_in[ps + tid] : 0.f;
@@ -224,7 +212,7 @@ __global__ __launch_bounds__(VBX_THREADS) void vbx_kernel(VbxArgs g) {
                 }
                 if (tid < de) alpha[(s - sb) * de + tid] = a_lds;
                 if (s < s_end) {      // (uniform)
-                    term = vbx_wave_sum(term);
+                    term = wave_sum(term);
                     if (lane == 0) cpart[w][s] = term;
                 }
             }
@@ -256,7 +244,7 @@ __global__ __launch_bounds__(VBX_THREADS) void vbx_kernel(VbxArgs g) {
             }
             __syncthreads();      // (alpha is written again by the next sixteen)
         }
-        e2 = vbx_wave_sum(e2);
+        e2 = wave_sum(e2);
         if (lane == 0) dred[w] = e2;
         __syncthreads();
         const double second = 0.5 * (double)g.fb * (((dred[0] + dred[1]) + dred[2]) + dred[3]);
@@ -297,7 +285,7 @@ __global__ __launch_bounds__(VBX_THREADS) void vbx_kernel(VbxArgs g) {
         // (6) the log-likelihood
         double tll = 0.0;
         for (int t = tid; t < T; t += VBX_THREADS) tll += log((double)nn[t]) + (double)mx[t];
-        tll = vbx_wave_sum(tll);
+        tll = wave_sum(tll);
         if (lane == 0) dred[w] = tll;
         // (7) backward and the priors
         if (w == 0) {
