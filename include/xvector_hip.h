@@ -537,7 +537,8 @@ size_t xv_backend_plda_cohort_workspace_bytes(int rows, int n_cohort, int d, int
 int xv_backend_plda_cohort_stats(void* stream, const float* x, int ldx, int rows, const int32_t* nidx, const float* cohort, int ldc,
                                  int n_cohort, int d, const float* coef, int ldcoef, int n_distinct, const float* g, const float* k0,
                                  int top_k, float* stats, void* ws, size_t ws_bytes);
-/* plda_dense (ivector-plda-scoring-dense without its per-recording PCA: the all-pairs matrix of one recording, for the clusterer below):
+/* plda_dense (ivector-plda-scoring-dense behind its per-recording PCA, which is xv_backend_pca_plda below: with that op's map, psi and tables
+ * the recipe's scores under --target-energy, with the global model's the scores without it; the all-pairs matrix of one recording, for the clusterer):
  * out[r][j] = the one-utterance log-likelihood ratio of rows r and j of x [n][ldx] (PLDA-normalised with one utterance), in the factored
  * form of plda_cohort_stats with the single table entry of n_utts = 1 (coef [2][ldk], g, k0 [1]): out[r][j] = (slab[r][j] + C[j]) + R[r].
  * The column-term and fold kernels and the GEMM are plda_cohort_stats' (the rows are their own cohort); the GEMM writes the slab into out
@@ -614,6 +615,43 @@ int xv_vbx(void* stream, const float* x, int64_t x_floats, const int64_t* x_offs
            int b, int d, int max_t, int max_s, int64_t total_t, int64_t total_ts, int64_t total_s, const float* phi, const float* gamma_in,
            const float* pi_in, float loop_prob, float fa, float fb, int max_iters, double epsilon, float* gamma, float* pi, double* elbo,
            int32_t* n_iters, int32_t* labels, void* ws, size_t ws_bytes);
+
+/* The per-recording PCA in front of dense PLDA scoring (Kaldi's ivector-plda-scoring-dense --target-energy: callhome_diarization/v2 scores
+ * with --target-energy 0.9), as recalled from ivector-plda-scoring-dense.cc and restated - the energy rule among it; agreement with a run
+ * of Kaldi is not pinned.  b recordings per call, one workgroup each, no hand-over between workgroups: a recording's result depends on its
+ * own inputs only and is the same bits every time and in every slot of a batch.
+ * Inputs, all on the device: x, a packed fp32 buffer of x_floats floats; recording r's rows [n[r]][ld[r]], ld[r] >= d, start at float
+ * x_offsets[r] (int64): centred, LDA-transformed, unit-length vectors (what the recipe feeds the scoring, up to ivector-normalize-length's
+ * factor sqrt(d)).  w, bt: double [d][d], the within- and between-class covariances of the PLDA model at the scale sqrt(d),
+ * W = T^-1 T^-T and B = T^-1 diag(psi) T^-T, symmetric; mu: double [d], the model's mean.  None of them is modified.
+ * The arithmetic is part of the operation (tests/pca_plda_ref.py restates it).  Per recording, everything in double from the fp32 rows,
+ * every sum in a fixed order:
+ *   m = (1 / n) sum x_i,  C = (1 / n) sum x_i x_i^T - m m^T = P diag(s) P^T, s descending, negative round-off floored at 0
+ *   the kept dimension: dim = 1, e = 0; while (e / sum s <= target) { e += s[dim - 1]; dim++; }  p = min(dim, d): one more than the smallest
+ *   k whose first k eigenvalues hold more than `target` of the energy (Kaldi's loop; Kaldi has no cap at d).  n = 1 or sum s = 0: p = 0,
+ *   "score with the global model" (Kaldi's "PCA failed"), and only p and s are written
+ *   Q = the first p rows of P^T;  W' = Q W Q^T,  B' = Q B Q^T,  mu' = Q mu
+ *   L = chol(W'), T1 = L^-1;  T1 B' T1^T = U diag(psi) U^T, psi descending, floored at 0;  T' = U^T T1
+ * Both eigenproblems are solved by a cyclic Jacobi method in a fixed parallel (round-robin) order that stops after the first sweep in which
+ * no off-diagonal element exceeds 2^-60 of the matrix's Frobenius norm, at most 40 sweeps (csrc/xv_backend_pca.hip states it).  A p above
+ * the rank of C takes a direction from C's null space: arbitrary, as in Kaldi, but the same bits every time.
+ * Outputs, d4 = d rounded up to 4, each fp32 value rounded once from double: p int32 [b]; a [b][d4][d4], recording r's map
+ * sqrt(d) T' Q in its first p rows and d columns, the rest zero (sqrt(d), not sqrt(p): the PCA sees Kaldi's rows of length sqrt(d));
+ * offset [b][d4] = -T' mu'; psi [b][d4]; the one-utterance tables of the log-likelihood ratio coef [b][2][d4] = (psi / (psi + 1), 1 / v),
+ * v = 1 + psi / (psi + 1), g [b][d4] = 1 / (psi + 1), k0 [b] = -0.5 sum ln v + 0.5 sum ln(psi + 1), all zero behind p: operands of
+ * xv_affine_forward (k = 1), xv_backend_plda_normalize with d = p, and xv_backend_plda_dense.  Diagnostics in double: s [b][d] (of the
+ * unit-length rows' covariance), psi64 [b][d] (p entries written); sweeps int32 [b][2], the sweeps of the two eigenproblems.
+ * p[r] = -1: recording r's entries (n outside 1 .. 2048, ld < d, rows outside x) would take the kernel outside the buffers of the call, it
+ * is skipped; -2: an eigenproblem reached the sweep cap; -3: W' is not positive definite.  A recording with p <= 0 has nothing but p (and, for
+ * p = 0, s and sweeps) written.  ws: xv_backend_pca_plda_workspace_bytes bytes, 16-byte aligned (four matrices of (d rounded up to 2)^2
+ * doubles per recording).  Refused by name: b <= 0, d outside 1 .. 256, max_n (the largest n, a host value the caller states) outside
+ * 1 .. 2048 (the clusterer's cap), a target outside (0, 1], a workspace too small.  The device arrays are NOT checked on the host side of
+ * this call (ops.backend_pca_plda checks the host arrays before the upload).  NaN inputs are undefined. */
+size_t xv_backend_pca_plda_workspace_bytes(int b, int d);
+int xv_backend_pca_plda(void* stream, const float* x, int64_t x_floats, const int64_t* x_offsets, const int32_t* n, const int32_t* ld, int b,
+                        int d, int max_n, double target, const double* w, const double* bt, const double* mu, int32_t* p, float* a,
+                        float* offset, float* psi, float* coef, float* g, float* k0, double* s, double* psi64, int32_t* sweeps, void* ws,
+                        size_t ws_bytes);
 
 /* Kernel-layout weights for xv_affine_forward: wt[o][j*c_pad + c] = kernel[j][c][o]
  * (TF layout [k][C][O] of tdnn/tdnnX_{conv,dense}/kernel, tdnn.py:39,57,75,96,115,147,166);

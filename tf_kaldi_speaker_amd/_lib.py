@@ -315,6 +315,9 @@ SIGNATURES = {
     "xv_backend_plda_cohort_stats": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _SZ]),
     "xv_backend_plda_dense_workspace_bytes": (_SZ, [_I, _I]),
     "xv_backend_plda_dense": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _I, _VP, _SZ]),
+    "xv_backend_pca_plda_workspace_bytes": (_SZ, [_I, _I]),
+    "xv_backend_pca_plda": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _I, _I, _I, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                 _VP, _VP, _VP, _SZ]),
     "xv_ahc_workspace_bytes": (_SZ, [C.c_int64]),
     "xv_ahc_cluster": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, C.c_int64, C.c_int64, _F, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "xv_vbx_workspace_bytes": (_SZ, [C.c_int64, C.c_int64, C.c_int64, _I]),

@@ -16,10 +16,10 @@ import os
 import numpy as np
 
 try:
-    from .._host import cat, device_ops, pitch4, steps, upload
+    from .._host import cat, device_ops, exclusive_offsets, pitch4, steps, upload
     from .scoring import DEFAULT_WORKSPACE_BYTES, center_mean
 except (ImportError, ValueError):
-    from _host import cat, device_ops, pitch4, steps, upload
+    from _host import cat, device_ops, exclusive_offsets, pitch4, steps, upload
     from misc.scoring import DEFAULT_WORKSPACE_BYTES, center_mean
 
 _LOG = logging.getLogger("tf_kaldi_speaker_amd")
@@ -203,6 +203,27 @@ def plda_coefficients(psi, distinct_n):
     g[:d] = 1.0 / (psi + 1.0)
     k0 = (-0.5 * np.log(v).sum(axis=1) + 0.5 * np.log(psi + 1.0).sum()).astype(np.float32)
     return coef, g, k0
+
+
+def plda_covariances(plda):
+    """(W, B, mu) of a PLDA model (mean, transform T, psi), fp64: the within-class covariance W = T^-1 T^-T and the between-class covariance
+    B = T^-1 diag(psi) T^-T, both symmetrised, and the mean - what xv_backend_pca_plda projects into a recording's subspace."""
+    t_inv = np.linalg.inv(np.asarray(plda["transform"], dtype=np.float64))
+    w, b = t_inv @ t_inv.T, (t_inv * np.asarray(plda["psi"], dtype=np.float64)[None, :]) @ t_inv.T
+    return 0.5 * (w + w.T), 0.5 * (b + b.T), np.asarray(plda["mean"], dtype=np.float64)
+
+
+PCA_NO_TARGET = 0.001      # a target energy this close to 1 means no PCA at all (ivector-plda-scoring-dense returns early)
+
+
+def check_target_energy(target_energy, what):
+    """None, or the target energy as a float in (0, 1]; anything else is refused in the name of `what`."""
+    if target_energy is None:
+        return None
+    t = float(target_energy)
+    if not 0.0 < t <= 1.0:
+        raise ValueError("%s: target_energy must lie in (0, 1] (got %r)" % (what, target_energy))
+    return t
 
 
 def _device_rows(torch, matrix, device, d, what):
@@ -398,6 +419,7 @@ class BackendScorer(object):
     MODES = ("lda_cos", "plda")
     _cohort, top_k = None, 0      # no cohort until cohort() sets one
     _dense_tables = None          # the one-utterance coefficient tables on the device, built by the first dense()
+    _pca_model = None             # (W, B, mean) of the PLDA model in float64 on the device, built by the first prepare_pca()
 
     def __init__(self, backend, mode="plda", device="cuda:0", workspace_bytes=DEFAULT_WORKSPACE_BYTES):
         if mode not in self.MODES:
@@ -462,10 +484,54 @@ class BackendScorer(object):
         rows = cat([self.ops.backend_affine(chain.unit(x[r0:r1]), chain.plda_w, chain.plda_b) for r0, r1 in steps(x.shape[0], PREPARE_ROWS)])
         return rows, chain.psi
 
-    def dense(self, prepared, out=None):
+    def prepare_pca(self, matrices, target_energy):
+        """The recordings of one batch behind ivector-plda-scoring-dense's per-recording PCA (ops.backend_pca_plda: one call for the batch).
+        matrices: the raw vectors of each recording (host [n, d] or device tensors, as prepare takes them); target_energy in (0, 1].
+        -> per recording (prepared rows, model): model = (p, coef, g, k0), the kept dimension and the recording's own one-utterance tables
+        for dense(prepared, model=model), the rows taken through the recording's map and normalised with its psi; model None where the
+        recording is scored with the global model (prepare's rows): a single row, a zero covariance, or a target within 0.001 of 1 - then
+        the op is not called at all."""
+        if self.mode != "plda":
+            raise ValueError("BackendScorer.prepare_pca: the per-recording PCA needs the plda mode (this scorer: mode %s)" % self.mode)
+        target = check_target_energy(target_energy, "BackendScorer.prepare_pca")
+        if target is None:
+            raise ValueError("BackendScorer.prepare_pca: target_energy must lie in (0, 1] (got None)")
+        torch, ops, chain = self.torch, self.ops, self.chain
+        units = [chain.unit(_device_rows(torch, m, self.device, self.d, "BackendScorer.prepare_pca")) for m in matrices]
+        if not units or target > 1.0 - PCA_NO_TARGET:
+            return [(chain.plda(u), None) for u in units]
+        if self._pca_model is None:
+            self._pca_model = tuple(upload(a, np.float64, self.device) for a in plda_covariances(self.backend.plda))
+        n = np.asarray([u.shape[0] for u in units], np.int64)
+        ld = int(units[0].shape[1])
+        x = torch.cat([u.reshape(-1) for u in units]) if len(units) > 1 else units[0].reshape(-1)
+        got = ops.backend_pca_plda(x, exclusive_offsets(n * ld), n, self.dim, *self._pca_model, target=target, ld=np.full(n.size, ld, np.int64))
+        kept = got["p"].cpu().numpy()
+        out = []
+        for j, u in enumerate(units):
+            p = int(kept[j])
+            if p < 0:
+                raise RuntimeError("BackendScorer.prepare_pca: xv_backend_pca_plda gave up on recording %d of the batch (p = %d: %s)"
+                                   % (j, p, {-1: "its rows lie outside the call's buffer", -2: "the eigensolver reached its sweep cap",
+                                             -3: "the projected within-class covariance is not positive definite"}.get(p, "unknown")))
+            if p == 0:
+                out.append((chain.plda(u), None))
+                continue
+            p4 = pitch4(p)
+            y = ops.backend_affine(u, got["a"][j, :p4], got["offset"][j, :p4])
+            y = ops.backend_plda_normalize(y, p, got["psi"][j, :p], out=y)
+            out.append((y, (p, got["coef"][j:j + 1], got["g"][j], got["k0"][j:j + 1])))
+        return out
+
+    def dense(self, prepared, out=None, model=None):
         """The score of every pair of the prepared rows (one utterance each), a device float32 [n, n] matrix: the cosine in the lda_cos mode
         (ops.score_dense), the log-likelihood ratio in the plda mode (ops.backend_plda_dense); no cohort enters.  out: a [n, n] view of any
-        pitch to write - misc/diarization.py hands views into one packed buffer; default a new matrix."""
+        pitch to write - misc/diarization.py hands views into one packed buffer; default a new matrix.  model: a recording's own
+        (p, coef, g, k0) from prepare_pca, with that call's rows; None: the global model."""
+        if model is not None:
+            if self.mode != "plda":
+                raise ValueError("BackendScorer.dense: a per-recording model needs the plda mode (this scorer: mode %s)" % self.mode)
+            return self.ops.backend_plda_dense(prepared, model[0], *model[1:], out=out)
         if self.mode == "lda_cos":
             return self.ops.score_dense(prepared, self.dim, out=out)
         if self._dense_tables is None:

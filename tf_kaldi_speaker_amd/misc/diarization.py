@@ -5,9 +5,10 @@ nothing is compared with a Kaldi run.
 Host side, NumPy only: speech segments from VAD decisions or a `segments` file, the window planner, the turns of an RTTM from clustered
 windows, RTTM files and a plain diarization error rate.  Device side: Diarizer, which takes the windows' embeddings of many recordings
 through a scorer's prepare -> dense into one packed buffer and clusters them in one ops.ahc_cluster call per batch; with VbxOptions the
-clusterer's labels start the VB-HMM clustering of the windows (VBx, ops.vbx: DESIGN.md section 6j) over the same batch.
-Not here: the per-recording PCA of ivector-plda-scoring-dense, threshold calibration, overlap detection,
-collars / md-eval, recordings of more than 2048 windows.
+clusterer's labels start the VB-HMM clustering of the windows (VBx, ops.vbx: DESIGN.md section 6j) over the same batch; with target_energy
+the PLDA scores of a recording come from its own model behind the per-recording PCA of ivector-plda-scoring-dense
+(ops.backend_pca_plda: DESIGN.md section 6k), one op call per batch.
+Not here: threshold calibration, overlap detection, collars / md-eval, recordings of more than 2048 windows.
 """
 import logging
 
@@ -177,19 +178,34 @@ class Diarizer(object):
         labels = diar.cluster({"rec1": matrix1, ...})               # {recording: int32 labels, one per row}
 
         diar = Diarizer(scorer, threshold=0.0, vbx=VbxOptions())    # ... and VBx behind the clusterer (a BackendScorer in the plda mode)
+        diar = Diarizer(scorer, threshold=0.0, target_energy=0.9)   # ... the recipe's per-recording PCA in front of the PLDA scores (plda mode)
 
     cluster() runs prepare -> dense per recording into one packed buffer of score matrices and one ops.ahc_cluster call over them, in
     batches such that the buffer and the clusterer's scratch of a call stay under the scorer's workspace_bytes.  With vbx the clusterer
     should stop early (too many speakers rather than too few): its labels give vbx_init's responsibilities, the windows go through the
     scorer's plda_space, and one ops.vbx call per batch re-assigns them and drops redundant speakers; the surviving speakers are numbered
     0, 1, ... by their first window.  A recording the clusterer leaves with more than 32 clusters is clustered once more down to 32.
-    After cluster(), vbx_report holds per recording (speakers before, speakers after, iterations, last ELBO)."""
+    After cluster(), vbx_report holds per recording (speakers before, speakers after, iterations, last ELBO).
+    With target_energy (None, or within 0.001 of 1: off, every result bit-identical) a batch goes through the scorer's prepare_pca - one
+    ops.backend_pca_plda call - and each recording is scored with its own model; a recording whose PCA gives none (a single window, a zero
+    covariance: p = 0) is scored with the global model.  VBx keeps running in the unreduced plda_space.  After cluster(), pca_report holds
+    per recording the kept dimension p (0: the global model)."""
 
-    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None):
+    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None, target_energy=None):
         if (threshold is None) == (reco2num_spk is None):
             raise ValueError("Diarizer: exactly one of threshold and reco2num_spk says when the merging stops")
         if vbx is not None and not hasattr(scorer, "plda_space"):
             raise ValueError("Diarizer: VBx needs a BackendScorer in the plda mode (its PLDA space), not %s" % type(scorer).__name__)
+        if target_energy is not None:
+            if getattr(scorer, "mode", None) != "plda" or not hasattr(scorer, "prepare_pca"):
+                raise ValueError("Diarizer: target_energy (the per-recording PCA of PLDA scoring) needs a BackendScorer in the plda mode, not %s%s"
+                                 % (type(scorer).__name__, " in the %s mode" % scorer.mode if hasattr(scorer, "mode") else ""))
+            target_energy = float(target_energy)
+            if not 0.0 < target_energy <= 1.0:
+                raise ValueError("Diarizer: target_energy must lie in (0, 1] (got %r)" % (target_energy,))
+            if target_energy > 1.0 - 0.001:      # (ivector-plda-scoring-dense returns early: no PCA at all)
+                target_energy = None
+        self.target_energy, self.pca_report = target_energy, {}
         self.scorer, self.threshold, self.reco2num_spk, self.vbx = scorer, threshold, reco2num_spk, vbx
         self.torch, self.ops = scorer.torch, scorer.ops
         self.vbx_report = {}
@@ -247,6 +263,10 @@ class Diarizer(object):
             targets = np.zeros(len(keys), np.int64)
         ld = np.asarray([pitch4(int(r)) for r in n], np.int64)
         cost = 4 * (n * ld + n * n)      # bytes of a recording: its matrix in the packed buffer and the clusterer's copy
+        if self.target_energy is not None:      # ... its unit-length rows packed for the op, the op's scratch and its fp32 outputs
+            dim4 = pitch4(self.scorer.dim)
+            cost = cost + 4 * n * dim4 + self.ops.backend_pca_plda_workspace_bytes(1, self.scorer.dim) + 4 * dim4 * (dim4 + 8)
+            self.pca_report = {}
         if self.vbx is not None:         # (VBx runs once the clusterer's buffers are gone: a batch must hold the larger of the two)
             cap_s, dim4 = self.ops.VBX_MAX_SPEAKERS, pitch4(self.scorer.dim)
             cost = np.maximum(cost, np.asarray([4 * r * dim4 + 8 * r * cap_s + self.ops.vbx_workspace_bytes([r], [cap_s], self.scorer.dim) for r in n], np.int64))
@@ -258,10 +278,16 @@ class Diarizer(object):
         for batch in batches:
             offsets = np.concatenate([[0], np.cumsum(n[batch] * ld[batch])]).astype(np.int64)
             packed = self.torch.empty(int(offsets[-1]), dtype=self.torch.float32, device=self.scorer.device)
+            own = None if self.target_energy is None else self.scorer.prepare_pca([embeddings[keys[i]] for i in batch], self.target_energy)
             for j, i in enumerate(batch):
-                prepared = self.scorer.prepare(embeddings[keys[i]])
                 view = packed[int(offsets[j]):int(offsets[j + 1])].view(int(n[i]), int(ld[i]))[:, :int(n[i])]
-                self.scorer.dense(prepared, out=view)
+                if own is None:
+                    self.scorer.dense(self.scorer.prepare(embeddings[keys[i]]), out=view)
+                else:
+                    prepared, model = own[j]
+                    self.pca_report[keys[i]] = 0 if model is None else int(model[0])
+                    self.scorer.dense(prepared, out=view, model=model)
+            del own
             labels = self._ahc(packed, offsets[:-1], n[batch], ld[batch], targets[batch])
             at = np.concatenate([[0], np.cumsum(n[batch])])
             if self.vbx is not None:

@@ -125,6 +125,10 @@ ARGUMENTS = {
     "vbx_epsilon": (("--vbx-epsilon",), dict(type=float, default=1e-4, help="VBx: stop once an iteration gains less than this on the ELBO.")),
     "vbx_init_smoothing": (("--vbx-init-smoothing",), dict(type=float, default=5.0, help="VBx: the clusterer's labels times this, a softmax per "
                                                                                          "window, are the first responsibilities.")),
+    "target_energy": (("--target-energy",), dict(type=float, default=None, help="Per-recording PCA in front of the PLDA scores, keeping this share "
+                                                                                "of the energy, in (0, 1] (ivector-plda-scoring-dense "
+                                                                                "--target-energy; the callhome recipe: 0.9).  Needs --scoring plda.  "
+                                                                                "Default: off.")),
     # positionals
     "rttm_out": (("rttm_out",), dict(type=str, help="The RTTM file to write.")),
     "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),

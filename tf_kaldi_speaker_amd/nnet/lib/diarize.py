@@ -3,7 +3,7 @@
 (extract_xvectors.sh's sliding windows, score_plda.sh, cluster.sh, make_rttm.py), restated - nothing is compared with a Kaldi run:
 
     python nnet/lib/diarize.py [-g GPU] [--cmn-window 300] [--window 1.5 --period 0.75 --min-segment 0.5] [--segments FILE | --vad RSPECIFIER]
-                               [--backend DIR --scoring {cosine,lda_cos,plda}] (--threshold T | --reco2num-spk FILE)
+                               [--backend DIR --scoring {cosine,lda_cos,plda} [--target-energy F]] (--threshold T | --reco2num-spk FILE)
                                [--vbx [--vbx-fa 0.3 --vbx-fb 17 --vbx-loop-prob 0.99 --vbx-max-iters 20 --vbx-epsilon 1e-4 --vbx-init-smoothing 5]]
                                [--write-embeddings WSPECIFIER] model_dir rspecifier rttm_out
 
@@ -12,17 +12,19 @@ CMN over the whole recording on the GPU (ops.frontend; as in the recipe it runs 
 segments (--segments: a Kaldi segments file; --vad: the voiced runs of the decisions; neither: the whole recording) are cut into windows
 (misc/diarization.py subsegments); the windows - row ranges of the normalised recording, gathered on the device - go through
 Trainer.predict_batch as device rows.  Then misc/diarization.py Diarizer: all-pairs scores per recording (cosine, or behind --backend the
-LDA cosine or the PLDA log-likelihood ratio), agglomerative clustering on the GPU (xv_ahc_cluster) down to --threshold or to the
+LDA cosine or the PLDA log-likelihood ratio - with --target-energy F behind ivector-plda-scoring-dense's per-recording PCA: each recording
+scored with the PLDA model projected into the leading directions of its own windows that hold F of the energy (xv_backend_pca_plda:
+DESIGN.md section 6k; one log line per recording gives the kept dimension; off by default, and then every output is what it was without
+the option), agglomerative clustering on the GPU (xv_ahc_cluster) down to --threshold or to the
 recording's entry in --reco2num-spk; with --vbx the clusterer's labels (it should stop early: too many speakers) start the VB-HMM
 clustering of the windows in the PLDA space (VBx, xv_vbx: DESIGN.md section 6j), which re-assigns them and drops redundant speakers - one log
 line per recording says speakers before and after, iterations and the last ELBO; and the turns: overlapping windows are cut at the midpoint
 of the overlap, abutting windows of one speaker merged.  Output: `SPEAKER <recording> 0 <start> <duration> <NA> <NA> <speaker> <NA> <NA>` lines, speakers numbered from 1 per
 recording.  --write-embeddings: the windows' embeddings, keyed `recording-startframe-endframe`.
 Refused: both or neither of --threshold / --reco2num-spk, --segments beside --vad, a back end without a --scoring that uses it (and the
-reverse), --vbx without --scoring plda or with an option outside its range, a --min-segment below the network's receptive field, a recording of more than 2048 windows (Kaldi's two-pass clustering of long
+reverse), --vbx without --scoring plda or with an option outside its range, --target-energy without --scoring plda or outside (0, 1], a --min-segment below the network's receptive field, a recording of more than 2048 windows (Kaldi's two-pass clustering of long
 recordings is not here), a recording without an entry in --reco2num-spk.
-Not here: waveform input (make_mfcc.py writes the archive this reads), the per-recording PCA of
-ivector-plda-scoring-dense, threshold calibration, overlap detection.
+Not here: waveform input (make_mfcc.py writes the archive this reads), threshold calibration, overlap detection.
 """
 import os
 import sys
@@ -71,7 +73,7 @@ def window_embeddings(trainer, ops, torch, matrix, windows, cmn_window):
 def main():
     log = _cli.logger()
     args = _cli.parser_for("gpu", "prep_cmn_window", "window", "period", "min_segment", "segments", "diar_vad", "backend", "diar_scoring", "threshold",
-                           "reco2num_spk", "vbx", "vbx_fa", "vbx_fb", "vbx_loop_prob", "vbx_max_iters", "vbx_epsilon", "vbx_init_smoothing", "write_embeddings", "model_dir", "rspecifier", "rttm_out").parse_args()
+                           "reco2num_spk", "vbx", "vbx_fa", "vbx_fb", "vbx_loop_prob", "vbx_max_iters", "vbx_epsilon", "vbx_init_smoothing", "target_energy", "write_embeddings", "model_dir", "rspecifier", "rttm_out").parse_args()
     if (args.threshold is None) == (not args.reco2num_spk):
         sys.exit("exactly one of --threshold and --reco2num-spk says when the merging stops")
     if args.segments and args.vad:
@@ -86,6 +88,10 @@ def main():
                          and args.vbx_init_smoothing >= 0 and args.vbx_epsilon == args.vbx_epsilon):
         sys.exit("--vbx: --vbx-loop-prob must lie strictly between 0 and 1, --vbx-fa and --vbx-fb be positive, --vbx-max-iters lie in 1 .. 64, "
                  "--vbx-init-smoothing not be negative")
+    if args.target_energy is not None and args.scoring != "plda":
+        sys.exit("--target-energy needs --scoring plda (the per-recording PCA projects the PLDA model of --backend), not --scoring %s" % args.scoring)
+    if args.target_energy is not None and not 0.0 < args.target_energy <= 1.0:
+        sys.exit("--target-energy must lie in (0, 1] (got %g)" % args.target_energy)
     if args.cmn_window < 0:
         sys.exit("--cmn-window must be 0 (off) or a number of frames")
     window, period, min_segment = (int(round(v / FRAME_SHIFT)) for v in (args.window, args.period, args.min_segment))
@@ -174,10 +180,12 @@ def main():
         if args.vbx:
             vbx = diarization.VbxOptions(fa=args.vbx_fa, fb=args.vbx_fb, loop_prob=args.vbx_loop_prob, max_iters=args.vbx_max_iters,
                                          epsilon=args.vbx_epsilon, init_smoothing=args.vbx_init_smoothing)
-        diarizer = diarization.Diarizer(scorer, threshold=args.threshold, reco2num_spk=reco2num_spk, vbx=vbx)
+        diarizer = diarization.Diarizer(scorer, threshold=args.threshold, reco2num_spk=reco2num_spk, vbx=vbx, target_energy=args.target_energy)
         labels = diarizer.cluster(embeddings)
     except ValueError as e:
         sys.exit(str(e))
+    for reco, kept in diarizer.pca_report.items():
+        log.info("[INFO] Recording %s: per-recording PCA: %s." % (reco, "%d of %d dimensions kept" % (kept, scorer.dim) if kept else "none, scored with the global model"))
     for reco, (before, after, iters, elbo) in diarizer.vbx_report.items():
         log.info("[INFO] Recording %s: VBx: %d speakers before, %d after, %d iterations, last ELBO %.6f." % (reco, before, after, iters, elbo))
     turns = {}

@@ -444,3 +444,61 @@ def vbx(x, x_offsets, t, d, phi, gamma, pi, s, ld=None, loop_prob=0.99, fa=0.3, 
               C.c_int64(total_ts), C.c_int64(total_s), _p(phi), _p(gamma), _p(pi), C.c_float(loop32), C.c_float(float(fa)), C.c_float(float(fb)),
               max_iters, C.c_double(float(epsilon)), _p(gamma_out), _p(pi_out), _p(elbo), _p(n_iters), _p(labels), _p(ws), C.c_size_t(ws_bytes))
     return gamma_out, pi_out, elbo, n_iters, labels
+
+
+PCA_MAX_DIM = 256      # the dimensions of the rows xv_backend_pca_plda takes
+
+
+def backend_pca_plda_workspace_bytes(b, d):
+    """Bytes of scratch xv_backend_pca_plda needs for b recordings in d dimensions."""
+    return int(_lib.load().xv_backend_pca_plda_workspace_bytes(int(b), int(d)))
+
+
+def backend_pca_plda(x, x_offsets, n, d, w, b, mu, target, ld=None):
+    """The per-recording PCA of ivector-plda-scoring-dense --target-energy for the recordings of one call (xv_backend_pca_plda;
+    include/xvector_hip.h states the arithmetic, tests/pca_plda_ref.py restates it).  x: a contiguous 1-D float32 device buffer; recording
+    i's rows [n[i], ld[i]] (ld None: d) start at float x_offsets[i]: centred, LDA-transformed, unit-length vectors.  w, b: float64 [d, d]
+    device tensors, the within- and between-class covariances of the PLDA model (misc.backend.plda_covariances); mu: float64 [d], its
+    mean.  target: the share of the energy to keep, in (0, 1].  x_offsets, n, ld: HOST integer arrays, checked here before the upload - the
+    kernel trusts them.
+    -> dict of device tensors, d4 = d rounded up to 4: p int32 [recordings] (0: no PCA for this recording, use the global model; -2 / -3: the
+    eigensolver reached its sweep cap / the projected within-class covariance is not positive definite), a float32 [recordings, d4, d4] (the
+    first p rows and d columns hold the map, the rest zero), offset, psi, g float32 [recordings, d4], coef float32 [recordings, 2, d4],
+    k0 float32 [recordings], s, psi64 float64 [recordings, d], sweeps int32 [recordings, 2].  What the kernel does not write - everything
+    but p (and s) of a recording with p <= 0, psi64 behind p - stays NaN (sweeps: -1)."""
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("backend_pca_plda: x must be a non-empty contiguous 1-D float32 tensor")
+    d, target = int(d), float(target)
+    if not 1 <= d <= PCA_MAX_DIM:
+        raise ValueError("backend_pca_plda: d must lie in 1 .. %d (got %d)" % (PCA_MAX_DIM, d))
+    if not 0.0 < target <= 1.0:
+        raise ValueError("backend_pca_plda: target must lie in (0, 1] (got %r)" % (target,))
+    n = host_ints(n, "backend_pca_plda: n", min_size=1)
+    count = n.size
+    if n.min() < 1:
+        raise ValueError("backend_pca_plda: recording %d has no row (n = %d)" % (int(np.argmax(n < 1)), int(n.min())))
+    if n.max() > AHC_MAX_N:
+        raise ValueError("backend_pca_plda: recording %d has %d rows, the cap is %d" % (int(np.argmax(n > AHC_MAX_N)), int(n.max()), AHC_MAX_N))
+    ld = np.full(count, d, np.int64) if ld is None else host_ints(ld, "backend_pca_plda: ld", n=count)
+    if (ld < d).any():
+        raise ValueError("backend_pca_plda: recording %d: the pitch %d is below the %d dimensions" % (int(np.argmax(ld < d)), int(ld[np.argmax(ld < d)]), d))
+    x_offsets = host_ints(x_offsets, "backend_pca_plda: x_offsets", n=count, dtype=np.int64)
+    spans_inside(x_offsets, (n.astype(np.int64) - 1) * ld.astype(np.int64) + d, x.numel(),
+                 "backend_pca_plda: a recording's rows lie outside the %d floats of x" % x.numel())
+    for t, shape, name in ((w, (d, d), "w"), (b, (d, d), "b"), (mu, (d,), "mu")):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError("backend_pca_plda: %s must be a contiguous float64 %s tensor on the rows' device" % (name, list(shape)))
+    dev, d4 = x.device, pitch4(d)
+    nan32 = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+    out = dict(p=torch.empty(count, dtype=torch.int32, device=dev), a=nan32(count, d4, d4), offset=nan32(count, d4), psi=nan32(count, d4),
+               coef=nan32(count, 2, d4), g=nan32(count, d4), k0=nan32(count),
+               s=torch.full((count, d), float("nan"), dtype=torch.float64, device=dev),
+               psi64=torch.full((count, d), float("nan"), dtype=torch.float64, device=dev),
+               sweeps=torch.full((count, 2), -1, dtype=torch.int32, device=dev))
+    ws_bytes = backend_pca_plda_workspace_bytes(count, d)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    off_d, n_d, ld_d = upload(x_offsets, np.int64, dev), upload(n, np.int32, dev), upload(ld, np.int32, dev)
+    _lib.call("xv_backend_pca_plda", _s(), _p(x), C.c_int64(x.numel()), _p(off_d), _p(n_d), _p(ld_d), count, d, int(n.max()), C.c_double(target),
+              _p(w), _p(b), _p(mu), _p(out["p"]), _p(out["a"]), _p(out["offset"]), _p(out["psi"]), _p(out["coef"]), _p(out["g"]), _p(out["k0"]),
+              _p(out["s"]), _p(out["psi64"]), _p(out["sweeps"]), _p(ws), C.c_size_t(ws_bytes))
+    return out

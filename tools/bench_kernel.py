@@ -27,6 +27,9 @@ sub-command per question (they used to be eight scripts):
   python tools/bench_kernel.py vbx [recordings=64] [T,S ...]     VB-HMM clustering (xv_vbx.hip): one call over 64 recordings at (T, D, S) = (200, 128, 6), (800, 128, 10)
                                                                 and (2000, 128, 16), 20 iterations, medians over alternated rounds, beside the float64 NumPy
                                                                 restatement of one recording on the CPU
+  python tools/bench_kernel.py pca_plda [b,n,D ...]              the per-recording PCA of PLDA scoring (xv_backend_pca.hip): one call over (b, n, D) = (256, 600, 128) and
+                                                                (64, 2048, 200) at a target energy of 0.9, medians over alternated rounds, beside the float64
+                                                                NumPy restatement of the same recordings on the CPU
   python tools/bench_kernel.py mfcc [utterances=256]             MFCC + energy VAD from waveforms (xv_mfcc.hip) on synthetic 16 kHz PCM, utterances of 4 - 20 s
   python tools/bench_kernel.py fbank [utterances=256]            xv_fbank (30 bins) against xv_mfcc on the same batch, alternated five times: medians and spread
   python tools/bench_kernel.py cm_encode [utterances=256]        'CM ' compression (xv_cm_encode.hip) of 400 - 2000 frames x 30 per utterance, both header forms,
@@ -695,6 +698,40 @@ def cmd_vbx(argv):
               % (recordings, t, d, s, iters, med, " ".join("%.2f" % v for v in times[(t, s)]), med * 1e3 / iters, cpu[(t, s)]), flush=True)
 
 
+def cmd_pca_plda(argv):
+    """One xv_backend_pca_plda call over b recordings of n windows in D dimensions at a target energy of 0.9 (the four-speaker generator of
+    tests/pca_plda_ref.py, one seed per recording): milliseconds per call, medians over five rounds that alternate the shapes.  Beside it the
+    host restatement of the same call - tests/pca_plda_ref.py estimate() per recording, NumPy float64 with the BLAS threads the environment
+    allows - on this box."""
+    from tf_kaldi_speaker_amd import ops
+    from tests import pca_plda_ref as P
+    shapes = [tuple(int(v) for v in a.split(",")) for a in argv] or [(256, 600, 128), (64, 2048, 200)]
+    target = 0.9
+    dev, cpu, kept = {}, {}, {}
+    for b, n, d in shapes:
+        c = P.case(d, n)
+        xs = [P.recording(seed, d, n) for seed in range(b)]
+        t0 = time.time()
+        ref = [P.estimate(x, c["w"], c["b"], c["mu"], target)["p"] for x in xs]
+        cpu[(b, n, d)] = (time.time() - t0) * 1e3
+        up = lambda a: torch.from_numpy(np.array(a)).cuda()
+        dev[(b, n, d)] = (torch.from_numpy(np.concatenate([x.ravel() for x in xs])).cuda(), np.arange(b, dtype=np.int64) * n * d, np.full(b, n, np.int64),
+                          up(c["w"]), up(c["b"]), up(c["mu"]))
+        got = ops.backend_pca_plda(*dev[(b, n, d)][:3], d, *dev[(b, n, d)][3:], target)
+        kept[(b, n, d)] = (got["p"].cpu().numpy(), np.asarray(ref), got["sweeps"].cpu().numpy())
+    times = {k: [] for k in shapes}
+    for _ in range(5):
+        for k in shapes:
+            x, off, nn, w, bb, mu = dev[k]
+            times[k].append(timeit(lambda: ops.backend_pca_plda(x, off, nn, k[2], w, bb, mu, target), 2, 1) / 1e3)
+    for k in shapes:
+        p, ref, sweeps = kept[k]
+        print("pca_plda: %3d recordings x (n, D) = (%4d, %3d), target 0.9: %9.2f ms per call (rounds %s); kept p %d .. %d (the restatement's for %d of %d), "
+              "sweeps %d .. %d and %d .. %d; float64 NumPy restatement, the same recordings one after another: %9.1f ms"
+              % (k[0], k[1], k[2], float(np.median(times[k])), " ".join("%.2f" % v for v in times[k]), p.min(), p.max(), int((p == ref).sum()), k[0],
+                 sweeps[:, 0].min(), sweeps[:, 0].max(), sweeps[:, 1].min(), sweeps[:, 1].max(), cpu[k]), flush=True)
+
+
 def cmd_mfcc(argv):
     """Frames per second of xv_mfcc alone and of xv_mfcc + xv_energy_vad on one padded batch (VoxCeleb conf: 16 kHz, 25 / 10 ms, 30 bins, 30
     coefficients); the bytes the kernel has to move (2 S bytes of new samples in, 4 num_ceps bytes out per frame, plus the zeroed padding
@@ -902,7 +939,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"ahc": cmd_ahc, "vbx": cmd_vbx, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
+COMMANDS = {"ahc": cmd_ahc, "vbx": cmd_vbx, "pca_plda": cmd_pca_plda, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
             "triplet": cmd_triplet, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The bits of every op of the scoring and back-end units (xv_score.hip, xv_backend.hip, xv_backend_cohort.hip) and of ops.vbx on seeded
-inputs at fixed shapes: one line `op  shape  sha256(output bytes)` each.  These ops promise the same bits every time, so the output of two
+"""The bits of every op of the scoring and back-end units (xv_score.hip, xv_backend.hip, xv_backend_cohort.hip), of ops.vbx and of
+ops.backend_pca_plda on seeded inputs at fixed shapes: one line `op  shape  sha256(output bytes)` each.  These ops promise the same bits every time, so the output of two
 builds of the library (XV_LIB=<another build> python3 tools/op_bits.py) must not differ in any line.  Needs the GPU."""
 import hashlib
 import os
@@ -12,7 +12,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from tf_kaldi_speaker_amd import ops                      # noqa: E402
 from tf_kaldi_speaker_amd.misc import backend as B        # noqa: E402
-from tests import vbx_ref                                 # noqa: E402
+from tests import pca_plda_ref, vbx_ref                   # noqa: E402
 
 rs = np.random.RandomState(20240)
 
@@ -111,9 +111,19 @@ def vbx():
     show("vbx", "(T, D, S)=(200, 128, 6) x 2, 5 iterations", *out)
 
 
+def pca_plda():
+    for d, n in ((36, 40), (130, 129)):      # the eigenproblems in LDS, and the first one in the workspace
+        c = pca_plda_ref.case(d, n)
+        xs = [pca_plda_ref.recording(seed, d, n) for seed in range(2)]
+        out = ops.backend_pca_plda(dev(np.concatenate([x.ravel() for x in xs])), np.arange(2, dtype=np.int64) * n * d, np.full(2, n, np.int64), d,
+                                   dev(np.array(c["w"])), dev(np.array(c["b"])), dev(np.array(c["mu"])), 0.9)
+        show("backend_pca_plda", "(n, D)=(%d, %d) x 2, target 0.9" % (n, d), *(out[k] for k in sorted(out)))
+
+
 if __name__ == "__main__":
     row_ops()
     cohort_ops()
     dense_ops()
     vbx()
+    pca_plda()
     torch.cuda.synchronize()
