@@ -566,14 +566,65 @@ int xv_backend_plda_dense(void* stream, const float* x, int ldx, int n, int d, c
  * Outputs: labels int32 [total_n], recording r's at the exclusive prefix of n; merges int32 [total_n - b][2] and merge_values fp32
  * [total_n - b], recording r's log at the exclusive prefix of n - 1, of which the first n_merges[r] entries are written; n_merges int32 [b].
  * total_n = sum n, sum_n2 = sum n^2, max_n = the largest n: host values the caller states.  ws: xv_ahc_workspace_bytes(sum_n2) bytes (T
- * of every recording, full symmetric storage).  Refused by name: b <= 0, max_n < 1, max_n > 2048 (longer recordings want Kaldi's two-pass
- * clustering: not here), totals that do not fit, a workspace too small.  The device arrays are NOT checked on the host side of this call
+ * of every recording, full symmetric storage).  Refused by name: b <= 0, max_n < 1, max_n > 2048 (longer recordings take Kaldi's two-pass
+ * clustering: xv_ahc_cluster_from and xv_ahc_cluster_sums below), totals that do not fit, a workspace too small.  The device arrays are NOT checked on the host side of this call
  * (ops.ahc_cluster checks the host arrays before the upload: n in 1 .. 2048, ld >= n, 0 <= target <= n, every matrix inside the buffer); a
  * recording whose entries would take the kernel outside the buffers of the call is skipped and gets n_merges = -1. */
 size_t xv_ahc_workspace_bytes(int64_t sum_n2);
 int xv_ahc_cluster(void* stream, const float* scores, int64_t scores_floats, const int64_t* mat_offsets, const int32_t* n, const int32_t* ld,
                    const int32_t* targets, int b, int max_n, int64_t total_n, int64_t sum_n2, float threshold, int32_t* labels,
                    int32_t* merges, float* merge_values, int32_t* n_merges, void* ws, size_t ws_bytes);
+
+/* The clusterer with a floor and two starts: the two stages of the two-pass clustering of long recordings (Kaldi's
+ * AgglomerativeClusterer::ClusterTwoPass behind agglomerative-cluster --first-pass-max-points, as recalled from agglomerative-clustering.cc
+ * and restated: contiguous subsets clustered down to ten times the wanted number of clusters, then the survivors against each other;
+ * nothing is compared with a Kaldi run, and Kaldi's max_spk_fraction is left out).  The arithmetic, the ties, the merge log, the labels,
+ * the layout of every output and the kernel body are xv_ahc_cluster's; tests/ahc2_ref.py restates what differs:
+ *   stop rule: recording r merges while its cluster count > floors[r] AND the best A >= threshold (one float per call; -inf: down to the
+ *   floor).  floors[r] lies in 1 .. n[r].
+ *   seeded = 0, from scores: T from the upper triangle of recording r's matrix at mat_offsets[r] / ld[r], every size 1 - a sub-block of a
+ *   larger matrix is a matrix at an offset on the larger one's pitch.  sizes is not read.
+ *   seeded = 1: recording r starts from n[r] clusters of sizes int32 [total_n] (recording r's at the exclusive prefix of n, each >= 1,
+ *   together at most 32768) and from T [n[r]][n[r]], full symmetric storage at pitch n[r], which the caller has left in ws at the exclusive
+ *   prefix of n^2 (xv_ahc_cluster_sums writes sizes and T in this layout); ws is modified.  scores, mat_offsets and ld are not read.
+ *   A = T[a][b] / (float)(size_a * size_b): the int32 product may now exceed 2^24; it is exact as an integer (at most 2^28) and converted
+ *   to fp32 once, round to nearest even, before the one fp32 divide.
+ * ws: xv_ahc_cluster_from_workspace_bytes(sum_n2) bytes.  Refused by name: what xv_ahc_cluster refuses, a seeded other than 0 / 1, a NaN
+ * threshold, a missing array of the chosen start.  The device arrays are NOT checked on the host side (ops.ahc_cluster_from checks the host
+ * arrays); a recording whose entries would take the kernel outside the buffers of the call, whose floor is outside 1 .. n or whose seeded
+ * sizes are wrong is skipped and gets n_merges = -1. */
+size_t xv_ahc_cluster_from_workspace_bytes(int64_t sum_n2);
+int xv_ahc_cluster_from(void* stream, const float* scores, int64_t scores_floats, const int64_t* mat_offsets, const int32_t* n,
+                        const int32_t* ld, const int32_t* floors, const int32_t* sizes, int seeded, int b, int max_n, int64_t total_n,
+                        int64_t sum_n2, float threshold, int32_t* labels, int32_t* merges, float* merge_values, int32_t* n_merges, void* ws,
+                        size_t ws_bytes);
+
+/* Cluster sums: the seed of the second pass from a recording's score matrix and its first-pass clusters.  b recordings per call; three
+ * launches in stream order, no atomics, no wait on another workgroup: the same bits every time.
+ * Inputs, all on the device: scores / scores_floats / mat_offsets / n / ld as for xv_ahc_cluster, n[r] in 1 .. 32768, only the upper
+ * triangle is read (e(i, j) = s[min(i,j)][max(i,j)], the diagonal is not read either); c int32 [b], recording r's clusters, 1 .. min(n[r],
+ * 2048); the clusters as member lists: members int32 [total_n], recording r's at the exclusive prefix of n - the rows 0 .. n[r] - 1 cluster
+ * by cluster, clusters ascending by their smallest member, a cluster's members ascending; starts int32 [total_c + b], recording r's
+ * c[r] + 1 entries at the exclusive prefix of c + 1: cluster B's members are members[starts[B] .. starts[B + 1]), starts[0] = 0,
+ * starts[c[r]] = n[r].
+ * The order of every sum is part of the operation (tests/ahc2_ref.py restates it with np.cumsum), for clusters A < B:
+ *   r_i[B] = the sequential double sum over the members j of B, ascending, of e(i, j)
+ *   T[A][B] = T[B][A] = fp32(the sequential double sum over the members i of A, ascending, of r_i[B]);  T[A][A] = 0
+ * (a sum starts from its first term, not from 0.0; a fp32 score enters a double sum exactly).
+ * Outputs: seed fp32 [sum_c2], recording r's T [c[r]][c[r]] at the exclusive prefix of c^2; sizes int32 [total_c], recording r's at the
+ * exclusive prefix of c: what xv_ahc_cluster_from takes as ws and sizes with n = c; status int32 [b]: 0, or -1 for a recording whose
+ * entries would take the kernels outside the buffers of the call (spans against the totals, starts not ascending from 0 to n, a member
+ * outside 0 .. n - 1): it is skipped.
+ * total_n = sum n, total_c = sum c, sum_c2 = sum c^2, sum_nc = sum n c, max_n, max_c: host values the caller states.  ws:
+ * xv_ahc_cluster_sums_workspace_bytes(b, sum_nc) bytes, 8-byte aligned (r_i[B] of every recording in double, and the prefixes).  Refused by
+ * name: b outside 1 .. 65535, max_n outside 1 .. 32768, max_c outside 1 .. min(max_n, 2048), totals that do not fit, a workspace too
+ * small.  The device arrays are NOT checked on the host side of this call (ops.ahc_cluster_sums checks the host arrays: that the lists are
+ * a partition in the stated order).  A NaN score is undefined. */
+size_t xv_ahc_cluster_sums_workspace_bytes(int b, int64_t sum_nc);
+int xv_ahc_cluster_sums(void* stream, const float* scores, int64_t scores_floats, const int64_t* mat_offsets, const int32_t* n,
+                        const int32_t* ld, const int32_t* c, const int32_t* members, const int32_t* starts, int b, int max_n, int max_c,
+                        int64_t total_n, int64_t total_c, int64_t sum_c2, int64_t sum_nc, float* seed, int32_t* sizes, int32_t* status,
+                        void* ws, size_t ws_bytes);
 
 /* VB-HMM clustering of x-vectors (VBx, Landini et al.: a Bayesian HMM whose states are speakers and whose state distributions come from
  * the PLDA model, started from the clusterer's labels), as recalled from BUT's VB_diarization.py and restated - agreement with a run of

@@ -320,6 +320,11 @@ SIGNATURES = {
                                  _VP, _VP, _VP, _SZ]),
     "xv_ahc_workspace_bytes": (_SZ, [C.c_int64]),
     "xv_ahc_cluster": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, C.c_int64, C.c_int64, _F, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "xv_ahc_cluster_from_workspace_bytes": (_SZ, [C.c_int64]),
+    "xv_ahc_cluster_from": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_int64, C.c_int64, _F, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "xv_ahc_cluster_sums_workspace_bytes": (_SZ, [_I, C.c_int64]),
+    "xv_ahc_cluster_sums": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _VP, _VP,
+                                 _VP, _VP, _SZ]),
     "xv_vbx_workspace_bytes": (_SZ, [C.c_int64, C.c_int64, C.c_int64, _I]),
     "xv_vbx": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, _F, _F, _F, _I, C.c_double,
                     _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),

@@ -7,8 +7,10 @@ windows, RTTM files and a plain diarization error rate.  Device side: Diarizer, 
 through a scorer's prepare -> dense into one packed buffer and clusters them in one ops.ahc_cluster call per batch; with VbxOptions the
 clusterer's labels start the VB-HMM clustering of the windows (VBx, ops.vbx: DESIGN.md section 6j) over the same batch; with target_energy
 the PLDA scores of a recording come from its own model behind the per-recording PCA of ivector-plda-scoring-dense
-(ops.backend_pca_plda: DESIGN.md section 6k), one op call per batch.
-Not here: threshold calibration, overlap detection, collars / md-eval, recordings of more than 2048 windows.
+(ops.backend_pca_plda: DESIGN.md section 6k), one op call per batch; a recording of more than first_pass_max_points windows is clustered in
+two passes (ops.ahc_cluster_two_pass: DESIGN.md section 6l), up to 32768 windows.
+Not here: threshold calibration, overlap detection, collars / md-eval, VBx or the per-recording PCA on recordings of
+more than 2048 windows.
 """
 import logging
 
@@ -16,6 +18,7 @@ import numpy as np
 
 _LOG = logging.getLogger("tf_kaldi_speaker_amd")
 DER_FRAME = 0.01      # seconds per frame of der()
+FIRST_PASS_CAP = 2048      # the most windows a subset of the first pass may hold: the clusterer's cap (ops.AHC_MAX_N)
 
 
 def speech_segments(vad, min_frames=1):
@@ -189,9 +192,13 @@ class Diarizer(object):
     With target_energy (None, or within 0.001 of 1: off, every result bit-identical) a batch goes through the scorer's prepare_pca - one
     ops.backend_pca_plda call - and each recording is scored with its own model; a recording whose PCA gives none (a single window, a zero
     covariance: p = 0) is scored with the global model.  VBx keeps running in the unreduced plda_space.  After cluster(), pca_report holds
-    per recording the kept dimension p (0: the global model)."""
+    per recording the kept dimension p (0: the global model).
+    first_pass_max_points (2 .. 2048; agglomerative-cluster's option and default): a recording of at most that many windows is clustered
+    as ever, bit for bit; a longer one, up to 32768 windows, in two passes (ops.ahc_cluster_two_pass: contiguous subsets down to ten times
+    the wanted clusters, then the survivors against each other) - both kinds may meet in one cluster() call.  xv_vbx and
+    xv_backend_pca_plda keep their cap: vbx or target_energy with a recording of more than 2048 windows is refused by name."""
 
-    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None, target_energy=None):
+    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None, target_energy=None, first_pass_max_points=2048):
         if (threshold is None) == (reco2num_spk is None):
             raise ValueError("Diarizer: exactly one of threshold and reco2num_spk says when the merging stops")
         if vbx is not None and not hasattr(scorer, "plda_space"):
@@ -209,11 +216,48 @@ class Diarizer(object):
         self.scorer, self.threshold, self.reco2num_spk, self.vbx = scorer, threshold, reco2num_spk, vbx
         self.torch, self.ops = scorer.torch, scorer.ops
         self.vbx_report = {}
+        self.first_pass_max_points = int(first_pass_max_points)
+        if not 2 <= self.first_pass_max_points <= FIRST_PASS_CAP:
+            raise ValueError("Diarizer: first_pass_max_points must lie in 2 .. %d (got %r)" % (FIRST_PASS_CAP, first_pass_max_points))
 
-    def _ahc(self, packed, offsets, n, ld, targets):
-        return self.ops.ahc_cluster(packed, offsets, n.astype(np.int32), ld.astype(np.int32),
-                                    threshold=0.0 if self.threshold is None else float(self.threshold),
-                                    targets=targets.astype(np.int32))[0].cpu().numpy()
+    def _ahc(self, packed, offsets, n, ld, targets, names):
+        """The clusterer over one batch -> the labels back to back.  The recordings of at most first_pass_max_points windows go through one
+        ops.ahc_cluster call; the longer ones through ops.ahc_cluster_two_pass, one call per stop rule (by threshold, by target)."""
+        threshold = 0.0 if self.threshold is None else float(self.threshold)
+        long = n > self.first_pass_max_points
+        if not long.any():
+            return self.ops.ahc_cluster(packed, offsets, n.astype(np.int32), ld.astype(np.int32), threshold=threshold,
+                                        targets=targets.astype(np.int32))[0].cpu().numpy()
+        at = np.concatenate([[0], np.cumsum(n)])
+        labels = np.empty(int(at[-1]), np.int32)
+        for pick, by_target in ((~long, None), (long & (targets == 0), False), (long & (targets > 0), True)):
+            idx = np.flatnonzero(pick)
+            if idx.size == 0:
+                continue
+            if by_target is None:
+                got = self.ops.ahc_cluster(packed, offsets[idx], n[idx].astype(np.int32), ld[idx].astype(np.int32), threshold=threshold,
+                                           targets=targets[idx].astype(np.int32))[0]
+            else:
+                try:
+                    got = self.ops.ahc_cluster_two_pass(packed, offsets[idx], n[idx], ld[idx], threshold=threshold,
+                                                        targets=targets[idx] if by_target else None, first_pass_max_points=self.first_pass_max_points)[0]
+                except ValueError as e:
+                    if not hasattr(e, "recording"):
+                        raise
+                    raise ValueError("Diarizer: recording %s: %s" % (names[idx[e.recording]], e.what))
+            got = got.cpu().numpy()
+            for j, lo in zip(idx, np.concatenate([[0], np.cumsum(n[idx])])):
+                labels[at[j]:at[j + 1]] = got[lo:lo + n[j]]
+        return labels
+
+    def _two_pass_bytes(self, rows, ld, target):
+        """What a recording of more than first_pass_max_points windows costs a batch: its matrix, the first pass's copies of the subsets, the
+        scratch of the cluster sums and the seed - for the most clusters the first pass can leave (with a target: ten times the target per
+        subset; by threshold: every window, up to the second pass's cap)."""
+        subsets = np.diff(self.ops.ahc_subsets(rows, self.first_pass_max_points))
+        survivors = int(np.minimum(subsets, 10 * target).sum()) if target > 0 else int(rows)
+        survivors = min(survivors, self.ops.AHC_MAX_N)
+        return int(4 * rows * ld + 4 * (subsets * subsets).sum() + self.ops.ahc_cluster_sums_workspace_bytes([rows], [survivors]) + 4 * survivors * survivors)
 
     def _vbx(self, names, matrices, labels, n):
         """ops.vbx over one batch: labels = the clusterer's, back to back.  -> the new labels, back to back."""
@@ -249,8 +293,12 @@ class Diarizer(object):
             from _host import greedy_batches, pitch4
         n = np.asarray([int(embeddings[k].shape[0]) for k in keys], np.int64)
         for k, rows in zip(keys, n):
-            if rows < 1 or rows > self.ops.AHC_MAX_N:
-                raise ValueError("Diarizer: recording %s has %d windows, 1 .. %d are taken" % (k, rows, self.ops.AHC_MAX_N))
+            if rows < 1 or rows > self.ops.AHC_MAX_POINTS:
+                raise ValueError("Diarizer: recording %s has %d windows, 1 .. %d are taken" % (k, rows, self.ops.AHC_MAX_POINTS))
+            for option, op, on in (("vbx", "xv_vbx", self.vbx is not None), ("target_energy", "xv_backend_pca_plda", self.target_energy is not None)):
+                if on and rows > self.ops.AHC_MAX_N:
+                    raise ValueError("Diarizer: recording %s has %d windows: %s= takes recordings of at most %d (%s keeps its cap; the two-pass "
+                                     "clustering alone goes further)" % (k, rows, option, self.ops.AHC_MAX_N, op))
         if self.reco2num_spk is not None:
             missing = [k for k in keys if k not in self.reco2num_spk]
             if missing:
@@ -263,6 +311,8 @@ class Diarizer(object):
             targets = np.zeros(len(keys), np.int64)
         ld = np.asarray([pitch4(int(r)) for r in n], np.int64)
         cost = 4 * (n * ld + n * n)      # bytes of a recording: its matrix in the packed buffer and the clusterer's copy
+        for i in np.flatnonzero(n > self.first_pass_max_points):
+            cost[i] = self._two_pass_bytes(int(n[i]), int(ld[i]), int(targets[i]))
         if self.target_energy is not None:      # ... its unit-length rows packed for the op, the op's scratch and its fp32 outputs
             dim4 = pitch4(self.scorer.dim)
             cost = cost + 4 * n * dim4 + self.ops.backend_pca_plda_workspace_bytes(1, self.scorer.dim) + 4 * dim4 * (dim4 + 8)
@@ -288,7 +338,7 @@ class Diarizer(object):
                     self.pca_report[keys[i]] = 0 if model is None else int(model[0])
                     self.scorer.dense(prepared, out=view, model=model)
             del own
-            labels = self._ahc(packed, offsets[:-1], n[batch], ld[batch], targets[batch])
+            labels = self._ahc(packed, offsets[:-1], n[batch], ld[batch], targets[batch], [keys[i] for i in batch])
             at = np.concatenate([[0], np.cumsum(n[batch])])
             if self.vbx is not None:
                 cap = self.ops.VBX_MAX_SPEAKERS
@@ -298,7 +348,7 @@ class Diarizer(object):
                               % (", ".join(keys[batch[j]] for j in many), cap, cap))
                     again = targets[batch].copy()
                     again[many] = cap
-                    relabel = self._ahc(packed, offsets[:-1], n[batch], ld[batch], again)
+                    relabel = self._ahc(packed, offsets[:-1], n[batch], ld[batch], again, [keys[i] for i in batch])
                     for j in many:
                         labels[at[j]:at[j + 1]] = relabel[at[j]:at[j + 1]]
                 del packed

@@ -129,6 +129,11 @@ ARGUMENTS = {
                                                                                 "of the energy, in (0, 1] (ivector-plda-scoring-dense "
                                                                                 "--target-energy; the callhome recipe: 0.9).  Needs --scoring plda.  "
                                                                                 "Default: off.")),
+    "first_pass_max_points": (("--first-pass-max-points",), dict(type=int, default=2048, help="A recording of more windows than this (2 .. 2048; "
+                                                                 "agglomerative-cluster's option) is clustered in two passes: contiguous subsets "
+                                                                 "of at most this many windows down to ten times the wanted clusters, then the "
+                                                                 "survivors against each other; up to 32768 windows.  Such a recording above 2048 "
+                                                                 "windows is refused with --vbx or --target-energy (their caps stay at 2048).")),
     # positionals
     "rttm_out": (("rttm_out",), dict(type=str, help="The RTTM file to write.")),
     "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),

@@ -5,7 +5,7 @@
     python nnet/lib/diarize.py [-g GPU] [--cmn-window 300] [--window 1.5 --period 0.75 --min-segment 0.5] [--segments FILE | --vad RSPECIFIER]
                                [--backend DIR --scoring {cosine,lda_cos,plda} [--target-energy F]] (--threshold T | --reco2num-spk FILE)
                                [--vbx [--vbx-fa 0.3 --vbx-fb 17 --vbx-loop-prob 0.99 --vbx-max-iters 20 --vbx-epsilon 1e-4 --vbx-init-smoothing 5]]
-                               [--write-embeddings WSPECIFIER] model_dir rspecifier rttm_out
+                               [--first-pass-max-points 2048] [--write-embeddings WSPECIFIER] model_dir rspecifier rttm_out
 
 rspecifier: an ark (or input pipe) of RAW feature matrices, one per recording, at a frame shift of 10 ms.  Per recording: sliding-window
 CMN over the whole recording on the GPU (ops.frontend; as in the recipe it runs before the cut and no frame is removed); the speech
@@ -16,14 +16,17 @@ LDA cosine or the PLDA log-likelihood ratio - with --target-energy F behind ivec
 scored with the PLDA model projected into the leading directions of its own windows that hold F of the energy (xv_backend_pca_plda:
 DESIGN.md section 6k; one log line per recording gives the kept dimension; off by default, and then every output is what it was without
 the option), agglomerative clustering on the GPU (xv_ahc_cluster) down to --threshold or to the
-recording's entry in --reco2num-spk; with --vbx the clusterer's labels (it should stop early: too many speakers) start the VB-HMM
+recording's entry in --reco2num-spk - a recording of more than --first-pass-max-points windows (Kaldi's option and default, 2048) in two
+passes, as agglomerative-cluster does it: contiguous subsets down to ten times the wanted clusters, then the survivors against each other
+over the whole score matrix (xv_ahc_cluster_from, xv_ahc_cluster_sums: DESIGN.md section 6l; up to 32768 windows); with --vbx the clusterer's labels (it should stop early: too many speakers) start the VB-HMM
 clustering of the windows in the PLDA space (VBx, xv_vbx: DESIGN.md section 6j), which re-assigns them and drops redundant speakers - one log
 line per recording says speakers before and after, iterations and the last ELBO; and the turns: overlapping windows are cut at the midpoint
 of the overlap, abutting windows of one speaker merged.  Output: `SPEAKER <recording> 0 <start> <duration> <NA> <NA> <speaker> <NA> <NA>` lines, speakers numbered from 1 per
 recording.  --write-embeddings: the windows' embeddings, keyed `recording-startframe-endframe`.
 Refused: both or neither of --threshold / --reco2num-spk, --segments beside --vad, a back end without a --scoring that uses it (and the
-reverse), --vbx without --scoring plda or with an option outside its range, --target-energy without --scoring plda or outside (0, 1], a --min-segment below the network's receptive field, a recording of more than 2048 windows (Kaldi's two-pass clustering of long
-recordings is not here), a recording without an entry in --reco2num-spk.
+reverse), --vbx without --scoring plda or with an option outside its range, --target-energy without --scoring plda or outside (0, 1], a --min-segment below the network's receptive field, a --first-pass-max-points outside 2 .. 2048, a recording of more than 32768 windows, a
+recording of more than 2048 windows together with --vbx or --target-energy (their kernels keep the cap of 2048), a recording whose first pass
+leaves more than 2048 clusters, a recording without an entry in --reco2num-spk.
 Not here: waveform input (make_mfcc.py writes the archive this reads), threshold calibration, overlap detection.
 """
 import os
@@ -73,7 +76,7 @@ def window_embeddings(trainer, ops, torch, matrix, windows, cmn_window):
 def main():
     log = _cli.logger()
     args = _cli.parser_for("gpu", "prep_cmn_window", "window", "period", "min_segment", "segments", "diar_vad", "backend", "diar_scoring", "threshold",
-                           "reco2num_spk", "vbx", "vbx_fa", "vbx_fb", "vbx_loop_prob", "vbx_max_iters", "vbx_epsilon", "vbx_init_smoothing", "target_energy", "write_embeddings", "model_dir", "rspecifier", "rttm_out").parse_args()
+                           "reco2num_spk", "vbx", "vbx_fa", "vbx_fb", "vbx_loop_prob", "vbx_max_iters", "vbx_epsilon", "vbx_init_smoothing", "target_energy", "first_pass_max_points", "write_embeddings", "model_dir", "rspecifier", "rttm_out").parse_args()
     if (args.threshold is None) == (not args.reco2num_spk):
         sys.exit("exactly one of --threshold and --reco2num-spk says when the merging stops")
     if args.segments and args.vad:
@@ -92,6 +95,8 @@ def main():
         sys.exit("--target-energy needs --scoring plda (the per-recording PCA projects the PLDA model of --backend), not --scoring %s" % args.scoring)
     if args.target_energy is not None and not 0.0 < args.target_energy <= 1.0:
         sys.exit("--target-energy must lie in (0, 1] (got %g)" % args.target_energy)
+    if not 2 <= args.first_pass_max_points <= 2048:
+        sys.exit("--first-pass-max-points must lie in 2 .. 2048 (got %d)" % args.first_pass_max_points)
     if args.cmn_window < 0:
         sys.exit("--cmn-window must be 0 (off) or a number of frames")
     window, period, min_segment = (int(round(v / FRAME_SHIFT)) for v in (args.window, args.period, args.min_segment))
@@ -149,8 +154,6 @@ def main():
         if not windows:
             log.info("[INFO] Recording %s: no speech segment of %d frames or more, skip." % (reco, min_segment))
             continue
-        if len(windows) > ops.AHC_MAX_N:
-            sys.exit("recording %s has %d windows, the clusterer takes %d (a longer --period, or cut the recording)" % (reco, len(windows), ops.AHC_MAX_N))
         emb = window_embeddings(trainer, ops, torch, matrix, windows, args.cmn_window)
         log.info("[INFO] Recording %s: %d frames, %d speech segments, %d windows." % (reco, frames, len(speech), len(windows)))
         if fp_emb is not None:
@@ -180,7 +183,8 @@ def main():
         if args.vbx:
             vbx = diarization.VbxOptions(fa=args.vbx_fa, fb=args.vbx_fb, loop_prob=args.vbx_loop_prob, max_iters=args.vbx_max_iters,
                                          epsilon=args.vbx_epsilon, init_smoothing=args.vbx_init_smoothing)
-        diarizer = diarization.Diarizer(scorer, threshold=args.threshold, reco2num_spk=reco2num_spk, vbx=vbx, target_energy=args.target_energy)
+        diarizer = diarization.Diarizer(scorer, threshold=args.threshold, reco2num_spk=reco2num_spk, vbx=vbx, target_energy=args.target_energy,
+                                        first_pass_max_points=args.first_pass_max_points)
         labels = diarizer.cluster(embeddings)
     except ValueError as e:
         sys.exit(str(e))

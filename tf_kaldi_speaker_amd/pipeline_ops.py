@@ -377,7 +377,220 @@ def ahc_cluster(scores, mat_offsets, n, ld=None, threshold=0.0, targets=None):
     return labels, merges[:total - b], values[:total - b], n_merges
 
 
-VBX_MAX_SPEAKERS = 32      # the speakers (HMM states) of one recording xv_vbx takes
+AHC_MAX_POINTS = 32768      # the rows of one recording the two-pass clustering takes (xv_ahc_cluster_sums; the sizes of a seed together)
+
+
+def _ahc_matrices(name, scores, mat_offsets, n, ld, cap):
+    """The host checks ahc_cluster makes of its matrices, for the ops of the two-pass clustering.  -> (n, ld, mat_offsets) as host arrays."""
+    if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous() or scores.numel() == 0:
+        raise ValueError("%s: scores must be a non-empty contiguous 1-D float32 tensor" % name)
+    n = host_ints(n, name + ": n", min_size=1)
+    b = n.size
+    if n.min() < 1:
+        raise ValueError("%s: recording %d has no row (n = %d)" % (name, int(np.argmax(n < 1)), int(n.min())))
+    if n.max() > cap:
+        raise ValueError("%s: recording %d has %d rows, the cap is %d" % (name, int(np.argmax(n > cap)), int(n.max()), cap))
+    ld = n if ld is None else host_ints(ld, name + ": ld", n=b)
+    if (ld < n).any():
+        i = int(np.argmax(ld < n))
+        raise ValueError("%s: recording %d: the pitch %d is below its %d rows" % (name, i, int(ld[i]), int(n[i])))
+    mat_offsets = host_ints(mat_offsets, name + ": mat_offsets", n=b, dtype=np.int64)
+    n64, ld64 = n.astype(np.int64), ld.astype(np.int64)
+    spans_inside(mat_offsets, (n64 - 1) * ld64 + n64, scores.numel(), "%s: a matrix lies outside the %d floats of scores" % (name, scores.numel()))
+    return n64, ld64, mat_offsets
+
+
+def ahc_cluster_from(scores, mat_offsets, n, ld=None, floors=None, threshold=float("-inf"), seed=None, sizes=None):
+    """The clusterer with a floor (xv_ahc_cluster_from; tests/ahc2_ref.py restates it): recording i merges while it has more than floors[i]
+    clusters (1 .. n[i]; None: 1) AND the best average score is >= threshold (-inf: down to the floor).  Two starts.  From scores (seed
+    None): scores, mat_offsets, n, ld as for ahc_cluster - a sub-block of a matrix is a matrix at an offset on that matrix's pitch.
+    Seeded: seed is a contiguous 1-D float32 device tensor that holds recording i's T [n[i], n[i]] (symmetric, pitch n[i]) at the exclusive
+    prefix of n^2 - it is the clusterer's scratch and is MODIFIED -, sizes a HOST integer array [sum n], each >= 1, a recording's together at
+    most 32768 (ahc_cluster_sums gives both); scores, mat_offsets and ld must be None.  -> ahc_cluster's four outputs."""
+    name = "ahc_cluster_from"
+    if seed is None:
+        if sizes is not None:
+            raise ValueError("%s: sizes belong to a seeded start (seed is None)" % name)
+        n, ld, mat_offsets = _ahc_matrices(name, scores, mat_offsets, n, ld, AHC_MAX_N)
+        dev = scores.device
+    else:
+        if scores is not None or mat_offsets is not None or ld is not None:
+            raise ValueError("%s: a seeded start reads no scores (scores, mat_offsets and ld must be None)" % name)
+        n = host_ints(n, name + ": n", min_size=1, dtype=np.int64)
+        if n.min() < 1 or n.max() > AHC_MAX_N:
+            i = int(np.argmax((n < 1) | (n > AHC_MAX_N)))
+            raise ValueError("%s: recording %d has %d clusters, 1 .. %d are taken" % (name, i, int(n[i]), AHC_MAX_N))
+        if seed.dtype != torch.float32 or seed.dim() != 1 or not seed.is_contiguous() or seed.numel() < int((n * n).sum()):
+            raise ValueError("%s: seed must be a contiguous 1-D float32 tensor of at least %d floats" % (name, int((n * n).sum())))
+        sizes = host_ints(sizes if sizes is not None else [], name + ": sizes", n=int(n.sum()))
+        members = np.add.reduceat(np.maximum(sizes, 0).astype(np.int64), exclusive_offsets(n))
+        wrong = (np.minimum.reduceat(sizes, exclusive_offsets(n)) < 1) | (members > AHC_MAX_POINTS)
+        if wrong.any():
+            raise ValueError("%s: recording %d: the sizes must be positive and add up to at most %d" % (name, int(np.argmax(wrong)), AHC_MAX_POINTS))
+        dev = seed.device
+    b = n.size
+    floors = np.ones(b, np.int32) if floors is None else host_ints(floors, name + ": floors", n=b)
+    if (floors < 1).any() or (floors > n).any():
+        i = int(np.argmax((floors < 1) | (floors > n)))
+        raise ValueError("%s: recording %d: floor %d outside 1 .. %d" % (name, i, int(floors[i]), int(n[i])))
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("%s: the threshold is NaN" % name)
+    total, sum_n2 = int(n.sum()), int((n * n).sum())
+    labels = torch.empty(total, dtype=torch.int32, device=dev)
+    merges = torch.empty((max(total - b, 1), 2), dtype=torch.int32, device=dev)
+    values = torch.empty(max(total - b, 1), dtype=torch.float32, device=dev)
+    n_merges = torch.empty(b, dtype=torch.int32, device=dev)
+    n_d, f_d = upload(n, np.int32, dev), upload(floors, np.int32, dev)
+    if seed is None:
+        ws_bytes = int(_lib.load().xv_ahc_cluster_from_workspace_bytes(C.c_int64(sum_n2)))
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+        off_d, ld_d, s_d = upload(mat_offsets, np.int64, dev), upload(ld, np.int32, dev), None
+    else:
+        ws, ws_bytes, off_d, ld_d, s_d = seed, seed.numel() * 4, None, None, upload(sizes, np.int32, dev)
+    _lib.call("xv_ahc_cluster_from", _s(), _p(scores), C.c_int64(scores.numel() if scores is not None else 0), _p(off_d), _p(n_d), _p(ld_d), _p(f_d),
+              _p(s_d), int(seed is not None), b, int(n.max()), C.c_int64(total), C.c_int64(sum_n2), C.c_float(threshold), _p(labels), _p(merges),
+              _p(values), _p(n_merges), _p(ws), C.c_size_t(ws_bytes))
+    return labels, merges[:total - b], values[:total - b], n_merges
+
+
+def ahc_member_lists(labels, n):
+    """Clusters as the member lists ahc_cluster_sums takes, from HOST labels [sum n] (recording i's n[i] back to back, numbered 0, 1, ... in
+    the order of their smallest members, as the clusterer numbers them).  -> (members int32 [sum n], starts int32 [sum (c + 1)], c int64 [b])."""
+    n = host_ints(n, "ahc_member_lists: n", min_size=1, dtype=np.int64)
+    labels = host_ints(labels, "ahc_member_lists: labels", n=int(n.sum()))
+    members, starts, c = [], [], []
+    for lo, hi in zip(exclusive_offsets(n), np.cumsum(n)):
+        lab = labels[lo:hi]
+        uniq, first = np.unique(lab, return_index=True)
+        if lab.size == 0 or uniq[0] != 0 or uniq[-1] != uniq.size - 1 or (np.diff(first) <= 0).any():
+            raise ValueError("ahc_member_lists: a recording's labels must be 0, 1, ... in the order of the clusters' smallest members")
+        members.append(np.argsort(lab, kind="stable").astype(np.int32))
+        starts.append(np.concatenate([[0], np.cumsum(np.bincount(lab))]).astype(np.int32))
+        c.append(uniq.size)
+    return np.concatenate(members), np.concatenate(starts), np.asarray(c, np.int64)
+
+
+def ahc_cluster_sums_workspace_bytes(n, c):
+    """Bytes of scratch xv_ahc_cluster_sums needs for recordings of n[i] rows in c[i] clusters (host integer arrays of one length)."""
+    n, c = np.asarray(n, dtype=np.int64), np.asarray(c, dtype=np.int64)
+    return int(_lib.load().xv_ahc_cluster_sums_workspace_bytes(int(n.size), C.c_int64(int((n * c).sum()))))
+
+
+def ahc_cluster_sums(scores, mat_offsets, n, ld, members, starts, c):
+    """The seed of a second clustering pass (xv_ahc_cluster_sums; include/xvector_hip.h states the order of every sum, tests/ahc2_ref.py
+    restates it): T[A][B] = the sum of the scores between the members of clusters A and B of each of b recordings, from the upper triangles
+    of their matrices (scores, mat_offsets, n <= 32768, ld as for ahc_cluster).  members, starts, c: HOST integer arrays as ahc_member_lists
+    gives them - recording i's rows cluster by cluster, clusters ascending by smallest member, members ascending; c[i] <= 2048 - checked
+    here before the upload.  -> (seed float32 [sum c^2], sizes int32 [sum c]), device tensors: what ahc_cluster_from takes for a seeded start."""
+    name = "ahc_cluster_sums"
+    n, ld, mat_offsets = _ahc_matrices(name, scores, mat_offsets, n, ld, AHC_MAX_POINTS)
+    b = n.size
+    c = host_ints(c, name + ": c", n=b, dtype=np.int64)
+    if (c < 1).any() or (c > np.minimum(n, AHC_MAX_N)).any():
+        i = int(np.argmax((c < 1) | (c > np.minimum(n, AHC_MAX_N))))
+        raise ValueError("%s: recording %d has %d clusters, 1 .. %d are taken" % (name, i, int(c[i]), int(min(n[i], AHC_MAX_N))))
+    members = host_ints(members, name + ": members", n=int(n.sum()))
+    starts = host_ints(starts, name + ": starts", n=int(c.sum()) + b)
+    for i, (m0, s0) in enumerate(zip(exclusive_offsets(n), exclusive_offsets(c + 1))):
+        st, mem = starts[s0:s0 + c[i] + 1], members[m0:m0 + n[i]]
+        if st[0] != 0 or st[-1] != n[i] or (np.diff(st) <= 0).any():
+            raise ValueError("%s: recording %d: starts must ascend from 0 to its %d rows" % (name, i, int(n[i])))
+        inner = np.ones(mem.size, bool)
+        inner[st[:-1]] = False      # (the first member of a cluster need not be above the last of the cluster before)
+        if not np.array_equal(np.sort(mem), np.arange(n[i])) or (np.diff(mem)[inner[1:]] <= 0).any() or (np.diff(mem[st[:-1]]) <= 0).any():
+            raise ValueError("%s: recording %d: members must hold every row once, clusters ascending by their smallest member, a cluster's "
+                             "members ascending" % (name, i))
+    dev = scores.device
+    seed = torch.empty(int((c * c).sum()), dtype=torch.float32, device=dev)
+    sizes = torch.empty(int(c.sum()), dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    ws_bytes = ahc_cluster_sums_workspace_bytes(n, c)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    off_d, n_d, ld_d, c_d = upload(mat_offsets, np.int64, dev), upload(n, np.int32, dev), upload(ld, np.int32, dev), upload(c, np.int32, dev)
+    mem_d, st_d = upload(members, np.int32, dev), upload(starts, np.int32, dev)
+    _lib.call("xv_ahc_cluster_sums", _s(), _p(scores), C.c_int64(scores.numel()), _p(off_d), _p(n_d), _p(ld_d), _p(c_d),
+              _p(mem_d), _p(st_d), b, int(n.max()), int(c.max()), C.c_int64(int(n.sum())), C.c_int64(int(c.sum())),
+              C.c_int64(int((c * c).sum())), C.c_int64(int((n * c).sum())), _p(seed), _p(sizes), _p(status), _p(ws), C.c_size_t(ws_bytes))
+    if int(status.min()) != 0:
+        raise RuntimeError("%s: xv_ahc_cluster_sums skipped recording %d" % (name, int(torch.argmin(status))))
+    return seed, sizes
+
+
+def ahc_subsets(n, first_pass_max_points):
+    """The contiguous subsets of the first pass for a recording of n rows: ceil(n / first_pass_max_points) of them, ceil(n / that number)
+    rows each, the last one shorter.  -> the boundaries, int64 [subsets + 1], from 0 to n."""
+    n, cap = int(n), int(first_pass_max_points)
+    subsets = -(-n // cap)
+    size = -(-n // subsets)
+    return np.minimum(np.arange(subsets + 1, dtype=np.int64) * size, n)
+
+
+def ahc_cluster_two_pass(scores, mat_offsets, n, ld=None, threshold=0.0, targets=None, first_pass_max_points=AHC_MAX_N):
+    """Two-pass clustering of recordings of up to 32768 rows (Kaldi's AgglomerativeClusterer::ClusterTwoPass, recalled and restated - not
+    compared with a Kaldi run, max_spk_fraction left out; tests/ahc2_ref.py restates this driver).  scores, mat_offsets, n, ld as for
+    ahc_cluster.  targets None: every recording merges while the best average score is >= threshold; else targets[i] >= 1 clusters for
+    every recording (a call has one stop rule).  A recording of more than first_pass_max_points (2 .. 2048) rows is cut into ahc_subsets;
+    one ahc_cluster_from call clusters every subset of every recording down to min(its rows, 10 x max(target, 1)) clusters (or until the
+    threshold stops it); ahc_cluster_sums adds up the scores between the surviving clusters, and one seeded ahc_cluster_from call merges
+    them down to the target (threshold -inf) or the threshold (floor 1).  A row's label is the second-pass label of its first-pass
+    cluster; final clusters are numbered by their smallest members.  A shorter recording is one subset that the first pass clusters to the
+    end; its second pass merges nothing.  The first pass's labels come back to the host between the passes (one synchronisation).
+    -> (labels int32 [sum n] on the device, first, second, subsets): first / second = (merges, merge_values, n_merges) of the two
+    ahc_cluster_from calls - the first per subset in order, in the subset's row numbers; the second per recording, in first-pass cluster
+    numbers -, subsets = [ahc_subsets(n[i])] per recording."""
+    name = "ahc_cluster_two_pass"
+    n, ld, mat_offsets = _ahc_matrices(name, scores, mat_offsets, n, ld, AHC_MAX_POINTS)
+    b, cap = n.size, int(first_pass_max_points)
+    if not 2 <= cap <= AHC_MAX_N:
+        raise ValueError("%s: first_pass_max_points must lie in 2 .. %d (got %d)" % (name, AHC_MAX_N, cap))
+    if targets is None:
+        targets = np.zeros(b, np.int64)
+    else:
+        targets = host_ints(targets, name + ": targets", n=b, dtype=np.int64)
+        if (targets < 1).any() or (targets > n).any():
+            i = int(np.argmax((targets < 1) | (targets > n)))
+            raise ValueError("%s: recording %d: target %d outside 1 .. %d (None: the threshold, for every recording)" % (name, i, int(targets[i]), int(n[i])))
+        threshold = float("-inf")
+    ends = np.maximum(targets, 1)      # where a recording's merging may end at the latest
+    subsets = [ahc_subsets(r, cap) for r in n]
+    sub_off, sub_n, sub_ld, sub_floor = [], [], [], []
+    for i, bounds in enumerate(subsets):
+        rows = np.diff(bounds)
+        sub_off.append(mat_offsets[i] + bounds[:-1] * (ld[i] + 1))
+        sub_n.append(rows)
+        sub_ld.append(np.full(rows.size, ld[i]))
+        sub_floor.append(np.minimum(rows, 10 * ends[i]) if rows.size > 1 else ends[i:i + 1])
+    sub_n = np.concatenate(sub_n)
+    labels1, merges1, values1, n_merges1 = ahc_cluster_from(scores, np.concatenate(sub_off), sub_n, np.concatenate(sub_ld), floors=np.concatenate(sub_floor),
+                                                            threshold=threshold)
+    local = labels1.cpu().numpy().astype(np.int64)
+    if int(n_merges1.min()) < 0:
+        raise RuntimeError("%s: xv_ahc_cluster_from skipped subset %d" % (name, int(torch.argmin(n_merges1))))
+    # a recording's first-pass clusters, numbered through its subsets: ascending by smallest member, since the subsets are contiguous
+    clusters, c, at = np.empty(int(n.sum()), np.int64), np.zeros(b, np.int64), 0
+    for i, bounds in enumerate(subsets):
+        for rows in np.diff(bounds):
+            clusters[at:at + rows] = c[i] + local[at:at + rows]
+            c[i] += local[at:at + rows].max() + 1
+            at += rows
+        if c[i] > AHC_MAX_N:
+            what = "the first pass leaves %d clusters, the second pass takes %d (lower the threshold or first_pass_max_points)" % (int(c[i]), AHC_MAX_N)
+            error = ValueError("%s: recording %d: %s" % (name, i, what))
+            error.recording, error.what = i, what      # (for a caller that knows the recording by name)
+            raise error
+    members, starts, _ = ahc_member_lists(clusters, n)
+    seed, _ = ahc_cluster_sums(scores, mat_offsets, n, ld, members, starts, c)
+    sizes = np.concatenate([np.bincount(clusters[lo:hi]) for lo, hi in zip(exclusive_offsets(n), np.cumsum(n))])
+    floors2 = np.where(n > cap, ends, c)      # (a short recording is done)
+    labels2, merges2, values2, n_merges2 = ahc_cluster_from(None, None, c, floors=floors2, threshold=threshold, seed=seed, sizes=sizes)
+    if int(n_merges2.min()) < 0:
+        raise RuntimeError("%s: xv_ahc_cluster_from skipped recording %d in the second pass" % (name, int(torch.argmin(n_merges2))))
+    index = upload(clusters + np.repeat(exclusive_offsets(c), n), np.int64, scores.device)
+    return labels2[index], (merges1, values1, n_merges1), (merges2, values2, n_merges2), subsets
+
+
+VBX_MAX_SPEAKERS = 32     # the speakers (HMM states) of one recording xv_vbx takes
 VBX_MAX_DIM = 256          # ... the dimensions of its rows
 VBX_MAX_ITERS = 64         # ... and the iterations of one call
 

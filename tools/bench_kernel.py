@@ -24,6 +24,8 @@ sub-command per question (they used to be eight scripts):
                                                                 n = 200 / 800 / 2000 windows, into a view of a packed buffer
   python tools/bench_kernel.py ahc [recordings=64] [n ...]      agglomerative clustering (xv_ahc.hip): one call over 64 recordings of n = 200 / 800 / 2000
                                                                 windows, medians over alternated rounds, beside scipy's average linkage on 16 CPUs
+  python tools/bench_kernel.py ahc2 [n ...]                     two-pass clustering of one long recording (xv_ahc_cluster_from, xv_ahc_cluster_sums): n = 4096 / 8192
+                                                                windows, the stages apart, the single pass at 2048 windows for scale
   python tools/bench_kernel.py vbx [recordings=64] [T,S ...]     VB-HMM clustering (xv_vbx.hip): one call over 64 recordings at (T, D, S) = (200, 128, 6), (800, 128, 10)
                                                                 and (2000, 128, 16), 20 iterations, medians over alternated rounds, beside the float64 NumPy
                                                                 restatement of one recording on the CPU
@@ -665,6 +667,77 @@ def cmd_ahc(argv):
               % (recordings, n, n - 1, med, " ".join("%.2f" % t for t in times[n]), med * 1e3 / (n - 1), cpu[n]), flush=True)
 
 
+def cmd_ahc2(argv):
+    """Two-pass clustering of ONE long recording (ops.ahc_cluster_two_pass, first_pass_max_points 2048, down to 4 speakers) at n = 4096 and
+    8192 windows, and the single pass (ops.ahc_cluster) over the first 2048 windows for scale: milliseconds per call, medians over five
+    rounds that alternate the sizes.  The stages apart: the first pass (ops.ahc_cluster_from over the subsets), the cluster sums (the bare
+    xv_ahc_cluster_sums entry on uploaded lists: its three launches and nothing else) and the seeded second pass on a fresh copy of the
+    seed.  Beside the sums: torch.sum over the recording's n x ld floats (a flat streaming read of the same matrix) and n^2 x 4 bytes at
+    0.82 of the 8 TB/s HBM peak (what DESIGN.md section 8 quotes for a flat streaming kernel)."""
+    import ctypes as C
+    from tf_kaldi_speaker_amd import _lib, ops
+    from tf_kaldi_speaker_amd._host import _p, _s, upload
+    sizes = [int(a) for a in argv] or [4096, 8192]
+    speakers, cap, inf = 4, 2048, float("-inf")
+    data = {}
+    for n in sizes + [cap]:
+        x = rs.randn(speakers, 64)[rs.randint(0, speakers, n)] + 0.6 * rs.randn(n, 64)
+        x /= np.linalg.norm(x, axis=1, keepdims=True)
+        xd = torch.from_numpy(x.astype(np.float32)).cuda()
+        ld = (n + 3) // 4 * 4
+        buf = torch.zeros(n * ld, device="cuda")
+        buf.view(n, ld)[:, :n] = xd @ xd.T
+        data[n] = (buf, ld)
+    stages = {}
+    for n in sizes:      # the stages' inputs, as ops.ahc_cluster_two_pass builds them
+        buf, ld = data[n]
+        bounds = ops.ahc_subsets(n, cap)
+        rows = np.diff(bounds)
+        first = (buf, bounds[:-1] * (ld + 1), rows, np.full(rows.size, ld), np.minimum(rows, 10 * speakers))
+        local = ops.ahc_cluster_from(*first[:4], floors=first[4], threshold=inf)[0].cpu().numpy().astype(np.int64)
+        clusters = np.concatenate([local[a:b] + 10 * speakers * k for k, (a, b) in enumerate(zip(bounds[:-1], bounds[1:]))])
+        members, starts, c = ops.ahc_member_lists(clusters, [n])
+        seed, dsizes = ops.ahc_cluster_sums(buf, [0], [n], [ld], members, starts, c)
+        cc = int(c[0])
+        dev = dict(off=upload([0], np.int64, "cuda"), n=upload([n], np.int32, "cuda"), ld=upload([ld], np.int32, "cuda"), c=upload(c, np.int32, "cuda"),
+                   members=upload(members, np.int32, "cuda"), starts=upload(starts, np.int32, "cuda"), seed=torch.empty_like(seed),
+                   sizes=torch.empty_like(dsizes), status=torch.empty(1, dtype=torch.int32, device="cuda"))
+        ws_bytes = ops.ahc_cluster_sums_workspace_bytes([n], c)
+        dev["ws"] = torch.empty(ws_bytes // 8, dtype=torch.float64, device="cuda")
+        bare = lambda buf=buf, n=n, cc=cc, d=dev, ws_bytes=ws_bytes: _lib.call(
+            "xv_ahc_cluster_sums", _s(), _p(buf), C.c_int64(buf.numel()), _p(d["off"]), _p(d["n"]), _p(d["ld"]), _p(d["c"]), _p(d["members"]), _p(d["starts"]),
+            1, n, cc, C.c_int64(n), C.c_int64(cc), C.c_int64(cc * cc), C.c_int64(n * cc), _p(d["seed"]), _p(d["sizes"]), _p(d["status"]), _p(d["ws"]),
+            C.c_size_t(ws_bytes))
+        bare()
+        assert int(dev["status"][0]) == 0 and torch.equal(dev["seed"], seed)
+        stages[n] = (first, bare, seed, dsizes.cpu().numpy(), cc, dev)
+    times = {}
+    for _ in range(5):
+        for n in sizes:
+            buf, ld = data[n]
+            first, bare, seed, hsizes, cc, dev = stages[n]
+            t = times.setdefault(n, {k: [] for k in ("two_pass", "first", "sums", "second", "stream")})
+            t["two_pass"].append(timeit(lambda: ops.ahc_cluster_two_pass(buf, [0], [n], [ld], targets=[speakers], first_pass_max_points=cap), 3, 1) / 1e3)
+            t["first"].append(timeit(lambda: ops.ahc_cluster_from(*first[:4], floors=first[4], threshold=inf), 3, 1) / 1e3)
+            t["sums"].append(timeit(bare, 20, 3) / 1e3)
+            t["second"].append(timeit(lambda: ops.ahc_cluster_from(None, None, [cc], floors=[speakers], seed=seed.clone(), sizes=hsizes), 5, 1) / 1e3)
+            t["stream"].append(timeit(lambda: buf.sum(), 20, 3) / 1e3)
+        buf, ld = data[cap]
+        times.setdefault(cap, {"single": []})["single"].append(timeit(lambda: ops.ahc_cluster(buf, [0], [cap], [ld], targets=[speakers]), 3, 1) / 1e3)
+    show = lambda v: "%9.3f ms (rounds %s)" % (float(np.median(v)), " ".join("%.3f" % a for a in v))
+    print("ahc2: single pass, n = %d down to %d clusters: %s" % (cap, speakers, show(times[cap]["single"])), flush=True)
+    for n in sizes:
+        t, cc = times[n], stages[n][4]
+        sums, bound = float(np.median(t["sums"])), 4.0 * n * n / (0.82 * 8e12) * 1e3
+        print("ahc2: n = %5d, %d subsets, %d survivors, down to %d clusters: two passes %s" % (n, len(ops.ahc_subsets(n, cap)) - 1, cc, speakers, show(t["two_pass"])))
+        print("ahc2: n = %5d   first pass %s" % (n, show(t["first"])))
+        print("ahc2: n = %5d   cluster sums, bare entry %s" % (n, show(t["sums"])))
+        print("ahc2: n = %5d   second pass, seeded (with the copy of the %d x %d seed) %s" % (n, cc, cc, show(t["second"])))
+        print("ahc2: n = %5d   torch.sum over the matrix's %d floats %s" % (n, data[n][0].numel(), show(t["stream"])))
+        print("ahc2: n = %5d   n^2 floats at 0.82 of 8 TB/s: %.4f ms; the cluster sums take %.1f x that, %.2f x the torch.sum" %
+              (n, bound, sums / bound, sums / float(np.median(t["stream"]))), flush=True)
+
+
 def cmd_vbx(argv):
     """One xv_vbx call over `recordings` recordings of T windows in 128 dimensions started from S speakers (the generator of tests/vbx_ref.py:
     S // 2 true speakers, each split in two), 20 iterations, never stopped: milliseconds per call, medians over five rounds that alternate
@@ -939,7 +1012,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"ahc": cmd_ahc, "vbx": cmd_vbx, "pca_plda": cmd_pca_plda, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
+COMMANDS = {"ahc": cmd_ahc, "ahc2": cmd_ahc2, "vbx": cmd_vbx, "pca_plda": cmd_pca_plda, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
             "triplet": cmd_triplet, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
