@@ -217,6 +217,50 @@ def test_packed_batches_decode_to_the_host_decoded_ones(nl, data, tmp_path):
     plain.stop()
 
 
+def test_packed_bytes_do_not_depend_on_the_ring_depth(nl, data):
+    """Batch i is a function of (seed, i) down to its raw bytes: a packed chunk's padding (up to 15 bytes of its 16-byte stride) is
+    zero, not whatever an earlier batch of another length left in the ring slot - the bytes are the same for every max_qsize."""
+    root, spklist, _ = data
+    streams, pads = {}, 0
+    for depth in (1, 2, 5):
+        q = nl.NativeRandomQueue(root, spklist, num_parallel=2, max_qsize=depth, seed=11, num_speakers=5, num_segments=3, min_len=40, max_len=65,
+                                 shuffle=True, packed=True)
+        q.start()
+        out = []
+        for _ in range(12):
+            buf, lab = np.full(15 * nl.packed_chunk_bytes(q.dim, 65), 0xA5, np.uint8), np.empty(15, np.int32)
+            t = q.fetch_packed_into(buf, lab)
+            stride, used = nl.packed_chunk_bytes(q.dim, t), 8 + 8 * q.dim + q.dim * t
+            raw = buf[:15 * stride].reshape(15, stride)
+            assert not raw[:, used:].any(), "depth %d: padding bytes of a %d-frame batch are not zero" % (depth, t)
+            pads += stride - used
+            out.append((t, raw.tobytes(), lab.tobytes()))
+        q.stop()
+        streams[depth] = out
+    assert pads > 0                                                    # the lengths drawn leave padding to compare
+    assert streams[1] == streams[2] == streams[5]
+
+
+@pytest.mark.parametrize("mapped", [True, False], ids=["mapped", "pread"])
+def test_hostile_arks_are_refused_by_the_shipped_library(mapped, tmp_path):
+    """tests/hostile_arks.py: headers with negative, zero and overflowing shapes, foreign markers, every truncation of a small matrix,
+    scp offsets off the matrix, utt2num_frames above the matrix and below 1, a second utterance with other columns.  The release build
+    refuses each by name through read_rows and through start() / fetch(), mapping on and off, as the instrumented build does
+    (tests/test_loader_sanitized.py) - in a child process, whose crash is this test's failure and not the run's end."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "XVIO_NO_MMAP"}
+    if not mapped:
+        env["XVIO_NO_MMAP"] = "1"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "hostile_arks.py"), str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       universal_newlines=True, env=env, timeout=120)
+    assert p.returncode == 0, "the child ended with status %d:\n%s" % (p.returncode, p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("HOSTILE ")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    assert json.loads(lines[0][len("HOSTILE "):]) == []
+
+
 def test_no_shuffle_starts_at_frame_zero_and_few_speakers_are_duplicated(nl, data):
     root, spklist, mats = data
     decoded = {utt: nl.read_rows(*_scp(root)[utt]) for utt in mats}

@@ -67,16 +67,29 @@ bool pread_all(int fd, void* buf, size_t n, off_t off) {
 struct Source {
     int fd = -1;
     const uint8_t* map = nullptr;
-    size_t size = 0;
+    size_t size = 0;             // the file's size when it was opened: no read reaches past it, mapped or not
+    Source() = default;
+    explicit Source(int fd_) : fd(fd_) {
+        struct stat st;
+        if (fd >= 0 && fstat(fd, &st) == 0 && st.st_size > 0) size = (size_t)st.st_size;
+    }
+    // owns its descriptor and its mapping: whoever drops a Source (an early return of xvio_loader_create included) releases both
+    Source(const Source&) = delete;
+    Source& operator=(const Source&) = delete;
+    Source(Source&& o) noexcept : fd(o.fd), map(o.map), size(o.size) { o.fd = -1; o.map = nullptr; o.size = 0; }
+    ~Source() { close_all(); }
+    // n bytes at off lie inside the file (no sum that can wrap: n and off come from headers this code did not write)
+    bool has(size_t n, int64_t off) const { return off >= 0 && n <= size && (size_t)off <= size - n; }
     bool get(void* dst, size_t n, int64_t off) const {
+        if (!has(n, off)) return false;
         if (!map) return pread_all(fd, dst, n, (off_t)off);
-        if (off < 0 || (size_t)off + n > size) return false;
         memcpy(dst, map + off, n);
         return true;
     }
     // n bytes at off: a pointer into the mapping, or into `scratch` after a pread
     const uint8_t* view(size_t n, int64_t off, std::vector<uint8_t>& scratch) const {
-        if (map) return (off >= 0 && (size_t)off + n <= size) ? map + off : nullptr;
+        if (!has(n, off)) return nullptr;
+        if (map) return map + off;
         scratch.resize(n);
         return pread_all(fd, scratch.data(), n, (off_t)off) ? scratch.data() : nullptr;
     }
@@ -86,11 +99,10 @@ struct Source {
     void open_map() {
         const char* no = getenv("XVIO_NO_MMAP");
         if (no && no[0] && no[0] != '0') return;
-        struct stat st;
-        if (fd < 0 || fstat(fd, &st) != 0 || st.st_size <= 0) return;
-        void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_SHARED, fd, 0);
+        if (fd < 0 || size == 0) return;
+        void* m = mmap(nullptr, size, PROT_READ, MAP_SHARED, fd, 0);
         if (m == MAP_FAILED) return;
-        map = (const uint8_t*)m; size = (size_t)st.st_size;
+        map = (const uint8_t*)m;
     }
     void close_all() {
         if (map) munmap((void*)map, size);
@@ -99,9 +111,34 @@ struct Source {
     }
 };
 
-// rows [start, start+length) of the matrix whose "\0B" marker sits at `off`; scratch is per-thread
+// The shape a matrix header states, for all three kinds: both extents positive and rows * cols * elem (the bytes of its data, elem 1 /
+// 4 / 8 for 'CM ' / 'FM ' / 'DM ') representable, so that every later product of a row range and cols is computed without overflow.
+int check_shape(const char* name, const char* kind, int32_t rows, int32_t cols, int elem) {
+    if (rows <= 0 || cols <= 0 || (int64_t)rows * cols > INT64_MAX / elem) return fail("%s: bad %s shape %d x %d", name, kind, rows, cols);
+    return 0;
+}
+
+// The row range [start, start+length) against the matrix's rows, in 64 bits (start and length are the caller's, up to INT32_MAX
+// each); length < 0 = everything from `start`.
+int check_range(const char* name, int32_t rows, int start, int* length) {
+    const int64_t len = *length < 0 ? (int64_t)rows - start : (int64_t)*length;
+    if (start < 0 || len < 0 || (int64_t)start + len > rows)
+        return fail("The number of frames is not enough for length %lld (%s: %d rows, start %d)", (long long)len, name, rows, start);
+    *length = (int)len;
+    return 0;
+}
+
+// What the loader's index says of the matrix it is about to read (0 = nothing): the columns of its stream, and the rows utt2num_frames
+// states - the start frame was drawn from that count, so a matrix with fewer rows is refused by name, wherever the chunk fell.
+int check_index(const char* name, int32_t rows, int32_t cols, int want_cols, int claimed_rows) {
+    if (want_cols > 0 && cols != want_cols) return fail("feature dimension changes inside %s", name);
+    if (claimed_rows > rows) return fail("The number of frames is not enough: utt2num_frames says %d, %s has %d rows", claimed_rows, name, rows);
+    return 0;
+}
+
+// rows [start, start+length) of the matrix whose "\0B" marker sits at `off`; scratch is per-thread; want_cols, claimed_rows: check_index
 int read_rows_fd(const Source& src, const char* name, int64_t off, int start, int length, float* out, int64_t capacity, int* rows_out,
-                 int* cols_out, std::vector<uint8_t>& scratch) {
+                 int* cols_out, std::vector<uint8_t>& scratch, int want_cols = 0, int claimed_rows = 0) {
     char head[5];
     if (!src.get(head, 5, off)) return fail("%s:%lld: cannot read the matrix header", name, (long long)off);
     if (head[0] != '\0' || head[1] != 'B') return fail("%s:%lld: not a binary Kaldi object", name, (long long)off);
@@ -111,10 +148,12 @@ int read_rows_fd(const Source& src, const char* name, int64_t off, int start, in
         if (!src.get(&g, 16, off)) return fail("%s: truncated CM header", name);
         off += 16;
         const int rows = g.rows, cols = g.cols;
-        if (rows <= 0 || cols <= 0) return fail("%s: bad CM shape %d x %d", name, rows, cols);
-        if (length < 0) length = rows - start;
-        if (start < 0 || start + length > rows) return fail("The number of frames is not enough for length %d (%s: %d rows, start %d)", length, name, rows, start);
+        if (check_shape(name, "CM", rows, cols, 1)) return 1;
+        if (check_index(name, rows, cols, want_cols, claimed_rows)) return 1;
+        if (check_range(name, rows, start, &length)) return 1;
         if ((int64_t)length * cols > capacity) return fail("%s: output buffer too small", name);
+        if (length == 0) { *rows_out = 0; *cols_out = cols; return 0; }      // no rows: nothing to read, at any start up to rows
+        if (!src.has((size_t)cols * 8, off)) return fail("%s: truncated CM column headers", name);     // before cols sizes an allocation
         std::vector<ColHeader> ch(cols);
         if (!src.get(ch.data(), (size_t)cols * 8, off)) return fail("%s: truncated CM column headers", name);
         off += (int64_t)cols * 8;
@@ -148,10 +187,11 @@ int read_rows_fd(const Source& src, const char* name, int64_t off, int start, in
     off += 10;
     int32_t rows, cols;
     memcpy(&rows, dims + 1, 4); memcpy(&cols, dims + 6, 4);
-    if (length < 0) length = rows - start;
-    if (start < 0 || start + length > rows) return fail("The number of frames is not enough for length %d (%s: %d rows)", length, name, rows);
+    if (check_shape(name, fm ? "FM" : "DM", rows, cols, fm ? 4 : 8)) return 1;
+    if (check_index(name, rows, cols, want_cols, claimed_rows)) return 1;
+    if (check_range(name, rows, start, &length)) return 1;
     if ((int64_t)length * cols > capacity) return fail("%s: output buffer too small", name);
-    const size_t esz = fm ? 4 : 8;
+    if (length == 0) { *rows_out = 0; *cols_out = cols; return 0; }
     const size_t count = (size_t)length * cols;
     if (fm) {
         if (!src.get(out, count * 4, off + (int64_t)start * cols * 4)) return fail("%s: truncated FM data", name);
@@ -160,7 +200,6 @@ int read_rows_fd(const Source& src, const char* name, int64_t off, int start, in
         if (!bytes) return fail("%s: truncated DM data", name);
         for (size_t i = 0; i < count; ++i) { double d; memcpy(&d, bytes + 8 * i, 8); out[i] = (float)d; }
     }
-    (void)esz;
     *rows_out = length; *cols_out = cols;
     return 0;
 }
@@ -168,7 +207,7 @@ int read_rows_fd(const Source& src, const char* name, int64_t off, int start, in
 // Packed form of rows [start, start+length) of a 'CM ' matrix, for decoding on the GPU (xv_cm_decode, include/xvector_hip.h): the
 // matrix header's (min, range), the per-column percentile headers and the rows' bytes, column after column - nothing is decoded here:
 //   [min f32][range f32][cols x (p0, p25, p75, p100) u16][cols x length u8]      (xvio_packed_chunk_bytes: padded to 16 bytes)
-int read_rows_packed(const Source& src, const char* name, int64_t off, int start, int length, uint8_t* out, int dim) {
+int read_rows_packed(const Source& src, const char* name, int64_t off, int start, int length, uint8_t* out, int dim, int claimed_rows) {
     char head[5];
     if (!src.get(head, 5, off)) return fail("%s:%lld: cannot read the matrix header", name, (long long)off);
     if (head[0] != '\0' || head[1] != 'B') return fail("%s:%lld: not a binary Kaldi object", name, (long long)off);
@@ -177,14 +216,19 @@ int read_rows_packed(const Source& src, const char* name, int64_t off, int start
     struct { float minv, range; int32_t rows, cols; } g;
     if (!src.get(&g, 16, off)) return fail("%s: truncated CM header", name);
     off += 16;
-    if (g.cols != dim) return fail("feature dimension changes inside %s", name);
-    if (start < 0 || length < 0 || start + length > g.rows) return fail("The number of frames is not enough for length %d (%s: %d rows, start %d)", length, name, g.rows, start);
+    if (check_shape(name, "CM", g.rows, g.cols, 1)) return 1;
+    if (check_index(name, g.rows, g.cols, dim, claimed_rows)) return 1;
+    if (length < 0) return fail("%s: a packed chunk needs its length", name);
+    if (check_range(name, g.rows, start, &length)) return 1;
     memcpy(out, &g.minv, 4); memcpy(out + 4, &g.range, 4);
     if (!src.get(out + 8, (size_t)dim * 8, off)) return fail("%s: truncated CM column headers", name);
     off += (int64_t)dim * 8;
     uint8_t* dst = out + 8 + (size_t)dim * 8;
     for (int c = 0; c < dim; ++c)
         if (!src.get(dst + (size_t)c * length, (size_t)length, off + (int64_t)c * g.rows + start)) return fail("%s: truncated CM data", name);
+    // the padding up to the chunk's stride: a ring slot is reused with another length, and the batch's bytes are a function of (seed, index)
+    uint8_t* end = dst + (size_t)dim * length;
+    memset(end, 0, (size_t)(out + xvio_packed_chunk_bytes(dim, length) - end));
     return 0;
 }
 
@@ -238,7 +282,7 @@ struct xvio_loader {
     std::string data_dir;
     int dim = 0;
     int total_speakers = 0;
-    std::vector<Source> fds;       // one per ark file, mapped
+    std::vector<Source> fds;       // one per ark file, mapped; owned (closed with the loader, however create ends)
     std::vector<std::string> ark_names;
     std::vector<Utt> utts;
     std::vector<std::vector<int>> spk_utts;   // per speaker (dense order of first appearance) -> utterance ids
@@ -303,14 +347,14 @@ int xvio_loader::fill(Slot& s, int64_t index, std::vector<uint8_t>& scratch) {
             int rows = 0, cols = 0;
             if (cfg.packed) {
                 uint8_t* dstp = s.packed.data() + (size_t)(i * G + j) * xvio_packed_chunk_bytes(dim, T);
-                if (read_rows_packed(fds[u.fd_index], ark_names[u.fd_index].c_str(), u.offset, start, T, dstp, dim)) {
+                if (read_rows_packed(fds[u.fd_index], ark_names[u.fd_index].c_str(), u.offset, start, T, dstp, dim, u.num_frames)) {
                     s.error = g_err;
                     return 1;
                 }
                 cols = dim;
             } else {
                 float* dst = s.features.data() + (size_t)(i * G + j) * T * dim;
-                if (read_rows_fd(fds[u.fd_index], ark_names[u.fd_index].c_str(), u.offset, start, T, dst, (int64_t)T * dim, &rows, &cols, scratch)) {
+                if (read_rows_fd(fds[u.fd_index], ark_names[u.fd_index].c_str(), u.offset, start, T, dst, (int64_t)T * dim, &rows, &cols, scratch, dim, u.num_frames)) {
                     s.error = g_err;
                     return 1;
                 }
@@ -385,10 +429,8 @@ extern "C" int xvio_read_rows(const char* ark_path, int64_t offset, int32_t star
     if (fd < 0) return fail("cannot open %s", ark_path);
     std::vector<uint8_t> scratch;
     int rows = 0, cols = 0;
-    Source one;
-    one.fd = fd;                  // a single sub-range read: plain pread, no mapping
+    Source one(fd);               // a single sub-range read: plain pread, no mapping
     int rc = read_rows_fd(one, ark_path, offset, start, length, out, capacity, &rows, &cols, scratch);
-    close(fd);
     *rows_out = rows; *cols_out = cols;
     return rc;
 }
@@ -440,7 +482,10 @@ extern "C" int xvio_loader_create(const xvio_config* cfg, xvio_loader** out) {
         std::ifstream f(dir + "/utt2num_frames");
         if (!f) return fail("[Error] Expect utt2num_frames exists in %s ", dir.c_str());
         std::string utt; int n;
-        while (f >> utt >> n) utt2frames[utt] = n;
+        while (f >> utt >> n) {
+            if (n <= 0) return fail("%s/utt2num_frames: utterance %s has %d frames", dir.c_str(), utt.c_str(), n);
+            utt2frames[utt] = n;
+        }
     }
     std::unordered_map<std::string, int> ark_index;
     {
@@ -466,10 +511,9 @@ extern "C" int xvio_loader_create(const xvio_config* cfg, xvio_loader** out) {
                 int fd = open(path.c_str(), O_RDONLY);
                 if (fd < 0) return fail("cannot open %s", path.c_str());
                 ai = (int)l->fds.size();
-                Source src;
-                src.fd = fd;
+                Source src(fd);
                 src.open_map();
-                l->fds.push_back(src);
+                l->fds.push_back(std::move(src));
                 l->ark_names.push_back(path);
                 ark_index[path] = ai;
             } else ai = a->second;
@@ -483,10 +527,8 @@ extern "C" int xvio_loader_create(const xvio_config* cfg, xvio_loader** out) {
         std::vector<float> row(1 << 16);
         int rows = 0, cols = 0;
         const Utt& u = l->utts[0];
-        if (read_rows_fd(l->fds[u.fd_index], l->ark_names[u.fd_index].c_str(), u.offset, 0, 1, row.data(), (int64_t)row.size(), &rows, &cols, scratch)) {
-            for (Source& f : l->fds) f.close_all();
+        if (read_rows_fd(l->fds[u.fd_index], l->ark_names[u.fd_index].c_str(), u.offset, 0, 1, row.data(), (int64_t)row.size(), &rows, &cols, scratch))
             return 1;
-        }
         l->dim = cols;
     }
     // speakers with at least one utterance form the population (data_loader.py:240-243)
@@ -523,8 +565,7 @@ extern "C" void xvio_loader_destroy(xvio_loader* l) {
     l->cv_free.notify_all();
     l->cv_ready.notify_all();
     for (auto& t : l->threads) t.join();
-    for (Source& f : l->fds) f.close_all();
-    delete l;
+    delete l;                     // its Sources close their descriptors and mappings
 }
 
 extern "C" int xvio_loader_dim(const xvio_loader* l) { return l ? l->dim : 0; }
