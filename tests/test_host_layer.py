@@ -418,10 +418,13 @@ def test_both_import_styles_need_no_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pkg = os.path.join(root, "tf_kaldi_speaker_amd")
-    check = "assert ops.mfcc is w.mfcc and ops.score_trials is p.score_trials and ops._p is h._p and h.device_ops('cpu')[1] is ops"
+    check = ("assert ops.mfcc is w.mfcc and ops.score_trials is p.score_trials and ops._p is h._p and h.device_ops('cpu')[1] is ops; "
+             "assert ops.ahc_cluster is d.ahc_cluster and ops.vbx is d.vbx and ops.AHC_MAX_N == d.AHC_MAX_N == diarization.FIRST_PASS_CAP == 2048")
     for path, code in ((root, "import tf_kaldi_speaker_amd.ops as ops, tf_kaldi_speaker_amd.pipeline_ops as p, tf_kaldi_speaker_amd.wave_ops as w, "
-                              "tf_kaldi_speaker_amd._host as h; from tf_kaldi_speaker_amd.misc import features, augment, scoring, backend; " + check),
-                       (pkg, "import ops, pipeline_ops as p, wave_ops as w, _host as h; from misc import features, augment, scoring, backend; " + check)):
+                              "tf_kaldi_speaker_amd.diar_ops as d, tf_kaldi_speaker_amd._host as h; "
+                              "from tf_kaldi_speaker_amd.misc import features, augment, scoring, backend, diarization; " + check),
+                       (pkg, "import ops, pipeline_ops as p, wave_ops as w, diar_ops as d, _host as h; "
+                             "from misc import features, augment, scoring, backend, diarization; " + check)):
         r = subprocess.run([sys.executable, "-c", code], cwd="/", env=dict(os.environ, PYTHONPATH=path, HIP_VISIBLE_DEVICES=""), capture_output=True,
                            text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]

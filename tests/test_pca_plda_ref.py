@@ -1,6 +1,6 @@
 """CPU checks of the per-recording PCA of PLDA scoring: the fp64 restatement tests/pca_plda_ref.py against the properties that define it,
 the decision-gap conditions of every case the GPU tests use, and the host layers' arguments (misc/backend.py, misc/diarization.py,
-pipeline_ops.py) that are refused before any launch."""
+diar_ops.py) that are refused before any launch."""
 import numpy as np
 import pytest
 

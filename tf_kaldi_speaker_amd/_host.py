@@ -1,7 +1,7 @@
 """What the host side of every op has in common: device buffers as ctypes arguments, the checks of host index arrays that the kernels
-leave to the caller (index arrays, spans inside a pool of samples, where waveform outputs go, the size of a constant table), pitches and
-offsets, and how the drivers in misc/ cut their work into calls.  ops.py, wave_ops.py, pipeline_ops.py and misc/ build on this module; it
-imports none of them at load time."""
+leave to the caller (index arrays, spans inside a pool of samples, the recordings of a diarization call, where waveform outputs go, the
+size of a constant table), pitches, offsets and bounds, and how the drivers in misc/ cut their work into calls and pack it.  ops.py,
+wave_ops.py, pipeline_ops.py, diar_ops.py and misc/ build on this module; it imports none of them at load time."""
 import ctypes as C
 
 import numpy as np
@@ -97,6 +97,48 @@ def spans_inside(offsets, lengths, size, msg, min_length=0):
         raise IndexError(msg)
 
 
+def f32_buffer(t, what):      # a pool of floats that index arrays point into: a non-empty contiguous 1-D float32 tensor -> its floats
+    if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() == 0:
+        raise ValueError("%s must be a non-empty contiguous 1-D float32 tensor" % what)
+    return t.numel()
+
+
+def recordings(name, buf, offsets, n, ld, cap, letter="n", d=None):
+    """The recordings of one call of a diarization op, checked - the kernels trust them - and refused in `name`: recording i lies at float
+    offsets[i] of the 1-D float32 buffer buf with n[i] rows (1 .. cap; `letter`: the op's name for n) on the pitch ld[i].  d None: a square
+    matrix of `scores` at `mat_offsets`, ld None: n; else rows of d floats of `x` at `x_offsets`, ld None: d.  -> (n, ld, offsets) int64."""
+    what, at, lies = ("scores", "mat_offsets", "a matrix lies") if d is None else ("x", "x_offsets", "a recording's rows lie")
+    floats = f32_buffer(buf, "%s: %s" % (name, what))
+    n = host_ints(n, "%s: %s" % (name, letter), min_size=1, dtype=np.int64)
+    if n.min() < 1:
+        raise ValueError("%s: recording %d has no row (%s = %d)" % (name, int(np.argmax(n < 1)), letter, int(n.min())))
+    if n.max() > cap:
+        raise ValueError("%s: recording %d has %d rows, the cap is %d" % (name, int(np.argmax(n > cap)), int(n.max()), cap))
+    width = n if d is None else np.full(n.size, d, np.int64)      # what a row holds: the least pitch
+    ld = width if ld is None else host_ints(ld, name + ": ld", n=n.size, dtype=np.int64)
+    if (ld < width).any():
+        i = int(np.argmax(ld < width))
+        raise ValueError("%s: recording %d: the pitch %d is below %s" % (name, i, int(ld[i]), "its %d rows" % n[i] if d is None else "the %d dimensions" % d))
+    offsets = host_ints(offsets, "%s: %s" % (name, at), n=n.size, dtype=np.int64)
+    spans_inside(offsets, (n - 1) * ld + width, floats, "%s: %s outside the %d floats of %s" % (name, lies, floats, what))
+    return n, ld, offsets
+
+
+def cluster_outputs(n, device):
+    """What a clusterer writes for recordings of n[i] rows, uninitialised: labels [sum n], merges [sum (n - 1), 2], merge_values [sum (n - 1)]
+    - one entry at the least - and n_merges [b].  -> (the four tensors to launch with, the four the op returns: the merge log cut to size)."""
+    total, b = int(n.sum()), n.size
+    shapes = ((total, torch.int32), ((max(total - b, 1), 2), torch.int32), (max(total - b, 1), torch.float32), (b, torch.int32))
+    labels, merges, values, n_merges = (torch.empty(shape, dtype=dtype, device=device) for shape, dtype in shapes)
+    return (labels, merges, values, n_merges), (labels, merges[:total - b], values[:total - b], n_merges)
+
+
+def pack_rows(matrices):      # [n_i, ld] device matrices on one pitch -> (x 1-D, offsets, n, ld [b]): one call's recordings; one alone is not copied
+    n = np.asarray([m.shape[0] for m in matrices], np.int64)
+    x = torch.cat([m.reshape(-1) for m in matrices]) if len(matrices) > 1 else matrices[0].reshape(-1)
+    return x, bounds(n)[:-1] * matrices[0].shape[1], n, np.full(n.size, matrices[0].shape[1], np.int64)
+
+
 def place_outputs(name, n_out, out_offsets, out_pcm, out_f32, device, min_samples=0):
     """Where the ops that write waveforms put them: out_offsets (None: the n_out [b] samples of each back to back), out_pcm (None: a new
     int16 tensor that just holds them, min_samples at the least) and out_f32 (True: a new float32 tensor of out_pcm's size, False: none,
@@ -144,6 +186,10 @@ def pitch4(d):      # d rounded up to 4 floats: the row pitch of a GEMM operand
 
 def exclusive_offsets(lengths):      # where each of a non-empty list of signals starts when they lie back to back (int64)
     return np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+
+
+def bounds(lengths):      # ... and where each ends: the int64 [b + 1] prefix, item i is bounds[i] .. bounds[i + 1]
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
 
 
 def greedy_batches(n_items, grow, cost_of, limit, max_items=None, too_big=None):

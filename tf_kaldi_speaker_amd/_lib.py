@@ -373,6 +373,16 @@ SIGNATURES = {
 XV_AUG_UTT_WORDS = 10       # include/xvector_hip.h: words per utterance / per noise entry of xv_augment's tables
 XV_AUG_NOISE_WORDS = 5
 XV_CM_HEADERS = {"quartiles": 0, "uniform": 1}      # XV_CM_HEADER_QUARTILES / XV_CM_HEADER_UNIFORM
+# The caps of the diarization kernels, as their units define them (tests/test_diar_ops_host.py holds each against the entry point's own
+# refusal); diar_ops.py, misc/diarization.py and the diarize.py driver read them here, where no device library is loaded.
+AHC_MAX_N = 2048            # csrc/xv_ahc.hip AHC_MAX_N: the rows of one recording a clusterer takes; the clusters a seeded start takes
+AHC_MAX_POINTS = 32768      # ... AHC_MAX_POINTS: the rows of one recording xv_ahc_cluster_sums takes; the sizes of a seed together
+VBX_MAX_ROWS = 2048         # csrc/xv_vbx.hip VBX_MAX_T: the rows of one recording xv_vbx takes
+VBX_MAX_SPEAKERS = 32       # ... VBX_MAX_S: its speakers (HMM states)
+VBX_MAX_DIM = 256           # ... VBX_MAX_D: the dimensions of its rows
+VBX_MAX_ITERS = 64          # ... VBX_MAX_ITERS: the iterations of one call
+PCA_MAX_ROWS = 2048         # csrc/xv_backend_pca.hip PCA_MAX_N: the rows of one recording xv_backend_pca_plda takes
+PCA_MAX_DIM = 256           # ... PCA_MAX_D: the dimensions of its rows
 XV_BWD_STAGES = 4
 XV_MAX_FRAME_LAYERS = 12
 _lib = None

@@ -16,10 +16,10 @@ import os
 import numpy as np
 
 try:
-    from .._host import cat, device_ops, exclusive_offsets, pitch4, steps, upload
+    from .._host import cat, device_ops, pack_rows, pitch4, steps, upload
     from .scoring import DEFAULT_WORKSPACE_BYTES, center_mean
 except (ImportError, ValueError):
-    from _host import cat, device_ops, exclusive_offsets, pitch4, steps, upload
+    from _host import cat, device_ops, pack_rows, pitch4, steps, upload
     from misc.scoring import DEFAULT_WORKSPACE_BYTES, center_mean
 
 _LOG = logging.getLogger("tf_kaldi_speaker_amd")
@@ -502,10 +502,8 @@ class BackendScorer(object):
             return [(chain.plda(u), None) for u in units]
         if self._pca_model is None:
             self._pca_model = tuple(upload(a, np.float64, self.device) for a in plda_covariances(self.backend.plda))
-        n = np.asarray([u.shape[0] for u in units], np.int64)
-        ld = int(units[0].shape[1])
-        x = torch.cat([u.reshape(-1) for u in units]) if len(units) > 1 else units[0].reshape(-1)
-        got = ops.backend_pca_plda(x, exclusive_offsets(n * ld), n, self.dim, *self._pca_model, target=target, ld=np.full(n.size, ld, np.int64))
+        x, offsets, n, ld = pack_rows(units)
+        got = ops.backend_pca_plda(x, offsets, n, self.dim, *self._pca_model, target=target, ld=ld)
         kept = got["p"].cpu().numpy()
         out = []
         for j, u in enumerate(units):

@@ -12,13 +12,19 @@ two passes (ops.ahc_cluster_two_pass: DESIGN.md section 6l), up to 32768 windows
 Not here: threshold calibration, overlap detection, collars / md-eval, VBx or the per-recording PCA on recordings of
 more than 2048 windows.
 """
+import collections
 import logging
 
 import numpy as np
 
+try:      # (_lib imports neither torch nor NumPy: the caps are read without a device library)
+    from .. import _lib
+except (ImportError, ValueError):
+    import _lib
+
 _LOG = logging.getLogger("tf_kaldi_speaker_amd")
 DER_FRAME = 0.01      # seconds per frame of der()
-FIRST_PASS_CAP = 2048      # the most windows a subset of the first pass may hold: the clusterer's cap (ops.AHC_MAX_N)
+FIRST_PASS_CAP = _lib.AHC_MAX_N      # the most windows a subset of the first pass may hold: the clusterer's cap
 
 
 def speech_segments(vad, min_frames=1):
@@ -173,6 +179,10 @@ def _first_appearance(labels):
     return np.argsort(np.argsort(first))[inverse].astype(np.int32)
 
 
+# One batch of Diarizer.cluster: keys, windows n, pitches ld, targets [b]; offsets / bounds [b + 1]: where recording j's score matrix lies in the packed buffer / its labels back to back
+_Batch = collections.namedtuple("_Batch", "keys n ld targets offsets bounds")
+
+
 class Diarizer(object):
     """Clusters the window embeddings of recordings behind a scorer (CosineScorer, or BackendScorer in either mode).
 
@@ -198,7 +208,7 @@ class Diarizer(object):
     the wanted clusters, then the survivors against each other) - both kinds may meet in one cluster() call.  xv_vbx and
     xv_backend_pca_plda keep their cap: vbx or target_energy with a recording of more than 2048 windows is refused by name."""
 
-    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None, target_energy=None, first_pass_max_points=2048):
+    def __init__(self, scorer, threshold=None, reco2num_spk=None, vbx=None, target_energy=None, first_pass_max_points=FIRST_PASS_CAP):
         if (threshold is None) == (reco2num_spk is None):
             raise ValueError("Diarizer: exactly one of threshold and reco2num_spk says when the merging stops")
         if vbx is not None and not hasattr(scorer, "plda_space"):
@@ -212,147 +222,149 @@ class Diarizer(object):
                 raise ValueError("Diarizer: target_energy must lie in (0, 1] (got %r)" % (target_energy,))
             if target_energy > 1.0 - 0.001:      # (ivector-plda-scoring-dense returns early: no PCA at all)
                 target_energy = None
-        self.target_energy, self.pca_report = target_energy, {}
+        self.target_energy, self.pca_report, self.vbx_report = target_energy, {}, {}
         self.scorer, self.threshold, self.reco2num_spk, self.vbx = scorer, threshold, reco2num_spk, vbx
-        self.torch, self.ops = scorer.torch, scorer.ops
-        self.vbx_report = {}
+        try:      # (here, not at load time: the host side of this module needs NumPy only)
+            from .. import _host
+        except (ImportError, ValueError):
+            import _host
+        self.torch, self.ops, self.host = scorer.torch, scorer.ops, _host
         self.first_pass_max_points = int(first_pass_max_points)
         if not 2 <= self.first_pass_max_points <= FIRST_PASS_CAP:
             raise ValueError("Diarizer: first_pass_max_points must lie in 2 .. %d (got %r)" % (FIRST_PASS_CAP, first_pass_max_points))
 
-    def _ahc(self, packed, offsets, n, ld, targets, names):
-        """The clusterer over one batch -> the labels back to back.  The recordings of at most first_pass_max_points windows go through one
-        ops.ahc_cluster call; the longer ones through ops.ahc_cluster_two_pass, one call per stop rule (by threshold, by target)."""
-        threshold = 0.0 if self.threshold is None else float(self.threshold)
-        long = n > self.first_pass_max_points
-        if not long.any():
-            return self.ops.ahc_cluster(packed, offsets, n.astype(np.int32), ld.astype(np.int32), threshold=threshold,
-                                        targets=targets.astype(np.int32))[0].cpu().numpy()
-        at = np.concatenate([[0], np.cumsum(n)])
-        labels = np.empty(int(at[-1]), np.int32)
-        for pick, by_target in ((~long, None), (long & (targets == 0), False), (long & (targets > 0), True)):
-            idx = np.flatnonzero(pick)
-            if idx.size == 0:
-                continue
-            if by_target is None:
-                got = self.ops.ahc_cluster(packed, offsets[idx], n[idx].astype(np.int32), ld[idx].astype(np.int32), threshold=threshold,
-                                           targets=targets[idx].astype(np.int32))[0]
-            else:
-                try:
-                    got = self.ops.ahc_cluster_two_pass(packed, offsets[idx], n[idx], ld[idx], threshold=threshold,
-                                                        targets=targets[idx] if by_target else None, first_pass_max_points=self.first_pass_max_points)[0]
-                except ValueError as e:
-                    if not hasattr(e, "recording"):
-                        raise
-                    raise ValueError("Diarizer: recording %s: %s" % (names[idx[e.recording]], e.what))
-            got = got.cpu().numpy()
-            for j, lo in zip(idx, np.concatenate([[0], np.cumsum(n[idx])])):
-                labels[at[j]:at[j + 1]] = got[lo:lo + n[j]]
-        return labels
+    def cluster(self, embeddings):
+        """embeddings: {recording: float32 [n, d] matrix} (host or device).  -> {recording: NumPy int32 [n]} in the mapping's order."""
+        keys, host = list(embeddings), self.host
+        if not keys:
+            return {}
+        n = self._windows(keys, embeddings)
+        targets = self._targets(keys, n)
+        ld = np.asarray([host.pitch4(int(r)) for r in n], np.int64)
+        cost = self._bytes(n, ld, targets)
+        self.pca_report, self.vbx_report, out = {}, {}, {}      # (the report of an option that is off stays empty)
+        for picked in host.greedy_batches(len(keys), lambda i, total=0: (total + int(cost[i]),), lambda total: total, self.scorer.workspace_bytes,
+                                          too_big=lambda i, c: "Diarizer: recording %s needs %d bytes of scores, the workspace holds %d"
+                                          % (keys[i], c, self.scorer.workspace_bytes)):
+            batch = _Batch([keys[i] for i in picked], n[picked], ld[picked], targets[picked], host.bounds(n[picked] * ld[picked]), host.bounds(n[picked]))
+            matrices = [embeddings[k] for k in batch.keys]
+            packed = self._scores(batch, matrices)
+            labels = self._ahc(packed, batch, batch.targets)
+            if self.vbx is not None:
+                labels = self._at_most_vbx_speakers(packed, batch, labels)
+                del packed      # (VBx runs once the clusterer's buffers are gone)
+                labels = self._vbx(batch, matrices, labels)
+            out.update((k, labels[lo:hi]) for k, lo, hi in zip(batch.keys, batch.bounds[:-1], batch.bounds[1:]))
+        return out
+
+    def _windows(self, keys, embeddings):      # -> the windows of each recording; one that the clusterer, VBx or the PCA does not take is refused by name
+        n = np.asarray([int(embeddings[k].shape[0]) for k in keys], np.int64)
+        for k, rows in zip(keys, n):
+            if rows < 1 or rows > _lib.AHC_MAX_POINTS:
+                raise ValueError("Diarizer: recording %s has %d windows, 1 .. %d are taken" % (k, rows, _lib.AHC_MAX_POINTS))
+            for option, op, cap, on in (("vbx", "xv_vbx", _lib.VBX_MAX_ROWS, self.vbx is not None),
+                                        ("target_energy", "xv_backend_pca_plda", _lib.PCA_MAX_ROWS, self.target_energy is not None)):
+                if on and rows > cap:
+                    raise ValueError("Diarizer: recording %s has %d windows: %s= takes recordings of at most %d (%s keeps its cap; the two-pass "
+                                     "clustering alone goes further)" % (k, rows, option, cap, op))
+        return n
+
+    def _targets(self, keys, n):      # -> the clusters each recording is merged down to (0: by the threshold)
+        if self.reco2num_spk is None:
+            return np.zeros(len(keys), np.int64)
+        missing = [k for k in keys if k not in self.reco2num_spk]
+        if missing:
+            raise ValueError("Diarizer: no number of speakers for recording %s" % missing[0])
+        targets = np.asarray([int(self.reco2num_spk[k]) for k in keys], np.int64)
+        if targets.min() < 1:
+            raise ValueError("Diarizer: recording %s: the number of speakers must be positive" % keys[int(np.argmin(targets))])
+        return np.minimum(targets, n)      # (fewer windows than speakers: every window its own cluster)
+
+    def _bytes(self, n, ld, targets):      # -> what each recording costs a batch, in bytes
+        ops, pitch4 = self.ops, self.host.pitch4
+        cost = 4 * (n * ld + n * n)      # its matrix in the packed buffer and the clusterer's copy
+        for i in np.flatnonzero(n > self.first_pass_max_points):
+            cost[i] = self._two_pass_bytes(int(n[i]), int(ld[i]), int(targets[i]))
+        if self.target_energy is not None:      # ... its unit-length rows packed for the op, the op's scratch and its fp32 outputs
+            dim4 = pitch4(self.scorer.dim)
+            cost = cost + 4 * n * dim4 + ops.backend_pca_plda_workspace_bytes(1, self.scorer.dim) + 4 * dim4 * (dim4 + 8)
+        if self.vbx is not None:         # (VBx runs once the clusterer's buffers are gone: a batch must hold the larger of the two)
+            cap, dim4 = _lib.VBX_MAX_SPEAKERS, pitch4(self.scorer.dim)
+            cost = np.maximum(cost, np.asarray([4 * r * dim4 + 8 * r * cap + ops.vbx_workspace_bytes([r], [cap], self.scorer.dim) for r in n], np.int64))
+        return cost
 
     def _two_pass_bytes(self, rows, ld, target):
         """What a recording of more than first_pass_max_points windows costs a batch: its matrix, the first pass's copies of the subsets, the
         scratch of the cluster sums and the seed - for the most clusters the first pass can leave (with a target: ten times the target per
         subset; by threshold: every window, up to the second pass's cap)."""
         subsets = np.diff(self.ops.ahc_subsets(rows, self.first_pass_max_points))
-        survivors = int(np.minimum(subsets, 10 * target).sum()) if target > 0 else int(rows)
-        survivors = min(survivors, self.ops.AHC_MAX_N)
+        survivors = min(int(np.minimum(subsets, 10 * target).sum()) if target > 0 else int(rows), _lib.AHC_MAX_N)
         return int(4 * rows * ld + 4 * (subsets * subsets).sum() + self.ops.ahc_cluster_sums_workspace_bytes([rows], [survivors]) + 4 * survivors * survivors)
 
-    def _vbx(self, names, matrices, labels, n):
+    def _scores(self, batch, matrices):      # prepare -> dense of every recording of the batch -> the packed buffer of their score matrices
+        scorer, packed = self.scorer, self.torch.empty(int(batch.offsets[-1]), dtype=self.torch.float32, device=self.scorer.device)
+        own = None if self.target_energy is None else scorer.prepare_pca(matrices, self.target_energy)
+        for j, (key, matrix) in enumerate(zip(batch.keys, matrices)):
+            rows = int(batch.n[j])
+            view = packed[int(batch.offsets[j]):int(batch.offsets[j + 1])].view(rows, int(batch.ld[j]))[:, :rows]
+            if own is None:
+                scorer.dense(scorer.prepare(matrix), out=view)
+            else:
+                prepared, model = own[j]
+                self.pca_report[key] = 0 if model is None else int(model[0])
+                scorer.dense(prepared, out=view, model=model)
+        return packed
+
+    def _ahc(self, packed, batch, targets):
+        """The clusterer over one batch -> the labels back to back.  The recordings of at most first_pass_max_points windows go through one
+        ops.ahc_cluster call; the longer ones through ops.ahc_cluster_two_pass, one call per stop rule (by threshold, by target)."""
+        ops, offsets, n, ld = self.ops, batch.offsets[:-1], batch.n, batch.ld
+        threshold = 0.0 if self.threshold is None else float(self.threshold)
+        long = n > self.first_pass_max_points
+        labels = np.empty(int(batch.bounds[-1]), np.int32)
+        for pick, by_target in ((~long, None), (long & (targets == 0), False), (long & (targets > 0), True)):
+            idx = np.flatnonzero(pick)
+            if idx.size == 0:
+                continue
+            if by_target is None:
+                got = ops.ahc_cluster(packed, offsets[idx], n[idx], ld[idx], threshold=threshold, targets=targets[idx])[0]
+            else:
+                try:
+                    got = ops.ahc_cluster_two_pass(packed, offsets[idx], n[idx], ld[idx], threshold=threshold, targets=targets[idx] if by_target else None,
+                                                   first_pass_max_points=self.first_pass_max_points)[0]
+                except ops.TwoPassRefusal as e:
+                    raise ValueError("Diarizer: recording %s: %s" % (batch.keys[idx[e.recording]], e.what))
+            got = got.cpu().numpy()
+            for j, lo in zip(idx, self.host.bounds(n[idx])):
+                labels[batch.bounds[j]:batch.bounds[j + 1]] = got[lo:lo + n[j]]
+        return labels
+
+    def _at_most_vbx_speakers(self, packed, batch, labels):      # the clusterer once more where it left more speakers than VBx takes
+        cap, at = _lib.VBX_MAX_SPEAKERS, batch.bounds
+        many = np.asarray([labels[lo:hi].max() >= cap for lo, hi in zip(at[:-1], at[1:])])
+        if many.any():      # ... down to that many, for the batch as it stands
+            _LOG.info("[INFO] Recording %s: more than %d clusters, clustered once more down to %d for VBx." % (", ".join(np.asarray(batch.keys)[many]), cap, cap))
+            relabel = self._ahc(packed, batch, np.where(many, cap, batch.targets))
+            for j in np.flatnonzero(many):
+                labels[at[j]:at[j + 1]] = relabel[at[j]:at[j + 1]]
+        return labels
+
+    def _vbx(self, batch, matrices, labels):
         """ops.vbx over one batch: labels = the clusterer's, back to back.  -> the new labels, back to back."""
-        opt, ops, torch = self.vbx, self.ops, self.torch
-        at = np.concatenate([[0], np.cumsum(n)])
+        opt, torch, at = self.vbx, self.torch, batch.bounds
         rows, psi = zip(*(self.scorer.plda_space(m) for m in matrices))
-        dim, ld = int(psi[0].numel()), int(rows[0].shape[1])
-        speakers = np.asarray([int(labels[at[j]:at[j + 1]].max()) + 1 for j in range(len(names))], np.int64)
-        gamma = np.concatenate([vbx_init(labels[at[j]:at[j + 1]], speakers[j], opt.init_smoothing).ravel() for j in range(len(names))])
+        x, offsets, n, ld = self.host.pack_rows(rows)
+        dim, recordings = int(psi[0].numel()), range(len(batch.keys))
+        speakers = np.asarray([int(labels[at[j]:at[j + 1]].max()) + 1 for j in recordings], np.int64)
+        gamma = np.concatenate([vbx_init(labels[at[j]:at[j + 1]], speakers[j], opt.init_smoothing).ravel() for j in recordings])
         pi = np.concatenate([np.full(k, 1.0 / k, np.float32) for k in speakers])
-        x = torch.cat([r.reshape(-1) for r in rows]) if len(rows) > 1 else rows[0].reshape(-1)
-        dev = x.device
-        gamma_d, _, elbo, n_iters, new = ops.vbx(x, at[:-1] * ld, n, dim, psi[0], torch.from_numpy(gamma).to(dev), torch.from_numpy(pi).to(dev), speakers,
-                                                 ld=np.full(len(names), ld, np.int64), loop_prob=opt.loop_prob, fa=opt.fa, fb=opt.fb,
-                                                 max_iters=opt.max_iters, epsilon=opt.epsilon)
+        gamma_d, _, elbo, n_iters, new = self.ops.vbx(x, offsets, n, dim, psi[0], torch.from_numpy(gamma).to(x.device), torch.from_numpy(pi).to(x.device), speakers, ld=ld,
+                                                      loop_prob=opt.loop_prob, fa=opt.fa, fb=opt.fb, max_iters=opt.max_iters, epsilon=opt.epsilon)
         new, elbo, n_iters = new.cpu().numpy(), elbo.cpu().numpy(), n_iters.cpu().numpy()
         out = np.empty_like(new)
-        for j, name in enumerate(names):
+        for j, name in enumerate(batch.keys):
             if n_iters[j] < 1:
                 raise RuntimeError("Diarizer: xv_vbx skipped recording %s (n_iters = %d)" % (name, int(n_iters[j])))
             out[at[j]:at[j + 1]] = _first_appearance(new[at[j]:at[j + 1]])
             self.vbx_report[name] = (int(speakers[j]), int(out[at[j]:at[j + 1]].max()) + 1, int(n_iters[j]), float(elbo[j, n_iters[j] - 1]))
-        return out
-
-    def cluster(self, embeddings):
-        """embeddings: {recording: float32 [n, d] matrix} (host or device).  -> {recording: NumPy int32 [n]} in the mapping's order."""
-        keys = list(embeddings)
-        if not keys:
-            return {}
-        try:      # (here, not at load time: the host side of this module needs NumPy only)
-            from .._host import greedy_batches, pitch4
-        except (ImportError, ValueError):
-            from _host import greedy_batches, pitch4
-        n = np.asarray([int(embeddings[k].shape[0]) for k in keys], np.int64)
-        for k, rows in zip(keys, n):
-            if rows < 1 or rows > self.ops.AHC_MAX_POINTS:
-                raise ValueError("Diarizer: recording %s has %d windows, 1 .. %d are taken" % (k, rows, self.ops.AHC_MAX_POINTS))
-            for option, op, on in (("vbx", "xv_vbx", self.vbx is not None), ("target_energy", "xv_backend_pca_plda", self.target_energy is not None)):
-                if on and rows > self.ops.AHC_MAX_N:
-                    raise ValueError("Diarizer: recording %s has %d windows: %s= takes recordings of at most %d (%s keeps its cap; the two-pass "
-                                     "clustering alone goes further)" % (k, rows, option, self.ops.AHC_MAX_N, op))
-        if self.reco2num_spk is not None:
-            missing = [k for k in keys if k not in self.reco2num_spk]
-            if missing:
-                raise ValueError("Diarizer: no number of speakers for recording %s" % missing[0])
-            targets = np.asarray([int(self.reco2num_spk[k]) for k in keys], np.int64)
-            if targets.min() < 1:
-                raise ValueError("Diarizer: recording %s: the number of speakers must be positive" % keys[int(np.argmin(targets))])
-            targets = np.minimum(targets, n)      # (fewer windows than speakers: every window its own cluster)
-        else:
-            targets = np.zeros(len(keys), np.int64)
-        ld = np.asarray([pitch4(int(r)) for r in n], np.int64)
-        cost = 4 * (n * ld + n * n)      # bytes of a recording: its matrix in the packed buffer and the clusterer's copy
-        for i in np.flatnonzero(n > self.first_pass_max_points):
-            cost[i] = self._two_pass_bytes(int(n[i]), int(ld[i]), int(targets[i]))
-        if self.target_energy is not None:      # ... its unit-length rows packed for the op, the op's scratch and its fp32 outputs
-            dim4 = pitch4(self.scorer.dim)
-            cost = cost + 4 * n * dim4 + self.ops.backend_pca_plda_workspace_bytes(1, self.scorer.dim) + 4 * dim4 * (dim4 + 8)
-            self.pca_report = {}
-        if self.vbx is not None:         # (VBx runs once the clusterer's buffers are gone: a batch must hold the larger of the two)
-            cap_s, dim4 = self.ops.VBX_MAX_SPEAKERS, pitch4(self.scorer.dim)
-            cost = np.maximum(cost, np.asarray([4 * r * dim4 + 8 * r * cap_s + self.ops.vbx_workspace_bytes([r], [cap_s], self.scorer.dim) for r in n], np.int64))
-            self.vbx_report = {}
-        out = {}
-        batches = greedy_batches(len(keys), lambda i, total=0: (total + int(cost[i]),), lambda total: total, self.scorer.workspace_bytes,
-                                 too_big=lambda i, c: "Diarizer: recording %s needs %d bytes of scores, the workspace holds %d"
-                                 % (keys[i], c, self.scorer.workspace_bytes))
-        for batch in batches:
-            offsets = np.concatenate([[0], np.cumsum(n[batch] * ld[batch])]).astype(np.int64)
-            packed = self.torch.empty(int(offsets[-1]), dtype=self.torch.float32, device=self.scorer.device)
-            own = None if self.target_energy is None else self.scorer.prepare_pca([embeddings[keys[i]] for i in batch], self.target_energy)
-            for j, i in enumerate(batch):
-                view = packed[int(offsets[j]):int(offsets[j + 1])].view(int(n[i]), int(ld[i]))[:, :int(n[i])]
-                if own is None:
-                    self.scorer.dense(self.scorer.prepare(embeddings[keys[i]]), out=view)
-                else:
-                    prepared, model = own[j]
-                    self.pca_report[keys[i]] = 0 if model is None else int(model[0])
-                    self.scorer.dense(prepared, out=view, model=model)
-            del own
-            labels = self._ahc(packed, offsets[:-1], n[batch], ld[batch], targets[batch], [keys[i] for i in batch])
-            at = np.concatenate([[0], np.cumsum(n[batch])])
-            if self.vbx is not None:
-                cap = self.ops.VBX_MAX_SPEAKERS
-                many = [j for j in range(len(batch)) if labels[at[j]:at[j + 1]].max() >= cap]
-                if many:      # the clusterer once more, down to the most speakers VBx takes, for the batch as it stands
-                    _LOG.info("[INFO] Recording %s: more than %d clusters, clustered once more down to %d for VBx."
-                              % (", ".join(keys[batch[j]] for j in many), cap, cap))
-                    again = targets[batch].copy()
-                    again[many] = cap
-                    relabel = self._ahc(packed, offsets[:-1], n[batch], ld[batch], again, [keys[i] for i in batch])
-                    for j in many:
-                        labels[at[j]:at[j + 1]] = relabel[at[j]:at[j + 1]]
-                del packed
-                labels = self._vbx([keys[i] for i in batch], [embeddings[keys[i]] for i in batch], labels, n[batch])
-            for j, i in enumerate(batch):
-                out[keys[i]] = labels[at[j]:at[j + 1]]
         return out

@@ -10,7 +10,12 @@ import random
 
 import numpy as np
 
-_BEST = "The default is to load the BEST checkpoint (according to valid_loss)."
+try:      # the caps behind the diarization options (no device library loads); flat, as the drivers run, or as the package's member
+    import _lib
+except ImportError:
+    from tf_kaldi_speaker_amd import _lib
+
+_BEST ="The default is to load the BEST checkpoint (according to valid_loss)."
 ARGUMENTS = {
     # options
     "cont": (("-c", "--cont"), dict(action="store_true", help="Continue training from an existing model.")),
@@ -121,7 +126,7 @@ ARGUMENTS = {
     "vbx_fb": (("--vbx-fb",), dict(type=float, default=17.0, help="VBx: the scaling factor of the speaker models' regularisation.")),
     "vbx_loop_prob": (("--vbx-loop-prob",), dict(type=float, default=0.99, help="VBx: the probability of staying with a speaker from one window "
                                                                                 "to the next.")),
-    "vbx_max_iters": (("--vbx-max-iters",), dict(type=int, default=20, help="VBx: the most iterations (1 .. 64).")),
+    "vbx_max_iters": (("--vbx-max-iters",), dict(type=int, default=20, help="VBx: the most iterations (1 .. %d)." % _lib.VBX_MAX_ITERS)),
     "vbx_epsilon": (("--vbx-epsilon",), dict(type=float, default=1e-4, help="VBx: stop once an iteration gains less than this on the ELBO.")),
     "vbx_init_smoothing": (("--vbx-init-smoothing",), dict(type=float, default=5.0, help="VBx: the clusterer's labels times this, a softmax per "
                                                                                          "window, are the first responsibilities.")),
@@ -129,11 +134,12 @@ ARGUMENTS = {
                                                                                 "of the energy, in (0, 1] (ivector-plda-scoring-dense "
                                                                                 "--target-energy; the callhome recipe: 0.9).  Needs --scoring plda.  "
                                                                                 "Default: off.")),
-    "first_pass_max_points": (("--first-pass-max-points",), dict(type=int, default=2048, help="A recording of more windows than this (2 .. 2048; "
+    "first_pass_max_points": (("--first-pass-max-points",), dict(type=int, default=_lib.AHC_MAX_N, help="A recording of more windows than this (2 .. %d; "
                                                                  "agglomerative-cluster's option) is clustered in two passes: contiguous subsets "
                                                                  "of at most this many windows down to ten times the wanted clusters, then the "
-                                                                 "survivors against each other; up to 32768 windows.  Such a recording above 2048 "
-                                                                 "windows is refused with --vbx or --target-energy (their caps stay at 2048).")),
+                                                                 "survivors against each other; up to %d windows.  Such a recording above %d "
+                                                                 "windows is refused with --vbx or --target-energy (their caps stay at %d)."
+                                                                 % (_lib.AHC_MAX_N, _lib.AHC_MAX_POINTS, _lib.VBX_MAX_ROWS, _lib.PCA_MAX_ROWS))),
     # positionals
     "rttm_out": (("rttm_out",), dict(type=str, help="The RTTM file to write.")),
     "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),

@@ -35,6 +35,7 @@ import sys
 import numpy as np
 
 import _cli
+import _lib      # (the caps of the kernels: no device library loads)
 from misc import diarization
 
 FRAME_SHIFT = 0.01      # seconds per frame of the features
@@ -87,16 +88,16 @@ def main():
         sys.exit("--backend is given but --scoring is cosine: choose --scoring lda_cos or plda")
     if args.vbx and args.scoring != "plda":
         sys.exit("--vbx needs --scoring plda (VBx models the windows in the PLDA space of --backend), not --scoring %s" % args.scoring)
-    if args.vbx and not (0.0 < args.vbx_loop_prob < 1.0 and args.vbx_fa > 0 and args.vbx_fb > 0 and 1 <= args.vbx_max_iters <= 64
+    if args.vbx and not (0.0 < args.vbx_loop_prob < 1.0 and args.vbx_fa > 0 and args.vbx_fb > 0 and 1 <= args.vbx_max_iters <= _lib.VBX_MAX_ITERS
                          and args.vbx_init_smoothing >= 0 and args.vbx_epsilon == args.vbx_epsilon):
-        sys.exit("--vbx: --vbx-loop-prob must lie strictly between 0 and 1, --vbx-fa and --vbx-fb be positive, --vbx-max-iters lie in 1 .. 64, "
-                 "--vbx-init-smoothing not be negative")
+        sys.exit("--vbx: --vbx-loop-prob must lie strictly between 0 and 1, --vbx-fa and --vbx-fb be positive, --vbx-max-iters lie in 1 .. %d, "
+                 "--vbx-init-smoothing not be negative" % _lib.VBX_MAX_ITERS)
     if args.target_energy is not None and args.scoring != "plda":
         sys.exit("--target-energy needs --scoring plda (the per-recording PCA projects the PLDA model of --backend), not --scoring %s" % args.scoring)
     if args.target_energy is not None and not 0.0 < args.target_energy <= 1.0:
         sys.exit("--target-energy must lie in (0, 1] (got %g)" % args.target_energy)
-    if not 2 <= args.first_pass_max_points <= 2048:
-        sys.exit("--first-pass-max-points must lie in 2 .. 2048 (got %d)" % args.first_pass_max_points)
+    if not 2 <= args.first_pass_max_points <= diarization.FIRST_PASS_CAP:
+        sys.exit("--first-pass-max-points must lie in 2 .. %d (got %d)" % (diarization.FIRST_PASS_CAP, args.first_pass_max_points))
     if args.cmn_window < 0:
         sys.exit("--cmn-window must be 0 (off) or a number of frames")
     window, period, min_segment = (int(round(v / FRAME_SHIFT)) for v in (args.window, args.period, args.min_segment))

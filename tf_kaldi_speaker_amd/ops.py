@@ -3,8 +3,9 @@
 Inputs/outputs are torch CUDA tensors used purely as device buffers; every
 function enqueues HIP kernels on torch's current stream.  No arithmetic is done
 by torch here.  These are what the per-kernel parity tests call.
-The ops of the pipeline stages around the network live in wave_ops.py (those that take PCM) and pipeline_ops.py (features, scores, the
-back end) and are re-exported here: callers write ops.mfcc, ops.score_trials ...
+The ops of the pipeline stages around the network live in wave_ops.py (those that take PCM), pipeline_ops.py (features, scores, the
+back end) and diar_ops.py (the recordings of a diarization call: clustering, VBx, the per-recording PCA) and are re-exported here:
+callers write ops.mfcc, ops.score_trials, ops.ahc_cluster ...
 """
 import ctypes as C
 
@@ -13,11 +14,13 @@ import torch
 try:
     from . import kinds
     from ._host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
-    from .pipeline_ops import *       # noqa: F401,F403 (its public names are the pipeline ops)
+    from .diar_ops import *           # noqa: F401,F403 (its public names are the diarization ops)
+    from .pipeline_ops import *       # noqa: F401,F403 (... the pipeline ops)
     from .wave_ops import *           # noqa: F401,F403 (and those of the ops that take PCM)
 except ImportError:
     import kinds
     from _host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
+    from diar_ops import *            # noqa: F401,F403
     from pipeline_ops import *        # noqa: F401,F403
     from wave_ops import *            # noqa: F401,F403
 
