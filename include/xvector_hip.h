@@ -945,7 +945,10 @@ int xv_l2_scaling_backward(void* stream, const float* x, const float* dy, int ro
 /* Loss family, loss.py:9-355. */
 enum { XV_LOSS_SOFTMAX = 0, XV_LOSS_ASOFTMAX = 1, XV_LOSS_AMSOFTMAX = 2, XV_LOSS_ARCSOFTMAX = 3,
        /* pairwise heads (below, "Pairwise loss heads"): no softmax/output variables whatever num_speakers says; options through xv_engine_set_pair_loss */
-       XV_LOSS_SEMIHARD_TRIPLET = 4, XV_LOSS_ANGULAR_TRIPLET = 5 };
+       XV_LOSS_SEMIHARD_TRIPLET = 4, XV_LOSS_ANGULAR_TRIPLET = 5,
+       /* the GE2E training loss (below, "GE2E training loss"): no softmax/output variables either, two trainable scalars ge2e/w and ge2e/b;
+        * options through xv_engine_set_ge2e_loss */
+       XV_LOSS_GE2E = 6 };
 /* ---- segment-level layers in one launch (rows <= XV_SEGMENT_MAX_ROWS chunks of a batch) ------------------------------
  * tf.layers.dense at tdnn.py:147,166 and the logits / gradient products of loss.py with M = chunks rows: the GEMM, its split-K sum
  * and the consumer's per-column work run in one launch.  ws: slabs (xv_op_workspace_bytes); tickets: one ZEROED uint32 per 32
@@ -1025,6 +1028,40 @@ int xv_pair_loss_backward(void* stream, const xv_pair_loss_config* cfg, const fl
 /* e2e_valid_loss (loss.py:637-705): x holds speakers x segments rows, speaker-major.  Rows l2-normalised, per-speaker centres (normalised
  * means), for a row's own speaker the normalised sum of the OTHER rows of that speaker, similarities x 20, mean sparse softmax cross-entropy. */
 int xv_e2e_valid_loss(void* stream, const float* x, int speakers, int segments, int d, int ldx, float* loss, void* ws, size_t ws_bytes);
+
+/* ---- GE2E training loss (loss.py:903-982; the NumPy statement model/test_utils.py:21-86), fp32 ----
+ * x [B][d] at row pitch ldx holds B = speakers x segments rows, speaker-major; the layout comes from cfg and labels are not read.
+ * segments >= 2, B <= 1024, d a multiple of 4, rows 16-byte aligned.  With l2(v) = v * rsqrt(max(|v|^2, 1e-12)) (l2_scaling(v, 1)):
+ *   x^_i = l2(x_i);   centre c^_k = l2(sum of speaker k's x^);   exclusive centre e^_i = l2(sum of the OTHER rows of i's speaker)
+ *   c_ik = x^_i . c^_k for k != spk(i),   c_i,own = x^_i . e^_i;      S_ik = |w| c_ik + b      (w, b: one device float each)
+ *   softmax       mean over rows of the sparse softmax cross-entropy of S_i against the row's own speaker
+ *   contrastive   mean over rows of 1 - sigmoid(S_i,own) + max(0, max_{k != own} sigmoid(S_ik)); the 0 is the masked entry of
+ *                 reduce_max((1 - mask) * sigmoid): it alone remains with one speaker and carries no gradient
+ * The kernels evaluate this from u = X^ X^T: x^_i . (sum of k) = sum_{m in k} u_im, |sum of k|^2 = sum_{m, m' in k} u_mm', and for the own
+ * speaker the same sums over the pairs that do not touch row i.
+ * Backward, with P = d loss / d S:  d w = sign(w) sum P_ik c_ik (sign(0) = 0, as tf.abs has it),  d b = sum P_ik (evaluated as that sum in
+ * both types; rounding noise around 0 in softmax),  d x through the centres and the row norms.  maximum(., 1e-12) passes no gradient to a
+ * clamped norm and the numerator keeps its factor rsqrt(1e-12); the contrastive maximum is taken where S is largest and a tie gives the
+ * whole gradient to the lowest index.  No atomics, every sum in a fixed order: two calls give the same bits.
+ * stats [4] (may be NULL): {d w, d b, 0, 0}.  xv_ge2e_loss_forward leaves G = x x^T, P, c and the norms in ws;
+ * xv_ge2e_loss_backward (same cfg, x, d, w, b, ws) reads them and writes dx [B][d] at row pitch lddx, dw [1] and db [1].
+ * ws in floats, with bp and np = B and speakers rounded up to 4 (diagnostics and tests read the forward's entries here):
+ *   G [B][bp] | d loss / d u [B][bp] | its symmetrised form [B][bp] | row partials [bp][4] | {1 / B, d w, d b, ...} [8] |
+ *   n_k [np] | P [B][np] without the mean's 1 / B | c [B][np] | the exclusive norms [bp] */
+enum { XV_GE2E_SOFTMAX = 0, XV_GE2E_CONTRASTIVE = 1 };
+typedef struct xv_ge2e_config {
+    int32_t struct_bytes;             /* = sizeof(xv_ge2e_config) of the header the host was built against; anything else is refused */
+    int32_t loss_type;                /* XV_GE2E_*: ge2e_loss_type */
+    int32_t speakers;                 /* num_speakers_per_batch */
+    int32_t segments;                 /* num_segments_per_speaker (not 1) */
+    int32_t valid_speakers;           /* num_valid_speakers_per_batch / num_valid_segments_per_speaker: the layout of a validation batch - read by the */
+    int32_t valid_segments;           /* engine (xv_engine_loss_forward with with_margin = 0), not by the op entry points below */
+} xv_ge2e_config;
+size_t xv_ge2e_loss_workspace_bytes(int speakers, int segments, int d);      /* 0 (and xv_last_error) for a layout or d outside the limits */
+int xv_ge2e_loss_forward(void* stream, const xv_ge2e_config* cfg, const float* x, int d, int ldx, const float* w, const float* b,
+                         float* loss, float* stats, void* ws, size_t ws_bytes);
+int xv_ge2e_loss_backward(void* stream, const xv_ge2e_config* cfg, const float* x, int d, int ldx, const float* w, const float* b,
+                          void* ws, size_t ws_bytes, float* dx, int lddx, float* dw, float* db);
 
 /* sum over a flat range of 0.5*scale*w^2 accumulated into *out (regularization_loss). */
 int xv_l2_reg_loss(void* stream, const float* w, size_t count, float scale, float* out_accum);
@@ -1153,6 +1190,12 @@ int xv_engine_loss_forward(xv_engine* e, void* stream, const int32_t* labels, in
  * valid_speakers x valid_segments rows (trainer.py:272-275; no backward follows it), the semi-hard kind the same loss as in training.
  * Stage 0 of the backward then has no head weight gradient: xv_pair_loss_backward writes d out, and tdnn7 / tdnn6 run unfused from there. */
 int xv_engine_set_pair_loss(xv_engine* e, const xv_pair_loss_config* cfg);
+/* loss_kind XV_LOSS_GE2E: the head's options, handed over after create; xv_engine_loss_forward without them is refused by name.  The head
+ * declares the trainable scalars ge2e/w and ge2e/b (outside the L2 regulariser; clipped, updated, all-reduced and stored like any other
+ * variable), no softmax/output variables, no auxiliary losses.  with_margin = 1: xv_ge2e_loss_forward on speakers x segments rows (a batch
+ * of another size is refused); with_margin = 0: xv_e2e_valid_loss on valid_speakers x valid_segments rows (no backward follows it).
+ * Stage 0 of the backward: xv_ge2e_loss_backward writes d out, d w and d b; tdnn7 / tdnn6 run unfused from there. */
+int xv_engine_set_ge2e_loss(xv_engine* e, const xv_ge2e_config* cfg);
 int xv_engine_backward(xv_engine* e, void* stream, int stage);
 /* Staged backward without the join at the end of stages 0..2: `stream` does not wait for the engine's weight-gradient stream,
  * so the next stage's data-gradient chain keeps overlapping it.  The slice of stage k is complete on any stream that called

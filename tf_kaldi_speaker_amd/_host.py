@@ -82,6 +82,27 @@ def pitched(t, what, whole=False):
     return t.shape[0], ld
 
 
+GE2E_MAX_ROWS = 1024        # csrc/xv_triplet.hip TP_MAX_B: the rows the pairwise and GE2E heads take
+
+
+def ge2e_rows(x, speakers, segments, d, what="ge2e loss"):
+    """(rows, pitch) of the embeddings x of a GE2E batch - speakers x segments speaker-major rows of d floats; what the entry points refuse
+    of a layout is refused here by name, before anything is allocated for it."""
+    b, ldx = pitched(x, "%s: x" % what)
+    n, m = int(speakers), int(segments)
+    if n < 1 or m < 1:
+        raise ValueError("%s: %d speakers x %d segments" % (what, n, m))
+    if m == 1:
+        raise ValueError("%s: num_segments_per_speaker is 1: a row needs another row of its speaker" % what)
+    if b != n * m:
+        raise ValueError("%s: %d rows are not %d speakers x %d segments" % (what, b, n, m))
+    if b > GE2E_MAX_ROWS:
+        raise ValueError("%s: %d rows, 2 .. %d are supported" % (what, b, GE2E_MAX_ROWS))
+    if d < 4 or d % 4 or d > x.shape[1]:
+        raise ValueError("%s: the embedding dimension %d must be a positive multiple of 4 (x has %d columns)" % (what, d, x.shape[1]))
+    return b, ldx
+
+
 def pcm_samples(t, what):      # the samples of a pool of signals: a contiguous 1-D int16 device tensor, or None (no pool)
     if t is None:
         return 0

@@ -180,6 +180,22 @@ class XvPairLossConfig(_SizedConfig):
     DEFAULTS = dict(kind=0, squared=0, triplet_type=0, margin_kind=2, margin=0.0, valid_speakers=0, valid_segments=0)
 
 
+class XvGe2eConfig(_SizedConfig):
+    """Mirror of `struct xv_ge2e_config` (include/xvector_hip.h): the options of the GE2E training loss; the defaults are the softmax type
+    on an unset layout (the entry points refuse 0 speakers)."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("loss_type", C.c_int32),
+        ("speakers", C.c_int32),
+        ("segments", C.c_int32),
+        ("valid_speakers", C.c_int32),
+        ("valid_segments", C.c_int32),
+    ]
+    DEFAULTS = dict(loss_type=0, speakers=0, segments=0, valid_speakers=0, valid_segments=0)
+
+
+GE2E_TYPES = {"softmax": 0, "contrastive": 1}                             # XV_GE2E_SOFTMAX / XV_GE2E_CONTRASTIVE
 PAIR_KINDS = {"semihard_triplet_loss": 0, "angular_triplet_loss": 1}      # XV_PAIR_SEMIHARD / XV_PAIR_ANGULAR
 TRIPLET_TYPES = {"all": 0, "hard": 1}                                     # XV_TRIPLET_ALL / XV_TRIPLET_HARD
 LOSS_KINDS = {
@@ -189,6 +205,7 @@ LOSS_KINDS = {
     "additive_angular_margin_softmax": 3,
     "semihard_triplet_loss": 4,          # XV_LOSS_SEMIHARD_TRIPLET / XV_LOSS_ANGULAR_TRIPLET: the pairwise heads (XvPairLossConfig carries their options)
     "angular_triplet_loss": 5,
+    "ge2e_loss": 6,                      # XV_LOSS_GE2E: the GE2E training loss (XvGe2eConfig carries its options)
 }
 OPTIMIZERS = {"sgd": 0, "momentum": 1, "adam": 2}
 PRECISIONS = {"f32": 0, "f16x3": 1}
@@ -338,6 +355,9 @@ SIGNATURES = {
     "xv_pair_loss_forward": (_I, [_VP, C.POINTER(XvPairLossConfig), _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _SZ]),
     "xv_pair_loss_backward": (_I, [_VP, C.POINTER(XvPairLossConfig), _VP, _I, _I, _I, _VP, _VP, _SZ, _VP, _I]),
     "xv_e2e_valid_loss": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _SZ]),
+    "xv_ge2e_loss_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "xv_ge2e_loss_forward": (_I, [_VP, C.POINTER(XvGe2eConfig), _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "xv_ge2e_loss_backward": (_I, [_VP, C.POINTER(XvGe2eConfig), _VP, _I, _I, _VP, _VP, _VP, _SZ, _VP, _I, _VP, _VP]),
     "xv_loss_weight_backward": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _I, _I, _F, _VP, _VP, _SZ]),
     "xv_l2_reg_loss": (_I, [_VP, _VP, _SZ, _F, _VP]),
     "xv_sgd_update": (_I, [_VP, _VP, _VP, _SZ, _F, _F]),
@@ -356,6 +376,7 @@ SIGNATURES = {
     "xv_engine_forward_lengths": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "xv_engine_loss_forward": (_I, [_VP, _VP, _VP, _I, _I]),
     "xv_engine_set_pair_loss": (_I, [_VP, C.POINTER(XvPairLossConfig)]),
+    "xv_engine_set_ge2e_loss": (_I, [_VP, C.POINTER(XvGe2eConfig)]),
     "xv_engine_backward": (_I, [_VP, _VP, _I]),
     "xv_engine_backward_async": (_I, [_VP, _VP, _I]),
     "xv_engine_stage_wait": (_I, [_VP, _VP, _I]),

@@ -5,7 +5,7 @@
 //   xv_engine_bwd.hip   streams, dz ring, join, stage events, layer backward in both precisions, the four backward stages
 //   xv_engine_step.hip  the RCCL exchange, the update, loss pointers, endpoint views
 //   xv_engine_pool.hip  the pooling layer (XvPooling): statistics, self-attention, ghost_vlad - one function per phase
-//   xv_engine_head.hip  the loss head (XvHead): none, the softmax family, pairwise - one function per phase
+//   xv_engine_head.hip  the loss head (XvHead): none, the softmax family, pairwise, GE2E - one function per phase
 // The four units above read neither the pooling kind nor the head kind: they call the phase functions declared at the end of this header.
 // No engine unit holds device code: every launch goes through a launcher of the kernel units (the unit headers below, include/xvector_hip.h).
 //
@@ -101,9 +101,9 @@ struct XvPooling {
 };
 
 // The loss head on the engine's output: its kind, sizes, variables, buffers and the state of the most recent loss (xv_engine_head.hip)
-enum { XV_HEAD_NONE = 0, XV_HEAD_SOFTMAX, XV_HEAD_PAIR };
+enum { XV_HEAD_NONE = 0, XV_HEAD_SOFTMAX, XV_HEAD_PAIR, XV_HEAD_GE2E };
 struct XvHead {
-    int kind = XV_HEAD_NONE;              // none: a predict-only engine | the softmax family (loss_kind 0..3) | pairwise (loss_kind 4 / 5, xv_triplet.hip)
+    int kind = XV_HEAD_NONE;              // none: a predict-only engine | the softmax family (loss_kind 0..3) | pairwise (loss_kind 4 / 5, xv_triplet.hip) | GE2E (loss_kind 6, xv_triplet.hip)
     bool has_loss() const { return kind != XV_HEAD_NONE; }
     int N = 0, ldl = 0;                   // speakers (0: no softmax/output variables) and the logits pitch
     int v_loss_kernel = -1, v_loss_bias = -1, v_ring = -1;
@@ -117,6 +117,10 @@ struct XvHead {
     xv_pair_loss_config pair_cfg = {};
     float *pair_ws = nullptr, *pair_stats = nullptr;
     size_t pair_ws_bytes = 0;
+    // the GE2E head: options from xv_engine_set_ge2e_loss, the trainable scalars ge2e/w and ge2e/b; it shares pair_ws / pair_stats / pair_e2e
+    bool ge2e_set = false;
+    xv_ge2e_config ge2e_cfg = {};
+    int v_ge2e_w = -1, v_ge2e_b = -1;
     // the most recent loss
     int32_t* labels_dev = nullptr;        // caller's pointer of the current step
     float lambda = 0.f;
@@ -318,7 +322,7 @@ int xvp_backward_join(xv_engine* e, hipStream_t s);
 int xvp_reg_loss(xv_engine* e, hipStream_t s);
 int xvp_endpoint(xv_engine* e, const std::string& n, const XvView& v);
 
-// ---- the loss head, one function per phase (xv_engine_head.hip, with xv_engine_set_pair_loss)
+// ---- the loss head, one function per phase (xv_engine_head.hip, with xv_engine_set_pair_loss / xv_engine_set_ge2e_loss)
 int xvh_check_config(const xv_config* c);                                  // engine_create: the checks of the loss fields
 void xvh_configure(xv_engine* e);                                          // kind, N, ldl; the auxiliary losses this loss never reaches are cleared
 void xvh_declare_variables(xv_engine* e);

@@ -1,6 +1,7 @@
 // Engine, the loss head (XvHead, e->head_): none (a predict-only engine), the softmax family (softmax, asoftmax, additive margin, additive
 // angular margin, with the ring / MHE auxiliary losses; loss.py:9-357, xv_loss.hip) and the pairwise heads (semi-hard / angular triplet and
-// the end-to-end validation loss; loss.py:358-705, xv_triplet.hip), one function per phase of the engine's life - configuration, variables,
+// the end-to-end validation loss; loss.py:358-705, xv_triplet.hip) and the GE2E training loss with its two trainable scalars (loss.py:903-982,
+// xv_triplet.hip), one function per phase of the engine's life - configuration, variables,
 // arena, workspace, weight preparation, loss forward, weight gradient, d out, ring gradient, regularisation, endpoints.  The only engine
 // unit that reads the loss kind: a new head is a new case in each function here.
 #include <algorithm>
@@ -10,10 +11,11 @@
 namespace {
 bool is_softmax(const xv_engine* e) { return e->head_.kind == XV_HEAD_SOFTMAX; }
 bool is_pair(const xv_engine* e) { return e->head_.kind == XV_HEAD_PAIR; }
+bool is_ge2e(const xv_engine* e) { return e->head_.kind == XV_HEAD_GE2E; }
 }  // namespace
 
 int xvh_check_config(const xv_config* cfg) {
-    XV_REQUIRE(cfg->loss_kind >= XV_LOSS_SOFTMAX && cfg->loss_kind <= XV_LOSS_ANGULAR_TRIPLET, "Not implement loss kind %d", cfg->loss_kind);
+    XV_REQUIRE(cfg->loss_kind >= XV_LOSS_SOFTMAX && cfg->loss_kind <= XV_LOSS_GE2E, "Not implement loss kind %d", cfg->loss_kind);
     if (cfg->loss_kind == XV_LOSS_ASOFTMAX && cfg->num_speakers > 0)
         XV_REQUIRE(cfg->margin_m == 1.f || cfg->margin_m == 2.f || cfg->margin_m == 4.f, "[ERROR] m=%d is not unsupported.", (int)cfg->margin_m);
     XV_REQUIRE(!cfg->aux_mhe || cfg->num_speakers == 0 || cfg->loss_kind != XV_LOSS_SOFTMAX,
@@ -26,11 +28,12 @@ void xvh_configure(xv_engine* e) {
     XvHead& h = e->head_;
     // no ring / MHE term, and the variable softmax_ringloss/r is never created:
     //  - asoftmax with m = 1 returns its plain cross entropy before aux_loss_func is reached (loss.py:110-115)
-    //  - the reference's triplet functions never call aux_loss_func (loss.py:358-634)
+    //  - the reference's triplet functions never call aux_loss_func (loss.py:358-634), nor does its GE2E loss (loss.py:903-982)
     if ((c.loss_kind == XV_LOSS_ASOFTMAX && c.margin_m == 1.f) || c.loss_kind >= XV_LOSS_SEMIHARD_TRIPLET) c.aux_ring = c.aux_mhe = 0;
     const bool pair = c.loss_kind == XV_LOSS_SEMIHARD_TRIPLET || c.loss_kind == XV_LOSS_ANGULAR_TRIPLET;
-    h.N = pair ? 0 : c.num_speakers;      // pairwise heads: no softmax/output variables
-    h.kind = pair ? XV_HEAD_PAIR : (h.N > 0 ? XV_HEAD_SOFTMAX : XV_HEAD_NONE);
+    const bool ge2e = c.loss_kind == XV_LOSS_GE2E;
+    h.N = pair || ge2e ? 0 : c.num_speakers;      // pairwise heads and GE2E: no softmax/output variables
+    h.kind = pair ? XV_HEAD_PAIR : (ge2e ? XV_HEAD_GE2E : (h.N > 0 ? XV_HEAD_SOFTMAX : XV_HEAD_NONE));
     h.ldl = h.N > 0 ? (int)xv_align(h.N, 4) : 0;
 }
 
@@ -47,9 +50,30 @@ extern "C" int xv_engine_set_pair_loss(xv_engine* e, const xv_pair_loss_config* 
     return 0;
 }
 
+extern "C" int xv_engine_set_ge2e_loss(xv_engine* e, const xv_ge2e_config* cfg) {
+    XV_REQUIRE(e && cfg, "engine_set_ge2e_loss: null argument");
+    XV_REQUIRE(is_ge2e(e), "engine_set_ge2e_loss: the engine's loss_kind %d is not ge2e_loss (6)", e->cfg.loss_kind);
+    XV_REQUIRE(cfg->struct_bytes == (int32_t)sizeof(xv_ge2e_config), "engine_set_ge2e_loss: xv_ge2e_config.struct_bytes is %d, this library's struct has %zu bytes",
+               cfg->struct_bytes, sizeof(xv_ge2e_config));
+    XV_REQUIRE(cfg->loss_type == XV_GE2E_SOFTMAX || cfg->loss_type == XV_GE2E_CONTRASTIVE,
+               "engine_set_ge2e_loss: The GE2E only support softmax and contrastive loss (loss_type %d)", cfg->loss_type);
+    XV_REQUIRE(cfg->speakers >= 1 && cfg->segments >= 1, "engine_set_ge2e_loss: %d speakers x %d segments", cfg->speakers, cfg->segments);
+    XV_REQUIRE(cfg->segments != 1, "engine_set_ge2e_loss: num_segments_per_speaker is 1: a row needs another row of its speaker (assert num_segments_per_speaker != 1)");
+    XV_REQUIRE((long)cfg->speakers * cfg->segments <= 1024, "engine_set_ge2e_loss: %d speakers x %d segments, 1 .. 1024 rows are supported", cfg->speakers,
+               cfg->segments);
+    XV_REQUIRE(cfg->valid_speakers >= 0 && cfg->valid_segments >= 0, "engine_set_ge2e_loss: negative validation layout %d x %d", cfg->valid_speakers, cfg->valid_segments);
+    e->head_.ge2e_cfg = *cfg;
+    e->head_.ge2e_set = true;
+    return 0;
+}
+
 void xvh_declare_variables(xv_engine* e) {
-    if (!is_softmax(e)) return;
     XvHead& h = e->head_;
+    if (is_ge2e(e)) {      // scalars (loss.py:923-924), as softmax_ringloss/r is; the host initialiser sets them from init_end2end_w / _b
+        h.v_ge2e_w = xve_add_var(e, "ge2e/w", {}, true);
+        h.v_ge2e_b = xve_add_var(e, "ge2e/b", {}, true);
+    }
+    if (!is_softmax(e)) return;
     h.v_loss_kernel = xve_add_var(e, "softmax/output/kernel", {e->Lout, h.N}, true);
     if (e->cfg.loss_kind == XV_LOSS_SOFTMAX) h.v_loss_bias = xve_add_var(e, "softmax/output/bias", {h.N}, true);
     if (e->cfg.aux_ring) h.v_ring = xve_add_var(e, "softmax_ringloss/r", {}, true);      // scalar, loss.py:1008-1011
@@ -69,6 +93,13 @@ void xvh_arena(xv_engine* e, const ArenaPlan& p, ArenaCursor& take) {
         take(h.wn, (size_t)e->Lout * h.ldl);
         take(h.wnt, (size_t)h.N * e->Lout);
         take(h.dwn, (size_t)e->Lout * h.ldl);
+    }
+    if (is_ge2e(e)) {      // one workspace for the validation loss and for the training loss in every N x M layout of as many rows as the heads take
+        const int rows = (int)std::min<size_t>(B, 1024);
+        h.pair_ws_bytes = xv_pair_loss_workspace_bytes(rows, e->Lout);
+        for (int m = 2; m <= rows; ++m) h.pair_ws_bytes = std::max(h.pair_ws_bytes, xv_ge2e_loss_workspace_bytes(rows / m, m, e->Lout));
+        take(h.pair_ws, h.pair_ws_bytes / sizeof(float));
+        take(h.pair_stats, 4);
     }
     if (is_pair(e)) {      // G, the pair-matrix gradient and its symmetrised form for as many rows as the heads take (xv_pair_loss_workspace_bytes)
         h.pair_ws_bytes = xv_pair_loss_workspace_bytes((int)std::min<size_t>(B, 1024), e->Lout);
@@ -109,6 +140,26 @@ int pair_loss_forward(xv_engine* e, hipStream_t s, const int32_t* labels) {
         return xv_e2e_valid_loss(s, e->out, h.pair_cfg.valid_speakers, h.pair_cfg.valid_segments, e->Lout, e->Lout, e->scalars + 0, h.pair_ws, h.pair_ws_bytes);
     }
     return xv_pair_loss_forward(s, &h.pair_cfg, e->out, b, e->Lout, e->Lout, labels, e->scalars + 0, h.pair_stats, h.pair_ws, h.pair_ws_bytes);
+}
+
+// GE2E: the training loss on speakers x segments rows with the scalars ge2e/w and ge2e/b; validation as the angular kind's
+int ge2e_loss_forward(xv_engine* e, hipStream_t s) {
+    XvHead& h = e->head_;
+    const int b = e->B;
+    XV_REQUIRE(h.ge2e_set, "engine_loss_forward: loss_kind %d (ge2e_loss) needs its options: call xv_engine_set_ge2e_loss first", e->cfg.loss_kind);
+    h.pair_e2e = !h.with_margin;      // trainer.py:272-275
+    e->reg_valid = false;
+    if (h.pair_e2e) {
+        XV_REQUIRE((long)h.ge2e_cfg.valid_speakers * h.ge2e_cfg.valid_segments == b,
+                   "engine_loss_forward: the end-to-end validation loss takes num_valid_speakers_per_batch x num_valid_segments_per_speaker = %d x %d rows, the batch has %d",
+                   h.ge2e_cfg.valid_speakers, h.ge2e_cfg.valid_segments, b);
+        return xv_e2e_valid_loss(s, e->out, h.ge2e_cfg.valid_speakers, h.ge2e_cfg.valid_segments, e->Lout, e->Lout, e->scalars + 0, h.pair_ws, h.pair_ws_bytes);
+    }
+    XV_REQUIRE((long)h.ge2e_cfg.speakers * h.ge2e_cfg.segments == b,
+               "engine_loss_forward: ge2e_loss takes num_speakers_per_batch x num_segments_per_speaker = %d x %d rows, the batch has %d", h.ge2e_cfg.speakers,
+               h.ge2e_cfg.segments, b);
+    return xv_ge2e_loss_forward(s, &h.ge2e_cfg, e->out, e->Lout, e->Lout, vptr(e, h.v_ge2e_w), vptr(e, h.v_ge2e_b), e->scalars + 0, h.pair_stats, h.pair_ws,
+                                h.pair_ws_bytes);
 }
 
 // the softmax family: logits on the normalised (or plain) speaker weights, the margin rows, the auxiliary losses
@@ -160,6 +211,7 @@ int softmax_loss_forward(xv_engine* e, hipStream_t s, const int32_t* labels, int
 }  // namespace
 
 int xvh_loss_forward(xv_engine* e, hipStream_t s, const int32_t* labels, int global_step) {
+    if (is_ge2e(e)) return ge2e_loss_forward(e, s);      // (labels are not read, as in the reference)
     return is_pair(e) ? pair_loss_forward(e, s, labels) : softmax_loss_forward(e, s, labels, global_step);
 }
 
@@ -225,6 +277,11 @@ int xvh_dout(xv_engine* e, hipStream_t s, bool sk, float** dz7_fused) {
     XvHead& h = e->head_;
     const int b = e->B;
     *dz7_fused = nullptr;
+    if (is_ge2e(e)) {      // d out, d w and d b from the forward's workspace (tdnn7 then runs unfused, as behind the pairwise heads)
+        XV_REQUIRE(!h.pair_e2e, "engine_backward: the last loss was the end-to-end validation loss, which has no backward");
+        return xv_ge2e_loss_backward(s, &h.ge2e_cfg, e->out, e->Lout, e->Lout, vptr(e, h.v_ge2e_w), vptr(e, h.v_ge2e_b), h.pair_ws, h.pair_ws_bytes, e->d_small0,
+                                     e->Lout, gptr(e, h.v_ge2e_w), gptr(e, h.v_ge2e_b));
+    }
     if (is_pair(e)) {      // pairwise heads: no head weight gradient; d out straight from the mined pair matrix (tdnn7 then runs unfused)
         XV_REQUIRE(!h.pair_e2e, "engine_backward: the last loss was the end-to-end validation loss, which has no backward");
         return xv_pair_loss_backward(s, &h.pair_cfg, e->out, b, e->Lout, e->Lout, h.labels_dev, h.pair_ws, h.pair_ws_bytes, e->d_small0, e->Lout);

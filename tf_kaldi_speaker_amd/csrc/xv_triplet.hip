@@ -8,6 +8,8 @@
 //   pair_sym_kernel           A = scale * (dG + dG^T) with the chain through the row norms folded into the diagonal
 //   pair_gemm_kernel<false>   d X = A X
 //   e2e_speaker_kernel / e2e_rows_kernel / e2e_finish_kernel   the validation loss from the same G
+// and, further down, the GE2E training loss (model/loss.py:903-982) on the same G and the same two products:
+//   ge2e_rows_kernel<TYPE> / ge2e_finish_kernel / ge2e_q_kernel
 // The two products are kernels of this unit and not xv_launch_gemm_nt / _tn: B = 8 .. 1024 rows against the 128-row tiles and the
 // split-K slabs of the launchers, and G must be symmetric to the bit.  No atomics; every sum has a fixed order, so
 // two calls give the same bits.  Ties in a min / max: the lowest index takes the whole gradient.  gfx950 only.
@@ -476,6 +478,193 @@ static int tp_gram(hipStream_t s, const float* x, int b, int d, int ldx, float* 
     return 0;
 }
 
+
+// ---- GE2E training loss (loss.py:903-982; include/xvector_hip.h "GE2E training loss") from the same u_ij = G_ij r_i r_j:
+//   t_ik = sum_{m in k} u_im = x^_i . (sum of speaker k),   n_k = sum_{m, m' in k} u_mm' = |sum of speaker k|^2 (e2e_speaker_kernel),
+//   c_ik = t_ik / sqrt(max(n_k, 1e-12)) for another speaker's k; for the own speaker both sums run over the pairs that do not touch row i
+//   ge2e_rows_kernel<TYPE>   one workgroup per row: c and P = d (sum of the row losses) / d S for the N speakers, the row's (loss, sum P c, sum P)
+//   ge2e_finish_kernel       the B partials in index order in double -> loss, d w, d b; scal = {1 / B, d w, d b}
+//   ge2e_q_kernel            Q = d (sum of the row losses) / d u [B x B] from P, c and the norms -> pair_sym_kernel -> pair_gemm_kernel<false>
+enum { GE_SOFTMAX = 0, GE_CONTRASTIVE = 1 };
+#define GE_MAX_N (TP_MAX_B / 2)      // at least two segments per speaker
+
+struct GeLayout { size_t nrm, p, c, ex, total; int np; };
+static GeLayout ge_layout(int n, int m) {
+    const TpLayout t = tp_layout(n * m);
+    GeLayout l;
+    l.np = (n + 3) / 4 * 4;
+    const size_t bn = (size_t)n * m * l.np;
+    l.nrm = t.total; l.p = l.nrm + l.np; l.c = l.p + bn; l.ex = l.c + bn; l.total = l.ex + t.bp;
+    return l;
+}
+
+// 1 / (1 + exp(-s)) without a difference of nearly equal numbers on either side: sigmoid(-s) is 1 - sigmoid(s) to its own rounding
+__device__ __forceinline__ float sigmoid_f(float s) {
+    const float e = expf(-fabsf(s)), hi = 1.f / (1.f + e);
+    return s >= 0.f ? hi : e * hi;
+}
+
+// One workgroup per row i.  cmat[i][k] = c_ik, pmat[i][k] = P_ik WITHOUT the 1 / B of the mean, exn[i] = the own speaker's exclusive norm,
+// part[i] = {row loss, sum_k P_ik c_ik, sum_k P_ik, 0}.  The contrastive maximum is taken where S is largest (the sigmoid is monotone and
+// saturates in fp32 long before S does); a tie goes to the lowest index.
+template <int TYPE>
+__global__ __launch_bounds__(256) void ge2e_rows_kernel(const float* __restrict__ G, int bp, int N, int M, const float* __restrict__ nrm,
+                                                        const float* __restrict__ wp, const float* __restrict__ bptr, int np,
+                                                        float* __restrict__ pmat, float* __restrict__ cmat, float* __restrict__ exn,
+                                                        float* __restrict__ part) {
+    XV_EW_PRIORITY();
+    __shared__ float s_u[TP_MAX_B], s_logit[GE_MAX_N], s_c[GE_MAX_N], s_red[256];
+    __shared__ int s_ri[256];
+    const int tid = threadIdx.x, i = blockIdx.x, B = N * M, own = i / M;
+    const float aw = fabsf(wp[0]), off = bptr[0];
+    const float ri = 1.f / sqrtf(fmaxf(G[(long)i * bp + i], TP_EPS));
+    for (int j = tid; j < B; j += 256) s_u[j] = G[(long)i * bp + j] * (ri * (1.f / sqrtf(fmaxf(G[(long)j * bp + j], TP_EPS))));
+    float ex = 0.f;      // |own speaker's sum without row i|^2, from the pairs of the own block that do not touch i
+    for (int p = tid; p < M * M; p += 256) {
+        const int a = own * M + p / M, b = own * M + p % M;
+        if (a == i || b == i) continue;
+        const float ra = 1.f / sqrtf(fmaxf(G[(long)a * bp + a], TP_EPS)), rb = 1.f / sqrtf(fmaxf(G[(long)b * bp + b], TP_EPS));
+        ex += G[(long)a * bp + b] * (ra * rb);
+    }
+    ex = block_sum(ex, s_red);
+    for (int s = tid; s < N; s += 256) {
+        float dot = 0.f;
+        for (int m = 0; m < M; ++m) {
+            const int j = s * M + m;
+            if (j != i) dot += s_u[j];
+        }
+        const float c = dot * (1.f / sqrtf(fmaxf(s == own ? ex : nrm[s], TP_EPS)));
+        s_c[s] = c;
+        s_logit[s] = aw * c + off;
+    }
+    __syncthreads();
+    float row = 0.f, pc = 0.f, ps = 0.f;
+    if (TYPE == GE_SOFTMAX) {
+        float mx = 0.f;
+        int mi = -1;
+        for (int s = tid; s < N; s += 256)
+            if (mi < 0 || -s_logit[s] < mx) { mx = -s_logit[s]; mi = s; }
+        block_argmin(mx, mi, s_red, s_ri);
+        const float top = -mx;
+        float z = 0.f;
+        for (int s = tid; s < N; s += 256) z += expf(s_logit[s] - top);
+        z = block_sum(z, s_red);
+        for (int s = tid; s < N; s += 256) {
+            const float p = expf(s_logit[s] - top) / z - (s == own ? 1.f : 0.f);
+            pmat[(long)i * np + s] = p; cmat[(long)i * np + s] = s_c[s];
+            pc += p * s_c[s]; ps += p;
+        }
+        row = (logf(z) + top) - s_logit[own];
+    } else {
+        float mx = 0.f;
+        int mi = -1;
+        for (int s = tid; s < N; s += 256)
+            if (s != own && (mi < 0 || -s_logit[s] < mx)) { mx = -s_logit[s]; mi = s; }
+        block_argmin(mx, mi, s_red, s_ri);
+        for (int s = tid; s < N; s += 256) {
+            const float sg = s_logit[s], d = sigmoid_f(sg) * sigmoid_f(-sg);
+            const float p = s == own ? -d : (s == mi ? d : 0.f);
+            pmat[(long)i * np + s] = p; cmat[(long)i * np + s] = s_c[s];
+            pc += p * s_c[s]; ps += p;
+        }
+        row = sigmoid_f(-s_logit[own]) + (mi >= 0 ? sigmoid_f(s_logit[mi]) : 0.f);      // (one speaker: the masked 0 is the maximum)
+    }
+    pc = block_sum(pc, s_red);
+    ps = block_sum(ps, s_red);
+    if (tid == 0) {
+        *(f32x4*)(part + 4 * (long)i) = f32x4{row, pc, ps, 0.f};
+        exn[i] = ex;
+    }
+}
+
+// part[B][4] in index order in double -> loss (the mean), stats {d w, d b, 0, 0}, scal = {1 / B, d w = sign(w) sum P c / B, d b = sum P / B}
+__global__ __launch_bounds__(256) void ge2e_finish_kernel(const float* __restrict__ part, int B, const float* __restrict__ wp, float* __restrict__ loss,
+                                                          float* __restrict__ stats, float* __restrict__ scal) {
+    __shared__ double s_d[3][256];
+    const int tid = threadIdx.x;
+    double a[3] = {0, 0, 0};
+    for (int r = tid; r < B; r += 256)
+        for (int c = 0; c < 3; ++c) a[c] += (double)part[4 * (long)r + c];
+    for (int c = 0; c < 3; ++c) s_d[c][tid] = a[c];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o)
+            for (int c = 0; c < 3; ++c) s_d[c][tid] += s_d[c][tid + o];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const double den = (double)B;
+    const float dw = (float)((double)sign_f(wp[0]) * (s_d[1][0] / den)), db = (float)(s_d[2][0] / den);
+    *loss = (float)(s_d[0][0] / den);
+    if (stats) { stats[0] = dw; stats[1] = db; stats[2] = 0.f; stats[3] = 0.f; }
+    scal[0] = (float)(1.0 / den); scal[1] = dw; scal[2] = db;
+}
+
+// One workgroup per row a of Q = d (sum of the row losses) / d u, every entry of u taken as a variable of its own (pair_sym_kernel adds Q^T).
+//   j in another speaker k:   |w| P_ak / sqrt(max(n_k, eps))                                                   (t_ak)
+//   j in the own speaker k:   -1/2 |w| / n_k sum_{i not in k} P_ik c_ik                                        (n_k; 0 where clamped)
+//                             + sum_{i in k, i != a, i != j} -1/2 |w| / ex_i P_ik c_ik, in index order         (ex_i; 0 where clamped)
+//                             + (j != a) |w| P_ak / sqrt(max(ex_a, eps))                                       (the exclusive t_a)
+// (t n^-3/2 = c / n).  Columns B .. bp are zeroed.
+__global__ __launch_bounds__(256) void ge2e_q_kernel(int N, int M, int bp, int np, const float* __restrict__ nrm, const float* __restrict__ pmat,
+                                                     const float* __restrict__ cmat, const float* __restrict__ exn, const float* __restrict__ wp,
+                                                     float* __restrict__ dp) {
+    XV_EW_PRIORITY();
+    __shared__ float s_de[TP_MAX_B], s_red[256];
+    const int tid = threadIdx.x, a = blockIdx.x, B = N * M, ka = a / M, r0 = ka * M;
+    const float aw = fabsf(wp[0]);
+    float v = 0.f;
+    for (int i = tid; i < B; i += 256)
+        if (i / M != ka) v += pmat[(long)i * np + ka] * cmat[(long)i * np + ka];
+    v = block_sum(v, s_red);
+    const float nk = nrm[ka];
+    const float dn = nk >= TP_EPS ? (-0.5f * aw) * (v / nk) : 0.f;
+    for (int m = tid; m < M; m += 256) {
+        const int i = r0 + m;
+        const float e = exn[i];
+        s_de[m] = e >= TP_EPS ? (-0.5f * aw) * ((pmat[(long)i * np + ka] * cmat[(long)i * np + ka]) / e) : 0.f;
+    }
+    __syncthreads();
+    const float own_t = aw * pmat[(long)a * np + ka] * (1.f / sqrtf(fmaxf(exn[a], TP_EPS)));
+#pragma unroll
+    for (int q = 0; q < TP_Q; ++q) {
+        const int j = tid + 256 * q;
+        if (j >= bp) continue;
+        float qv = 0.f;
+        if (j < B) {
+            const int k = j / M;
+            if (k != ka) qv = aw * pmat[(long)a * np + k] * (1.f / sqrtf(fmaxf(nrm[k], TP_EPS)));
+            else {
+                qv = dn;
+                for (int m = 0; m < M; ++m)
+                    if (r0 + m != a && r0 + m != j) qv += s_de[m];
+                if (j != a) qv += own_t;
+            }
+        }
+        dp[(long)a * bp + j] = qv;
+    }
+}
+
+static int ge_check(const char* who, const xv_ge2e_config* cfg, const float* x, int d, int ldx, const float* w, const float* b, const void* ws,
+                    size_t ws_bytes) {
+    XV_REQUIRE(cfg, "%s: null xv_ge2e_config", who);
+    XV_REQUIRE(cfg->struct_bytes == (int32_t)sizeof(xv_ge2e_config), "%s: xv_ge2e_config.struct_bytes is %d, this library's struct has %zu bytes", who,
+               cfg->struct_bytes, sizeof(xv_ge2e_config));
+    XV_REQUIRE(cfg->loss_type == XV_GE2E_SOFTMAX || cfg->loss_type == XV_GE2E_CONTRASTIVE, "%s: The GE2E only support softmax and contrastive loss (loss_type %d)",
+               who, cfg->loss_type);
+    XV_REQUIRE(cfg->speakers >= 1 && cfg->segments >= 1, "%s: %d speakers x %d segments", who, cfg->speakers, cfg->segments);
+    XV_REQUIRE(cfg->segments != 1, "%s: num_segments_per_speaker is 1: a row needs another row of its speaker (assert num_segments_per_speaker != 1)", who);
+    XV_REQUIRE((long)cfg->speakers * cfg->segments <= TP_MAX_B, "%s: %d speakers x %d segments, 1 .. %d rows are supported", who, cfg->speakers,
+               cfg->segments, TP_MAX_B);
+    XV_REQUIRE(d >= 4 && d % 4 == 0, "%s: the embedding dimension %d must be a positive multiple of 4", who, d);
+    XV_REQUIRE(ldx >= d && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0, "%s: x needs 16-byte aligned rows (pitch %d, dimension %d)", who, ldx, d);
+    XV_REQUIRE(w && b, "%s: w and b (one device float each) must be given", who);
+    const size_t need = ge_layout(cfg->speakers, cfg->segments).total * sizeof(float);
+    XV_REQUIRE(ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= need, "%s: the workspace needs %zu bytes (xv_ge2e_loss_workspace_bytes), 16-byte aligned; %zu given",
+               who, need, ws_bytes);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" size_t xv_pair_loss_workspace_bytes(int b, int d) {
@@ -554,4 +743,64 @@ extern "C" int xv_e2e_valid_loss(void* stream, const float* x, int speakers, int
     e2e_finish_kernel<<<1, 256, 0, s>>>(row_loss, b, loss);
     XV_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" size_t xv_ge2e_loss_workspace_bytes(int speakers, int segments, int d) {
+    if (speakers < 1 || segments < 2 || (long)speakers * segments > TP_MAX_B) {
+        xv_set_error("ge2e_loss_workspace_bytes: %d speakers x %d segments; at least 2 segments per speaker and 2 .. %d rows are supported", speakers,
+                     segments, TP_MAX_B);
+        return 0;
+    }
+    if (d < 4 || d % 4) {
+        xv_set_error("ge2e_loss_workspace_bytes: the embedding dimension %d must be a positive multiple of 4", d);
+        return 0;
+    }
+    return ge_layout(speakers, segments).total * sizeof(float);
+}
+
+extern "C" int xv_ge2e_loss_forward(void* stream, const xv_ge2e_config* cfg, const float* x, int d, int ldx, const float* w, const float* b,
+                                    float* loss, float* stats, void* ws, size_t ws_bytes) {
+    int rc = ge_check("ge2e_loss_forward", cfg, x, d, ldx, w, b, ws, ws_bytes);
+    if (rc) return rc;
+    XV_REQUIRE(loss, "ge2e_loss_forward: loss must be given");
+    hipStream_t s = (hipStream_t)stream;
+    const int n = cfg->speakers, m = cfg->segments, rows = n * m;
+    const TpLayout l = tp_layout(rows);
+    const GeLayout g = ge_layout(n, m);
+    float* f = (float*)ws;
+    rc = tp_gram(s, x, rows, d, ldx, f + l.g, l.bp);
+    if (rc) return rc;
+    e2e_speaker_kernel<<<n, 64, 0, s>>>(f + l.g, l.bp, m, f + g.nrm);
+    XV_LAUNCH_CHECK();
+    if (cfg->loss_type == XV_GE2E_SOFTMAX)
+        ge2e_rows_kernel<GE_SOFTMAX><<<rows, 256, 0, s>>>(f + l.g, l.bp, n, m, f + g.nrm, w, b, g.np, f + g.p, f + g.c, f + g.ex, f + l.part);
+    else
+        ge2e_rows_kernel<GE_CONTRASTIVE><<<rows, 256, 0, s>>>(f + l.g, l.bp, n, m, f + g.nrm, w, b, g.np, f + g.p, f + g.c, f + g.ex, f + l.part);
+    XV_LAUNCH_CHECK();
+    ge2e_finish_kernel<<<1, 256, 0, s>>>(f + l.part, rows, w, loss, stats, f + l.scal);
+    XV_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int xv_ge2e_loss_backward(void* stream, const xv_ge2e_config* cfg, const float* x, int d, int ldx, const float* w, const float* b, void* ws,
+                                     size_t ws_bytes, float* dx, int lddx, float* dw, float* db) {
+    int rc = ge_check("ge2e_loss_backward", cfg, x, d, ldx, w, b, ws, ws_bytes);
+    if (rc) return rc;
+    XV_REQUIRE(dx && lddx >= d && lddx % 4 == 0 && ((uintptr_t)dx & 15) == 0, "ge2e_loss_backward: dx needs 16-byte aligned rows (pitch %d, dimension %d)",
+               lddx, d);
+    XV_REQUIRE(dw && db, "ge2e_loss_backward: dw and db (one device float each) must be given");
+    hipStream_t s = (hipStream_t)stream;
+    const int n = cfg->speakers, m = cfg->segments, rows = n * m;
+    const TpLayout l = tp_layout(rows);
+    const GeLayout g = ge_layout(n, m);
+    float* f = (float*)ws;
+    ge2e_q_kernel<<<rows, 256, 0, s>>>(n, m, l.bp, g.np, f + g.nrm, f + g.p, f + g.c, f + g.ex, w, f + l.dp);
+    XV_LAUNCH_CHECK();
+    pair_sym_kernel<<<rows, 256, 0, s>>>(f + l.g, f + l.dp, rows, l.bp, 1, f + l.scal, f + l.a);
+    XV_LAUNCH_CHECK();
+    pair_gemm_kernel<false><<<dim3(xv_cdiv(d, 64), xv_cdiv(rows, 64)), 256, 0, s>>>(f + l.a, l.bp, x, ldx, rows, d, rows, dx, lddx);
+    XV_LAUNCH_CHECK();
+    rc = xv_copy_2d(s, dw, 1, f + l.scal + 1, 1, 1, 1);
+    if (rc) return rc;
+    return xv_copy_2d(s, db, 1, f + l.scal + 2, 1, 1, 1);
 }

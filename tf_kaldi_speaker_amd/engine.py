@@ -70,18 +70,29 @@ def make_config(feat_dim, num_speakers=0, loss_func="softmax", margin_m=0.0, lam
                 att_key_num_nodes=(1500, 1500), att_key_network_type=3, att_use_scale=True, aux_loss_func=(), ring_loss_init=20.0,
                 ring_loss_lambda=0.01, mhe_lambda=0.01, frame_layers=None, network_relu_type="relu", max_rows=0,
                 vlad_num_centers=0, vlad_num_ghosts=0, vlad_final_l2_norm=False, margin=0.0, triplet_loss_squared=False, triplet_type="all",
-                loss_type="additive_margin_softmax", num_valid_speakers_per_batch=0, num_valid_segments_per_speaker=0):
+                loss_type="additive_margin_softmax", num_valid_speakers_per_batch=0, num_valid_segments_per_speaker=0,
+                ge2e_loss_type="softmax", init_end2end_w=10.0, init_end2end_b=-5.0, num_speakers_per_batch=0, num_segments_per_speaker=0):
     """loss_func "semihard_triplet_loss" / "angular_triplet_loss" (loss kinds 4 / 5): the options margin, triplet_loss_squared, triplet_type,
     loss_type (the margin on the angular loss's positive side) and the N x M layout of an end-to-end validation batch travel on the returned
     config as `.pair_loss` (an XvPairLossConfig); Engine hands them to xv_engine_set_pair_loss.  No softmax/output variables are created for
     these kinds, whatever num_speakers says, and aux_loss_func is not evaluated (the reference's triplet functions never call it).
+    loss_func "ge2e_loss" (loss kind 6): ge2e_loss_type, the training layout num_speakers_per_batch x num_segments_per_speaker and the
+    validation layout travel as `.ge2e_loss` (an XvGe2eConfig; Engine hands them to xv_engine_set_ge2e_loss), init_end2end_w / _b as
+    `.ge2e_init`, which init_variables reads for the trainable scalars ge2e/w and ge2e/b.  No softmax/output variables, no auxiliary losses.
     What a pooling kind or a loss kind reads of these keywords, and what it refuses, is its record's in kinds.py."""
     kw = dict(locals())
     pooling, head = kinds.pooling(pooling_type), kinds.loss(loss_func)
     if optimizer not in OPTIMIZERS:
         raise SystemExit("Optimizer %s is not supported." % optimizer)
     c = XvConfig()
-    c.pair_loss = None
+    c.pair_loss = c.ge2e_loss = c.ge2e_init = None
+    if head.family == kinds.GE2E:
+        if aux_loss_func:
+            log.info("%s: aux_loss_func %s is not evaluated with this loss (the reference's GE2E loss never calls it)" % (loss_func, list(aux_loss_func)))
+            aux_loss_func = ()
+        c.ge2e_loss = _ops.ge2e_loss_config(ge2e_loss_type, num_speakers_per_batch, num_segments_per_speaker,
+                                            valid_speakers=num_valid_speakers_per_batch, valid_segments=num_valid_segments_per_speaker)
+        c.ge2e_init = {"ge2e/w": float(init_end2end_w), "ge2e/b": float(init_end2end_b)}
     if head.family == kinds.PAIR:
         if aux_loss_func:
             log.info("%s: aux_loss_func %s is not evaluated with this loss (the reference's triplet functions never call it)" % (loss_func, list(aux_loss_func)))
@@ -134,6 +145,8 @@ class Engine(object):
         self.h = h
         if getattr(config, "pair_loss", None) is not None:
             _lib.check(self.lib.xv_engine_set_pair_loss(h, C.byref(config.pair_loss)), "xv_engine_set_pair_loss")
+        if getattr(config, "ge2e_loss", None) is not None:
+            _lib.check(self.lib.xv_engine_set_ge2e_loss(h, C.byref(config.ge2e_loss)), "xv_engine_set_ge2e_loss")
         self.n_all = self.lib.xv_engine_variables_count(h)
         self.n_train = self.lib.xv_engine_trainable_count(h)
         self.n_opt = self.lib.xv_engine_optimizer_state_count(h)
@@ -193,9 +206,11 @@ class Engine(object):
 
     def init_variables(self, seed=0):
         """kinds.initial_value of every variable, drawn from one RandomState(seed) in table order: Glorot-uniform kernels, zero biases,
-        gamma=1, beta=0, moving_mean=0, moving_variance=1, the ring loss's radius = config.ring_loss_init."""
+        gamma=1, beta=0, moving_mean=0, moving_variance=1, the ring loss's radius = config.ring_loss_init, the GE2E loss's w and b =
+        init_end2end_w and init_end2end_b (config.ge2e_init)."""
         rs = np.random.RandomState(seed)
-        self.set_variables({name: kinds.initial_value(name.rsplit("/", 1)[1], shape, rs, self.config.ring_loss_init if name == "softmax_ringloss/r" else None)
+        constants = dict(getattr(self.config, "ge2e_init", None) or {}, **{"softmax_ringloss/r": self.config.ring_loss_init})
+        self.set_variables({name: kinds.initial_value(name.rsplit("/", 1)[1], shape, rs, constants.get(name))
                             for name, (shape, _, _) in self.table.items()})
 
     # ---- graph execution ------------------------------------------------------------

@@ -6,7 +6,7 @@ options it refuses by name - `refuse(d, last_relu)` with the engine's frame laye
 and, for a pooling kind, its endpoint names and the params prefixes that belong in tdnn()'s graph key.  A condition that two refusal sites
 state is evaluated by one function here; each site keeps its own wording.  The C library checks the numbers again: it is the authority for the ABI.
 
-Readers: engine.make_config, ops.pair_loss_config, model/tdnn.py, model/loss.py, model/pooling.py, model/trainer.py.  None of them compares
+Readers: engine.make_config, ops.pair_loss_config, ops.ge2e_loss_config, model/tdnn.py, model/loss.py, model/pooling.py, model/trainer.py.  None of them compares
 against a kind's name.  A new kind is a record here, its code in _lib.py and its C unit ("Adding a kind").
 """
 from collections import OrderedDict
@@ -146,7 +146,8 @@ def pooling(name):
 
 
 # ---- loss kinds ---------------------------------------------------------------------------------------------------------------------
-SOFTMAX, PAIR, REFUSED = "softmax family", "pairwise head", "refused"
+SOFTMAX, PAIR, GE2E, REFUSED = "softmax family", "pairwise head", "GE2E head", "refused"
+HEADS_WITHOUT_SPEAKERS = (PAIR, GE2E)      # no softmax/output variables: configured whatever num_speakers says; validated on end2end batches
 
 
 def _margin_keywords(prefix):
@@ -185,9 +186,26 @@ def _angular_check(margin, triplet_type, loss_type):
         raise NotImplementedError("[ERROR] m=%d is not unsupported if %s is selected." % (margin, loss_type))
 
 
+def check_ge2e(ge2e_loss_type, num_segments_per_speaker):
+    """The assert of loss.py:937 and the ValueError of loss.py:980, for every site that takes the GE2E loss's options."""
+    assert int(num_segments_per_speaker) != 1
+    if ge2e_loss_type not in _lib.GE2E_TYPES:
+        raise ValueError("The GE2E only support softmax and contrastive loss")
+
+
+def _ge2e_keywords(d):      # loss.py:916-936; the validation layout: loss.py:657-658
+    check_ge2e(d["ge2e_loss_type"], d["num_segments_per_speaker"])
+    assert "num_valid_speakers_per_batch" in d and "num_valid_segments_per_speaker" in d, "Valid parameters should be set if E2E loss is selected"
+    return dict(ge2e_loss_type=d["ge2e_loss_type"], init_end2end_w=float(d["init_end2end_w"]), init_end2end_b=float(d["init_end2end_b"]),
+                num_speakers_per_batch=int(d["num_speakers_per_batch"]), num_segments_per_speaker=int(d["num_segments_per_speaker"]),
+                num_valid_speakers_per_batch=int(d["num_valid_speakers_per_batch"]),
+                num_valid_segments_per_speaker=int(d["num_valid_segments_per_speaker"]), aux_loss_func=tuple(d.get("aux_loss_func") or ()))
+
+
 def _loss(name, family, prefix=None, keywords=_none, integer_margins=None, check=_none):
     """prefix: of the margin options in a params dict ("amsoftmax" -> amsoftmax_m, amsoftmax_lambda_min, ...); integer_margins: the only
-    margins the kind takes; check(margin, triplet_type, loss_type): what ops.pair_loss_config refuses for a pairwise head."""
+    margins the kind takes; check: what the kind's op-level config refuses - check(margin, triplet_type, loss_type) in ops.pair_loss_config
+    for a pairwise head, check(ge2e_loss_type, num_segments_per_speaker) in ops.ge2e_loss_config for the GE2E head."""
     return Kind(name=name, family=family, code=_lib.LOSS_KINDS.get(name), pair_code=_lib.PAIR_KINDS.get(name), prefix=prefix,
                 keywords=_margin_keywords(prefix) if prefix else keywords, integer_margins=integer_margins, check=check)
 
@@ -199,6 +217,7 @@ LOSSES = OrderedDict((k.name, k) for k in (
     _loss("additive_angular_margin_softmax", SOFTMAX, "arcsoftmax"),
     _loss("semihard_triplet_loss", PAIR, keywords=_semihard_keywords),
     _loss("angular_triplet_loss", PAIR, keywords=_angular_keywords, check=_angular_check),
+    _loss("ge2e_loss", GE2E, keywords=_ge2e_keywords, check=check_ge2e),
     # the centre-based triplet loss (loss.py:708): named so that its refusal can say what it is
     _loss("generalized_angular_triplet_loss", REFUSED)))
 MARGINS = OrderedDict((n, k) for n, k in LOSSES.items() if k.prefix)      # the kinds that put a margin on the target: the values of loss_type
@@ -247,7 +266,8 @@ _CONSTANT_LEAVES = {"gamma": 1.0, "moving_variance": 1.0, "alpha": 0.01}
 
 def initial_value(leaf, shape, rs, constant=None):
     """The initial float32 array of the variable whose name ends in `leaf`, drawing from the numpy RandomState `rs` where it is random.
-    constant: the value where the configuration gives one - the ring loss's radius "r" (ring_loss_init, loss.py:1009-1011)."""
+    constant: the value where the configuration gives one - the ring loss's radius "r" (ring_loss_init, loss.py:1009-1011), the GE2E
+    loss's "w" and "b" (init_end2end_w, init_end2end_b, loss.py:923-924)."""
     shape = tuple(shape)
     if constant is not None:
         return np.full(shape, constant, np.float32)

@@ -11,6 +11,7 @@ reuse_variables=True sees the same weight (loss.py:96-102; model/common.Variable
 
 The pairwise heads (loss.py:358-705) have no variables: semihard_triplet_loss, angular_triplet_loss and e2e_valid_loss return
 (loss, endpoints{"loss", "labels"}) from csrc/xv_triplet.hip; their gradient is ops.pair_loss_backward, and the engine's stage 0.
+ge2e_loss (loss.py:903-982) has the two scalars "<name>/w" and "<name>/b" in the same store; its gradient is ops.ge2e_loss_backward.
 """
 from collections import OrderedDict
 
@@ -151,6 +152,20 @@ def e2e_valid_loss(features, labels, num_outputs, params, is_training=None, reus
         "Valid parameters should be set if E2E loss is selected"
     loss = ops.e2e_valid_loss(x, int(params.num_valid_speakers_per_batch), int(params.num_valid_segments_per_speaker))
     return _pair_endpoints(loss, y)
+
+
+def ge2e_loss(features, labels, num_outputs, params, is_training=None, reuse_variables=None, name="ge2e"):
+    """loss.py:903-982: the features are arranged by speaker, params.num_speakers_per_batch x params.num_segments_per_speaker; labels are not
+    read.  params.ge2e_loss_type ("softmax", "contrastive"); the variables "<name>/w" and "<name>/b" start from params.init_end2end_w and
+    params.init_end2end_b.  -> (loss, endpoints{"loss", "labels", "stats", "w", "b"})"""
+    x, y = _embeddings(features, labels)
+    w = get_variable(name + "/w", (), reuse_variables, init=float(params.init_end2end_w))
+    b = get_variable(name + "/b", (), reuse_variables, init=float(params.init_end2end_b))
+    cfg = ops.ge2e_loss_config(params.ge2e_loss_type, int(params.num_speakers_per_batch), int(params.num_segments_per_speaker))
+    loss, stats, _ = ops.ge2e_loss(cfg, x, w.reshape(1), b.reshape(1))
+    total, endpoints = _pair_endpoints(loss, y, stats)
+    endpoints["w"], endpoints["b"] = w, b
+    return total, endpoints
 
 
 def generalized_angular_triplet_loss(*a, **k):

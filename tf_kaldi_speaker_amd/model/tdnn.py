@@ -100,9 +100,9 @@ def engine_config(params, dim, num_speakers=0, loss_type="softmax", max_batch=12
     kw.update(kinds.pooling(d["pooling_type"]).keywords(d))
     if d.get("feature_norm", False):
         assert "feature_scaling_factor" in d, "If feature normalization is applied, scaling factor is necessary."
-    # a pairwise head has no speakers to count: it is configured whatever num_speakers says; the softmax family only with an output layer
+    # a pairwise or GE2E head has no speakers to count: it is configured whatever num_speakers says; the softmax family only with an output layer
     # (an unknown loss_type goes to make_config, which names it)
-    head = num_speakers or kinds.family(loss_type) == kinds.PAIR
+    head = num_speakers or kinds.family(loss_type) in kinds.HEADS_WITHOUT_SPEAKERS
     if head and loss_type in kinds.LOSSES:
         kw.update(kinds.LOSSES[loss_type].keywords(d))
     return E.make_config(dim, num_speakers, loss_func=loss_type if head else "softmax", **kw)

@@ -360,9 +360,9 @@ class Trainer(object):
             # N speakers x M segments per batch, speaker-major, as the end-to-end validation loss needs them (trainer.py:667-680)
             assert "num_valid_speakers_per_batch" in p.dict and "num_valid_segments_per_speaker" in p.dict, \
                 "Valid parameters should be set if E2E loss is selected"
-            if kinds.family(self.loss_type) != kinds.PAIR:
+            if kinds.family(self.loss_type) not in kinds.HEADS_WITHOUT_SPEAKERS:
                 raise NotImplementedError("end2end validation batches belong to %s, not to %s"
-                                          % (" / ".join(n for n in kinds.LOSSES if kinds.family(n) == kinds.PAIR), self.loss_type))
+                                          % (" / ".join(n for n in kinds.LOSSES if kinds.family(n) in kinds.HEADS_WITHOUT_SPEAKERS), self.loss_type))
         curr_step = 0
         if os.path.isfile(os.path.join(self.model, "checkpoint")):
             curr_step = self.load()

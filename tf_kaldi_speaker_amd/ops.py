@@ -13,13 +13,13 @@ import torch
 
 try:
     from . import kinds
-    from ._host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
+    from ._host import _f32, _lib, _p, _s, _ws, f32_values, ge2e_rows, pitch4, pitched, workspace
     from .diar_ops import *           # noqa: F401,F403 (its public names are the diarization ops)
     from .pipeline_ops import *       # noqa: F401,F403 (... the pipeline ops)
     from .wave_ops import *           # noqa: F401,F403 (and those of the ops that take PCM)
 except ImportError:
     import kinds
-    from _host import _f32, _lib, _p, _s, _ws, f32_values, pitch4, pitched, workspace
+    from _host import _f32, _lib, _p, _s, _ws, f32_values, ge2e_rows, pitch4, pitched, workspace
     from diar_ops import *            # noqa: F401,F403
     from pipeline_ops import *        # noqa: F401,F403
     from wave_ops import *            # noqa: F401,F403
@@ -481,6 +481,48 @@ def e2e_valid_loss(x, speakers, segments, d=None, ws=None):
     loss = _f32((1,), x)
     _lib.call("xv_e2e_valid_loss", _s(), _p(x), int(speakers), int(segments), d, ldx, _p(loss), _p(ws), C.c_size_t(ws.numel() * 4))
     return loss
+
+
+def ge2e_loss_config(ge2e_loss_type, speakers, segments, valid_speakers=0, valid_segments=0):
+    """The xv_ge2e_config of "ge2e_loss" with the reference's asserts (kinds.check_ge2e: loss.py:937, 980): ge2e_loss_type "softmax" /
+    "contrastive" on speakers x segments speaker-major rows."""
+    kinds.loss("ge2e_loss", kinds.GE2E).check(ge2e_loss_type, segments)
+    return _lib.XvGe2eConfig(loss_type=_lib.GE2E_TYPES[ge2e_loss_type], speakers=int(speakers), segments=int(segments),
+                             valid_speakers=int(valid_speakers), valid_segments=int(valid_segments))
+
+
+def _ge2e_args(cfg, x, w, b, d, ws):
+    d = x.shape[1] if d is None else int(d)
+    rows, ldx = ge2e_rows(x, cfg.speakers, cfg.segments, d)
+    f32_values(w, 1, "ge2e loss: w")
+    f32_values(b, 1, "ge2e loss: b")
+    need = int(_lib.load().xv_ge2e_loss_workspace_bytes(cfg.speakers, cfg.segments, d))
+    if need == 0:
+        _lib.check(2, "xv_ge2e_loss_workspace_bytes")
+    if ws is None:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    return rows, d, ldx, ws
+
+
+def ge2e_loss(cfg, x, w, b, d=None, ws=None):
+    """x: [speakers * segments, >= d] float32 view with contiguous rows, speaker-major (d: x.shape[1]); w, b: one device float each.
+    -> (loss [1], stats [4] = {d w, d b, 0, 0}, ws); ws holds what ge2e_loss_backward reads."""
+    rows, d, ldx, ws = _ge2e_args(cfg, x, w, b, d, ws)
+    loss, stats = _f32((1,), x), _f32((4,), x)
+    _lib.call("xv_ge2e_loss_forward", _s(), C.byref(cfg), _p(x), d, ldx, _p(w), _p(b), _p(loss), _p(stats), _p(ws), C.c_size_t(ws.numel() * 4))
+    return loss, stats, ws
+
+
+def ge2e_loss_backward(cfg, x, w, b, ws, d=None, out=None):
+    """(d loss / d x [rows, d] - or into `out`, a [rows, >= d] view with contiguous rows -, d w [1], d b [1]) from the workspace ge2e_loss left."""
+    if ws is None:
+        raise ValueError("ge2e loss: the backward needs the workspace ge2e_loss returned for the same cfg, x, w and b")
+    rows, d, ldx, ws = _ge2e_args(cfg, x, w, b, d, ws)
+    dx = _f32((rows, d), x) if out is None else out
+    _, lddx = pitched(dx, "ge2e loss: dx")
+    dw, db = _f32((1,), x), _f32((1,), x)
+    _lib.call("xv_ge2e_loss_backward", _s(), C.byref(cfg), _p(x), d, ldx, _p(w), _p(b), _p(ws), C.c_size_t(ws.numel() * 4), _p(dx), lddx, _p(dw), _p(db))
+    return dx, dw, db
 
 
 def add_norm_grad(x, dnorm, dx):

@@ -13,6 +13,10 @@ sub-command per question (they used to be eight scripts):
                                                                 passes alternated with stat_pool_forward on the same tensor - medians, bytes, ratios
   python tools/bench_kernel.py triplet                          the pairwise loss heads (xv_triplet.hip): forward and backward of every kind at 64 speakers x
                                                                 10 segments x 512 and at 128 x 512, the e2e validation loss; warm and cold, alternated rounds
+  python tools/bench_kernel.py ge2e                             the GE2E training loss (xv_triplet.hip): forward and backward of both types at 64 x 10 and
+                                                                32 x 4 rows x 512, beside the angular head on the same rows; warm and cold
+  python tools/bench_kernel.py ge2e steps <parent tree> [rounds]   the S1-shaped step with the GE2E head against the angular-triplet step of a checkout
+                                                                of the parent commit, alternated fresh processes
   python tools/bench_kernel.py triplet steps <parent tree> [rounds] the S1-shaped training step with a pairwise head against the AM-Softmax step of a checkout
                                                                 of the parent commit and of this tree, fresh processes, alternated
   python tools/bench_kernel.py segment                          the segment-level GEMMs: one-launch form (xv_skinny.hip) against GEMM + slab-sum launches
@@ -350,6 +354,7 @@ def triplet_steps(argv):
         B, T, head = 128, 200, argv[1]
         kw = dict(loss_func="additive_margin_softmax", margin_m=0.2) if head == "softmax" else (
             dict(loss_func="angular_triplet_loss", margin=0.1, triplet_type="all", loss_type="additive_margin_softmax") if head == "angular" else
+            dict(loss_func="ge2e_loss", ge2e_loss_type=head[5:], num_speakers_per_batch=B // 2, num_segments_per_speaker=2) if head.startswith("ge2e_") else
             dict(loss_func="semihard_triplet_loss", margin=0.2, feature_norm=True, feature_scaling_factor=1.0))
         eng = E.Engine(E.make_config(30, 7351, last_layer_linear=True, max_batch=B, max_frames=T, precision="f32", **kw), device="cuda:0")
         eng.init_variables(seed=0)
@@ -368,6 +373,9 @@ def triplet_steps(argv):
     parent, rounds = os.path.abspath(argv[1]), int(argv[2]) if len(argv) > 2 else 5
     runs = [("parent commit, AM-Softmax", "softmax", parent), ("this tree, AM-Softmax", "softmax", None), ("this tree, angular_triplet_loss", "angular", None),
             ("this tree, semihard_triplet_loss", "semihard", None)]
+    if argv[0] == "ge2e-steps":      # ge2e steps <parent tree> [rounds]: the GE2E step (64 speakers x 2 segments) against the parent's angular-triplet step
+        runs = [("parent commit, angular_triplet_loss", "angular", parent), ("this tree, ge2e_loss softmax", "ge2e_softmax", None),
+                ("this tree, ge2e_loss contrastive", "ge2e_contrastive", None)]
     ms = {label: [] for label, _, _ in runs}
     for _ in range(rounds):
         for label, head, lib in runs:
@@ -434,6 +442,56 @@ def cmd_triplet(argv):
                 for cold in (False, True):
                     t[(name, cold)].append(once(fn, cold))
         print("%d speakers x %d segments x 512 (B = %d)" % (n_spk, n_seg, b))
+        for name, _ in calls:
+            for cold in (False, True):
+                v = sorted(t[(name, cold)])
+                print("  %-36s %s %8.1f us (%7.1f .. %7.1f)" % (name, "cold" if cold else "warm", v[len(v) // 2], v[0], v[-1]), flush=True)
+
+
+def cmd_ge2e(argv):
+    """Forward (G = X X^T, the speaker norms, the row kernel, the final sum: 4 launches) and backward (Q, symmetrise, d X = A X, two scalar copies:
+    5 launches) of the GE2E training loss in both types, beside the angular "all" head's forward and the pairwise backward on the same rows:
+    seven rounds, in each every call once warm and once cold (a 300 MB fill in front); medians over the rounds.
+    ge2e steps <checkout of the parent commit, library built> [rounds=5]: the S1-shaped step with this head against the parent's angular step."""
+    if argv and argv[0] == "steps":
+        return triplet_steps(["ge2e-steps"] + argv[1:])
+    from tf_kaldi_speaker_amd import ops
+    flush = torch.empty(300 << 18, dtype=torch.float32, device="cuda")
+
+    def once(fn, cold):
+        if cold:
+            flush.fill_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+    rounds = 7
+    print("# GE2E training loss, D = 512, w = 10, b = -5; %d rounds, every call once warm and once cold per round; us = median over the rounds (min .. max)," % rounds)
+    print("# between two events around the op (the ops' own allocations of loss / stats / dx / dw / db included)")
+    w, b = torch.tensor([10.0], device="cuda"), torch.tensor([-5.0], device="cuda")
+    angular = ops.pair_loss_config("angular_triplet_loss", margin=0.1, triplet_type="all")
+    for n_spk, n_seg in ((64, 10), (32, 4)):
+        x = rnd(n_spk * n_seg, 512) + 0.5 * rnd(n_spk, 512).repeat_interleave(n_seg, dim=0)
+        y = torch.arange(n_spk, dtype=torch.int32, device="cuda").repeat_interleave(n_seg).contiguous()
+        dx = torch.empty_like(x)
+        calls = []
+        for name in ("softmax", "contrastive"):
+            cfg = ops.ge2e_loss_config(name, n_spk, n_seg)
+            _, _, ws = ops.ge2e_loss(cfg, x, w, b)
+            calls.append(("ge2e %s forward" % name, lambda cfg=cfg, ws=ws: ops.ge2e_loss(cfg, x, w, b, ws=ws)))
+            calls.append(("ge2e %s backward" % name, lambda cfg=cfg, ws=ws: ops.ge2e_loss_backward(cfg, x, w, b, ws, out=dx)))
+        _, _, wsa = ops.pair_loss(angular, x, y)
+        calls.append(("angular all am 0.1 forward", lambda: ops.pair_loss(angular, x, y, ws=wsa)))
+        calls.append(("angular all am 0.1 backward", lambda: ops.pair_loss_backward(angular, x, y, wsa, out=dx)))
+        for _, fn in calls:
+            for _ in range(3):
+                fn()
+        t = {(name, cold): [] for name, _ in calls for cold in (False, True)}
+        for _ in range(rounds):
+            for name, fn in calls:
+                for cold in (False, True):
+                    t[(name, cold)].append(once(fn, cold))
+        print("%d speakers x %d segments x 512 (B = %d)" % (n_spk, n_seg, n_spk * n_seg))
         for name, _ in calls:
             for cold in (False, True):
                 v = sorted(t[(name, cold)])
@@ -1013,7 +1071,7 @@ def cmd_resample(argv):
 
 
 COMMANDS = {"ahc": cmd_ahc, "ahc2": cmd_ahc2, "vbx": cmd_vbx, "pca_plda": cmd_pca_plda, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
-            "triplet": cmd_triplet, "segment": cmd_segment, "staged": cmd_staged}
+            "triplet": cmd_triplet, "ge2e": cmd_ge2e, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:
