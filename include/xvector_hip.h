@@ -626,6 +626,55 @@ int xv_ahc_cluster_sums(void* stream, const float* scores, int64_t scores_floats
                         int64_t total_n, int64_t total_c, int64_t sum_c2, int64_t sum_nc, float* seed, int32_t* sizes, int32_t* status,
                         void* ws, size_t ws_bytes);
 
+/* Labels at many cuts of one merge log: a threshold changes xv_ahc_cluster's stop rule and nothing else, so the log of a run down to one
+ * cluster (every target 1) holds the labels of every threshold as a prefix.  b recordings x cuts cuts per call, one workgroup per
+ * (recording, cut), one launch, no hand-over between workgroups; nothing replays sequentially and nothing is floating point behind the
+ * comparisons with the threshold: the same bits every time.
+ * Inputs, all on the device: the log exactly as xv_ahc_cluster leaves it - merges int32 [total_n - b][2], merge_values fp32 [total_n - b],
+ * n_merges int32 [b], n int32 [b] (recording r's entries at the exclusive prefix of n - 1) - and, shared by all recordings, thresholds
+ * fp32 [cuts], min_clusters int32 [cuts] (>= 1) and max_clusters int32 [cuts] (>= min_clusters).
+ * The rule for cut k of recording r (tests/diar_eval_ref.py restates it):
+ *   p = the number of leading log entries with A >= thresholds[k]: it ends at the first entry that fails, not at the count of those that
+ *   pass - an fp32 log need not be monotone;
+ *   p = min(p, n - min_clusters[k]), then p = max(p, n - max_clusters[k]), either clamped into 0 .. n_merges[r];
+ *   the first p merges are applied, b into a: parent[b] = a, independent writes; every row finds its root, and the roots are numbered by
+ *   a prefix count - a cluster's id is its smallest member and labels 0, 1, ... follow ascending id, as xv_ahc_cluster numbers them.
+ * With min_clusters = 1 and max_clusters >= n the labels are those of xv_ahc_cluster(threshold = thresholds[k]); with min_clusters =
+ * max_clusters = t those of xv_ahc_cluster(target = t), bit for bit.
+ * Outputs: labels int32 [cuts][total_n], recording r's at the exclusive prefix of n in every cut; clusters int32 [cuts][b], the clusters
+ * of each (cut, recording).  A recording with n_merges < 0 or > n - 1, or whose entries lead outside the buffers of the call (n, the
+ * totals, an entry without 0 <= a < b < n), and a cut with a NaN threshold or clamps out of order, get clusters = -1 and no labels.
+ * Refused by name: b <= 0, max_n outside 1 .. 2048, a total_n that does not fit, cuts outside 1 .. 65535.  The device arrays are NOT
+ * checked on the host side of this call (ops.ahc_cut checks the host arrays before the upload and refuses a NaN threshold by name). */
+int xv_ahc_cut(void* stream, const int32_t* merges, const float* merge_values, const int32_t* n_merges, const int32_t* n, int b, int max_n,
+               int64_t total_n, const float* thresholds, const int32_t* min_clusters, const int32_t* max_clusters, int cuts, int32_t* labels,
+               int32_t* clusters);
+
+/* Diarization error counts per (recording, cut): what md-eval counts on 10 ms frames, restated from its definition - nothing is compared
+ * with a run of md-eval.  b recordings x cuts label sets per call, one workgroup per (recording, cut), one launch.
+ * Inputs, all on the device.  Per recording, for all cuts: ref_mask uint32 [total_frames], bit s set if reference speaker s talks in the
+ * frame; scored uint8 [total_frames], 0: the frame is not scored (a collar, ignored overlap); frame_window int32 [total_frames], the window
+ * of the recording that owns the frame, or -1; recording r's frames are frame_offsets[r] .. frame_offsets[r + 1] (int64 [b + 1]), its
+ * windows' labels lie at win_offsets[r] .. win_offsets[r + 1] (int64 [b + 1]) of a cut's labels; speakers int32 [b], its reference
+ * speakers, 1 .. 32 (mask bits at and above are not read).  Per cut: labels int32 [cuts][total_n] (xv_ahc_cut's, or any labels in
+ * 0 .. clusters - 1), clusters int32 [cuts][b], out_offsets int64 [cuts][b]: where the block of (cut, recording) starts in overlap.
+ * The arithmetic (tests/diar_eval_ref.py restates it), over the scored frames of the recording, h = the label of the frame's window or
+ * none, [h] = 1 if there is one, else 0:
+ *   speech += popcount(ref);  miss += max(0, popcount(ref) - [h]);  fa += max(0, [h] - popcount(ref));
+ *   overlap[s][h] += 1 for every set bit s of ref.
+ * Outputs: totals int64 [cuts][b][3] = (speech, miss, fa); overlap int32 [overlap_ints], the block of (cut, recording) packed
+ * [speakers[r]][clusters[cut][r]] at out_offsets; status int32 [cuts][b]: 0 counted; 1 not counted, the cut has more than 256 clusters
+ * (the histogram is 32 x 256 counters in LDS); -1 not counted, clusters < 1 or entries that lead outside the buffers of the call (offsets,
+ * speakers, a window or a label out of range).  A block that is not counted has totals 0 and writes no overlap.
+ * Every output is an integer and integer adds commute (the histogram takes LDS atomic adds): the result is exact, independent of the
+ * order of summation, and the same bytes every time.
+ * Refused by name: b <= 0, cuts outside 1 .. 65535, negative totals, a missing array.  The device arrays are NOT checked on the host side
+ * of this call (ops.diar_frames and ops.diar_confusion check the host arrays before the upload). */
+int xv_diar_confusion(void* stream, const uint32_t* ref_mask, const uint8_t* scored, const int32_t* frame_window, const int64_t* frame_offsets,
+                      const int64_t* win_offsets, const int32_t* speakers, int b, int64_t total_frames, int64_t total_n, const int32_t* labels,
+                      const int32_t* clusters, const int64_t* out_offsets, int cuts, int64_t overlap_ints, int64_t* totals, int32_t* overlap,
+                      int32_t* status);
+
 /* VB-HMM clustering of x-vectors (VBx, Landini et al.: a Bayesian HMM whose states are speakers and whose state distributions come from
  * the PLDA model, started from the clusterer's labels), as recalled from BUT's VB_diarization.py and restated - agreement with a run of
  * that code is not pinned.  b recordings per call, one workgroup each, every iteration in the one launch, no hand-over between

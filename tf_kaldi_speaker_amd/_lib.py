@@ -342,6 +342,8 @@ SIGNATURES = {
     "xv_ahc_cluster_sums_workspace_bytes": (_SZ, [_I, C.c_int64]),
     "xv_ahc_cluster_sums": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _VP, _VP,
                                  _VP, _VP, _SZ]),
+    "xv_ahc_cut": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, C.c_int64, _VP, _VP, _VP, _I, _VP, _VP]),
+    "xv_diar_confusion": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, C.c_int64, C.c_int64, _VP, _VP, _VP, _I, C.c_int64, _VP, _VP, _VP]),
     "xv_vbx_workspace_bytes": (_SZ, [C.c_int64, C.c_int64, C.c_int64, _I]),
     "xv_vbx": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, _F, _F, _F, _I, C.c_double,
                     _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
@@ -398,6 +400,8 @@ XV_CM_HEADERS = {"quartiles": 0, "uniform": 1}      # XV_CM_HEADER_QUARTILES / X
 # refusal); diar_ops.py, misc/diarization.py and the diarize.py driver read them here, where no device library is loaded.
 AHC_MAX_N = 2048            # csrc/xv_ahc.hip AHC_MAX_N: the rows of one recording a clusterer takes; the clusters a seeded start takes
 AHC_MAX_POINTS = 32768      # ... AHC_MAX_POINTS: the rows of one recording xv_ahc_cluster_sums takes; the sizes of a seed together
+DIAR_MAX_SPEAKERS = 32      # csrc/xv_diar_eval.hip DE_MAX_SPEAKERS: the reference speakers of one recording xv_diar_confusion takes (a bit each)
+DIAR_MAX_CLUSTERS = 256     # ... DE_MAX_CLUSTERS: the hypothesis clusters of one (recording, cut) it counts
 VBX_MAX_ROWS = 2048         # csrc/xv_vbx.hip VBX_MAX_T: the rows of one recording xv_vbx takes
 VBX_MAX_SPEAKERS = 32       # ... VBX_MAX_S: its speakers (HMM states)
 VBX_MAX_DIM = 256           # ... VBX_MAX_D: the dimensions of its rows

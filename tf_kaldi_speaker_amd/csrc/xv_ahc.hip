@@ -420,6 +420,109 @@ __global__ __launch_bounds__(AHCS_THREADS) void ahc_sums_fold_kernel(AhcSumsArgs
     T[(long)B * c + A] = t;
 }
 
+// ---- labels at many cuts of one merge log (xv_ahc_cut; include/xvector_hip.h states the rule, tests/diar_eval_ref.py restates it).  A
+// threshold changes the clusterer's stop rule and nothing else, so the log of a run down to one cluster holds the labels of every
+// threshold as a prefix.  One workgroup per (recording, cut), no hand-over between workgroups, integers only behind the comparison of the
+// logged values with the threshold: the same bits every time.
+//   p      the first log entry that fails A >= threshold (a min over the failing entries: an fp32 log need not be monotone), then the two
+//          clamps of the cut
+//   forest parent[b] = a for the first p entries: independent 4-byte LDS stores, since a row leaves once.  An entry is taken only with
+//          0 <= a < b < n, so that a log the caller got wrong can neither leave the arrays nor close a cycle (the walk below ends)
+//   labels every row walks to its root (its cluster's smallest member); the roots are numbered by a prefix count: a ballot per wave and
+//          AHC_COLS x AHC_WAVES wave totals, summed by one thread
+__device__ __forceinline__ int ahc_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+struct AhcCutArgs {
+    const int32_t* merges; const float* merge_values; const int32_t* n_merges; const int32_t* n;
+    const float* thresholds; const int32_t* min_clusters; const int32_t* max_clusters;
+    int b; long total_n;
+    int32_t* labels; int32_t* clusters;
+};
+
+__global__ __launch_bounds__(AHC_THREADS) void ahc_cut_kernel(AhcCutArgs g) {
+    __shared__ int parent[AHC_MAX_N];
+    __shared__ int rank[AHC_MAX_N];
+    __shared__ int wave_roots[AHC_COLS * AHC_WAVES];
+    __shared__ long red_n[AHC_WAVES];
+    __shared__ int red_p[AHC_WAVES];
+    __shared__ int any_bad;
+    const int r = blockIdx.x, cut = blockIdx.y, tid = threadIdx.x, lane = tid & (XV_WAVE - 1), w = tid / XV_WAVE;
+    long pn = 0;      // (the exclusive prefix of n, counts clamped as in the clusterer)
+    for (int i = tid; i < r; i += AHC_THREADS) pn += min(max(g.n[i], 1), AHC_MAX_N);
+#pragma unroll
+    for (int off = XV_WAVE / 2; off; off >>= 1) pn += __shfl_xor(pn, off);
+    if (lane == 0) red_n[w] = pn;
+    if (tid == 0) any_bad = 0;
+    __syncthreads();
+    pn = 0;
+#pragma unroll
+    for (int i = 0; i < AHC_WAVES; ++i) pn += red_n[i];
+    const long pm = pn - r;
+    const int n = g.n[r], nm = g.n_merges[r];
+    const float threshold = g.thresholds[cut];
+    const int lo = g.min_clusters[cut], hi = g.max_clusters[cut];
+    int32_t* count_out = g.clusters + (long)cut * g.b + r;
+    // (uniform; the log's n - 1 slots must end inside the total_n - b of the call, as the labels inside total_n)
+    if (n < 1 || n > AHC_MAX_N || nm < 0 || nm > n - 1 || pn + n > g.total_n || pm + n - 1 > g.total_n - g.b || lo < 1 || hi < lo || threshold != threshold) {
+        if (tid == 0) *count_out = -1;
+        return;
+    }
+    int p = nm;
+    for (int i = tid; i < nm; i += AHC_THREADS)
+        if (!(g.merge_values[pm + i] >= threshold)) { p = i; break; }      // (a thread's entries ascend: its first failing one)
+#pragma unroll
+    for (int off = XV_WAVE / 2; off; off >>= 1) p = min(p, __shfl_xor(p, off));
+    if (lane == 0) red_p[w] = p;
+    for (int k = tid; k < n; k += AHC_THREADS) parent[k] = k;
+    __syncthreads();
+    p = red_p[0];
+#pragma unroll
+    for (int i = 1; i < AHC_WAVES; ++i) p = min(p, red_p[i]);
+    p = ahc_clamp(min(p, n - lo), 0, nm);
+    p = ahc_clamp(max(p, n - hi), 0, nm);
+    for (int i = tid; i < p; i += AHC_THREADS) {
+        const int a = g.merges[2 * (pm + i)], c = g.merges[2 * (pm + i) + 1];
+        if (a >= 0 && a < c && c < n) parent[c] = a;
+        else any_bad = 1;      // (every writer stores the same value)
+    }
+    __syncthreads();
+    if (any_bad) {      // (uniform)
+        if (tid == 0) *count_out = -1;
+        return;
+    }
+    int root[AHC_COLS];
+#pragma unroll
+    for (int u = 0; u < AHC_COLS; ++u) {
+        if (u * AHC_THREADS >= n) break;      // (uniform: the ballot is taken by whole waves)
+        const int k = u * AHC_THREADS + tid;
+        int at = k < n ? k : 0;
+        while (parent[at] != at) at = parent[at];
+        root[u] = at;
+        const unsigned long long m = __ballot(k < n && at == k);
+        if (k < n) rank[k] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_roots[u * AHC_WAVES + w] = __popcll(m);
+    }
+    __syncthreads();
+    if (tid == 0) {      // the exclusive prefix of the wave totals, the clusters of this cut behind it
+        int sum = 0;
+        for (int i = 0; i < AHC_COLS * AHC_WAVES && (i / AHC_WAVES) * AHC_THREADS < n; ++i) {
+            const int c = wave_roots[i];
+            wave_roots[i] = sum;
+            sum += c;
+        }
+        *count_out = sum;
+    }
+    __syncthreads();
+    int32_t* out = g.labels + (long)cut * g.total_n + pn;
+#pragma unroll
+    for (int u = 0; u < AHC_COLS; ++u) {
+        if (u * AHC_THREADS >= n) break;
+        const int k = u * AHC_THREADS + tid;
+        // (a root's rank: its place among the roots of its wave's 64 rows, behind the roots of the waves before)
+        if (k < n) out[k] = rank[root[u]] + wave_roots[(root[u] / AHC_THREADS) * AHC_WAVES + (root[u] % AHC_THREADS) / XV_WAVE];
+    }
+}
+
 extern "C" size_t xv_ahc_workspace_bytes(int64_t sum_n2) { return (size_t)(sum_n2 > 0 ? sum_n2 : 0) * sizeof(float); }
 
 extern "C" int xv_ahc_cluster(void* stream, const float* scores, int64_t scores_floats, const int64_t* mat_offsets, const int32_t* n,
@@ -507,6 +610,26 @@ extern "C" int xv_ahc_cluster_sums(void* stream, const float* scores, int64_t sc
     hipLaunchKernelGGL(ahc_sums_rows_kernel, dim3(xv_cdiv(max_n, AHCS_ROWS), xv_cdiv(max_c, AHCS_CLUSTERS), b), dim3(AHCS_THREADS), 0, s, g);
     XV_LAUNCH_CHECK();
     hipLaunchKernelGGL(ahc_sums_fold_kernel, dim3(xv_cdiv(max_c, AHCS_THREADS), max_c, b), dim3(AHCS_THREADS), 0, s, g);
+    XV_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int xv_ahc_cut(void* stream, const int32_t* merges, const float* merge_values, const int32_t* n_merges, const int32_t* n, int b,
+                          int max_n, int64_t total_n, const float* thresholds, const int32_t* min_clusters, const int32_t* max_clusters, int cuts,
+                          int32_t* labels, int32_t* clusters) {
+    XV_REQUIRE(b > 0, "ahc_cut: no recording in the call (b=%d)", b);
+    XV_REQUIRE(max_n >= 1, "ahc_cut: a recording needs at least one row (largest n=%d)", max_n);
+    XV_REQUIRE(max_n <= AHC_MAX_N, "ahc_cut: a recording of %d rows exceeds the cap of %d", max_n, AHC_MAX_N);
+    XV_REQUIRE(cuts > 0 && cuts <= 65535, "ahc_cut: 1 .. 65535 cuts in a call (cuts=%d)", cuts);
+    XV_REQUIRE(total_n >= b && total_n <= (int64_t)b * max_n, "ahc_cut: total_n does not fit b recordings of at most %d rows", max_n);
+    XV_REQUIRE(n_merges && n && thresholds && min_clusters && max_clusters && labels && clusters, "ahc_cut: bad arguments");
+    XV_REQUIRE(total_n == b || (merges && merge_values), "ahc_cut: merges and merge_values are needed (some recording has two rows or more)");
+    AhcCutArgs g;
+    g.merges = merges; g.merge_values = merge_values; g.n_merges = n_merges; g.n = n;
+    g.thresholds = thresholds; g.min_clusters = min_clusters; g.max_clusters = max_clusters;
+    g.b = b; g.total_n = (long)total_n;
+    g.labels = labels; g.clusters = clusters;
+    hipLaunchKernelGGL(ahc_cut_kernel, dim3(b, cuts), dim3(AHC_THREADS), 0, (hipStream_t)stream, g);
     XV_LAUNCH_CHECK();
     return 0;
 }

@@ -1,7 +1,9 @@
 """Op-level wrappers of the diarization kernels (include/xvector_hip.h): the ops that take the recordings of one call as ragged arrays in
-one 1-D float32 buffer - the agglomerative clusterers and the cluster sums of the two-pass clustering (csrc/xv_ahc.hip), VBx (csrc/xv_vbx.hip)
-and the per-recording PCA of PLDA scoring (csrc/xv_backend_pca.hip); the dense scores they cluster are pipeline_ops.py's.  ops.py re-exports
+one 1-D float32 buffer - the agglomerative clusterers, the cluster sums of the two-pass clustering and the cuts of a merge log
+(csrc/xv_ahc.hip), VBx (csrc/xv_vbx.hip) and the per-recording PCA of PLDA scoring (csrc/xv_backend_pca.hip) - and the error counts of
+diarization scoring (csrc/xv_diar_eval.hip); the dense scores they cluster are pipeline_ops.py's.  ops.py re-exports
 every public name here: callers write ops.ahc_cluster.  The kernels trust their index arrays: _host.recordings checks them before the upload."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -14,6 +16,7 @@ except ImportError:
 
 AHC_MAX_N, AHC_MAX_POINTS, PCA_MAX_ROWS, PCA_MAX_DIM = _lib.AHC_MAX_N, _lib.AHC_MAX_POINTS, _lib.PCA_MAX_ROWS, _lib.PCA_MAX_DIM      # (_lib.py says what each one caps)
 VBX_MAX_ROWS, VBX_MAX_SPEAKERS, VBX_MAX_DIM, VBX_MAX_ITERS = _lib.VBX_MAX_ROWS, _lib.VBX_MAX_SPEAKERS, _lib.VBX_MAX_DIM, _lib.VBX_MAX_ITERS
+DIAR_MAX_SPEAKERS, DIAR_MAX_CLUSTERS = _lib.DIAR_MAX_SPEAKERS, _lib.DIAR_MAX_CLUSTERS
 
 
 def ahc_workspace_bytes(n):
@@ -234,6 +237,113 @@ def ahc_cluster_two_pass(scores, mat_offsets, n, ld=None, threshold=0.0, targets
         raise RuntimeError("%s: xv_ahc_cluster_from skipped recording %d in the second pass" % (name, int(torch.argmin(n_merges2))))
     index = upload(clusters + np.repeat(exclusive_offsets(c), n), np.int64, scores.device)
     return labels2[index], (merges1, values1, n_merges1), (merges2, values2, n_merges2), subsets
+
+
+def ahc_cut(merges, merge_values, n_merges, n, thresholds, min_clusters=None, max_clusters=None):
+    """The labels of b recordings at many cuts of one merge log, in one launch (xv_ahc_cut; include/xvector_hip.h states the rule,
+    tests/diar_eval_ref.py restates it).  merges, merge_values, n_merges: ahc_cluster's outputs for recordings of n[i] rows, as it leaves
+    them on the device - of a run with every target 1 for the labels of any threshold.  thresholds: HOST floats [cuts]; cut k applies the
+    leading log entries whose value is >= thresholds[k] (float32), up to the first that fails, but leaves at least min_clusters[k] (None:
+    1) and at most max_clusters[k] (None: no limit) clusters.  n, thresholds, min_clusters, max_clusters are checked here before the
+    upload.  -> (labels int32 [cuts, sum n], clusters int32 [cuts, b]), device tensors; with the defaults cut k's labels are those of
+    ahc_cluster(threshold=thresholds[k]), with min_clusters = max_clusters = t those of ahc_cluster(targets=t).  A recording whose
+    n_merges is negative gets clusters -1."""
+    name = "ahc_cut"
+    n = host_ints(n, name + ": n", min_size=1, dtype=np.int64)
+    if n.min() < 1 or n.max() > AHC_MAX_N:
+        i = int(np.argmax((n < 1) | (n > AHC_MAX_N)))
+        raise ValueError("%s: recording %d has %d rows, 1 .. %d are taken" % (name, i, int(n[i]), AHC_MAX_N))
+    b, total = n.size, int(n.sum())
+    thresholds = np.asarray(thresholds, dtype=np.float32)
+    if thresholds.ndim != 1 or thresholds.size == 0:
+        raise ValueError("%s: thresholds must be a non-empty 1-D array (cuts <= 0)" % name)
+    if np.isnan(thresholds).any():
+        raise ValueError("%s: threshold %d is NaN" % (name, int(np.argmax(np.isnan(thresholds)))))
+    cuts = thresholds.size
+    lo = np.ones(cuts, np.int32) if min_clusters is None else host_ints(min_clusters, name + ": min_clusters", n=cuts)
+    hi = np.full(cuts, AHC_MAX_N, np.int32) if max_clusters is None else host_ints(max_clusters, name + ": max_clusters", n=cuts)
+    if (lo < 1).any() or (hi < lo).any():
+        k = int(np.argmax((lo < 1) | (hi < lo)))
+        raise ValueError("%s: cut %d: min_clusters %d and max_clusters %d must satisfy 1 <= min_clusters <= max_clusters" % (name, k, int(lo[k]), int(hi[k])))
+    for t, dtype, floats, what in ((merges, torch.int32, 2 * (total - b), "merges"), (merge_values, torch.float32, total - b, "merge_values"), (n_merges, torch.int32, b, "n_merges")):
+        if t.dtype != dtype or not t.is_contiguous() or t.numel() != floats:
+            raise ValueError("%s: %s must be a contiguous %s tensor of %d values (ahc_cluster's output for these recordings)" % (name, what, str(dtype).replace("torch.", ""), floats))
+    dev = n_merges.device
+    labels = torch.empty((cuts, total), dtype=torch.int32, device=dev)
+    clusters = torch.empty((cuts, b), dtype=torch.int32, device=dev)
+    n_d, t_d, lo_d, hi_d = upload(n, np.int32, dev), upload(thresholds, np.float32, dev), upload(lo, np.int32, dev), upload(hi, np.int32, dev)
+    _lib.call("xv_ahc_cut", _s(), _p(merges), _p(merge_values), _p(n_merges), _p(n_d), b, int(n.max()), C.c_int64(total), _p(t_d), _p(lo_d), _p(hi_d), cuts,
+              _p(labels), _p(clusters))
+    return labels, clusters
+
+
+# The reference of the recordings of diar_confusion calls, checked and on the device: ref_mask int32 (the bits of a uint32), scored uint8,
+# frame_window int32 [sum frames]; frame_offsets, win_offsets int64 [b + 1] and speakers int32 [b] there, and frames, n, speakers on the host
+DiarFrames = collections.namedtuple("DiarFrames", "ref_mask scored frame_window frame_offsets win_offsets speakers_d frames n speakers")
+
+
+def diar_frames(ref_mask, scored, frame_window, frames, n, speakers, device):
+    """The reference side of diar_confusion, uploaded once for every call (every batch of cuts) that scores against it.  HOST arrays, the
+    recordings back to back: ref_mask uint32 [sum frames] (bit s: reference speaker s talks), scored [sum frames] (0: not scored),
+    frame_window int32 [sum frames] (the window of its recording that owns the frame, -1: none); frames, n, speakers [b]: the frames,
+    windows and reference speakers (1 .. 32) of each recording.  Checked here - the kernel trusts them.  -> DiarFrames."""
+    name = "diar_frames"
+    frames = host_ints(frames, name + ": frames", min_size=1, dtype=np.int64)
+    b = frames.size
+    n = host_ints(n, name + ": n", n=b, dtype=np.int64)
+    speakers = host_ints(speakers, name + ": speakers", n=b, dtype=np.int64)
+    if frames.min() < 0 or n.min() < 1:
+        raise ValueError("%s: recording %d has %d frames and %d windows" % (name, int(np.argmax((frames < 0) | (n < 1))), int(frames.min()), int(n.min())))
+    if speakers.min() < 1 or speakers.max() > DIAR_MAX_SPEAKERS:
+        i = int(np.argmax((speakers < 1) | (speakers > DIAR_MAX_SPEAKERS)))
+        raise ValueError("%s: recording %d has %d reference speakers, 1 .. %d are taken" % (name, i, int(speakers[i]), DIAR_MAX_SPEAKERS))
+    total = int(frames.sum())
+    ref_mask, scored, frame_window = np.asarray(ref_mask), np.asarray(scored), np.asarray(frame_window)
+    if ref_mask.dtype != np.uint32 or ref_mask.shape != (total,):
+        raise ValueError("%s: ref_mask must be a uint32 array of %d frames" % (name, total))
+    if scored.shape != (total,) or scored.dtype.kind not in "biu":
+        raise ValueError("%s: scored must be a boolean or integer array of %d frames" % (name, total))
+    frame_window = host_ints(frame_window, name + ": frame_window", n=total)
+    at = bounds(frames)
+    for i in range(b):
+        own, mask = frame_window[at[i]:at[i + 1]], ref_mask[at[i]:at[i + 1]]
+        if own.size and (own.min() < -1 or own.max() >= n[i]):
+            raise IndexError("%s: recording %d: frame_window holds a value outside -1 .. %d" % (name, i, int(n[i]) - 1))
+        if mask.size and speakers[i] < 32 and int(mask.max()) >> int(speakers[i]):
+            raise ValueError("%s: recording %d: ref_mask has a bit at or above its %d speakers" % (name, i, int(speakers[i])))
+    return DiarFrames(upload(ref_mask.view(np.int32), np.int32, device), upload(scored != 0, np.uint8, device), upload(frame_window, np.int32, device),
+                      upload(at, np.int64, device), upload(bounds(n), np.int64, device), upload(speakers, np.int32, device), frames, n, speakers)
+
+
+def diar_confusion(reference, labels, clusters):
+    """Diarization error counts of b recordings at many cuts in one launch (xv_diar_confusion; include/xvector_hip.h states the
+    arithmetic, tests/diar_eval_ref.py restates it).  reference: diar_frames' result.  labels: int32 [cuts, sum n] on the device, a window's
+    cluster in 0 .. clusters - 1 (ahc_cut's labels, or VBx's); clusters: int [cuts, b], the clusters of each (cut, recording) - a device
+    tensor (ahc_cut's: it comes to the host here, one synchronisation) or a host array.
+    -> (totals int64 [cuts, b, 3] = (scored speaker time, miss, false alarm) in frames; overlap int32 1-D, the frames reference speaker s
+    shares with cluster h, the block of (cut k, recording i) packed [speakers[i], clusters[k, i]] at out_offsets[k, i]; out_offsets HOST
+    int64 [cuts, b]; status int32 [cuts, b]: 0 counted, 1 not counted - more than 256 clusters -, -1 not counted - clusters below 1 or
+    entries out of range), the tensors on the device.  All integers: exact, and the same bytes every time."""
+    name = "diar_confusion"
+    b, total_n = reference.n.size, int(reference.n.sum())
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[1] != total_n or labels.shape[0] < 1 or not labels.is_contiguous():
+        raise ValueError("%s: labels must be a contiguous int32 [cuts, %d] tensor" % (name, total_n))
+    cuts, dev = labels.shape[0], labels.device
+    host = clusters.cpu().numpy() if isinstance(clusters, torch.Tensor) else np.asarray(clusters)
+    if host.shape != (cuts, b) or host.dtype.kind not in "iu":
+        raise ValueError("%s: clusters must be an integer [%d, %d] array" % (name, cuts, b))
+    host = host.astype(np.int64)
+    sizes = np.where((host >= 1) & (host <= DIAR_MAX_CLUSTERS), host * reference.speakers[None, :], 0).reshape(-1)      # (a block that is not counted holds nothing)
+    out_offsets = exclusive_offsets(sizes).reshape(cuts, b)
+    overlap_ints = int(sizes.sum())
+    totals = torch.empty((cuts, b, 3), dtype=torch.int64, device=dev)
+    overlap = torch.empty(max(overlap_ints, 1), dtype=torch.int32, device=dev)
+    status = torch.empty((cuts, b), dtype=torch.int32, device=dev)
+    c_d, o_d = upload(host.reshape(-1), np.int32, dev), upload(out_offsets.reshape(-1), np.int64, dev)
+    _lib.call("xv_diar_confusion", _s(), _p(reference.ref_mask), _p(reference.scored), _p(reference.frame_window), _p(reference.frame_offsets),
+              _p(reference.win_offsets), _p(reference.speakers_d), b, C.c_int64(int(reference.frames.sum())), C.c_int64(total_n), _p(labels), _p(c_d), _p(o_d), cuts,
+              C.c_int64(overlap_ints), _p(totals), _p(overlap), _p(status))
+    return totals, overlap[:overlap_ints], out_offsets, status
 
 
 def vbx_workspace_bytes(t, s, d):

@@ -9,8 +9,12 @@ clusterer's labels start the VB-HMM clustering of the windows (VBx, ops.vbx: DES
 the PLDA scores of a recording come from its own model behind the per-recording PCA of ivector-plda-scoring-dense
 (ops.backend_pca_plda: DESIGN.md section 6k), one op call per batch; a recording of more than first_pass_max_points windows is clustered in
 two passes (ops.ahc_cluster_two_pass: DESIGN.md section 6l), up to 32768 windows.
-Not here: threshold calibration, overlap detection, collars / md-eval, VBx or the per-recording PCA on recordings of
-more than 2048 windows.
+Tuning the threshold on a development set (nnet/lib/tune_diarization.py): Diarizer.sweep gives the labels of every
+threshold from one clustering (the merge log and its cuts, ops.ahc_cut); reference_frames and frame_windows put a reference RTTM - with a
+collar, and one of three rules for overlapped speech - and the windows on 10 ms frames; DerSweep counts the errors of every (recording,
+threshold) on the device (ops.diar_confusion) and pools the DER: md-eval restated from its definition, not compared with a run of it.
+Not here: unsupervised threshold calibration, overlap detection, UEM files, VBx or the per-recording PCA on
+recordings of more than 2048 windows.
 """
 import collections
 import logging
@@ -72,19 +76,26 @@ def subsegments(start, end, window, period, min_segment, log=None):
         t, k = t + period, k + 1
 
 
+def _midpoint_cut(subsegs):
+    """The windows sorted by start; where two consecutive ones overlap, the first ends and the second starts at the midpoint of the overlap.
+    -> [[start, end, the window's index in subsegs]]."""
+    order = sorted(range(len(subsegs)), key=lambda i: (subsegs[i][0], subsegs[i][1]))
+    cut = [[float(subsegs[i][0]), float(subsegs[i][1]), i] for i in order]
+    for a, b in zip(cut[:-1], cut[1:]):
+        if a[1] > b[0]:
+            a[1] = b[0] = 0.5 * (a[1] + b[0])
+    return cut
+
+
 def rttm_turns(subsegs, labels):
     """Speaker turns from clustered windows: subsegs [(start, end)] (any unit), labels one per window.  The windows are sorted by start;
     where two consecutive windows overlap, the first ends and the second starts at the midpoint of the overlap; then abutting windows of
     one label are merged.  -> list of (start, end, label)."""
     if len(subsegs) != len(labels):
         raise ValueError("rttm_turns: %d windows, %d labels" % (len(subsegs), len(labels)))
-    order = sorted(range(len(subsegs)), key=lambda i: (subsegs[i][0], subsegs[i][1]))
-    cut = [[float(subsegs[i][0]), float(subsegs[i][1]), int(labels[i])] for i in order]
-    for a, b in zip(cut[:-1], cut[1:]):
-        if a[1] > b[0]:
-            a[1] = b[0] = 0.5 * (a[1] + b[0])
     turns = []
-    for s, e, l in cut:
+    for s, e, i in _midpoint_cut(subsegs):
+        l = int(labels[i])
         if turns and turns[-1][2] == l and turns[-1][1] == s:
             turns[-1][1] = e
         else:
@@ -148,6 +159,59 @@ def der(ref, hyp):
     return miss / speech, fa / speech, conf / speech, (miss + fa + conf) / speech
 
 
+OVERLAP_RULES = ("score", "ignore", "first")      # what reference_frames does where reference turns overlap
+
+
+def popcount32(x):      # the set bits of each uint32 of an array -> int64
+    x = np.asarray(x, np.uint32).astype(np.int64)
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    return (((x + (x >> 4)) & 0x0F0F0F0F) * 0x01010101 & 0xFFFFFFFF) >> 24
+
+
+def _frame(t):      # the 10 ms frame of a boundary at t seconds, not below 0 (as _frame_labels places it)
+    return max(int(round(t / DER_FRAME)), 0)
+
+
+def reference_frames(turns, frames, collar=0.0, overlap="score"):
+    """The reference of one recording on its `frames` 10 ms frames, as md-eval sees it (restated from its definition, not compared with a
+    run of it): turns [(start, end, speaker)] in seconds, a boundary at t being frame int(round(t / DER_FRAME)).  collar (seconds, md-eval's
+    -c): with C = int(round(collar / DER_FRAME)) the frames q - C <= f < q + C around every start and end q of every turn are not scored.
+    overlap: "score" - every reference speaker of a frame counts; "ignore" (md-eval's -1) - frames with two or more reference speakers are
+    not scored; "first" - der()'s rule: the turn that starts first owns the frame.  Speakers are numbered in the order of their first turn.
+    -> (ref_mask uint32 [frames]: bit s set if speaker s talks, scored uint8 [frames], the speakers' names); more than 32 speakers are refused."""
+    if overlap not in OVERLAP_RULES:
+        raise ValueError("reference_frames: overlap must be one of %s (got %r)" % (", ".join(OVERLAP_RULES), overlap))
+    if not collar >= 0.0:
+        raise ValueError("reference_frames: the collar must not be negative (got %r)" % (collar,))
+    frames, c = int(frames), int(round(collar / DER_FRAME))
+    mask, scored, names = np.zeros(frames, np.uint32), np.ones(frames, np.uint8), {}
+    for s, e, l in sorted(turns, key=lambda t: (t[0], t[1])):
+        k = names.setdefault(l, len(names))
+        if k >= _lib.DIAR_MAX_SPEAKERS:
+            raise ValueError("reference_frames: more than %d reference speakers in a recording (%s is one too many)" % (_lib.DIAR_MAX_SPEAKERS, l))
+        span = mask[_frame(s):_frame(e)]
+        if overlap == "first":
+            span[span == 0] = np.uint32(1 << k)
+        else:
+            span |= np.uint32(1 << k)
+        for q in (int(round(s / DER_FRAME)), int(round(e / DER_FRAME))):
+            scored[max(q - c, 0):max(q + c, 0)] = 0
+    if overlap == "ignore":
+        scored[popcount32(mask) >= 2] = 0
+    return mask, scored, list(names)
+
+
+def frame_windows(subsegs, frames):
+    """The window that owns each of a recording's `frames` 10 ms frames under rttm_turns' midpoint rule: subsegs [(start, end)] in seconds;
+    a frame between two windows' boundaries (placed as reference_frames places them) belongs to that window, where two still overlap to
+    the one that starts first (der()'s rule), and -1 says none.  It does not depend on the labels: once per recording.  -> int32 [frames]."""
+    own = np.full(int(frames), -1, np.int32)
+    for s, e, i in reversed(_midpoint_cut(subsegs)):
+        own[_frame(s):_frame(e)] = i
+    return own
+
+
 def vbx_init(labels, num_speakers, smoothing=5.0):
     """The responsibilities VBx starts from: one-hot rows of the clusterer's labels times `smoothing`, a softmax per row (smoothing 5: 0.99
     on the labelled speaker of two, less with more speakers).  -> float32 [len(labels), num_speakers]; host arithmetic in double."""
@@ -189,6 +253,7 @@ class Diarizer(object):
         diar = Diarizer(scorer, threshold=0.2)                      # merge while the best average score is >= the threshold
         diar = Diarizer(scorer, reco2num_spk={"rec1": 2, ...})      # or: merge down to the given number of speakers
         labels = diar.cluster({"rec1": matrix1, ...})               # {recording: int32 labels, one per row}
+        labels = diar.sweep({"rec1": matrix1, ...}, [0.1, 0.2])     # {recording: int32 [thresholds, rows]}: cluster() at every threshold, one clustering
 
         diar = Diarizer(scorer, threshold=0.0, vbx=VbxOptions())    # ... and VBx behind the clusterer (a BackendScorer in the plda mode)
         diar = Diarizer(scorer, threshold=0.0, target_energy=0.9)   # ... the recipe's per-recording PCA in front of the PLDA scores (plda mode)
@@ -257,6 +322,74 @@ class Diarizer(object):
             out.update((k, labels[lo:hi]) for k, lo, hi in zip(batch.keys, batch.bounds[:-1], batch.bounds[1:]))
         return out
 
+    def sweep(self, embeddings, thresholds, vbx_grid=None):
+        """The labels cluster() would give at each of `thresholds` (whatever stop rule this Diarizer was made with), label for label, at
+        the cost of one clustering: the scores once per recording, as cluster() takes them (target_energy included); one ops.ahc_cluster
+        call per batch with every target 1 - the full merge log - and one ops.ahc_cut call for all thresholds.  With vbx each cut's labels
+        take cluster()'s route: max_clusters = 32 in the cut replaces the second clustering of a recording with more clusters than VBx
+        takes, then ops.vbx per cut; vbx_grid (a list of VbxOptions) runs that for each entry in place of self.vbx.  A recording of more
+        than first_pass_max_points windows has no single log: ops.ahc_cluster_two_pass once per threshold, and a log line says so.
+        -> {recording: NumPy int32 [cuts, n]} in the mapping's order; with vbx_grid int32 [len(vbx_grid), cuts, n].  vbx_report holds the
+        last cut's entries."""
+        thresholds = np.asarray(thresholds, np.float64)
+        if thresholds.ndim != 1 or thresholds.size == 0 or np.isnan(thresholds).any():
+            raise ValueError("Diarizer: sweep takes a non-empty list of thresholds, none of them NaN")
+        if vbx_grid is not None and (self.vbx is None or not len(vbx_grid)):
+            raise ValueError("Diarizer: vbx_grid needs a Diarizer with vbx and at least one entry")
+        keys, host = list(embeddings), self.host
+        if not keys:
+            return {}
+        n = self._windows(keys, embeddings)
+        ld = np.asarray([host.pitch4(int(r)) for r in n], np.int64)
+        targets = np.zeros(len(keys), np.int64)
+        cost = self._bytes(n, ld, targets) + 4 * thresholds.size * n      # (... and the labels of every cut)
+        self.pca_report, self.vbx_report, out = {}, {}, {}
+        for picked in host.greedy_batches(len(keys), lambda i, total=0: (total + int(cost[i]),), lambda total: total, self.scorer.workspace_bytes,
+                                          too_big=lambda i, c: "Diarizer: recording %s needs %d bytes of scores, the workspace holds %d"
+                                          % (keys[i], c, self.scorer.workspace_bytes)):
+            batch = _Batch([keys[i] for i in picked], n[picked], ld[picked], targets[picked], host.bounds(n[picked] * ld[picked]), host.bounds(n[picked]))
+            matrices = [embeddings[k] for k in batch.keys]
+            packed = self._scores(batch, matrices)
+            labels = self._ahc_cuts(packed, batch, thresholds)
+            del packed
+            if vbx_grid is not None:
+                labels = np.stack([[self._vbx(batch, matrices, cut, opt) for cut in labels] for opt in vbx_grid])
+            elif self.vbx is not None:
+                labels = np.stack([self._vbx(batch, matrices, cut) for cut in labels])
+            out.update((k, labels[..., lo:hi]) for k, lo, hi in zip(batch.keys, batch.bounds[:-1], batch.bounds[1:]))
+        return out
+
+    def _ahc_cuts(self, packed, batch, thresholds):
+        """The clusterer's labels of one batch at every threshold -> int32 [cuts, windows of the batch]: the recordings of at most
+        first_pass_max_points windows through one merge log and its cuts, the longer ones through the two passes, once per threshold."""
+        ops, host, n = self.ops, self.host, batch.n
+        long = n > self.first_pass_max_points
+        labels = np.empty((thresholds.size, int(batch.bounds[-1])), np.int32)
+        idx = np.flatnonzero(~long)
+        if idx.size:
+            _, merges, values, n_merges = ops.ahc_cluster(packed, batch.offsets[idx], n[idx], batch.ld[idx], targets=np.ones(idx.size, np.int64))
+            cap = None if self.vbx is None else np.full(thresholds.size, _lib.VBX_MAX_SPEAKERS, np.int32)
+            got, clusters = ops.ahc_cut(merges, values, n_merges, n[idx], thresholds, max_clusters=cap)
+            skipped = clusters.min(dim=0)[0].cpu().numpy() < 1
+            if skipped.any():
+                raise RuntimeError("Diarizer: xv_ahc_cut skipped recording %s" % batch.keys[idx[int(np.argmax(skipped))]])
+            got = got.cpu().numpy()
+            for j, lo in zip(idx, host.bounds(n[idx])):
+                labels[:, batch.bounds[j]:batch.bounds[j + 1]] = got[:, lo:lo + n[j]]
+        idx = np.flatnonzero(long)
+        if idx.size:
+            _LOG.info("[INFO] Recording %s: more than %d windows, no single merge log: clustered in two passes once per threshold (%d times)."
+                      % (", ".join(batch.keys[j] for j in idx), self.first_pass_max_points, thresholds.size))
+            # the long recordings as a batch of their own on the same packed buffer (_ahc reads a matrix's start, not where it ends)
+            own = _Batch([batch.keys[j] for j in idx], n[idx], batch.ld[idx], batch.targets[idx], np.append(batch.offsets[idx], batch.offsets[-1]), host.bounds(n[idx]))
+            for k, threshold in enumerate(thresholds):
+                one = self._ahc(packed, own, own.targets, threshold=float(threshold))
+                if self.vbx is not None:
+                    one = self._at_most_vbx_speakers(packed, own, one)
+                for j, lo, hi in zip(idx, own.bounds[:-1], own.bounds[1:]):
+                    labels[k, batch.bounds[j]:batch.bounds[j + 1]] = one[lo:hi]
+        return labels
+
     def _windows(self, keys, embeddings):      # -> the windows of each recording; one that the clusterer, VBx or the PCA does not take is refused by name
         n = np.asarray([int(embeddings[k].shape[0]) for k in keys], np.int64)
         for k, rows in zip(keys, n):
@@ -315,11 +448,13 @@ class Diarizer(object):
                 scorer.dense(prepared, out=view, model=model)
         return packed
 
-    def _ahc(self, packed, batch, targets):
+    def _ahc(self, packed, batch, targets, threshold=None):
         """The clusterer over one batch -> the labels back to back.  The recordings of at most first_pass_max_points windows go through one
-        ops.ahc_cluster call; the longer ones through ops.ahc_cluster_two_pass, one call per stop rule (by threshold, by target)."""
+        ops.ahc_cluster call; the longer ones through ops.ahc_cluster_two_pass, one call per stop rule (by threshold, by target).
+        threshold None: this Diarizer's."""
         ops, offsets, n, ld = self.ops, batch.offsets[:-1], batch.n, batch.ld
-        threshold = 0.0 if self.threshold is None else float(self.threshold)
+        if threshold is None:
+            threshold = 0.0 if self.threshold is None else float(self.threshold)
         long = n > self.first_pass_max_points
         labels = np.empty(int(batch.bounds[-1]), np.int32)
         for pick, by_target in ((~long, None), (long & (targets == 0), False), (long & (targets > 0), True)):
@@ -349,9 +484,9 @@ class Diarizer(object):
                 labels[at[j]:at[j + 1]] = relabel[at[j]:at[j + 1]]
         return labels
 
-    def _vbx(self, batch, matrices, labels):
-        """ops.vbx over one batch: labels = the clusterer's, back to back.  -> the new labels, back to back."""
-        opt, torch, at = self.vbx, self.torch, batch.bounds
+    def _vbx(self, batch, matrices, labels, opt=None):
+        """ops.vbx over one batch: labels = the clusterer's, back to back; opt None: this Diarizer's options.  -> the new labels, back to back."""
+        opt, torch, at = opt or self.vbx, self.torch, batch.bounds
         rows, psi = zip(*(self.scorer.plda_space(m) for m in matrices))
         x, offsets, n, ld = self.host.pack_rows(rows)
         dim, recordings = int(psi[0].numel()), range(len(batch.keys))
@@ -368,3 +503,83 @@ class Diarizer(object):
             out[at[j]:at[j + 1]] = _first_appearance(new[at[j]:at[j + 1]])
             self.vbx_report[name] = (int(speakers[j]), int(out[at[j]:at[j + 1]].max()) + 1, int(n_iters[j]), float(elbo[j, n_iters[j] - 1]))
         return out
+
+
+class DerSweep(object):
+    """The diarization error of many label sets against one reference, counted on the device: md-eval's figures (-c collar, -1) restated
+    from its definition - nothing is compared with a run of md-eval.
+
+        sweep = DerSweep(device, {"rec1": ref_turns, ...}, {"rec1": [(start, end), ...], ...}, collar=0.25)     # seconds; once
+        table = sweep.score(diarizer.sweep(embeddings, thresholds))                                            # any number of times
+
+    The reference frames (reference_frames) and the owning windows (frame_windows) of every recording are built and uploaded once
+    (ops.diar_frames); a recording has as many 10 ms frames as its last reference turn or window needs.  score(labels) takes
+    {recording: int [cuts, n]} (one label per window and cut), runs one ops.diar_confusion call over all recordings and cuts, and maps
+    the speakers of every (recording, cut) one to one such that the matched time over the scored frames is largest
+    (scipy.optimize.linear_sum_assignment on the counted overlap, as der() does): speaker error = sum of min(reference speakers, [a
+    hypothesis speaker]) - matched.  -> DerTable."""
+
+    def __init__(self, device, reference, subsegs, collar=0.0, overlap="score"):
+        try:
+            from .. import _host
+        except (ImportError, ValueError):
+            import _host
+        self.torch, self.ops, self.device = _host.device_ops(device)
+        self.keys = list(reference)
+        if set(self.keys) != set(subsegs):
+            odd = sorted(set(self.keys) ^ set(subsegs))[0]
+            raise ValueError("DerSweep: recording %s has %s" % (odd, "a reference but no windows" if odd in reference else "windows but no reference"))
+        if not self.keys:
+            raise ValueError("DerSweep: no recording")
+        masks, flags, owners, self.names = [], [], [], {}
+        for k in self.keys:
+            frames = _frame(max([e for _, e, _ in reference[k]] + [e for _, e in subsegs[k]]))
+            mask, scored, self.names[k] = reference_frames(reference[k], frames, collar, overlap)
+            if not self.names[k]:
+                raise ValueError("DerSweep: recording %s has no reference turn" % k)
+            masks.append(mask), flags.append(scored), owners.append(frame_windows(subsegs[k], frames))
+        self.n = np.asarray([len(subsegs[k]) for k in self.keys], np.int64)
+        self.speakers = np.asarray([len(self.names[k]) for k in self.keys], np.int64)
+        self.frames = self.ops.diar_frames(np.concatenate(masks), np.concatenate(flags), np.concatenate(owners), [m.size for m in masks], self.n,
+                                           self.speakers, self.device)
+
+    def score(self, labels):
+        from scipy.optimize import linear_sum_assignment
+        per = [np.asarray(labels[k]) for k in self.keys]
+        for k, lab, n in zip(self.keys, per, self.n):
+            if lab.ndim != 2 or lab.shape != (per[0].shape[0], n) or lab.dtype.kind not in "iu" or lab.shape[0] < 1 or lab.min() < 0:
+                raise ValueError("DerSweep: recording %s: labels must be a non-negative integer [cuts, %d] array, the cuts of every recording alike" % (k, n))
+        clusters = np.stack([lab.max(axis=1) + 1 for lab in per], axis=1)
+        stacked = self.torch.from_numpy(np.ascontiguousarray(np.concatenate(per, axis=1), dtype=np.int32)).to(self.device)
+        totals, overlap, offsets, status = self.ops.diar_confusion(self.frames, stacked, clusters)
+        totals, overlap, status = totals.cpu().numpy(), overlap.cpu().numpy(), status.cpu().numpy()
+        error = np.zeros(status.shape, np.int64)
+        for k, i in zip(*np.nonzero(status == 0)):
+            shared = overlap[offsets[k, i]:offsets[k, i] + self.speakers[i] * clusters[k, i]].reshape(self.speakers[i], clusters[k, i])
+            rows, cols = linear_sum_assignment(-shared)
+            error[k, i] = totals[k, i, 0] - totals[k, i, 1] - int(shared[rows, cols].sum())
+        return DerTable(self.keys, totals[..., 0], totals[..., 1], totals[..., 2], error, status, clusters)
+
+
+class DerTable(object):
+    """DerSweep.score's counts in frames, int64 [cuts, recordings]: speech (scored reference speaker time), miss, fa (false alarm), error
+    (speaker error); status int32 (ops.diar_confusion's: 0 counted) and clusters per (cut, recording).  pooled(k): cut k's (miss, false
+    alarm, speaker error, DER) over all recordings - summed counts over summed scored speaker time, md-eval's overall figure - or None if a
+    recording of the cut was not counted; why_not(k) then names the first such recording and the reason."""
+
+    def __init__(self, keys, speech, miss, fa, error, status, clusters):
+        self.keys, self.speech, self.miss, self.fa, self.error, self.status, self.clusters = keys, speech, miss, fa, error, status, clusters
+        if int(speech[0].sum()) == 0:      # (the scored reference time does not depend on the cut)
+            raise ValueError("DerSweep: the reference holds no scored speech")
+
+    def pooled(self, k):
+        if (self.status[k] != 0).any():
+            return None
+        speech, parts = int(self.speech[k].sum()), [int(c[k].sum()) for c in (self.miss, self.fa, self.error)]
+        return tuple(p / speech for p in parts) + (sum(parts) / speech,)
+
+    def why_not(self, k):
+        i = int(np.argmax(self.status[k] != 0))
+        if self.status[k, i] == 1:
+            return "recording %s has %d clusters, %d are counted" % (self.keys[i], int(self.clusters[k, i]), _lib.DIAR_MAX_CLUSTERS)
+        return "recording %s was skipped by xv_diar_confusion (status %d)" % (self.keys[i], int(self.status[k, i]))

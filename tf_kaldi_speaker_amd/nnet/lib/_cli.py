@@ -140,7 +140,20 @@ ARGUMENTS = {
                                                                  "survivors against each other; up to %d windows.  Such a recording above %d "
                                                                  "windows is refused with --vbx or --target-energy (their caps stay at %d)."
                                                                  % (_lib.AHC_MAX_N, _lib.AHC_MAX_POINTS, _lib.VBX_MAX_ROWS, _lib.PCA_MAX_ROWS))),
+    "thresholds": (("--thresholds",), dict(type=str, default="", help="The thresholds to try: `first:step:last` (both ends included) or `a,b,c`.")),
+    "collar": (("--collar",), dict(type=float, default=0.25, help="Seconds around every boundary of a reference turn, on either side, that are "
+                                                                  "not scored (md-eval -c).")),
+    "overlap": (("--overlap",), dict(type=str, default="score", choices=("score", "ignore", "first"),
+                                     help="Frames with two or more reference speakers: score every speaker, do not score the frame (md-eval "
+                                          "-1), or give it to the turn that starts first.")),
+    "vbx_fa_list": (("--vbx-fa",), dict(type=str, default="0.3", help="VBx: the values of the statistics' scaling factor to try, `a,b,c`.")),
+    "vbx_fb_list": (("--vbx-fb",), dict(type=str, default="17", help="VBx: the values of the regularisation's scaling factor to try, `a,b,c`.")),
+    "vbx_loop_prob_list": (("--vbx-loop-prob",), dict(type=str, default="0.99", help="VBx: the loop probabilities to try, `a,b,c`.")),
+    "ref_rttm": (("--ref-rttm",), dict(type=str, default="", help="The reference RTTM of the development recordings.")),
     # positionals
+    "embeddings_rspecifier": (("embeddings_rspecifier",), dict(type=str, help="ark: or scp: rspecifier of the windows' embeddings, keyed "
+                                                                              "`recording-startframe-endframe` (diarize.py --write-embeddings).")),
+    "tune_out_dir": (("out_dir",), dict(type=str, help="Receives der_table.txt and threshold.")),
     "rttm_out": (("rttm_out",), dict(type=str, help="The RTTM file to write.")),
     "plan": (("plan",), dict(type=str, help="The plan file (read; written with --make-plan).")),
     "augment_out_dir": (("out_dir",), dict(type=str, nargs="?", default="", help="Receives wav/<key>.wav and wav.scp (not needed with --make-plan).")),

@@ -27,7 +27,8 @@ Refused: both or neither of --threshold / --reco2num-spk, --segments beside --va
 reverse), --vbx without --scoring plda or with an option outside its range, --target-energy without --scoring plda or outside (0, 1], a --min-segment below the network's receptive field, a --first-pass-max-points outside 2 .. 2048, a recording of more than 32768 windows, a
 recording of more than 2048 windows together with --vbx or --target-energy (their kernels keep the cap of 2048), a recording whose first pass
 leaves more than 2048 clusters, a recording without an entry in --reco2num-spk.
-Not here: waveform input (make_mfcc.py writes the archive this reads), threshold calibration, overlap detection.
+Not here: waveform input (make_mfcc.py writes the archive this reads), overlap detection; tune_diarization.py chooses
+the --threshold on a development set.
 """
 import os
 import sys

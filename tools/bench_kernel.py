@@ -30,6 +30,8 @@ sub-command per question (they used to be eight scripts):
                                                                 windows, medians over alternated rounds, beside scipy's average linkage on 16 CPUs
   python tools/bench_kernel.py ahc2 [n ...]                     two-pass clustering of one long recording (xv_ahc_cluster_from, xv_ahc_cluster_sums): n = 4096 / 8192
                                                                 windows, the stages apart, the single pass at 2048 windows for scale
+  python tools/bench_kernel.py diar_tune [recordings=64] [n=600] threshold tuning (xv_ahc_cut, xv_diar_confusion): Diarizer.sweep + DerSweep over 13 thresholds against 13 x
+                                                                (Diarizer.cluster + rttm_turns + der()), alternated rounds, the sweep's parts and the two ops alone
   python tools/bench_kernel.py vbx [recordings=64] [T,S ...]     VB-HMM clustering (xv_vbx.hip): one call over 64 recordings at (T, D, S) = (200, 128, 6), (800, 128, 10)
                                                                 and (2000, 128, 16), 20 iterations, medians over alternated rounds, beside the float64 NumPy
                                                                 restatement of one recording on the CPU
@@ -796,6 +798,91 @@ def cmd_ahc2(argv):
               (n, bound, sums / bound, sums / float(np.median(t["stream"]))), flush=True)
 
 
+def cmd_diar_tune(argv):
+    """Threshold tuning over `recordings` synthetic recordings of n windows in 128 dimensions (4 speakers, cosine scores) at 13 thresholds.
+    The sweep side: Diarizer.sweep (one clustering, xv_ahc_cut) + DerSweep (its set-up, then xv_diar_confusion and the assignments).  The
+    baseline side, the only route without them: 13 x (Diarizer.cluster + rttm_turns + der() per recording).  Host clock around each side,
+    ending in a device synchronise; five rounds that alternate the two sides, medians with min .. max; the sweep's parts apart; the two
+    ops alone (events, 20 calls back to back).  collar 0 and overlap "first" are der()'s rules: the two sides must give the same DER."""
+    from tf_kaldi_speaker_amd import ops
+    from tf_kaldi_speaker_amd.misc import diarization as D
+    from tf_kaldi_speaker_amd.misc import scoring as S
+    recordings = int(argv[0]) if argv else 64
+    n = int(argv[1]) if len(argv) > 1 else 600
+    thresholds = [float(t) for t in np.linspace(0.0, 0.6, 13)]
+    windows = [(0.01 * s, 0.01 * e) for s, e in D.subsegments(0, 75 * (n + 1), 150, 75, 50)]
+    emb, reference, subsegs = {}, {}, {}
+    for i in range(recordings):
+        who = np.repeat(rs.randint(0, 4, n // 8 + 1), 8)[:n]      # turns of eight windows
+        x = rs.randn(4, 128)[who] + 0.6 * rs.randn(n, 128)
+        key = "rec%03d" % i
+        emb[key], subsegs[key] = x.astype(np.float32), windows
+        reference[key] = [(s, e, "spk%d" % l) for s, e, l in D.rttm_turns(windows, who)]
+    scorer = S.CosineScorer("cuda:0")
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.time() - t0) * 1e3, out
+
+    def sweep_side():
+        parts = {}
+        parts["sweep"], labels = clock(lambda: D.Diarizer(scorer, threshold=0.0).sweep(emb, thresholds))
+        parts["set-up"], der = clock(lambda: D.DerSweep("cuda:0", reference, subsegs, collar=0.0, overlap="first"))
+        parts["score"], table = clock(lambda: der.score(labels))
+        return parts, [table.pooled(k)[3] if table.pooled(k) else float("nan") for k in range(len(thresholds))]      # (NaN: a cut of more than 256 clusters)
+
+    def baseline_side():
+        ders = []
+        for t in thresholds:
+            labels = D.Diarizer(scorer, threshold=t).cluster(emb)
+            counts = np.zeros(2)
+            for key in emb:
+                turns = D.rttm_turns(windows, labels[key])
+                speech = sum(int(round(e / D.DER_FRAME)) - int(round(s / D.DER_FRAME)) for s, e, _ in reference[key])      # (its turns do not overlap)
+                counts += speech * D.der(reference[key], turns)[3], speech
+            ders.append(counts[0] / counts[1])
+        return ders
+
+    sweep_side(), baseline_side()      # warm
+    times = {"sweep side": [], "baseline side": [], "sweep": [], "set-up": [], "score": []}
+    for _ in range(5):
+        ms, (parts, swept) = clock(sweep_side)
+        times["sweep side"].append(ms)
+        for k, v in parts.items():
+            times[k].append(v)
+        ms, base = clock(baseline_side)
+        times["baseline side"].append(ms)
+        assert np.allclose(np.where(np.isnan(swept), base, swept), base, rtol=0, atol=1e-12), (swept, base)
+    show = lambda v: "%9.2f ms (min %.2f .. max %.2f)" % (float(np.median(v)), min(v), max(v))
+    print("diar_tune: %d recordings x %d windows x 128, %d thresholds, cosine; pooled DER per threshold %s" % (recordings, n, len(thresholds), " ".join("%.4f" % d for d in swept)))
+    print("diar_tune: sweep side (Diarizer.sweep + DerSweep)                 %s" % show(times["sweep side"]))
+    print("diar_tune: baseline side (%d x (Diarizer.cluster + rttm_turns + der)) %s" % (len(thresholds), show(times["baseline side"])))
+    print("diar_tune: the baseline takes %.2f x the sweep (medians)" % (float(np.median(times["baseline side"])) / float(np.median(times["sweep side"]))))
+    for k, what in (("sweep", "Diarizer.sweep: scores, one merge log, its cuts, labels to the host"), ("set-up", "DerSweep set-up: reference frames, owning windows, upload"),
+                    ("score", "DerSweep.score: labels up, xv_diar_confusion, counts down, %d assignments" % (recordings * len(thresholds)))):
+        print("diar_tune:   %-90s %s" % (what, show(times[k])))
+    # the two ops alone
+    ld = (n + 3) // 4 * 4
+    buf = torch.zeros(recordings * n * ld, device="cuda")
+    for i, x in enumerate(emb.values()):
+        xd = torch.from_numpy(x / np.linalg.norm(x, axis=1, keepdims=True)).cuda()
+        buf[i * n * ld:(i + 1) * n * ld].view(n, ld)[:, :n] = xd @ xd.T
+    nn = np.full(recordings, n, np.int64)
+    _, merges, values, n_merges = ops.ahc_cluster(buf, np.arange(recordings, dtype=np.int64) * n * ld, nn, np.full(recordings, ld), targets=np.ones(recordings, np.int64))
+    labels, clusters = ops.ahc_cut(merges, values, n_merges, nn, thresholds)
+    der = D.DerSweep("cuda:0", reference, subsegs, collar=0.0, overlap="first")
+    host_clusters = clusters.cpu().numpy()
+    frames = int(der.frames.frames.sum())
+    print("diar_tune: ops.ahc_cluster down to one cluster, the %d recordings in one call: %9.1f us" % (recordings, timeit(lambda: ops.ahc_cluster(
+        buf, np.arange(recordings, dtype=np.int64) * n * ld, nn, np.full(recordings, ld), targets=np.ones(recordings, np.int64)), 3, 1)))
+    print("diar_tune: ops.ahc_cut, %d recordings x %d cuts in one launch (with its four small uploads):        %9.1f us" % (recordings, len(thresholds), timeit(lambda: ops.ahc_cut(merges, values, n_merges, nn, thresholds), 20, 3)))
+    print("diar_tune: ops.diar_confusion, %d recordings x %d cuts, %d frames each cut (with its two uploads): %9.1f us; clusters per cut %s" % (
+        recordings, len(thresholds), frames, timeit(lambda: ops.diar_confusion(der.frames, labels, host_clusters), 20, 3), " ".join("%d" % c for c in host_clusters.sum(axis=1))), flush=True)
+
+
 def cmd_vbx(argv):
     """One xv_vbx call over `recordings` recordings of T windows in 128 dimensions started from S speakers (the generator of tests/vbx_ref.py:
     S // 2 true speakers, each split in two), 20 iterations, never stopped: milliseconds per call, medians over five rounds that alternate
@@ -1070,7 +1157,7 @@ def cmd_resample(argv):
                  int(clipped.sum())), flush=True)
 
 
-COMMANDS = {"ahc": cmd_ahc, "ahc2": cmd_ahc2, "vbx": cmd_vbx, "pca_plda": cmd_pca_plda, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
+COMMANDS = {"ahc": cmd_ahc, "ahc2": cmd_ahc2, "diar_tune": cmd_diar_tune, "vbx": cmd_vbx, "pca_plda": cmd_pca_plda, "dense": cmd_dense, "resample": cmd_resample, "augment": cmd_augment, "cm_encode": cmd_cm_encode, "mfcc": cmd_mfcc, "fbank": cmd_fbank, "backend": cmd_backend, "plda_cohort": cmd_plda_cohort, "score": cmd_score, "gemm": cmd_gemm, "gemm16": cmd_gemm16, "elementwise": cmd_elementwise, "width": cmd_width, "pitch": cmd_pitch, "pool": cmd_pool, "vlad": cmd_vlad,
             "triplet": cmd_triplet, "ge2e": cmd_ge2e, "segment": cmd_segment, "staged": cmd_staged}
 
 if __name__ == "__main__":
